@@ -9,15 +9,20 @@ BASELINE.json configs[4] at one GPU: 8K (7680x4320) 10-bit, 4x2 tiles, full in-l
 own picture stream (weak scaling, no data-path collective — see DESIGN.md §multi-GPU); the barrier and the
 max-over-ranks clock of torch.distributed run over gloo (an idle RCCL communicator in the process costs the
 kernels ~13 % here), RCCL is created for the additional tile-sharded measurement, which does exchange data.
-The timed region runs with --pipeline-depth pictures in flight (default 3; the one-at-a-time time is reported
-beside it).
+The timed region runs with --pipeline-depth pictures in flight (default 3).
 
-Also reported:
+A plain run (`bench.py --gpus N --steps K --warmup W`) sets up, warms up, times exactly K steps once, writes the last step's
+output frame if --dump-outputs DIR is given, and prints the result line.  Everything else runs only with --full: the
+one-at-a-time pass with its per-stage times, the repeated timed regions (ms_per_step_spread), the frame checks against the
+CPU oracle, the legs beside the headline (rotating references, dependent chain, PCIe-inclusive, tile-sharded at N > 1) and:
+
   roofline      — the dominant kernel's algorithmic bytes per launch (SURVEY.md §8d accounting, computed
                   from the actual lists) / its average duration from HIP events on the library's stream,
                   against the 8 TB/s HBM3E peak;
   cpu_baseline  — the REAL reference functions (oracle/_ref, SSE/AVX tables where the reference has them) replaying a
-                  bounded sample of the same recipe on this box's host cores, one picture stream per thread.
+                  bounded sample of the same recipe on this box's host cores, one picture stream per thread;
+  end_to_end    — a synthetic bitstream of the workload's geometry through the reference CLI, on the reference library
+                  and on the glue library (where both are built).
 """
 import argparse
 import ctypes
@@ -31,15 +36,20 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 HBM_PEAK_GBS = 8000.0   # MI355X_MICROARCH.md: 8.0 TB/s spec (6.3 TB/s measured copy ceiling)
+WARMUP_MIN_S = 0.5      # after the --warmup steps, the warm-up goes on for at least this long before the timed region
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=1200, help="steps of THE timed region (default: ~0.5 s of device time at the default workload)")
-    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=20, help="warm-up steps before the timed region (then whole rounds of the lanes for at least %.1f s more)" % WARMUP_MIN_S)
+    ap.add_argument("--full", action="store_true", help="also run everything beside the headline: the one-at-a-time pass (stage_ms, roofline), "
+                    "the repeated timed regions, the frame checks, the legs, the CPU baseline and the end-to-end leg (off: a plain run times --steps steps once)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the frame the last timed step decoded as DIR/<plane>.npy "
+                    "(float32; planes above the size budget as a fixed seeded sample of their samples)")
     ap.add_argument("--repeats", type=int, default=0, help="the timed region of --steps steps is run this many times back to back, each bracketed by a "
-                    "synchronisation; ms_per_step / value are the MEDIAN region, ms_per_step_spread the min / max (default: 25 for <= 200 steps, else 5)")
+                    "synchronisation; ms_per_step / value are the MEDIAN region, ms_per_step_spread the min / max (default: 1; with --full 25 for <= 200 steps, else 5)")
     ap.add_argument("--workload", default="c5_8k10_8tiles")
     ap.add_argument("--pipeline-depth", type=int, default=3, help="pictures in flight per GPU in the timed region (1..32)")
     ap.add_argument("--intra-batch", type=int, default=0, help="intra workloads: the timed region's steps go out in groups of this many pictures with ONE intra stage "
@@ -140,18 +150,19 @@ def main():
     if args.stages != 31:
         ctx.set_stages(args.stages)
 
-    # (1) one picture at a time (pipeline depth 1): clean per-stage device timings for the roofline figures
-    for _ in range(args.warmup):
-        ctx.decode_resident(handle)
-    ctx.wait()
     side_steps = max(1, min(args.steps, 200))   # the legs beside the timed region run a bounded number of steps
-    ctx.timing_reset()
-    t0 = time.perf_counter()
-    for _ in range(side_steps):
-        ctx.decode_resident(handle)
-    ctx.wait()
-    dt_serial = (time.perf_counter() - t0) * args.steps / side_steps
-    n_dec, avg_total_ms, stage_ms = ctx.timing_collect()
+    if args.full:
+        # (1) one picture at a time (pipeline depth 1): clean per-stage device timings for the roofline figures
+        for _ in range(args.warmup):
+            ctx.decode_resident(handle)
+        ctx.wait()
+        ctx.timing_reset()
+        t0 = time.perf_counter()
+        for _ in range(side_steps):
+            ctx.decode_resident(handle)
+        ctx.wait()
+        dt_serial = (time.perf_counter() - t0) * args.steps / side_steps
+        n_dec, avg_total_ms, stage_ms = ctx.timing_collect()
     # (2) THE timed region: the same K steps with --pipeline-depth pictures in flight (m355_set_pipeline_depth: consecutive decodes
     # go round the lanes; every step still runs the whole chain for one picture, into the next of `depth` destination frames —
     # reusing a frame waits for its previous decode through the frame events)
@@ -174,7 +185,13 @@ def main():
             i += b
     run_steps(args.warmup)
     ctx.wait()
-    repeats = args.repeats if args.repeats > 0 else (25 if args.steps <= 200 else 5)
+    # then whole rounds of the lanes until the warm-up has lasted WARMUP_MIN_S: at C5 a 20-step region timed right after 5 warm-up
+    # steps ran ~4 % slower than one timed after half a second of decoding (clocks and caches not yet at steady state)
+    t_w = time.perf_counter()
+    while time.perf_counter() - t_w < WARMUP_MIN_S:
+        run_steps(8 * len(handles))
+        ctx.wait()
+    repeats = args.repeats if args.repeats > 0 else ((25 if args.steps <= 200 else 5) if args.full else 1)
     regions, enq = [], []
     for _ in range(repeats):                  # R timed regions of exactly K steps each: the run carries its own noise bar
         if dist:
@@ -199,8 +216,10 @@ def main():
     t_enq = enq[order[repeats // 2]]
     spread = {"repeats": repeats, "min": 1e3 * regions[order[0]] / args.steps, "median": 1e3 * dt / args.steps, "max": 1e3 * regions[order[-1]] / args.steps,
               "p10": 1e3 * regions[order[repeats // 10]] / args.steps, "p90": 1e3 * regions[order[min(repeats - 1, (9 * repeats) // 10)]] / args.steps}
-    if rank == 0 and args.stages == 31 and not args.no_verify:
-        last = (args.warmup + repeats * args.steps - 1) % len(handles)
+    last = (args.steps - 1) % len(handles)        # the frame of the last timed step (run_steps() starts at handles[0] in every region)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, ctx.frame_download(dsts[last]))
+    if args.full and rank == 0 and args.stages == 31 and not args.no_verify:
         seen["headline"] = (ctx.frame_hash(dsts[last], capi.HASH_MD5), std_refs)
     ctx.set_pipeline_depth(1)
 
@@ -208,7 +227,7 @@ def main():
     # two frames (2 x 99.5 MB at C5: inside the 256 MiB Infinity Cache), a stream's pictures read different ones.  Four pairs = 796 MB at
     # C5: every picture's windows come from HBM, not from the last-level cache.
     cold = None
-    if not args.no_cold_refs and rank == 0 and cfg["n_refs"] >= 1:
+    if args.full and not args.no_cold_refs and rank == 0 and cfg["n_refs"] >= 1:
         nr, n_sets = cfg["n_refs"], 4
         sets = []
         for k in range(n_sets):
@@ -254,7 +273,7 @@ def main():
     # assignment; frames rotate), decoded with the same number of pictures in flight — every decode waits for the SAO of its
     # references (per-frame events in the library).  What a real P/B chain sees, next to the independent-picture headline.
     chain = None
-    if not args.no_dependent_chain and rank == 0 and cfg["n_refs"] >= 1:
+    if args.full and not args.no_dependent_chain and rank == 0 and cfg["n_refs"] >= 1:
         nr = cfg["n_refs"]
         frames = [ctx.frame_create_for(pp) for _ in range(nr + 1)]
         for i in range(nr):
@@ -301,7 +320,7 @@ def main():
     # there with 16 threads, standing in for the parser's recorder threads), then validated, scheduled, copied to the device
     # and decoded, every step.  "submit_only": the same with the lists already lying in the arenas (three rotate).
     with_upload = None
-    if not args.no_with_upload and rank == 0:
+    if args.full and not args.no_with_upload and rank == 0:
         ctx.set_pipeline_depth(args.pipeline_depth)
         st = {}
         for _ in range(13):                  # the rotating arenas (three) are allocated on first use
@@ -381,19 +400,15 @@ def main():
             return
         emitted.append(1)
         ab = synth.algorithmic_bytes(pic)
-        launches = {"inter": 1, "residual": 1, "intra": 1, "deblock": 2, "sao": 1}   # kernel launches per stage and picture
-        dom = max(("inter", "residual", "intra", "deblock", "sao"), key=lambda s: stage_ms[s])
-        per_launch_ms = stage_ms[dom] / max(1, launches[dom])
-        achieved = (ab[dom] / max(1, launches[dom])) / (per_launch_ms * 1e-3) / 1e9 if per_launch_ms > 0 else 0.0
-        try:
-            copy_gbs = ctx.measure_copy_rate(1 << 30, 9)          # this box's device-to-device copy rate (read + written bytes): the achievable ceiling
-        except Exception:  # noqa: BLE001
-            copy_gbs = None
         out = {
             "metric": "decoded CTBs/s", "value": world * args.steps * n_ctbs / dt, "unit": "CTB64/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * dt / args.steps,
             "repeats": repeats, "ms_per_step_spread": spread,
-            "ms_per_step_one_in_flight": 1e3 * dt_serial / args.steps, "pictures_in_flight": args.pipeline_depth, "intra_batch": batch,
+        }
+        if args.full:
+            out["ms_per_step_one_in_flight"] = 1e3 * dt_serial / args.steps
+        out.update({
+            "pictures_in_flight": args.pipeline_depth, "intra_batch": batch,
             "host_enqueue_ms_per_step": 1e3 * t_enq / args.steps,
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "u8" if pp["bit_depth_luma"] <= 8 else "u16", "data": "synthetic",
@@ -403,15 +418,26 @@ def main():
                        "ctbs_per_picture": n_ctbs, "stages": "inter+residual+intra+deblock+sao" if args.stages == 31 else "DIAGNOSTIC mask %d" % args.stages, "parallelism": "pictures/%d" % world},
             "algorithmic_bytes_per_ctb": ab["total"] / n_ctbs,
             "pipeline_GBps": ab["total"] * args.steps / dt / 1e9,
-            "stage_ms": {k: round(v, 4) for k, v in stage_ms.items()},
-            "roofline": {"bound": "hbm", "kernel": "k_" + dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": pmc_traffic(args.workload, "k_" + dom),
-                         "launch_ms": per_launch_ms, "algorithmic_bytes_per_launch": ab[dom] / max(1, launches[dom]),
-                         "pictures_in_flight": 1,     # launch_ms / stage_ms: one picture at a time; `value`: args.pipeline_depth in flight
-                         "traffic_total": pmc_traffic_total(args.workload),
-                         # the ceiling a copy kernel reaches on THIS box (m355_measure_copy_rate: 1 GiB read + 1 GiB written per launch) and the fraction of it
-                         "copy_ceiling_GBps": copy_gbs, "frac_of_copy_ceiling": (achieved / copy_gbs) if copy_gbs else None},
-        }
+        })
+        if args.full:
+            launches = {"inter": 1, "residual": 1, "intra": 1, "deblock": 2, "sao": 1}   # kernel launches per stage and picture
+            dom = max(("inter", "residual", "intra", "deblock", "sao"), key=lambda s: stage_ms[s])
+            per_launch_ms = stage_ms[dom] / max(1, launches[dom])
+            achieved = (ab[dom] / max(1, launches[dom])) / (per_launch_ms * 1e-3) / 1e9 if per_launch_ms > 0 else 0.0
+            try:
+                copy_gbs = ctx.measure_copy_rate(1 << 30, 9)          # this box's device-to-device copy rate (read + written bytes): the achievable ceiling
+            except Exception:  # noqa: BLE001
+                copy_gbs = None
+            out["stage_ms"] = {k: round(v, 4) for k, v in stage_ms.items()}
+            out["roofline"] = {"bound": "hbm", "kernel": "k_" + dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                               "frac": achieved / HBM_PEAK_GBS, "traffic": pmc_traffic(args.workload, "k_" + dom),
+                               "launch_ms": per_launch_ms, "algorithmic_bytes_per_launch": ab[dom] / max(1, launches[dom]),
+                               "pictures_in_flight": 1,     # launch_ms / stage_ms: one picture at a time; `value`: args.pipeline_depth in flight
+                               "traffic_total": pmc_traffic_total(args.workload),
+                               # the ceiling a copy kernel reaches on THIS box (m355_measure_copy_rate: 1 GiB read + 1 GiB written per launch) and the fraction of it
+                               "copy_ceiling_GBps": copy_gbs, "frac_of_copy_ceiling": (achieved / copy_gbs) if copy_gbs else None}
+        if args.dump_outputs:
+            out["outputs"] = args.dump_outputs
         verdicts = verify_legs(seen, cfg, pic, synth, worklist) if seen else {}
         if "headline" in verdicts:
             out["verified"] = verdicts["headline"]
@@ -438,9 +464,9 @@ def main():
             out["dependent_chain"] = chain
         if cold is not None:
             out["rotating_references"] = cold
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(cfg, synth, worklist)
-        if not args.no_end_to_end and world == 1:
+        if args.full and not args.no_end_to_end and world == 1:
             e2e = end_to_end(cfg)
             if e2e is not None:
                 out["end_to_end"] = e2e
@@ -448,7 +474,7 @@ def main():
         os.write(real_stdout, (json.dumps(out) + "\n").encode())
 
     sharded = None
-    if dist and not args.no_tile_shard and (world > 1 or args.force_tile_shard):
+    if dist and not args.no_tile_shard and ((args.full and world > 1) or args.force_tile_shard):
         # The tile-sharded leg is the only part that runs collectives on the GPUs (RCCL).  It must never cost the main line:
         # exceptions are reported inside the JSON, and if the leg does not come back within the limit (a wedged collective
         # cannot be interrupted from Python) every rank prints / exits on its own from a watchdog thread.
@@ -467,6 +493,24 @@ def main():
     ctx.close()
     if dist:
         dist.destroy_process_group()
+
+
+DUMP_BUDGET = 12 << 20     # float32 samples over all planes (48 MiB): larger frames are written as a fixed seeded sample
+
+
+def dump_outputs(out_dir, planes):
+    """--dump-outputs: the planes of the frame the last timed step decoded, as out_dir/{y,cb,cr}.npy in float32.  When the frame holds more
+    than DUMP_BUDGET samples every plane is cut to the same fraction of its samples, at positions drawn from a fixed seed (sorted, in
+    raster order), so that two runs with the same arguments write comparable arrays."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(a.size for a in planes)
+    for c, (name, a) in enumerate(zip(("y", "cb", "cr"), planes)):
+        flat = a.reshape(-1)
+        if total > DUMP_BUDGET:
+            k = (flat.size * DUMP_BUDGET) // total
+            flat = flat[np.sort(np.random.default_rng(0x5EED + c).choice(flat.size, k, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), flat.astype(np.float32) if total > DUMP_BUDGET else a.astype(np.float32))
 
 
 def verify_legs(seen, cfg, pic, synth, worklist):

@@ -10,7 +10,7 @@ wait $BP
 cat gpurun_out/clk/idle.txt | grep -i "level\|sclk\|mclk"; echo ---; cat gpurun_out/clk/busy.txt
 # try forcing the high performance level, then measure again
 rocm-smi --setperflevel high > gpurun_out/clk/set.txt 2>&1; tail -3 gpurun_out/clk/set.txt
-timeout 120 python bench.py --no-cpu-baseline --no-with-upload --no-dependent-chain --no-end-to-end --workload c2_1080p_intra --steps 300 --warmup 10 --pipeline-depth 1 2>>gpurun_out/clk/bench.err | python -c "
+timeout 120 python bench.py --full --no-cpu-baseline --no-with-upload --no-dependent-chain --no-end-to-end --workload c2_1080p_intra --steps 300 --warmup 10 --pipeline-depth 1 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('perflevel high: %.4f ms/pic intra=%.4f' % (d['ms_per_step'], d['stage_ms']['intra']))"
 rocm-smi --setperflevel auto >> gpurun_out/clk/set.txt 2>&1

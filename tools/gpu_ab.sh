@@ -4,7 +4,7 @@ TAG=$1; VARS=$2; OUT=$PWD/gpurun_out/$TAG; mkdir -p $OUT; export TMPDIR=/tmp
 if [[ "$3" == *tests* ]]; then
   timeout 900 python -m pytest tests -m gpu -x -q --timeout 600 > $OUT/pytest.log 2>&1; echo "pytest exit $?" >> $OUT/pytest.log; tail -3 $OUT/pytest.log
 fi
-B="--no-cpu-baseline --no-with-upload --no-dependent-chain --no-end-to-end"
+B="--full --no-cpu-baseline --no-with-upload --no-dependent-chain --no-end-to-end"
 for v in $VARS; do
   if [ "$v" = base ]; then unset M355_LIB; else export M355_LIB=$PWD/libde265_amd/variants/$v.so; fi
   for w in ${WORKLOADS:-c2_1080p_intra c3_4k_inter c5_8k10_8tiles}; do

@@ -2,7 +2,7 @@
 # k_inter_jobs of one or more kernel variants: event time (bench stage_ms) + fabric traffic (separate PMC passes).
 # usage: tools/pmc_inter.sh base|<variant> ...     -> gpurun_out/pmc_inter/<variant>.txt
 REPO=$PWD; export TMPDIR=/tmp
-FL="--no-cpu-baseline --no-with-upload --no-dependent-chain --no-end-to-end"
+FL="--full --no-cpu-baseline --no-with-upload --no-dependent-chain --no-end-to-end"
 for v in "$@"; do
   if [ "$v" = base ]; then unset M355_LIB; else export M355_LIB=$REPO/libde265_amd/variants/$v.so; fi
   OUT=$REPO/gpurun_out/pmc_inter/$v; rm -rf $OUT; mkdir -p $OUT

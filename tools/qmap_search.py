@@ -11,7 +11,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CHAIN = bool(os.environ.get("QMAP_CHAIN"))
-B = ["--no-cpu-baseline", "--no-with-upload", "--no-end-to-end", "--no-cold-refs", "--no-verify"] + ([] if CHAIN else ["--no-dependent-chain"])
+B = ["--full", "--no-cpu-baseline", "--no-with-upload", "--no-end-to-end", "--no-cold-refs", "--no-verify"] + ([] if CHAIN else ["--no-dependent-chain"])
 
 
 def rgs(n, kmax):
