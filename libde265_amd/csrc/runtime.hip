@@ -50,16 +50,6 @@ hipError_t ev_query(m355_ctx* c, const EvRef& r) {
   return e.ticket == r.ticket ? hipEventQuery(e.ev) : hipSuccess;
 }
 
-void select_lane(m355_ctx* c, int lane) {
-  if (lane == c->active) return;
-#define PARK_FIELD(f) c->lanes[c->active].f = c->f;
-#define LOAD_FIELD(f) c->f = c->lanes[lane].f;
-  LANE_FIELDS(PARK_FIELD)
-  LANE_FIELDS(LOAD_FIELD)
-#undef PARK_FIELD
-#undef LOAD_FIELD
-  c->active = lane;
-}
 /* The HIP runtime multiplexes its streams onto a few hardware queues PER STREAM PRIORITY (GPU_MAX_HW_QUEUES, default 4), and
  * kernels of different streams that share a hardware queue mostly run one after the other.  Three lanes (six streams) do well on
  * the default priority's queues.  Every further group of three lanes belongs to the next priority class, whose streams have
@@ -112,13 +102,10 @@ static void lane_destroy(Lane& l)
 }
 /* all work of the context, on every lane */
 hipError_t sync_all(m355_ctx* c) {
-  hipError_t e = hipStreamSynchronize(c->stream);
-  for (int k = 0; k < M355_MAX_LANES; k++)
-    if (k != c->active && c->lanes[k].stream) { hipError_t e2 = hipStreamSynchronize(c->lanes[k].stream); if (e == hipSuccess) e = e2; }
-  if (c->stream_hi) { hipError_t e2 = hipStreamSynchronize(c->stream_hi); if (e == hipSuccess) e = e2; }
-  for (hipStream_t bs : c->batch_stream) if (bs) { hipError_t e2 = hipStreamSynchronize(bs); if (e == hipSuccess) e = e2; }
-  for (int k = 0; k < M355_MAX_LANES; k++)
-    if (k != c->active && c->lanes[k].stream_hi) { hipError_t e2 = hipStreamSynchronize(c->lanes[k].stream_hi); if (e == hipSuccess) e = e2; }
+  hipError_t e = hipSuccess;
+  auto sync = [&](hipStream_t s) { if (s) { hipError_t e2 = hipStreamSynchronize(s); if (e == hipSuccess) e = e2; } };
+  for (const Lane& l : c->lanes) { sync(l.stream); sync(l.stream_hi); }
+  for (hipStream_t bs : c->batch_stream) sync(bs);
   return e;
 }
 
@@ -175,12 +162,12 @@ int copy_tiles(m355_ctx* c, const m355_pic_params& pp, Frame* f, int k0, int k1,
           if ((wb | (x * bpp)) & 3) return fail(M355_ERR_INVALID, "tile rectangle is not a whole number of 32-bit words");
           TileCopyRect& t = a.r[n++];
           t.plane = (uint32_t)cc; t.xb = (uint32_t)(x * bpp); t.y = (uint32_t)y; t.wb = (uint32_t)wb; t.h = (uint32_t)h; t.pad = 0; t.ofs = o;
-          if (n == M355_TILE_COPY_RECTS) { m355_launch_tiles_copy(a, n, xbuf, to_slot, c->stream); n = 0; }
+          if (n == M355_TILE_COPY_RECTS) { m355_launch_tiles_copy(a, n, xbuf, to_slot, lane(c).stream); n = 0; }
         }
         o += wb * h;
       }
   }
-  m355_launch_tiles_copy(a, n, xbuf, to_slot, c->stream);
+  m355_launch_tiles_copy(a, n, xbuf, to_slot, lane(c).stream);
   return M355_OK;
 }
 
@@ -204,14 +191,8 @@ int m355_create(int device, m355_ctx** out)
   HIPCHK(hipSetDevice(device));
   m355_ctx* c = new m355_ctx;
   c->device = device;
-  {
-    Lane l;
-    int rc = lane_create(c, l, 0);
-    if (rc) { lane_destroy(l); delete c; return rc; }
-#define LOAD_FIELD(f) c->f = l.f;
-    LANE_FIELDS(LOAD_FIELD)                       /* lane 0 is the active one: it lives in the context's own fields */
-#undef LOAD_FIELD
-  }
+  int rc = lane_create(c, c->lanes[0], 0);
+  if (rc) { lane_destroy(c->lanes[0]); delete c; return rc; }
   *out = c;
   return M355_OK;
 }
@@ -259,15 +240,7 @@ void m355_destroy(m355_ctx* c)
   if (c->status_words) hipHostFree(c->status_words);
   if (c->stage) hipHostFree(c->stage);
   for (hipEvent_t e : c->dl_evs) if (e) hipEventDestroy(e);
-  {
-    /* the active lane lives in the context's own fields: collect it into a Lane and destroy both */
-    Lane a;
-#define MOVE_FIELD(f) a.f = c->f;
-    LANE_FIELDS(MOVE_FIELD)
-#undef MOVE_FIELD
-    lane_destroy(a);
-    for (int k = 0; k < M355_MAX_LANES; k++) if (k != c->active) lane_destroy(c->lanes[k]);
-  }
+  for (Lane& l : c->lanes) lane_destroy(l);
   delete c;
 }
 
@@ -291,7 +264,7 @@ int m355_set_pipeline_depth(m355_ctx* c, int depth)
 }
 
 /* the stream the active lane's last decode / phase ran on (an intra picture on lane 3.. runs on the lane's class stream, decode()) */
-void* m355_stream(m355_ctx* c) { return (void*)(c->last_stream ? c->last_stream : c->stream); }
+void* m355_stream(m355_ctx* c) { const Lane& l = lane(c); return (void*)(l.last_stream ? l.last_stream : l.stream); }
 
 /* ------------------------------------------------------------------------------ frames -------- */
 
@@ -307,10 +280,10 @@ int m355_frame_create(m355_ctx* c, int width, int height, int cf, int bdl, int b
   Frame& f = c->frames[idx];
   f = Frame();
   frame_geometry(f, width, height, cf, bdl, bdc);
-  int rc = frame_alloc(f, c->stream);
+  int rc = frame_alloc(f, lane(c).stream);
   if (rc) { frame_free(f); return -rc; }
   /* the zero fill is this frame's first write: whichever lane touches the frame next orders itself after it */
-  ev_mark(c, c->stream, &f.wr);
+  ev_mark(c, lane(c).stream, &f.wr);
   return idx;
 }
 Frame* get_frame(m355_ctx* c, int h) {
@@ -346,7 +319,7 @@ static int frame_stage_down(m355_ctx* c, Frame* f, int cidx, void* dst, size_t d
   const size_t rb = (size_t)f->pw[cidx] * f->bpp[cidx];
   int rc = stage_reserve(c, rb * f->ph[cidx]);
   if (rc) return rc;
-  hipStream_t st = f->wr_stream ? f->wr_stream : c->stream;
+  hipStream_t st = f->wr_stream ? f->wr_stream : lane(c).stream;
   HIPCHK(hipMemcpy2DAsync(c->stage, rb, f->plane[cidx], (size_t)f->stride[cidx] * f->bpp[cidx], rb, f->ph[cidx], hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   if (dst_pitch == rb) memcpy(dst, c->stage, rb * f->ph[cidx]);
@@ -360,8 +333,9 @@ static int frame_stage_up(m355_ctx* c, Frame* f, int cidx, const void* src, size
   if (rc) return rc;
   if (src_pitch == rb) memcpy(c->stage, src, rb * f->ph[cidx]);
   else for (int y = 0; y < f->ph[cidx]; y++) memcpy((uint8_t*)c->stage + (size_t)y * rb, (const uint8_t*)src + (size_t)y * src_pitch, rb);
-  HIPCHK(hipMemcpy2DAsync(f->plane[cidx], (size_t)f->stride[cidx] * f->bpp[cidx], c->stage, rb, rb, f->ph[cidx], hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
+  const hipStream_t st = lane(c).stream;
+  HIPCHK(hipMemcpy2DAsync(f->plane[cidx], (size_t)f->stride[cidx] * f->bpp[cidx], c->stage, rb, rb, f->ph[cidx], hipMemcpyHostToDevice, st));
+  HIPCHK(hipStreamSynchronize(st));
   return M355_OK;
 }
 int m355_frame_upload(m355_ctx* c, int h, int cidx, const void* src, ptrdiff_t stride)
@@ -394,7 +368,7 @@ int m355_frame_download_async(m355_ctx* c, int h, void* const dst[3], const ptrd
      the writer's own stream it never did.  They still run beside the host and beside the other lanes' decodes; the lane's next
      picture waits for them. */
   if (c->dl_evs.empty()) {
-    std::vector<hipEvent_t> evs(128, nullptr);              /* swapped in only when every event exists */
+    std::vector<hipEvent_t> evs(128, nullptr);              /* installed only when every event exists */
     for (auto& e : evs)
       if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) {
         for (hipEvent_t x : evs) if (x) hipEventDestroy(x);
@@ -404,7 +378,7 @@ int m355_frame_download_async(m355_ctx* c, int h, void* const dst[3], const ptrd
   }
   hipEvent_t ev_done = c->dl_evs[c->dl_ev_next];            /* (a ring: never re-recorded while an earlier record may still be waited for) */
   c->dl_ev_next = (c->dl_ev_next + 1) % (int)c->dl_evs.size();
-  hipStream_t cs = f->wr_stream ? f->wr_stream : c->stream;                     /* (no decode of this context wrote it: uploads and fills are synchronous) */
+  hipStream_t cs = f->wr_stream ? f->wr_stream : lane(c).stream;                /* (no decode of this context wrote it: uploads and fills are synchronous) */
   if (!f->wr_stream) ev_wait(c, cs, f->wr);
   for (int cc = 0; cc < 3; cc++) {
     if (!f->pw[cc]) continue;
@@ -434,17 +408,18 @@ int m355_frame_fill(m355_ctx* c, int h, int vl, int vc)
   if (!f) return fail(M355_ERR_INVALID, "bad frame handle %d", h);
   hipSetDevice(c->device);
   HIPCHK(sync_all(c));
+  const hipStream_t st = lane(c).stream;
   for (int cc = 0; cc < 3; cc++) {
     if (!f->pw[cc]) continue;
     const size_t n = (size_t)f->stride[cc] * f->ph[cc];
     const int v = cc ? vc : vl;
-    if (f->bpp[cc] == 1) { HIPCHK(hipMemsetAsync(f->plane[cc], v, n, c->stream)); HIPCHK(sync_all(c)); }
+    if (f->bpp[cc] == 1) { HIPCHK(hipMemsetAsync(f->plane[cc], v, n, st)); HIPCHK(sync_all(c)); }
     else {
       int rc = stage_reserve(c, n * 2);
       if (rc) return rc;
       std::fill((uint16_t*)c->stage, (uint16_t*)c->stage + n, (uint16_t)v);
-      HIPCHK(hipMemcpyAsync(f->plane[cc], c->stage, n * 2, hipMemcpyHostToDevice, c->stream));
-      HIPCHK(hipStreamSynchronize(c->stream));
+      HIPCHK(hipMemcpyAsync(f->plane[cc], c->stage, n * 2, hipMemcpyHostToDevice, st));
+      HIPCHK(hipStreamSynchronize(st));
     }
   }
   return M355_OK;
@@ -465,16 +440,17 @@ int m355_measure_copy_rate(m355_ctx* c, size_t bytes, int iters, double* gbps)
   HIPCHK(sync_all(c));
   void *a = nullptr, *b = nullptr;
   if (hipMalloc(&a, bytes) != hipSuccess || hipMalloc(&b, bytes) != hipSuccess) { if (a) hipFree(a); return fail(M355_ERR_NOMEM, "hipMalloc(%zu) failed", bytes); }
-  hipMemsetAsync(a, 0x5A, bytes, c->stream);
+  const hipStream_t st = lane(c).stream;
+  hipMemsetAsync(a, 0x5A, bytes, st);
   hipEvent_t e0, e1;
   hipEventCreate(&e0); hipEventCreate(&e1);
   const size_t n16 = bytes / 16;
   const unsigned grid = (unsigned)std::min<size_t>((n16 + 255) / 256, 256 * 32);
   std::vector<float> ms((size_t)iters, 0.f);
   for (int i = -2; i < iters; i++) {
-    hipEventRecord(e0, c->stream);
-    hipLaunchKernelGGL(k_copy_rate, dim3(grid), dim3(256), 0, c->stream, (const uint4*)a, (uint4*)b, n16);
-    hipEventRecord(e1, c->stream);
+    hipEventRecord(e0, st);
+    hipLaunchKernelGGL(k_copy_rate, dim3(grid), dim3(256), 0, st, (const uint4*)a, (uint4*)b, n16);
+    hipEventRecord(e1, st);
     hipEventSynchronize(e1);
     if (i >= 0) hipEventElapsedTime(&ms[(size_t)i], e0, e1);
   }
@@ -537,11 +513,12 @@ int m355_frame_hash(m355_ctx* c, int h, int type, m355_picture_hash* out)
   }
   a.first[3] = nw;
   uint32_t acc[4] = {0, 0, 0, 0};
-  HIPCHK(hipMemsetAsync(c->hash_acc, 0, 4 * sizeof(uint32_t), c->stream));
-  m355_launch_frame_hash(a, type, c->stream);
+  const hipStream_t st = lane(c).stream;
+  HIPCHK(hipMemsetAsync(c->hash_acc, 0, 4 * sizeof(uint32_t), st));
+  m355_launch_frame_hash(a, type, st);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(acc, c->hash_acc, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipMemcpyAsync(acc, c->hash_acc, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
   for (int cc = 0; cc < np; cc++) {
     if (type == M355_HASH_CRC) out->crc[cc] = (uint16_t)(acc[cc] ^ m355_crc_init_term((uint64_t)a.pl[cc].row_bytes * a.pl[cc].h));
     else out->checksum[cc] = acc[cc];
@@ -647,9 +624,8 @@ int m355_wait(m355_ctx* c)
   HIPCHK(sync_all(c));
   for (auto& f : c->frames) { f.wr = EvRef(); f.dl_pending = false; for (int k = 0; k < M355_MAX_LANES; k++) f.rd[k] = EvRef(); }   /* everything is complete */
   uint32_t t = 0;
-  HIPCHK(hipMemcpy(&t, c->timeout, 4, hipMemcpyDeviceToHost));
-  for (int k = 0; k < M355_MAX_LANES; k++)
-    if (k != c->active && c->lanes[k].timeout) { uint32_t t2 = 0; HIPCHK(hipMemcpy(&t2, c->lanes[k].timeout, 4, hipMemcpyDeviceToHost)); t |= t2; }
+  for (const Lane& l : c->lanes)
+    if (l.timeout) { uint32_t t2 = 0; HIPCHK(hipMemcpy(&t2, l.timeout, 4, hipMemcpyDeviceToHost)); t |= t2; }
   /* lists checked on the device (recorded in place): the first rejected decode not reported yet (everything has finished) */
   {
     m355_ctx::Status* first = nullptr;
@@ -664,9 +640,7 @@ int m355_wait(m355_ctx* c)
     if (first) return status_of(c, *first);
   }
   if (t) {
-    hipMemsetAsync(c->timeout, 0, 4, c->stream);
-    for (int k = 0; k < M355_MAX_LANES; k++)
-      if (k != c->active && c->lanes[k].timeout) hipMemsetAsync(c->lanes[k].timeout, 0, 4, c->lanes[k].stream);
+    for (const Lane& l : c->lanes) if (l.timeout) hipMemsetAsync(l.timeout, 0, 4, l.stream);
     sync_all(c);
     return fail(M355_ERR_TIMEOUT, "intra wavefront spin bound exceeded");
   }

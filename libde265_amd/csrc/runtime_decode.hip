@@ -10,7 +10,7 @@ extern "C" {
 /* frames, scratch and the device descriptor of one decode of `r` */
 bool chain_residuals_forced();
 
-int prepare(m355_ctx* c, Resident& r, DevPic& d_out, bool& want_sao_out) {
+int prepare(m355_ctx* c, Resident& r, DevPic& d_out, bool& want_sao_out, hipStream_t st) {
   hipSetDevice(c->device);
   const m355_picture& pic = r.hdr;
   const m355_pic_params& pp = pic.pp;
@@ -41,7 +41,7 @@ int prepare(m355_ctx* c, Resident& r, DevPic& d_out, bool& want_sao_out) {
   if (!r.refs_valid || memcmp(r.refs_host, refs, sizeof(refs)) != 0) {
     if (!r.fresh) HIPCHK(sync_all(c));       /* a decode in flight may still read the table / the staging copy */
     memcpy(r.refs_host, refs, sizeof(refs));
-    HIPCHK(hipMemcpyAsync(r.refs_dev, r.refs_host, sizeof(refs), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(r.refs_dev, r.refs_host, sizeof(refs), hipMemcpyHostToDevice, st));
     r.refs_valid = true;
   }
   d.refs = r.refs_dev;
@@ -62,13 +62,14 @@ int prepare(m355_ctx* c, Resident& r, DevPic& d_out, bool& want_sao_out) {
     d.inter_tabs = tab;
   }
   /* scratch */
+  Lane& L = lane(c);
   int rc;
   {
     /* edge_tu | edge_pb | cb_cu in one allocation (one memset per picture, k_meta.hip); pb_of separate */
     const size_t u4 = (size_t)d.w4 * d.h4, ncb = (size_t)d.wcb * d.hcb;
     const size_t need = ((2 * u4 + 63) & ~(size_t)63) + ncb * 4 + 64;
-    if ((rc = grow(&c->edge_tu, &c->cap_u4, need, c->stream, false))) return rc;
-    if ((rc = grow(&c->pb_of, &c->cap_cb, u4, c->stream, true))) return rc;
+    if ((rc = grow(&L.edge_tu, &L.cap_u4, need, st, false))) return rc;
+    if ((rc = grow(&L.pb_of, &L.cap_cb, u4, st, true))) return rc;
   }
   {
     /* k_intra's halo granules: per component ctbW right columns of ph / 2 granules and ctbH bottom rows of pw / 2; zero at
@@ -78,9 +79,9 @@ int prepare(m355_ctx* c, Resident& r, DevPic& d_out, bool& want_sao_out) {
       d.edge_col_ofs[cc] = (uint32_t)n; n += (size_t)d.ctbW * (size_t)(dst->ph[cc] >> 1);
       d.edge_row_ofs[cc] = (uint32_t)n; n += (size_t)d.ctbH * (size_t)(dst->pw[cc] >> 1);
     }
-    if ((rc = grow(&c->edge, &c->cap_edge, n + 1, c->stream, true))) return rc;
+    if ((rc = grow(&L.edge, &L.cap_edge, n + 1, st, true))) return rc;
   }
-  if ((rc = grow(&c->cuf, &c->cap_cuf, (size_t)pic.n_cus + (size_t)r.halo.n_units + 1, c->stream, false))) return rc;
+  if ((rc = grow(&L.cuf, &L.cap_cuf, (size_t)pic.n_cus + (size_t)r.halo.n_units + 1, st, false))) return rc;
   /* (Inter residuals are added to the prediction samples in place, behind k_inter_jobs.  Handing them to k_inter_jobs' write-back as int16
      tiles — round 4's "fused" order, the default with one picture in flight then — saves 80 MB per 8K picture and was measured again with
      round 5's lean k_inter_jobs: it loses at every depth, C5 0.362-0.368 against 0.346-0.356 ms with three pictures in flight, 0.486-0.494
@@ -93,44 +94,44 @@ int prepare(m355_ctx* c, Resident& r, DevPic& d_out, bool& want_sao_out) {
   /* (pictures of a one-stream lane only — up to 4K, launch_prediction: an 8K picture's kernels fill the GPU, its transforms gain nothing in front) */
   const bool tiles = (c->depth >= sched::chain_residual_tiles_min_depth || chain_residuals_forced()) && (long long)pic.pp.width * pic.pp.height <= sched::one_stream_max_samples;
   const size_t res_need = res_intra + (tiles ? res_tiles : 0) + 1;
-  if ((rc = grow(&c->resbuf, &c->cap_res, res_need, c->stream, false))) return rc;
-  d.res_tiles = tiles ? c->resbuf + res_intra : nullptr;     /* (resbuf itself: below, with the lane's other scratch) */
+  if ((rc = grow(&L.resbuf, &L.cap_res, res_need, st, false))) return rc;
+  d.res_tiles = tiles ? L.resbuf + res_intra : nullptr;     /* (resbuf itself: below, with the lane's other scratch) */
   d.res_front = 0;
-  if ((rc = grow(&c->sao_nb, &c->cap_sao, (size_t)d.nCtb * 3, c->stream, false))) return rc;
+  if ((rc = grow(&L.sao_nb, &L.cap_sao, (size_t)d.nCtb * 3, st, false))) return rc;
   {
     /* inter jobs of 4 x 8 luma samples: a list of disjoint prediction blocks makes at most one per 16 luma samples (8x4 blocks),
        and at most one per 32 plus eight per block; the counts themselves are made on the device (k_job_count / k_job_scan) */
     const size_t area = (size_t)pp.width * pp.height;
     const size_t cap = pic.n_pbs > 0 ? std::min(area / 16, area / 32 + 8 * (size_t)pic.n_pbs) + 256 : 1;
     const size_t n_chunks = ((size_t)(pic.n_pbs > 0 ? pic.n_pbs : 0) + 255) / 256;
-    if ((rc = grow(&c->jobs, &c->cap_jobs, cap, c->stream, false))) return rc;
-    if ((rc = grow(&c->job_base, &c->cap_jobbase, n_chunks * 4 + 8, c->stream, true))) return rc;
-    d.jobs_cap = (uint32_t)cap; d.job_base = c->job_base; d.job_tot = c->job_base + n_chunks * 4;
+    if ((rc = grow(&L.jobs, &L.cap_jobs, cap, st, false))) return rc;
+    if ((rc = grow(&L.job_base, &L.cap_jobbase, n_chunks * 4 + 8, st, true))) return rc;
+    d.jobs_cap = (uint32_t)cap; d.job_base = L.job_base; d.job_tot = L.job_base + n_chunks * 4;
   }
-  if ((rc = grow(&c->iplan, &c->cap_iplan, (size_t)r.n_iplan + 8, c->stream, false))) return rc;
+  if ((rc = grow(&L.iplan, &L.cap_iplan, (size_t)r.n_iplan + 8, st, false))) return rc;
 
   const bool want_sao = (c->stages & M355_STAGE_SAO) && (pp.flags & M355_PF_SAO_ENABLED);
   Frame* target = dst;
   if (want_sao) {
-    if (!c->work.used || c->work.w != dst->w || c->work.h != dst->h || c->work.cf != dst->cf || c->work.bdl != dst->bdl || c->work.bdc != dst->bdc) {
+    if (!L.work.used || L.work.w != dst->w || L.work.h != dst->h || L.work.cf != dst->cf || L.work.bdl != dst->bdl || L.work.bdc != dst->bdc) {
       HIPCHK(sync_all(c));
-      if (c->work.used) frame_free(c->work);
-      frame_geometry(c->work, dst->w, dst->h, dst->cf, dst->bdl, dst->bdc);
-      if ((rc = frame_alloc(c->work, c->stream))) return rc;
+      if (L.work.used) frame_free(L.work);
+      frame_geometry(L.work, dst->w, dst->h, dst->cf, dst->bdl, dst->bdc);
+      if ((rc = frame_alloc(L.work, st))) return rc;
     }
-    target = &c->work;
+    target = &L.work;
   }
   for (int cc = 0; cc < 3; cc++) {
     d.pw[cc] = dst->pw[cc]; d.ph[cc] = dst->ph[cc];
     d.plane[cc] = target->plane[cc]; d.stride[cc] = target->stride[cc];
     d.out_plane[cc] = dst->plane[cc]; d.out_stride[cc] = dst->stride[cc];
   }
-  d.edge_tu = c->edge_tu; d.edge_pb = c->edge_tu + (size_t)d.w4 * d.h4;
-  d.cb_cu = (uint32_t*)(c->edge_tu + (((size_t)2 * d.w4 * d.h4 + 63) & ~(size_t)63));
-  d.cuf = c->cuf; d.pb_of = c->pb_of;
+  d.edge_tu = L.edge_tu; d.edge_pb = L.edge_tu + (size_t)d.w4 * d.h4;
+  d.cb_cu = (uint32_t*)(L.edge_tu + (((size_t)2 * d.w4 * d.h4 + 63) & ~(size_t)63));
+  d.cuf = L.cuf; d.pb_of = L.pb_of;
   d.fill_pb_of_in_meta = ((c->stages & M355_STAGE_INTER) && m355_inter_uses_jobs(d)) ? 0 : 1;   /* else k_inter_jobs writes it */
-  d.jobs = c->jobs; d.sao_nb = c->sao_nb; d.iplan = c->iplan;
-  d.resbuf = c->resbuf; d.edge = c->edge; d.ticket = c->ticket; d.timeout = c->timeout;
+  d.jobs = L.jobs; d.sao_nb = L.sao_nb; d.iplan = L.iplan;
+  d.resbuf = L.resbuf; d.edge = L.edge; d.ticket = L.ticket; d.timeout = L.timeout;
   {
     /* intra pictures: k_intra's workgroups are persistent (k_intra.hip); with several pictures in flight every picture gets a
        share of the GPU's workgroup slots (2 per CU for this kernel) — enough for its active wavefront, not a slot per CTB */
@@ -145,7 +146,7 @@ int prepare(m355_ctx* c, Resident& r, DevPic& d_out, bool& want_sao_out) {
     if (!d.intra_keeper && r.dp.intra_dense) {
       /* ... or when nothing else is in flight right now, whatever the depth: the intra picture a stream's other pictures wait for */
       bool idle = true;
-      for (int i = 0; i < c->depth && idle; i++) if (i != c->active && ev_query(c, c->lanes[i].last) != hipSuccess) idle = false;
+      for (int i = 0; i < c->depth && idle; i++) if (&c->lanes[i] != &L && ev_query(c, c->lanes[i].last) != hipSuccess) idle = false;
       d.intra_keeper = idle;
     }
     /* (test hook: the interpreter finishes every launch before the next call, so its pipeline is always idle — M355_TEST_NO_KEEPER=1
@@ -168,10 +169,11 @@ hipError_t frame_event(hipEvent_t* e) {
   return hipEventCreateWithFlags(e, hipEventDisableTiming);
 }
 
-/* The prediction half of a decode on the active lane: the metadata planes (read first by k_intra) are rasterised on the side
+/* The prediction half of a decode on the active lane, enqueued on `st`: the metadata planes (read first by k_intra) are rasterised on the side
  * stream while the main stream runs job list -> inter prediction, which do not read them; the residual stage then runs in two
  * launches side by side — 32x32 + 16x16 blocks on the main stream, 8x8 + 4x4 on the side stream — and k_intra follows the join.
- * ev: the decode's timing events [1..4] (after meta jobs / inter / residual / intra) or nullptr. */
+ * ev: the decode's timing events [1..4] (after meta jobs / inter / residual / intra) or nullptr.  Returns the stream the decode
+ * continues on: `st`, or `chain` after a dependent chain's hand-over. */
 /* M355_PF_CLEAR_DST: a new picture starts from zero in the reference (image.cc:164); the planes being reconstructed are this
  * lane's working planes (SAO rewrites every sample of the destination) or the destination itself — then, for lists checked on
  * the device, by a kernel behind the decode's gate: a rejected picture must leave its destination frame untouched
@@ -189,8 +191,8 @@ void clear_target(m355_ctx* c, const DevPic& d, Frame* tgt, bool gated, hipStrea
    k_residual_add behind it —, chain or not: the CPU tier's interpreter finishes every launch before the next call, so no reference is ever "still being written" there */
 bool chain_residuals_forced() { static const bool on = getenv("M355_TEST_CHAIN_RESIDUALS") != nullptr; return on; }
 
-void launch_prediction(m355_ctx* c, const Resident& r, const DevPic& d, bool hbd, hipEvent_t* ev, bool with_intra, hipStream_t chain, Frame* hazard_dst) {
-  hipStream_t st = c->stream;
+hipStream_t launch_prediction(m355_ctx* c, const Resident& r, const DevPic& d, bool hbd, hipStream_t st, hipEvent_t* ev, bool with_intra, hipStream_t chain, Frame* hazard_dst) {
+  Lane& L = lane(c);
   /* an intra picture keeps to its lane's main stream: its side work (metadata planes, border plans: 0.07 ms) is nothing beside k_intra,
      and half as many streams compete for the runtime's hardware queues when many such pictures are in flight (C2 0.340 ms per picture
      = 1.50 M CTB64/s at depth 9, profiles/r03_v_*; forked: 0.59 at depth 8) — and so does a picture of up to 4K: the fork / join of the
@@ -199,7 +201,7 @@ void launch_prediction(m355_ctx* c, const Resident& r, const DevPic& d, bool hbd
      flight, profiles/r04_al_*: C3 / C4 0.110 -> 0.098 / 0.100 ms on one stream, C5 0.347 -> 0.351); one intra picture at a time with its
      planes forked beside the residuals: 0.881 -> 0.896 ms (profiles/r05_v20_*) */
   const bool single = d.intra_dense || (long long)d.pp.width * d.pp.height <= sched::one_stream_max_samples;
-  hipStream_t s2 = single ? st : c->stream2;
+  hipStream_t s2 = single ? st : L.stream2;
   /* the zero fill of the metadata planes rides in the picture's first main-stream launch (k_job_count), in FRONT of the fork: the
      side stream's scatters then start behind it — one launch less per inter picture */
   /* (the fill is shared out over the launch's workgroups, one per 256 PBs: with a handful of them a fill of its own is faster;
@@ -215,7 +217,7 @@ void launch_prediction(m355_ctx* c, const Resident& r, const DevPic& d, bool hbd
   const bool res_front = (chain || chain_residuals_forced()) && d.res_tiles && (c->stages & M355_STAGE_RESIDUAL) && d.pp.bit_depth_luma <= 15 && d.pp.bit_depth_chroma <= 15 &&
                          d.rb_count[0] + d.rb_count[1] + d.rb_count[2] + d.rb_count[3] > 0;
   if (clear_in_count) m355_launch_job_count(d, true, st);
-  if (!single) { hipEventRecord(c->ev_fork, st); hipStreamWaitEvent(s2, c->ev_fork, 0); }
+  if (!single) { hipEventRecord(L.ev_fork, st); hipStreamWaitEvent(s2, L.ev_fork, 0); }
   /* transform edges and border plans in ONE launch (a packet less per picture: C3 0.098 -> 0.093 ms, profiles/r05_a_switches_merge.txt) */
   if (single && clear_in_count && (c->stages & M355_STAGE_INTRA)) {
     /* one stream: the planes' scatters and the job list are independent roles of ONE launch (k_meta_planes_jobs) */
@@ -237,7 +239,7 @@ void launch_prediction(m355_ctx* c, const Resident& r, const DevPic& d, bool hbd
        streams (one after the other on the main stream, without the second fork, was measured 1 % slower at C5 with three
        pictures in flight: 0.3573-0.3605 against 0.3538-0.3580 ms, profiles/r04_am_residual_streams_ab.txt) */
     hipStream_t sr = !single ? s2 : st;
-    if (sr != st) { hipEventRecord(c->ev_fork2, st); hipStreamWaitEvent(s2, c->ev_fork2, 0); }
+    if (sr != st) { hipEventRecord(L.ev_fork2, st); hipStreamWaitEvent(s2, L.ev_fork2, 0); }
     if (tu_plan_with_residuals) m355_launch_residual_tu_plan(dd, hbd, st);
     else if (sr == st) m355_launch_residual_both(dd, hbd, st);       /* (one stream: one launch, k_residual.hip) */
     else {
@@ -258,13 +260,13 @@ void launch_prediction(m355_ctx* c, const Resident& r, const DevPic& d, bool hbd
        queue really sleeps on cost a dependent 4K picture 25-40 us: profiles/r05_v25_*) */
     EvRef front;
     if (ev_mark(c, st, &front) == M355_OK) {
-      c->stream = st = chain; ev_wait(c, st, front);
+      st = chain; ev_wait(c, st, front);
       if (ev) hipEventRecord(ev[1], st);      /* (timed decode: the 'inter' interval starts behind the hand-over, the wait for the reference's stages is booked on 'meta') */
     }
   }
   /* (a picture without SAO writes its destination from here on: its readers / last writer are waited for HERE, not in front of the metadata kernels —
      the destination of a chain's picture is often a frame the picture before it still reads) */
-  if (hazard_dst) dst_hazards(c, hazard_dst, true);
+  if (hazard_dst) dst_hazards(c, hazard_dst, true, st);
   if (c->depth >= 2)
     for (int i = 0; i < M355_MAX_REF_FRAMES; i++) {
       Frame* f = r.hdr.ref_frames[i] >= 0 ? get_frame(c, r.hdr.ref_frames[i]) : nullptr;
@@ -274,25 +276,40 @@ void launch_prediction(m355_ctx* c, const Resident& r, const DevPic& d, bool hbd
   if (ev) hipEventRecord(ev[2], st);
   if ((c->stages & M355_STAGE_RESIDUAL) && !res_front) launch_residuals(d);
   else if (res_front) m355_launch_residual_add(d, hbd, st);
-  if (!single) { hipEventRecord(c->ev_join, s2); hipStreamWaitEvent(st, c->ev_join, 0); }     /* join */
+  if (!single) { hipEventRecord(L.ev_join, s2); hipStreamWaitEvent(st, L.ev_join, 0); }     /* join */
   if (ev) hipEventRecord(ev[3], st);
   if (with_intra && (c->stages & M355_STAGE_INTRA)) m355_launch_intra(d, hbd, st, clear_in_count);   /* (m355_decode_batch launches several pictures' intra stage as one kernel) */
   if (ev) hipEventRecord(ev[4], st);
+  return st;
 }
 
 /* write-after-write / write-after-read on the destination: waited for right before the first kernel that writes it — the SAO
    stage when SAO runs (everything before writes this lane's working planes), else the first stage */
-void dst_hazards(m355_ctx* c, Frame* dstf, bool piped) {
-  if (dstf->dl_pending) hipStreamWaitEvent(c->stream, dstf->ev_dl, 0);     /* (stays pending for the HOST until m355_frame_download_wait / m355_wait) */
+void dst_hazards(m355_ctx* c, Frame* dstf, bool piped, hipStream_t st) {
+  if (dstf->dl_pending) hipStreamWaitEvent(st, dstf->ev_dl, 0);     /* (stays pending for the HOST until m355_frame_download_wait / m355_wait) */
   if (!piped) return;
-  ev_wait(c, c->stream, dstf->wr);
-  for (int k = 0; k < M355_MAX_LANES; k++) ev_wait(c, c->stream, dstf->rd[k]);
+  ev_wait(c, st, dstf->wr);
+  for (int k = 0; k < M355_MAX_LANES; k++) ev_wait(c, st, dstf->rd[k]);
+}
+
+/* ONE mark behind the last kernel on `st` into the lists (their arenas), the destination frame (its next reader / writer) and the lane
+   (its next decode, which may run on the lane's other stream): -> r.done */
+int mark_done(m355_ctx* c, Resident& r, Frame* dstf, hipStream_t st) {
+  const int rc = ev_mark(c, st, &r.done);
+  if (rc) return rc;
+  r.fresh = false;
+  dstf->wr_stream = st; dstf->wr = r.done;
+  lane(c).last = r.done; lane(c).last_stream = st;
+  return M355_OK;
 }
 
 /* One decode = decode_pre (lane, hazards, validation, every stage in front of the intra stage [and, with_intra, that stage]) +
  * decode_post (in-loop filters, events, status slot).  m355_decode_batch runs the pre part of several intra pictures on their lanes,
  * ONE k_intra launch for all of them, then their post parts. */
-struct DecodeState { DevPic d; bool want_sao = false; hipEvent_t* ev = nullptr; hipStream_t saved_stream = nullptr; bool swapped = false; hipStream_t chain = nullptr; };
+struct DecodeState {
+  DevPic d; bool want_sao = false; hipEvent_t* ev = nullptr;
+  hipStream_t st = nullptr;    /* what the decode runs on: the lane's stream, its stream_hi or the batch's stream — after a chain's hand-over, the chain's */
+};
 
 /* front: PRE_ALL = everything up to and including the intra stage; PRE_NO_INTRA = without k_intra; PRE_HAZARDS = lane, hazards, validation and
    clearing only (m355_decode_batch launches the stages itself, one launch per stage for all its pictures) */
@@ -326,27 +343,22 @@ static int decode_pre(m355_ctx* c, Resident& r, bool rotate, DecodeState& S, int
       const bool split = c->depth >= sched::chain_split_min_depth;
       for (int k = 0; k < c->depth; k++) {
         const int l = (c->active + 1 + k) % c->depth;
-        if (((l == c->active ? c->stream : c->lanes[l].stream) != chain) == split) { lane = l; break; }
+        if ((c->lanes[l].stream != chain) == split) { lane = l; break; }
       }
     }
     select_lane(c, lane);
   }
-  /* which stream: an intra picture on lane 3.. takes the lane's class stream (lane_class_priority); the whole decode addresses
-     c->stream, which is that stream until decode_post returns (a batch keeps to the lanes' ordinary streams: its pictures overlap
-     inside one kernel, not through hardware queues) */
-  {
-    hipStream_t run = on_stream ? on_stream : c->stream;   /* (a batch on a stream of its own: its lanes lend their scratch only) */
-    if (!on_stream && with_intra && r.dp.intra_dense && c->active >= sched::intra_class_first_lane && lane_priorities_mode() == 2 && lane_class_priority(c->active) != 0) {
-      if (!c->stream_hi) HIPCHK(hipStreamCreateWithPriority(&c->stream_hi, hipStreamNonBlocking, lane_class_priority(c->active)));
-      run = c->stream_hi;
-    }
-    ev_wait(c, run, c->last);                              /* the lane's scratch and working planes (when its last decode ran on its other stream) */
-    S.saved_stream = c->stream; S.swapped = run != c->stream;
-    c->stream = run;
-    if (chain && chain != run && mode == PRE_ALL) { S.chain = chain; S.swapped = true; }   /* (launch_prediction moves the decode onto `chain`; decode_post restores) */
+  /* which stream: the lane's, or for an intra picture on lane 3.. the lane's class stream (lane_class_priority); a batch keeps to the lanes'
+     ordinary streams: its pictures overlap inside one kernel, not through hardware queues */
+  Lane& L = lane(c);
+  hipStream_t st = on_stream ? on_stream : L.stream;       /* (a batch on a stream of its own: its lanes lend their scratch only) */
+  if (!on_stream && with_intra && r.dp.intra_dense && c->active >= sched::intra_class_first_lane && lane_priorities_mode() == 2 && lane_class_priority(c->active) != 0) {
+    if (!L.stream_hi) HIPCHK(hipStreamCreateWithPriority(&L.stream_hi, hipStreamNonBlocking, lane_class_priority(c->active)));
+    st = L.stream_hi;
   }
+  ev_wait(c, st, L.last);                                  /* the lane's scratch and working planes (when its last decode ran on its other stream) */
   DevPic& d = S.d;
-  int rc = prepare(c, r, d, S.want_sao);
+  int rc = prepare(c, r, d, S.want_sao, st);
   if (rc) return rc;
   const bool want_sao = S.want_sao;
   const m355_pic_params& pp = r.hdr.pp;
@@ -355,9 +367,8 @@ static int decode_pre(m355_ctx* c, Resident& r, bool rotate, DecodeState& S, int
   Frame* dstf = get_frame(c, r.hdr.dst_frame);
   if (piped) {
     /* read-after-write: the lists (uploaded on whichever lane was active); the reference frames' last writers: launch_prediction */
-    ev_wait(c, c->stream, r.up);
+    ev_wait(c, st, r.up);
   }
-  hipStream_t st = c->stream;
   hipEvent_t* ev = nullptr;
   if (with_intra && c->timing_on) {                        /* (a batch's decodes are not stage-timed: their intra stage is shared) */
     if (c->ev_used >= 4096) c->ev_used = 0;                 /* bounded ring */
@@ -371,16 +382,17 @@ static int decode_pre(m355_ctx* c, Resident& r, bool rotate, DecodeState& S, int
   /* write-after-read / -write on the destination of a picture without SAO: in front of its first writer — the clearing fill if there is one, else
      k_inter (launch_prediction, behind a chain picture's change of stream) */
   const bool hazards_late = !want_sao && piped && mode != PRE_HAZARDS && !(pp.flags & M355_PF_CLEAR_DST);
-  if (!want_sao && !hazards_late) dst_hazards(c, dstf, piped);
-  if (pp.flags & M355_PF_CLEAR_DST) clear_target(c, d, want_sao ? &c->work : dstf, r.device_validate && !want_sao, st);
+  if (!want_sao && !hazards_late) dst_hazards(c, dstf, piped, st);
+  if (pp.flags & M355_PF_CLEAR_DST) clear_target(c, d, want_sao ? &L.work : dstf, r.device_validate && !want_sao, st);
   if (!with_intra) d.intra_keeper = 0;                     /* (a batch's shared intra stage is the 12-wave kernel: it needs the planner's launch) */
-  if (mode != PRE_HAZARDS) launch_prediction(c, r, d, hbd, ev, with_intra, S.chain, hazards_late ? dstf : nullptr);
+  /* (launch_prediction moves a dependent chain's picture onto `chain`) */
+  if (mode != PRE_HAZARDS) st = launch_prediction(c, r, d, hbd, st, ev, with_intra, with_intra && chain != st ? chain : nullptr, hazards_late ? dstf : nullptr);
+  S.st = st;
   return M355_OK;
 }
 
 static int decode_post(m355_ctx* c, Resident& r, DecodeState& S, bool filters = true)
 {
-  struct StreamRestore { m355_ctx* c; DecodeState& S; ~StreamRestore() { if (S.swapped) c->stream = S.saved_stream; } } restore{c, S};
   const DevPic& d = S.d;
   const bool want_sao = S.want_sao;
   hipEvent_t* ev = S.ev;
@@ -388,24 +400,21 @@ static int decode_post(m355_ctx* c, Resident& r, DecodeState& S, bool filters = 
   const bool hbd = pp.bit_depth_luma > 8;
   const bool piped = c->depth >= 2;
   Frame* dstf = get_frame(c, r.hdr.dst_frame);
-  hipStream_t st = c->stream;
+  const hipStream_t st = S.st;
   const bool deblock = filters && (c->stages & M355_STAGE_DEBLOCK) && (pp.flags & M355_PF_DEBLOCK_ENABLED);
   /* (the horizontal-edge pass inside the SAO kernel was built, is bit-exact on hardware and loses: C5 0.357 -> 0.392 ms per picture,
      SAO 50 -> 104 us for 24 us less deblocking — profiles/r05_a_switches_fuse_dbh.txt, tools/experiments/sao_fused_deblock_h.patch) */
   if (deblock) m355_launch_deblock(d, hbd, st);
   if (ev) hipEventRecord(ev[5], st);
-  if (filters && want_sao) { dst_hazards(c, dstf, piped); m355_launch_sao(d, hbd, st); }
+  if (filters && want_sao) { dst_hazards(c, dstf, piped, st); m355_launch_sao(d, hbd, st); }
   if (ev) hipEventRecord(ev[6], st);
   /* ONE mark behind the decode's last kernel for everything that has to know when it is over: the lists' arenas, the destination
      frame's next reader / writer, the reference frames' next writer, the lane's next decode, the status slot */
-  EvRef done;
   {
-    const int rcm = ev_mark(c, st, &done);
+    const int rcm = mark_done(c, r, dstf, st);
     if (rcm) return rcm;
   }
-  r.done = done; r.fresh = false;
-  dstf->wr_stream = st;
-  dstf->wr = done;
+  const EvRef done = r.done;
   for (int i = 0; i < M355_MAX_REF_FRAMES; i++) {
     Frame* f = r.hdr.ref_frames[i] >= 0 ? get_frame(c, r.hdr.ref_frames[i]) : nullptr;
     if (f) f->rd[c->active] = done;
@@ -425,12 +434,11 @@ static int decode_post(m355_ctx* c, Resident& r, DecodeState& S, bool filters = 
     s.done = done;
     if (r.device_validate) {
       if (!c->status_words) HIPCHK(hipHostMalloc(&c->status_words, 16 * M355_STATUS_RING, hipHostMallocDefault));
-      hipMemcpyAsync(c->status_words + 4 * (c->serial % M355_STATUS_RING), c->timeout, 16, hipMemcpyDeviceToHost, st);
+      hipMemcpyAsync(c->status_words + 4 * (c->serial % M355_STATUS_RING), lane(c).timeout, 16, hipMemcpyDeviceToHost, st);
       const int rcm = ev_mark(c, st, &s.done);
       if (rcm) return rcm;
     }
   }
-  c->last = done; c->last_stream = st;                       /* (the lane's next decode may run on the lane's other stream) */
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(M355_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e));
   {
@@ -439,7 +447,7 @@ static int decode_post(m355_ctx* c, Resident& r, DecodeState& S, bool filters = 
     if (dbg) {
       hipStreamSynchronize(st);
       uint32_t t = 0;
-      hipMemcpy(&t, c->timeout, 4, hipMemcpyDeviceToHost);
+      hipMemcpy(&t, lane(c).timeout, 4, hipMemcpyDeviceToHost);
       if (t) fprintf(stderr, "m355: decode %llu (epoch %u, %d pbs, %d ibs, %d cus, lane %d): intra wait gave up\n", c->serial, d.epoch, d.n_pbs, d.n_ibs, d.n_cus, c->active);
     }
   }
@@ -448,9 +456,8 @@ static int decode_post(m355_ctx* c, Resident& r, DecodeState& S, bool filters = 
 
 int decode(m355_ctx* c, Resident& r, bool rotate) {
   DecodeState S;
-  int rc = decode_pre(c, r, rotate, S, PRE_ALL);
-  if (rc) { if (S.swapped) c->stream = S.saved_stream; return rc; }
-  return decode_post(c, r, S);
+  const int rc = decode_pre(c, r, rotate, S, PRE_ALL);
+  return rc ? rc : decode_post(c, r, S);
 }
 
 /* status of one finished decode from its ring slot: M355_OK, or M355_ERR_INVALID with the rejected record in the message */
@@ -527,12 +534,11 @@ int m355_decode_batch(m355_ctx* c, const int* handles, int n)
   for (int k = 0; k < n; k++) {
     Resident& r = c->resident[handles[k]];
     const int rc = decode_pre(c, r, true, S[k], bs ? PRE_HAZARDS : PRE_NO_INTRA, bs);
-    if (S[k].swapped) { c->stream = S[k].saved_stream; S[k].swapped = false; }   /* (select_lane parks c->stream with the lane) */
     if (rc) { rc_late = rc; break; }                 /* the pictures in front of it are finished as a shorter batch */
     lane[k] = c->active;
     if (!bs) {
       if (!c->batch_ev_pre[k] && hipEventCreateWithFlags(&c->batch_ev_pre[k], hipEventDisableTiming) != hipSuccess) return fail(M355_ERR_HIP, "hipEventCreate failed");
-      hipEventRecord(c->batch_ev_pre[k], c->stream);
+      hipEventRecord(c->batch_ev_pre[k], S[k].st);
     }
     n_ok++;
   }
@@ -546,8 +552,7 @@ int m355_decode_batch(m355_ctx* c, const int* handles, int n)
     HIPCHK(hipEventCreateWithFlags(&b.ev, hipEventDisableTiming));
   }
   if (b.pending) { hipEventSynchronize(b.ev); b.pending = false; }     /* (M355_BATCH_RING batches ago) */
-  select_lane(c, lane[0]);
-  hipStream_t st0 = bs ? bs : c->stream;
+  const hipStream_t st0 = S[0].st;                   /* the batch's stream, or the first lane's */
   int max_work = 0; long total = 0;
   for (int k = 0; k < n_ok; k++) {
     b.host[k] = S[k].d;
@@ -588,18 +593,14 @@ int m355_decode_batch(m355_ctx* c, const int* handles, int n)
     }
     if (dbk) m355_launch_deblock_batch(HostBatch{b.host, b.dev, n_ok, dbk}, hbd, st0);
     if (sao) {
-      hipStream_t keep = c->stream;
-      c->stream = bs;
-      for (int k = 0; k < n_ok; k++) if ((sao >> k) & 1u) dst_hazards(c, get_frame(c, c->resident[handles[k]].hdr.dst_frame), c->depth >= 2);
-      c->stream = keep;
+      for (int k = 0; k < n_ok; k++) if ((sao >> k) & 1u) dst_hazards(c, get_frame(c, c->resident[handles[k]].hdr.dst_frame), c->depth >= 2, bs);
       m355_launch_sao_batch(HostBatch{b.host, b.dev, n_ok, sao}, hbd, st0);
     }
     hipEventRecord(b.ev, st0);     /* the filter launches read the slot's records too: the slot is free behind THEM */
   }
   for (int k = 0; k < n_ok; k++) {
     select_lane(c, lane[k]);
-    if (bs) { S[k].saved_stream = c->stream; c->stream = bs; S[k].swapped = true; }      /* (decode_post puts the lane's stream back) */
-    else if (k) hipStreamWaitEvent(c->stream, b.ev, 0);
+    if (!bs && k) hipStreamWaitEvent(S[k].st, b.ev, 0);
     const int rc = decode_post(c, c->resident[handles[k]], S[k], !bs);
     if (rc && !rc_late) rc_late = rc;
   }

@@ -168,22 +168,21 @@ struct Resident {
   std::vector<uint32_t> sched_order, sched_cand, sched_bucket, sched_u32b;   /* ... and of the work list (order, counting-sort buckets, plan bases) */
 };
 
-/* Everything ONE picture in flight writes: streams, working planes, metadata / job / residual scratch.  The context's
- * own fields of the same names are the ACTIVE lane; select_lane() exchanges them with a parked copy, so all the code
- * below keeps addressing c->stream, c->work, c->resbuf ... (m355_set_pipeline_depth(ctx, n) decodes consecutive
- * pictures round-robin on n lanes: the dependency-bound tail of one picture's intra stage and its filters overlap
- * the next picture's prediction; frame hazards are ordered with per-frame events). */
+/* Everything ONE picture in flight writes: streams, working planes, metadata / job / residual scratch.  The context holds
+ * M355_MAX_LANES of them and addresses the active one as lane(c) (m355_set_pipeline_depth(ctx, n) decodes consecutive pictures
+ * round-robin on n lanes: the dependency-bound tail of one picture's intra stage and its filters overlap the next picture's
+ * prediction; frame hazards are ordered with per-frame events). */
 struct Lane {
-  hipStream_t stream = nullptr, stream2 = nullptr;
+  hipStream_t stream = nullptr, stream2 = nullptr;   /* stream2: metadata planes are rasterised on it while k_inter / k_residual run */
   hipEvent_t ev_fork = nullptr, ev_fork2 = nullptr, ev_join = nullptr;
   /* intra pictures on lanes 3.. run on a stream of the lane's priority class (own hardware queues, lane_class below); the lane's
      scratch is shared by both streams: a decode waits for the lane's previous one when that ran on the other stream */
   hipStream_t stream_hi = nullptr, last_stream = nullptr;
   EvRef last;                  /* behind the lane's last decode */
-  Frame work;
+  Frame work;                  /* pre-SAO working planes */
   uint32_t *pb_of = nullptr, *ticket = nullptr, *timeout = nullptr;
   unsigned long long* edge = nullptr;   /* k_intra halo granules */
-  uint8_t *edge_tu = nullptr, *cuf = nullptr;
+  uint8_t *edge_tu = nullptr, *cuf = nullptr;   /* edge_tu also holds edge_pb and cb_cu (one allocation) */
   int16_t* resbuf = nullptr;
   uint32_t* jobs = nullptr;
   uint16_t* sao_nb = nullptr;
@@ -194,14 +193,9 @@ struct Lane {
 
 struct m355_ctx {
   int device = 0;
-  Lane lanes[M355_MAX_LANES];  /* parked lanes; lanes[active] is stale: the active lane lives in the fields below */
+  Lane lanes[M355_MAX_LANES];
   int depth = 1, active = 0;   /* pipeline depth, index of the active lane */
   std::vector<std::pair<uint32_t, uint32_t*>> inter_tabs;   /* k_inter_jobs' tap tables per (plane type, bit depths): m355_inter_tables */
-  hipStream_t stream = nullptr;
-  hipStream_t stream2 = nullptr;           /* side stream: metadata planes are rasterised while k_inter / k_residual run */
-  hipEvent_t ev_fork = nullptr, ev_fork2 = nullptr, ev_join = nullptr;
-  hipStream_t stream_hi = nullptr, last_stream = nullptr;   /* (of the active lane, as in Lane) */
-  EvRef last;
   /* the ring of marks (EvRef): a slot is taken over M355_EV_RING marks later, behind a host wait for its old mark — so "the slot
      carries another ticket" means "that mark has passed" */
   struct EvSlot { hipEvent_t ev = nullptr; unsigned long long ticket = 0; };
@@ -219,17 +213,6 @@ struct m355_ctx {
   Resident transient[M355_TRANSIENT_MAX];
   int next_transient = 0;
   int transient_ring() const { return 3; }
-  Frame work;                  /* pre-SAO working planes */
-  /* scratch */
-  uint32_t *pb_of = nullptr, *ticket = nullptr, *timeout = nullptr;
-  unsigned long long* edge = nullptr;   /* k_intra halo granules */
-  uint8_t *edge_tu = nullptr, *cuf = nullptr;   /* edge_tu also holds edge_pb and cb_cu (one allocation) */
-  int16_t* resbuf = nullptr;
-  uint32_t* jobs = nullptr;
-  uint16_t* sao_nb = nullptr;
-  uint16_t* iplan = nullptr;
-  uint32_t* job_base = nullptr;
-  size_t cap_cb = 0, cap_u4 = 0, cap_edge = 0, cap_cuf = 0, cap_res = 0, cap_jobs = 0, cap_sao = 0, cap_iplan = 0, cap_jobbase = 0;
   uint32_t epoch = 0;
   /* per-decode status (m355_decode_status): the last M355_STATUS_RING decodes; a device-validated decode copies its lane's gate
      words into `words` (pinned) behind its last kernel */
@@ -268,9 +251,8 @@ struct m355_ctx {
   struct ScanCache { int ctbW = 0, ctbH = 0, ntc = 0, ntr = 0; decltype(m355_pic_params::col_bd) col_bd; decltype(m355_pic_params::row_bd) row_bd;
                      std::vector<uint32_t> ctb_ts, ts2rs; std::vector<uint16_t> tile_id; } scan;
 };
-
-#define LANE_FIELDS(X) X(stream) X(stream2) X(stream_hi) X(last_stream) X(last) X(ev_fork) X(ev_fork2) X(ev_join) X(work) X(pb_of) X(edge) X(ticket) X(timeout) X(edge_tu) X(cuf) \
-  X(resbuf) X(jobs) X(sao_nb) X(iplan) X(job_base) X(cap_jobbase) X(cap_iplan) X(cap_cb) X(cap_u4) X(cap_edge) X(cap_cuf) X(cap_res) X(cap_jobs) X(cap_sao)
+static inline Lane& lane(m355_ctx* c) { return c->lanes[c->active]; }   /* the lane the next decode / phase / transfer addresses */
+static inline void select_lane(m355_ctx* c, int index) { c->active = index; }
 
 /* ---- shared between the parts ---- */
 struct TileRect { int x0, y0, x1, y1; };   /* luma samples */
@@ -316,7 +298,7 @@ extern "C" {
 void clear_target(m355_ctx* c, const DevPic& d, Frame* tgt, bool gated, hipStream_t st);
 int copy_tiles(m355_ctx* c, const m355_pic_params& pp, Frame* f, int k0, int k1, int skip, int nranks, char* xbuf, size_t slot, bool to_slot);
 int decode(m355_ctx* c, Resident& r, bool rotate = true);
-void dst_hazards(m355_ctx* c, Frame* dstf, bool piped);
+void dst_hazards(m355_ctx* c, Frame* dstf, bool piped, hipStream_t st);
 int ev_mark(m355_ctx* c, hipStream_t st, EvRef* out);
 hipError_t ev_query(m355_ctx* c, const EvRef& r);
 hipError_t ev_sync(m355_ctx* c, const EvRef& r);
@@ -325,10 +307,10 @@ Frame* get_frame(m355_ctx* c, int h);
 void halo_layout(const m355_pic_params& pp, HaloLayout& h);
 int lane_class_priority(int index);
 int lane_priorities_mode();
-void launch_prediction(m355_ctx* c, const Resident& r, const DevPic& d, bool hbd, hipEvent_t* ev, bool with_intra = true, hipStream_t chain = nullptr, Frame* hazard_dst = nullptr);
+hipStream_t launch_prediction(m355_ctx* c, const Resident& r, const DevPic& d, bool hbd, hipStream_t st, hipEvent_t* ev, bool with_intra = true, hipStream_t chain = nullptr, Frame* hazard_dst = nullptr);
 void make_layout(const m355_arena_caps& k, int nCtb, int halo_units, bool sharded, bool with_ib_input, Lay& L);
-int prepare(m355_ctx* c, Resident& r, DevPic& d_out, bool& want_sao_out);
-void select_lane(m355_ctx* c, int lane);
+int mark_done(m355_ctx* c, Resident& r, Frame* dstf, hipStream_t st);
+int prepare(m355_ctx* c, Resident& r, DevPic& d_out, bool& want_sao_out, hipStream_t st);
 size_t slot_bytes(const m355_pic_params& pp, int nranks);
 int status_of(m355_ctx* c, m355_ctx::Status& s);
 hipError_t sync_all(m355_ctx* c);

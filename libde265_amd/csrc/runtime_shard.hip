@@ -56,38 +56,23 @@ int m355_decode_phase(m355_ctx* c, int h, int phase, void* xbuf)
      exchange of this picture against it while other pictures' phases run on the other lanes. */
   const bool piped = c->depth >= 2;
   if (phase == 0) { if (piped) select_lane(c, (c->active + 1) % c->depth); r.lane = c->active; }
-  else if (r.lane != c->active) select_lane(c, r.lane);
-  hipStream_t st = c->stream;
+  else select_lane(c, r.lane);
+  Lane& L = lane(c);
+  const hipStream_t st = L.stream;
   const m355_pic_params& pp = r.hdr.pp;
   const bool hbd = pp.bit_depth_luma > 8;
   const size_t meta_bytes = (size_t)r.halo.n_units * 16;
   if (phase == 0) {
-    int rc = prepare(c, r, r.live, r.live_sao);
+    int rc = prepare(c, r, r.live, r.live_sao, st);
     if (rc) return rc;
     r.live_valid = true;
   }
   const DevPic& d = r.live;
   const bool deblock = (c->stages & M355_STAGE_DEBLOCK) && (pp.flags & M355_PF_DEBLOCK_ENABLED);
   Frame* dstf = get_frame(c, r.hdr.dst_frame);
-  auto dst_hazards = [&]() {     /* as in decode(): right before the first write of the destination frame */
-    if (dstf->dl_pending) hipStreamWaitEvent(st, dstf->ev_dl, 0);
-    if (!piped) return;
-    ev_wait(c, st, dstf->wr);
-    for (int k = 0; k < M355_MAX_LANES; k++) ev_wait(c, st, dstf->rd[k]);
-  };
-  auto dst_written = [&]() -> int {
-    EvRef done;
-    const int rcm = ev_mark(c, st, &done);                   /* one mark: the lists, the lane, the destination frame */
-    if (rcm) return rcm;
-    r.done = done; r.fresh = false;
-    dstf->wr_stream = st;
-    c->last = done; c->last_stream = st;
-    dstf->wr = done;
-    return M355_OK;
-  };
   switch (phase) {
     case 0: {
-      ev_wait(c, st, c->last);                               /* the lane's scratch and working planes (decode()) */
+      ev_wait(c, st, L.last);                                /* the lane's scratch and working planes (decode()) */
       /* the exchange buffers of m355_decode_sharded belong to the handle, not to a lane: a second decode of the same lists
          starts behind the last unpack of the one before */
       if (r.xb[0]) ev_wait(c, st, r.done);
@@ -95,9 +80,9 @@ int m355_decode_phase(m355_ctx* c, int h, int phase, void* xbuf)
         ev_wait(c, st, r.up);
       }
       if (r.device_validate) m355_launch_validate(d, st);
-      if (!r.live_sao) dst_hazards();
-      if (pp.flags & M355_PF_CLEAR_DST) clear_target(c, d, r.live_sao ? &c->work : dstf, r.device_validate && !r.live_sao, st);
-      launch_prediction(c, r, d, hbd, nullptr);
+      if (!r.live_sao) dst_hazards(c, dstf, piped, st);     /* (as in decode(): right before the first write of the destination frame) */
+      if (pp.flags & M355_PF_CLEAR_DST) clear_target(c, d, r.live_sao ? &L.work : dstf, r.device_validate && !r.live_sao, st);
+      launch_prediction(c, r, d, hbd, st, nullptr);
       if (piped) {    /* the reference frames are not read after this phase */
         EvRef read;
         bool marked = false;
@@ -123,19 +108,19 @@ int m355_decode_phase(m355_ctx* c, int h, int phase, void* xbuf)
       break;
     case 3: {
       m355_launch_halo_unpack(d, r.halo, hbd, 3, r.xprev, nullptr, st);
-      if (r.live_sao) { dst_hazards(); m355_launch_sao(d, hbd, st); }
+      if (r.live_sao) { dst_hazards(c, dstf, piped, st); m355_launch_sao(d, hbd, st); }
       if (r.shard_n > 1) {     /* (a single rank owns every tile: nothing to hand to anybody) */
         int rc = copy_tiles(c, pp, dstf, r.shard_rank, r.shard_rank + 1, -1, r.shard_n, (char*)xbuf, slot_bytes(pp, r.shard_n), true);
         if (rc) return rc;
       }
-      int rc = dst_written();    /* a non-reference picture ends here: its tiles stay where they were decoded */
+      int rc = mark_done(c, r, dstf, st);    /* a non-reference picture ends here: its tiles stay where they were decoded */
       if (rc) return rc;
       break;
     }
     case 4: {
       int rc = copy_tiles(c, pp, dstf, 0, r.shard_n, r.shard_rank, r.shard_n, (char*)r.xprev, slot_bytes(pp, r.shard_n), false);
       if (rc) return rc;
-      rc = dst_written();
+      rc = mark_done(c, r, dstf, st);
       if (rc) return rc;
       r.live_valid = false;
       break;
@@ -189,7 +174,7 @@ static int shard_buffers(m355_ctx* c, int h)
     if (b < 0) return M355_ERR_INVALID;
     r.xb_bytes[k] = (size_t)b;
     HIPCHK(hipMalloc(&r.xb[k], (size_t)b + 256));
-    HIPCHK(hipMemsetAsync(r.xb[k], 0, (size_t)b + 256, c->stream));
+    HIPCHK(hipMemsetAsync(r.xb[k], 0, (size_t)b + 256, lane(c).stream));
     if (k < 3) mx = std::max(mx, (size_t)b);
   }
   int peers[256];
@@ -200,7 +185,7 @@ static int shard_buffers(m355_ctx* c, int h)
   { static std::atomic<unsigned long long> epochs{0}; r.xb_epoch = ++epochs; }
   r.xscratch_pitch = (mx + 255) & ~(size_t)255;
   if (np) HIPCHK(hipMalloc(&r.xscratch, (r.xscratch_pitch + 256) * (size_t)np));
-  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipStreamSynchronize(lane(c).stream));
   return M355_OK;
 }
 
@@ -226,9 +211,9 @@ int m355_decode_sharded(m355_ctx* c, int h, int gather)
       if (N <= 1 || k >= last) continue;                       /* a single rank owns every tile: nothing to exchange */
       c->xchg_h = h; c->xchg_k = k;
       if (k < 3) {
-        if (!r.peers.empty() && (rc = c->comm.halo_sum(c->comm.user, r.xb[k], r.xb_bytes[k], r.peers.data(), (int)r.peers.size(), r.xscratch, (void*)c->stream)))
+        if (!r.peers.empty() && (rc = c->comm.halo_sum(c->comm.user, r.xb[k], r.xb_bytes[k], r.peers.data(), (int)r.peers.size(), r.xscratch, (void*)lane(c).stream)))
           return ipc ? rc : fail(M355_ERR_HIP, "halo exchange %d failed (%d)", k, rc);      /* (the interprocess transport has said what failed) */
-      } else if ((rc = c->comm.all_gather(c->comm.user, r.xb[3], r.xb_bytes[3] / (size_t)N, r.shard_rank, N, (void*)c->stream)))
+      } else if ((rc = c->comm.all_gather(c->comm.user, r.xb[3], r.xb_bytes[3] / (size_t)N, r.shard_rank, N, (void*)lane(c).stream)))
         return ipc ? rc : fail(M355_ERR_HIP, "tile all-gather failed (%d)", rc);
     }
     return M355_OK;
@@ -248,21 +233,22 @@ int m355_shard_time_exchange(m355_ctx* c, int h, int which, int iters, float* ms
   if (r.shard_n <= 1) return M355_OK;
   hipSetDevice(c->device);
   HIPCHK(sync_all(c));
+  const hipStream_t st = lane(c).stream;
   hipEvent_t e0, e1;
   HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
   auto once = [&]() -> int {
     c->xchg_h = h; c->xchg_k = which;
     int rc1 = 0;
-    if (which < 3) rc1 = r.peers.empty() ? 0 : c->comm.halo_sum(c->comm.user, r.xb[which], r.xb_bytes[which], r.peers.data(), (int)r.peers.size(), r.xscratch, (void*)c->stream);
-    else rc1 = c->comm.all_gather(c->comm.user, r.xb[3], r.xb_bytes[3] / (size_t)r.shard_n, r.shard_rank, r.shard_n, (void*)c->stream);
+    if (which < 3) rc1 = r.peers.empty() ? 0 : c->comm.halo_sum(c->comm.user, r.xb[which], r.xb_bytes[which], r.peers.data(), (int)r.peers.size(), r.xscratch, (void*)st);
+    else rc1 = c->comm.all_gather(c->comm.user, r.xb[3], r.xb_bytes[3] / (size_t)r.shard_n, r.shard_rank, r.shard_n, (void*)st);
     return c->ipc ? ipc_end_picture(c, rc1) : rc1;         /* (the interprocess transport counts every exchange round as a picture of its own) */
   };
   int rc = 0;
   for (int i = 0; i < 2 && !rc; i++) rc = once();
-  hipEventRecord(e0, c->stream);
+  hipEventRecord(e0, st);
   for (int i = 0; i < iters && !rc; i++) rc = once();
-  hipEventRecord(e1, c->stream);
-  hipError_t he = hipStreamSynchronize(c->stream);
+  hipEventRecord(e1, st);
+  hipError_t he = hipStreamSynchronize(st);
   float ms = 0.f;
   if (he == hipSuccess) hipEventElapsedTime(&ms, e0, e1);
   hipEventDestroy(e0); hipEventDestroy(e1);
@@ -607,14 +593,15 @@ int m355_shard_rccl_selftest(m355_ctx* c, size_t words)
   HIPCHK(hipMalloc(&gat, bytes * (size_t)N + 256));
   std::vector<uint32_t> h(words), back(words * (size_t)N);
   for (size_t i = 0; i < words; i++) h[i] = val(me, i);
+  const hipStream_t st = lane(c).stream;
   int rc = M355_OK;
   do {
     if (hipMemcpy(buf, h.data(), bytes, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(gat + words * (size_t)me, h.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) { rc = fail(M355_ERR_HIP, "copy failed"); break; }
-    int e = rccl_halo_sum(c, buf, bytes, peers.data(), (int)peers.size(), scratch, (void*)c->stream);
+    int e = rccl_halo_sum(c, buf, bytes, peers.data(), (int)peers.size(), scratch, (void*)st);
     if (e) { rc = fail(M355_ERR_HIP, "halo exchange over RCCL failed (%d)", e); break; }
-    e = rccl_all_gather(c, gat, bytes, me, N, (void*)c->stream);
+    e = rccl_all_gather(c, gat, bytes, me, N, (void*)st);
     if (e) { rc = fail(M355_ERR_HIP, "ncclAllGather failed (%d)", e); break; }
-    if (hipStreamSynchronize(c->stream) != hipSuccess) { rc = fail(M355_ERR_HIP, "the exchange did not complete: %s", hipGetErrorString(hipGetLastError())); break; }
+    if (hipStreamSynchronize(st) != hipSuccess) { rc = fail(M355_ERR_HIP, "the exchange did not complete: %s", hipGetErrorString(hipGetLastError())); break; }
     if (hipMemcpy(h.data(), buf, bytes, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(back.data(), gat, bytes * (size_t)N, hipMemcpyDeviceToHost) != hipSuccess) { rc = fail(M355_ERR_HIP, "copy failed"); break; }
     for (size_t i = 0; i < words && !rc; i++) {
       uint32_t want = val(me, i);

@@ -988,12 +988,12 @@ int upload(m355_ctx* c, Resident& r, const m355_picture* pic) {
       const bool used = i < ns && seg[i].bytes && i != L.i_ibin;
       const size_t b = used ? seg[i].ofs : 0, e = used ? seg[i].ofs + seg[i].bytes : 0;
       if (used && run_e > run_b && b - run_e <= 4096) { run_e = e; continue; }      /* small gap: one copy */
-      if (run_e > run_b) HIPCHK(hipMemcpyAsync(r.dev + run_b, r.host + run_b, run_e - run_b, hipMemcpyHostToDevice, c->stream));
+      if (run_e > run_b) HIPCHK(hipMemcpyAsync(r.dev + run_b, r.host + run_b, run_e - run_b, hipMemcpyHostToDevice, lane(c).stream));
       run_b = b; run_e = e;
     }
   }
   {
-    const int rcm = ev_mark(c, c->stream, &r.up);  /* a decode on another lane continues behind the copy of the lists */
+    const int rcm = ev_mark(c, lane(c).stream, &r.up);  /* a decode on another lane continues behind the copy of the lists */
     if (rcm) return rcm;
   }
 
