@@ -8,7 +8,7 @@
  *   work lists  : the PODs of include/de265_mi355x.h, uploaded verbatim (SoA per list);
  *   metadata    : per-min-CB CU index plane, per-4x4 transform/prediction edge bytes and PB index
  *                 plane — rasterised on the device from the CU / TU-leaf / PB lists (k_meta.hip);
- *   residuals   : int16, one contiguous nT*nT tile per deferred (intra) block.
+ *   residuals   : int16 (int32 at 16 bits per sample, m355_res32), one contiguous nT*nT tile per deferred (intra) block.
  */
 #ifndef M355_K_COMMON_H
 #define M355_K_COMMON_H
@@ -252,6 +252,11 @@ static inline bool m355_inter_uses_jobs(const DevPic& p)
   return p.pp.chroma_format_idc <= 1 && bdmax <= 12 && p.pw[0] >= 16 && (p.pp.chroma_format_idc == 0 || p.pw[1] >= 8);
 }
 
+/* deferred residuals (intra blocks) as int32: at 16 bits per sample |r| > 32767 changes Clip(pred + r), so an int16 entry is not the sum the reference
+   adds (transform_add / add_residual take the untruncated value).  k_residual stores them and k_intra reads them in their W16 instantiations, which only
+   such pictures take; the buffer holds res_len int32 entries then.  Every narrower picture keeps the int16 entries. */
+template <class PP> __host__ __device__ static inline bool m355_res32(const PP& pp) { return pp.bit_depth_luma >= 16 || pp.bit_depth_chroma >= 16; }
+
 #define M355_TILE_COPY_RECTS 48
 struct TileCopyArgs { char* plane[3]; size_t pitch[3]; TileCopyRect r[M355_TILE_COPY_RECTS]; };
 void m355_launch_tiles_copy(const TileCopyArgs& a, int n, void* xbuf, bool to_slot, hipStream_t st);
@@ -305,7 +310,7 @@ void m355_launch_residual_batch(const HostBatch& b, bool hbd, bool big, hipStrea
 void m355_launch_intra_plan_batch(const HostBatch& b, hipStream_t st);
 void m355_launch_deblock_batch(const HostBatch& b, bool hbd, hipStream_t st);
 void m355_launch_sao_batch(const HostBatch& b, bool hbd, hipStream_t st);
-void m355_launch_intra_batch(const DevPic& first, bool hbd, const DevPic* dev_pics, int n, int max_work, uint32_t* ticket, int grid, hipStream_t st);   /* intra pictures of one geometry in ONE launch */
+void m355_launch_intra_batch(const DevPic& first, bool hbd, bool res32, const DevPic* dev_pics, int n, int max_work, uint32_t* ticket, int grid, hipStream_t st);   /* intra pictures of one geometry in ONE launch */
 void m355_launch_deblock(const DevPic& p, bool hbd, hipStream_t st);
 void m355_launch_deblock_pass(const DevPic& p, bool hbd, bool vertical, hipStream_t st);   /* one direction (tile sharding) */
 void m355_launch_sao(const DevPic& p, bool hbd, hipStream_t st);

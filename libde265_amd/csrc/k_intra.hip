@@ -113,7 +113,7 @@ template <int CF> __global__ void __launch_bounds__(256) k_tu_plan(DevPic p, int
 #ifndef M355_INTRA_SPARSE_WAVES_PER_EU
 #define M355_INTRA_SPARSE_WAVES_PER_EU 6   /* (the register budget of an inter picture's kernel at 4:2:0 / 4:0:0: 6 -> 80 registers and one spilled pair = 6 workgroups per CU, C5's intra stage 0.0467 -> 0.0424 ms, C3 / C4 unchanged: profiles/r05_v22_intra_w6_ab.txt; 4 -> 96 registers = 5 workgroups; 4:2:2 / 4:4:4 are bounded by their LDS) */
 #endif
-template <class PIX, int CF, int NW, bool DENSE, bool BATCH>
+template <class PIX, int CF, int NW, bool DENSE, bool BATCH, bool W16>
 __global__ void __launch_bounds__(64 * NW) M355_WAVES_PER_EU((DENSE || CF >= 2) ? 4 : M355_INTRA_SPARSE_WAVES_PER_EU) k_intra(DevPic p0, int work_n, const DevPic* __restrict__ pics, int n_pics, uint32_t* batch_ticket)
 {
   if (!BATCH) M355_GATE(p0);
@@ -137,6 +137,9 @@ __global__ void __launch_bounds__(64 * NW) M355_WAVES_PER_EU((DENSE || CF >= 2) 
   __shared__ uint32_t s_need[3][MAXCTB];         /* per component and CTB row, which 8-sample vectors some block's border reads */
   __shared__ uint32_t s_cover[3][MAXCTB / 4];    /* per component and row of 4x4 units, which units an intra block of this CTB writes */
   __shared__ uint32_t s_hneed[3][8];             /* ... and which halo entries (bit h: top entries 0 .. 2cw, then the left column) */
+  /* (W16: bit hi = halo[hi] was read from the picture and is final — at 16 bits a sample may equal HALO_NOT_READY, and such an entry has no granule
+     to poll: it would spin to the bound) */
+  __shared__ uint32_t s_hfinal[W16 ? 3 : 1][W16 ? (HALO_N + 31) / 32 : 1];
   /* the halo keeper's slots (below): granule address and halo element per lane and slot */
   __shared__ uint32_t s_kp_idx[(DENSE && NW == M355_INTRA_KEEPER_NW) ? 5 * 64 : 1];      /* (an index into DevPic.edge: the load stays a GLOBAL one — a pointer out of LDS makes it flat, and a flat load also counts as an LDS operation, which the wave waits for in front of every barrier) */
   __shared__ uint16_t s_kp_h1[(DENSE && NW == M355_INTRA_KEEPER_NW) ? 5 * 64 : 1];
@@ -208,6 +211,10 @@ __global__ void __launch_bounds__(64 * NW) M355_WAVES_PER_EU((DENSE || CF >= 2) 
   const int cw = (1 << l2c) >> csw, ch = (1 << l2c) >> csh;
   const int x0c = (ctbX << l2c) >> csw, y0c = (ctbY << l2c) >> csh;
   const int bd = (c && comp) ? p.pp.bit_depth_chroma : p.pp.bit_depth_luma;
+  /* 16 bits per sample (W16, k_common.h m355_res32): a block's residual is read from the buffer's int32 entries where it is added, not staged in the
+     16-bit body */
+  const bool res32 = W16 && m355_res32(p.pp);
+  const int32_t* res32buf = (const int32_t*)p.resbuf;
   const int cs = comp ? c : 0;
   PIX* plane = (PIX*)p.plane[cs];
   const int stride = p.stride[cs], pw = p.pw[cs], ph = p.ph[cs];
@@ -287,7 +294,7 @@ __global__ void __launch_bounds__(64 * NW) M355_WAVES_PER_EU((DENSE || CF >= 2) 
      disjoint, the staging below leaves covered units alone, a border entry only ever points at a sample that has been
      reconstructed — and the lane that predicts a sample reads its residual from the element it then overwrites.  Two blocks at a
      time (4 samples = one row segment per lane and step, up to four steps per block): their loads are in flight together. ---- */
-  {
+  if (!res32) {
     int taken = 0;                                           /* blocks of this component seen so far (wave-uniform) */
     for (uint32_t kbase = 0; kbase < ctbinfo.ib_count; kbase += 64) {
       uint32_t rw0 = rf0, rw1 = rf1, rw2 = rf2;
@@ -350,6 +357,7 @@ __global__ void __launch_bounds__(64 * NW) M355_WAVES_PER_EU((DENSE || CF >= 2) 
   if (comp && g == 0) {
     for (int y = lane; y < ch; y += 64) s_need[cs][y] = 0;
     if (lane < 8) s_hneed[cs][lane] = 0;
+    if (W16 && lane < (HALO_N + 31) / 32) s_hfinal[W16 ? cs : 0][lane] = 0;
     if (lane == 0) halo[HALO_N] = (uint16_t)(1u << (bd - 1));   /* the constant cell */
     if (lane < MAXCTB / 4) s_cover[cs][lane] = 0;
     wave_sync();
@@ -470,6 +478,10 @@ __global__ void __launch_bounds__(64 * NW) M355_WAVES_PER_EU((DENSE || CF >= 2) 
       uint32_t val = hpl[u];
       if (hintra[u]) val = ((uint32_t)(hgr[u] >> 32) == epoch && !p.test_halo_late) ? (uint32_t)((hgr[u] >> (16 * ((htop[u] ? hx[u] : hy[u]) & 1))) & 0xFFFFu) : HALO_NOT_READY;
       if (htop[u]) halo[h] = (uint16_t)val; else halo[HALO_TOP_N + h - (2 * cw + 1)] = (uint16_t)val;
+      if (W16 && !hintra[u] && val == HALO_NOT_READY) {
+        const int hi = htop[u] ? h : HALO_TOP_N + h - (2 * cw + 1);
+        atomicOr(&s_hfinal[W16 ? cs : 0][hi >> 5], 1u << (hi & 31));
+      }
     }
   }
   __syncthreads();     /* bodies, halos, residuals and the plan staged */
@@ -637,6 +649,7 @@ __global__ void __launch_bounds__(64 * NW) M355_WAVES_PER_EU((DENSE || CF >= 2) 
       uint32_t bv0 = 0;
       int rs0 = 0;
       if (__builtin_expect(d_small, 1)) { bv0 = body[code0]; rs0 = (int)(int16_t)body[d_baddr]; }
+      if (res32 && d_small && (e0 & M355_IBX_HAS_RES)) rs0 = lane < (1 << (2 * d_log2)) ? res32buf[e1 + lane] : 0;   /* (lane = y * nT + x) */
       const int log2 = d_log2, nT = 1 << log2, cls = d_cls, angle = d_angle, inv = d_inv;
       const int mode = (int)((e0 >> 19) & 63u);
       const bool vert = mode >= 18;
@@ -656,7 +669,8 @@ __global__ void __launch_bounds__(64 * NW) M355_WAVES_PER_EU((DENSE || CF >= 2) 
         rs = rs0 & (has_res ? -1 : 0);
         if (__builtin_expect(__any((int)(bv == HALO_NOT_READY)), 0)) {
           /* a halo sample its CTB has not published yet: poll its granule */
-          const bool pending = bv == HALO_NOT_READY && code0 >= (uint32_t)HALO_BASE && code0 < (uint32_t)(HALO_BASE + HALO_N);
+          bool pending = bv == HALO_NOT_READY && code0 >= (uint32_t)HALO_BASE && code0 < (uint32_t)(HALO_BASE + HALO_N);
+          if (W16 && pending) pending = !((s_hfinal[W16 ? cs : 0][(code0 - HALO_BASE) >> 5] >> ((code0 - HALO_BASE) & 31)) & 1u);
           if (__any((int)pending))
             bv = d_poll_halo(d_edge_row(p, cs, ctbY - 1, 0), d_edge_col(p, cs, ctbX - 1, 0), p.timeout, halo, (int)code0 - HALO_BASE, bv, pending, x0c, y0c, epoch);
         }
@@ -750,7 +764,8 @@ __global__ void __launch_bounds__(64 * NW) M355_WAVES_PER_EU((DENSE || CF >= 2) 
 #pragma unroll
           for (int q = 0; q < 3; q++) {
             if (64 * q >= nEnt) continue;
-            const bool pending = lane + 64 * q < nEnt && val[q] == HALO_NOT_READY && cd[q] >= (uint32_t)HALO_BASE && cd[q] < (uint32_t)(HALO_BASE + HALO_N);
+            bool pending = lane + 64 * q < nEnt && val[q] == HALO_NOT_READY && cd[q] >= (uint32_t)HALO_BASE && cd[q] < (uint32_t)(HALO_BASE + HALO_N);
+            if (W16 && pending) pending = !((s_hfinal[W16 ? cs : 0][(cd[q] - HALO_BASE) >> 5] >> ((cd[q] - HALO_BASE) & 31)) & 1u);
             if (__any((int)pending))
               val[q] = d_poll_halo(d_edge_row(p, cs, ctbY - 1, 0), d_edge_col(p, cs, ctbX - 1, 0), p.timeout, halo, (int)cd[q] - HALO_BASE, val[q], pending, x0c, y0c, epoch);
           }
@@ -832,6 +847,7 @@ __global__ void __launch_bounds__(64 * NW) M355_WAVES_PER_EU((DENSE || CF >= 2) 
                   ta[u] = BRD(i1); tb[u] = BRD(fa[u] ? i2 : i1);   /* (no read beyond the border when the second tap has weight 0) */
                 }
                 rs[u] = (int)(int16_t)body[d_bofs + y * BODY_PITCH + x] & res_on;
+                if (res32) rs[u] = has_res ? res32buf[e1 + y * nT + x] : 0;
               }
 #pragma unroll
               for (int u = 0; u < 4; u++) {
@@ -924,39 +940,57 @@ __global__ void __launch_bounds__(64 * NW) M355_WAVES_PER_EU((DENSE || CF >= 2) 
 #define M355_INTRA_SPARSE_NW 4    /* inter pictures: up to 2 luma + 1 + 1 chroma waves per CTB */
 #endif
 
-template <class PIX, int CF>
+template <class PIX, int CF, bool W16>
 static void launch_intra_cf(const DevPic& p, bool ticket_zero, hipStream_t st)
 {
   if (!ticket_zero) hipMemsetAsync(p.ticket, 0, 4, st);      /* (an inter picture's k_job_count zeroes it: one packet less) */
   /* dense intra pictures: 12 waves (up to 8 luma + 2 + 2 chroma blocks of a level at once); sparse ones: 4 (3 and 6 measured
      slower) */
   const dim3 dense_grid(p.intra_grid > 0 && p.intra_grid < p.n_intra_work ? p.intra_grid : p.n_intra_work);
-  if (p.intra_dense && p.intra_keeper) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_intra<PIX, CF, M355_INTRA_KEEPER_NW, true, false>), dense_grid, dim3(64 * M355_INTRA_KEEPER_NW), 0, st, p, p.n_intra_work, (const DevPic*)nullptr, 1, (uint32_t*)nullptr);
-  else if (p.intra_dense) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_intra<PIX, CF, M355_INTRA_DENSE_NW, true, false>), dense_grid, dim3(64 * M355_INTRA_DENSE_NW), 0, st, p, p.n_intra_work, (const DevPic*)nullptr, 1, (uint32_t*)nullptr);
-  else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_intra<PIX, CF, M355_INTRA_SPARSE_NW, false, false>), dim3(p.n_intra_work), dim3(64 * M355_INTRA_SPARSE_NW), 0, st, p, p.n_intra_work, (const DevPic*)nullptr, 1, (uint32_t*)nullptr);
+  if (p.intra_dense && p.intra_keeper) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_intra<PIX, CF, M355_INTRA_KEEPER_NW, true, false, W16>), dense_grid, dim3(64 * M355_INTRA_KEEPER_NW), 0, st, p, p.n_intra_work, (const DevPic*)nullptr, 1, (uint32_t*)nullptr);
+  else if (p.intra_dense) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_intra<PIX, CF, M355_INTRA_DENSE_NW, true, false, W16>), dense_grid, dim3(64 * M355_INTRA_DENSE_NW), 0, st, p, p.n_intra_work, (const DevPic*)nullptr, 1, (uint32_t*)nullptr);
+  else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_intra<PIX, CF, M355_INTRA_SPARSE_NW, false, false, W16>), dim3(p.n_intra_work), dim3(64 * M355_INTRA_SPARSE_NW), 0, st, p, p.n_intra_work, (const DevPic*)nullptr, 1, (uint32_t*)nullptr);
 }
 
 void m355_launch_intra(const DevPic& p, bool hbd, hipStream_t st, bool ticket_zero)
 {
   if (!p.n_intra_work) return;
+  if (hbd && m355_res32(p.pp)) {
+    switch (p.pp.chroma_format_idc) {
+      case 0: launch_intra_cf<uint16_t, 0, true>(p, ticket_zero, st); break;
+      case 1: launch_intra_cf<uint16_t, 1, true>(p, ticket_zero, st); break;
+      case 2: launch_intra_cf<uint16_t, 2, true>(p, ticket_zero, st); break;
+      default: launch_intra_cf<uint16_t, 3, true>(p, ticket_zero, st); break;
+    }
+    return;
+  }
   switch (p.pp.chroma_format_idc) {
-    case 0: if (hbd) launch_intra_cf<uint16_t, 0>(p, ticket_zero, st); else launch_intra_cf<uint8_t, 0>(p, ticket_zero, st); break;
-    case 1: if (hbd) launch_intra_cf<uint16_t, 1>(p, ticket_zero, st); else launch_intra_cf<uint8_t, 1>(p, ticket_zero, st); break;
-    case 2: if (hbd) launch_intra_cf<uint16_t, 2>(p, ticket_zero, st); else launch_intra_cf<uint8_t, 2>(p, ticket_zero, st); break;
-    default: if (hbd) launch_intra_cf<uint16_t, 3>(p, ticket_zero, st); else launch_intra_cf<uint8_t, 3>(p, ticket_zero, st); break;
+    case 0: if (hbd) launch_intra_cf<uint16_t, 0, false>(p, ticket_zero, st); else launch_intra_cf<uint8_t, 0, false>(p, ticket_zero, st); break;
+    case 1: if (hbd) launch_intra_cf<uint16_t, 1, false>(p, ticket_zero, st); else launch_intra_cf<uint8_t, 1, false>(p, ticket_zero, st); break;
+    case 2: if (hbd) launch_intra_cf<uint16_t, 2, false>(p, ticket_zero, st); else launch_intra_cf<uint8_t, 2, false>(p, ticket_zero, st); break;
+    default: if (hbd) launch_intra_cf<uint16_t, 3, false>(p, ticket_zero, st); else launch_intra_cf<uint8_t, 3, false>(p, ticket_zero, st); break;
   }
 }
 
 /* several intra pictures of one geometry in ONE launch (k_intra<BATCH>): first = the pictures' common parameters, dev_pics = their
    DevPic records in device memory, ticket = a zeroed word of its own, grid = persistent workgroups */
-template <class PIX, int CF>
+template <class PIX, int CF, bool W16 = false>
 static void launch_intra_batch_cf(const DevPic& first, const DevPic* dev_pics, int n, int max_work, uint32_t* ticket, int grid, hipStream_t st)
 {
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_intra<PIX, CF, M355_INTRA_DENSE_NW, true, true>), dim3(grid), dim3(64 * M355_INTRA_DENSE_NW), 0, st, first, max_work, dev_pics, n, ticket);
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_intra<PIX, CF, M355_INTRA_DENSE_NW, true, true, W16>), dim3(grid), dim3(64 * M355_INTRA_DENSE_NW), 0, st, first, max_work, dev_pics, n, ticket);
 }
-void m355_launch_intra_batch(const DevPic& first, bool hbd, const DevPic* dev_pics, int n, int max_work, uint32_t* ticket, int grid, hipStream_t st)
+void m355_launch_intra_batch(const DevPic& first, bool hbd, bool res32, const DevPic* dev_pics, int n, int max_work, uint32_t* ticket, int grid, hipStream_t st)
 {
   if (max_work <= 0 || n <= 0) return;
+  if (hbd && res32) {      /* (some picture of the batch is 16-bit: the W16 kernel decides per picture) */
+    switch (first.pp.chroma_format_idc) {
+      case 0: launch_intra_batch_cf<uint16_t, 0, true>(first, dev_pics, n, max_work, ticket, grid, st); break;
+      case 1: launch_intra_batch_cf<uint16_t, 1, true>(first, dev_pics, n, max_work, ticket, grid, st); break;
+      case 2: launch_intra_batch_cf<uint16_t, 2, true>(first, dev_pics, n, max_work, ticket, grid, st); break;
+      default: launch_intra_batch_cf<uint16_t, 3, true>(first, dev_pics, n, max_work, ticket, grid, st); break;
+    }
+    return;
+  }
   switch (first.pp.chroma_format_idc) {
     case 0: if (hbd) launch_intra_batch_cf<uint16_t, 0>(first, dev_pics, n, max_work, ticket, grid, st); else launch_intra_batch_cf<uint8_t, 0>(first, dev_pics, n, max_work, ticket, grid, st); break;
     case 1: if (hbd) launch_intra_batch_cf<uint16_t, 1>(first, dev_pics, n, max_work, ticket, grid, st); else launch_intra_batch_cf<uint8_t, 1>(first, dev_pics, n, max_work, ticket, grid, st); break;

@@ -22,7 +22,7 @@
    border entry e of a block comes from, substitution already applied. */
 #define HALO_TOP_N (2 * MAXCTB + 2)
 #define HALO_N (HALO_TOP_N + MAXCTB)
-#define HALO_NOT_READY 0xFFFFu       /* (a 16-bit-deep picture may hold this value as a sample: the poll then succeeds at once) */
+#define HALO_NOT_READY 0xFFFFu       /* (a 16-bit-deep picture may hold this value as a sample: from an intra block the poll then succeeds at once, one read from the picture k_intra marks final, s_hfinal) */
 #define COMP_LDS(body) ((body) + HALO_N + 8)   /* elements per component: body + halo + constant cell (+ alignment) */
 
 /* z-scan order inside a CTB (pps.cc:608-623 MinTbAddrZS, low bits): Morton code of the min-TB coordinates */

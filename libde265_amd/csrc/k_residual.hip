@@ -312,7 +312,7 @@ __device__ __forceinline__ void d_res_add_row(M355_GLOBAL PIX* d, uint32_t* w, c
   }
 }
 
-template <int LOG2, class PIX, bool PRE>
+template <int LOG2, class PIX, bool PRE, bool W16 = false>
 __device__ __forceinline__ void d_res_finish(const DevPic& p, const m355_rb* rbs, const m355_rb& rb, bool active, int c, int tbi, uint32_t* cfp, uint32_t* w, const uint32_t* eb)
 {
   constexpr int NT = ResGeom<LOG2, PIX>::NT;
@@ -349,7 +349,14 @@ __device__ __forceinline__ void d_res_finish(const DevPic& p, const m355_rb* rbs
 
   if (!active) return;
   const int y = c;
-  if ((rb.flags & M355_RBF_DEFERRED) || p.res_front) {
+  if (W16 && (rb.flags & M355_RBF_DEFERRED) && m355_res32(p.pp)) {
+    /* 16 bits per sample: the residual as it is (int32 entries, k_intra adds them) — an int16 clip changes pred + r once |r| > 32767.  Only the
+       4x4 DST add clips to int16 in the reference (fallback-dct.cc:269-336); with cross-component prediction it is transform_idst_4x4 + add_residual */
+    int32_t* out = (int32_t*)p.resbuf + rb.res_ofs + y * NT;
+    const bool clip16 = rb.kind == M355_RK_DST && !(p.pp.flags & M355_PF_CROSS_COMPONENT_PRED);
+#pragma unroll
+    for (int i = 0; i < NT; i++) out[i] = clip16 ? d_clip3(-32768, 32767, res[i]) : res[i];
+  } else if ((rb.flags & M355_RBF_DEFERRED) || p.res_front) {
     /* (a chain picture's front launch: the block's tile — found by size bin and index, no offset table — instead of the add) */
     int16_t* out = (rb.flags & M355_RBF_DEFERRED) ? p.resbuf + rb.res_ofs + y * NT : p.res_tiles + p.res_tile_base[LOG2 - 2] + (size_t)tbi * (NT * NT) + y * NT;
 #pragma unroll
@@ -357,7 +364,7 @@ __device__ __forceinline__ void d_res_finish(const DevPic& p, const m355_rb* rbs
   } else d_res_add_row<LOG2, PIX>(d, w, res, bd);
 }
 
-template <int LOG2, class PIX>
+template <int LOG2, class PIX, bool W16>
 __device__ __forceinline__ void d_residual_group(const DevPic& p, const m355_rb* rbs, int rb_n, int group, uint32_t* smem)
 {
   typedef ResGeom<LOG2, PIX> G;
@@ -372,7 +379,7 @@ __device__ __forceinline__ void d_residual_group(const DevPic& p, const m355_rb*
      flight at a loop header */
   uint32_t w[G::NVP], eb[RES_GB];
   d_res_issue<LOG2, PIX, true>(p, rb, active, c, tbi, w, eb);
-  d_res_finish<LOG2, PIX, true>(p, rbs, rb, active, c, tbi, cfp, w, eb);
+  d_res_finish<LOG2, PIX, true, W16>(p, rbs, rb, active, c, tbi, cfp, w, eb);
 }
 
 /* Two launches, issued side by side on the lane's two streams (runtime_decode.hip, launch_prediction): 32x32 + 16x16 blocks (2 / 4 per
@@ -382,7 +389,7 @@ __device__ __forceinline__ void d_residual_group(const DevPic& p, const m355_rb*
 #define RES_LDS_DWORDS_SMALL (8 * RES_WPG * (4 * 8 + 8 * 5))   /* 8x8: 8 blocks per wave (4x4: 16 x 20 dwords fit too) */
 /* blocks per workgroup: RES_WPG waves * 64/nT */
 __host__ __device__ static inline int res_groups(int n, int per_wave) { return (n + per_wave * RES_WPG - 1) / (per_wave * RES_WPG); }
-template <class PIX, bool BIG>
+template <class PIX, bool BIG, bool W16>
 __device__ __forceinline__ void k_residual_body(const DevPic& p, int ng_hi, uint32_t* s_buf, int g = (int)blockIdx.x, const bool xcd_order = false)
 {
   M355_GATE(p);
@@ -401,41 +408,41 @@ __device__ __forceinline__ void k_residual_body(const DevPic& p, int ng_hi, uint
     g = hi ? gg : ng_hi + gg;
   }
   if (BIG) {
-    if (g < ng_hi) d_residual_group<5, PIX>(p, p.rb_bin[3], p.rb_count[3], g, s_buf);
-    else d_residual_group<4, PIX>(p, p.rb_bin[2], p.rb_count[2], g - ng_hi, s_buf);
+    if (g < ng_hi) d_residual_group<5, PIX, W16>(p, p.rb_bin[3], p.rb_count[3], g, s_buf);
+    else d_residual_group<4, PIX, W16>(p, p.rb_bin[2], p.rb_count[2], g - ng_hi, s_buf);
   } else {
-    if (g < ng_hi) d_residual_group<3, PIX>(p, p.rb_bin[1], p.rb_count[1], g, s_buf);
-    else d_residual_group<2, PIX>(p, p.rb_bin[0], p.rb_count[0], g - ng_hi, s_buf);
+    if (g < ng_hi) d_residual_group<3, PIX, W16>(p, p.rb_bin[1], p.rb_count[1], g, s_buf);
+    else d_residual_group<2, PIX, W16>(p, p.rb_bin[0], p.rb_count[0], g - ng_hi, s_buf);
   }
 }
 
-template <class PIX, bool BIG>
+template <class PIX, bool BIG, bool W16>
 __global__ void __launch_bounds__(64 * RES_WPG) __attribute__((amdgpu_waves_per_eu(4))) k_residual(DevPic p, int ng_hi)
 {
   __shared__ __attribute__((aligned(16))) uint32_t s_buf[BIG ? RES_LDS_DWORDS : RES_LDS_DWORDS_SMALL];
-  k_residual_body<PIX, BIG>(p, ng_hi, s_buf, (int)blockIdx.x, true);
+  k_residual_body<PIX, BIG, W16>(p, ng_hi, s_buf, (int)blockIdx.x, true);
 }
 /* BOTH launches as roles of one: workgroups [0, n_big) take the 32x32 + 16x16 groups, the rest the 8x8 + 4x4 groups.  For pictures on a one-stream lane
    (up to 4K: runtime_decode.hip launch_prediction), where the two launches stand one behind the other and neither fills the GPU — the occupancy the
    separate small-block kernel buys (66 registers) is not what a 4K picture's 13 us launch waits for */
-template <class PIX>
+template <class PIX, bool W16>
 __global__ void __launch_bounds__(64 * RES_WPG) __attribute__((amdgpu_waves_per_eu(4))) k_residual_both(DevPic p, int n_big, int ng_hi_big, int ng_hi_small)
 {
   __shared__ __attribute__((aligned(16))) uint32_t s_buf[RES_LDS_DWORDS > RES_LDS_DWORDS_SMALL ? RES_LDS_DWORDS : RES_LDS_DWORDS_SMALL];
   const int g = (int)blockIdx.x;
-  if (g < n_big) k_residual_body<PIX, true>(p, ng_hi_big, s_buf, g);
-  else k_residual_body<PIX, false>(p, ng_hi_small, s_buf, g - n_big);
+  if (g < n_big) k_residual_body<PIX, true, W16>(p, ng_hi_big, s_buf, g);
+  else k_residual_body<PIX, false, W16>(p, ng_hi_small, s_buf, g - n_big);
 }
 /* ... and with them the transform-edge scatter (k_meta_tu.h) and the border plans (k_intra_plan.h), which only k_intra and the deblocking filter read: workgroups
    [n_res, n_res + nb_tu) walk the transform leaves (64 per workgroup), the rest plan work item r / n_parts, part r % n_parts (one wave each).  On a one-stream
    lane they stood as a launch of their own (k_tu_plan) in front of k_inter: 14 us of a 4K picture's 176 */
-template <class PIX, int CF>
+template <class PIX, int CF, bool W16>
 __global__ void __launch_bounds__(64 * RES_WPG) __attribute__((amdgpu_waves_per_eu(4))) k_residual_tu_plan(DevPic p, int n_res, int n_big, int ng_hi_big, int ng_hi_small, int nb_tu, int work_n, int n_parts)
 {
   __shared__ __attribute__((aligned(16))) uint32_t s_buf[RES_LDS_DWORDS > RES_LDS_DWORDS_SMALL ? RES_LDS_DWORDS : RES_LDS_DWORDS_SMALL];
   const int g = (int)blockIdx.x;
-  if (g < n_big) { k_residual_body<PIX, true>(p, ng_hi_big, s_buf, g); return; }
-  if (g < n_res) { k_residual_body<PIX, false>(p, ng_hi_small, s_buf, g - n_big); return; }
+  if (g < n_big) { k_residual_body<PIX, true, W16>(p, ng_hi_big, s_buf, g); return; }
+  if (g < n_res) { k_residual_body<PIX, false, W16>(p, ng_hi_small, s_buf, g - n_big); return; }
   const int q = g - n_res;
   if (q < nb_tu) { k_meta_tu_body(p, q); return; }
   k_intra_plan_body<CF>(p, work_n, (q - nb_tu) / n_parts, (q - nb_tu) % n_parts, n_parts);
@@ -495,23 +502,27 @@ void m355_launch_residual_add(const DevPic& p, bool hbd, hipStream_t st)
 }
 
 /* batch form (intra pictures) */
-template <class PIX, bool BIG>
+template <class PIX, bool BIG, bool W16>
 __global__ void __launch_bounds__(64 * RES_WPG) __attribute__((amdgpu_waves_per_eu(4))) k_residual_batch(DevBatch b)
 {
   __shared__ __attribute__((aligned(16))) uint32_t s_buf[BIG ? RES_LDS_DWORDS : RES_LDS_DWORDS_SMALL];
   M355_BATCH_PIC(b);
-  k_residual_body<PIX, BIG>(p, BIG ? res_groups(p.rb_count[3], 2) : res_groups(p.rb_count[1], 8), s_buf);
+  k_residual_body<PIX, BIG, W16>(p, BIG ? res_groups(p.rb_count[3], 2) : res_groups(p.rb_count[1], 8), s_buf);
 }
 
 template <class PIX, bool BIG>
 static void launch_res_batch(const HostBatch& b, hipStream_t st)
 {
   int n = 0;
+  bool res32 = false;      /* (a batch may mix depths: the W16 kernel decides per picture) */
   for (int k = 0; k < b.n; k++) if ((b.on >> k) & 1u) {
     const DevPic& p = b.host[k];
     n = std::max(n, BIG ? res_groups(p.rb_count[3], 2) + res_groups(p.rb_count[2], 4) : res_groups(p.rb_count[1], 8) + res_groups(p.rb_count[0], 16));
+    res32 = res32 || m355_res32(p.pp);
   }
-  if (n) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_residual_batch<PIX, BIG>), dim3(n, 1, b.n), dim3(64 * RES_WPG), 0, st, DevBatch{b.dev, b.on});
+  if (!n) return;
+  if constexpr (sizeof(PIX) == 2) if (res32) { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_residual_batch<PIX, BIG, true>), dim3(n, 1, b.n), dim3(64 * RES_WPG), 0, st, DevBatch{b.dev, b.on}); return; }
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_residual_batch<PIX, BIG, false>), dim3(n, 1, b.n), dim3(64 * RES_WPG), 0, st, DevBatch{b.dev, b.on});
 }
 void m355_launch_residual_batch(const HostBatch& b, bool hbd, bool big, hipStream_t st)
 {
@@ -523,7 +534,8 @@ template <class PIX, bool BIG>
 static void launch_res(const DevPic& p, int n, int ng_hi, hipStream_t st)
 {
   const dim3 blk(64 * RES_WPG);
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_residual<PIX, BIG>), dim3(n), blk, 0, st, p, ng_hi);
+  if constexpr (sizeof(PIX) == 2) if (m355_res32(p.pp)) { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_residual<PIX, BIG, true>), dim3(n), blk, 0, st, p, ng_hi); return; }
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_residual<PIX, BIG, false>), dim3(n), blk, 0, st, p, ng_hi);
 }
 
 void m355_launch_residual_both(const DevPic& p, bool hbd, hipStream_t st)
@@ -531,19 +543,20 @@ void m355_launch_residual_both(const DevPic& p, bool hbd, hipStream_t st)
   const int ng2 = res_groups(p.rb_count[0], 16), ng3 = res_groups(p.rb_count[1], 8), ng4 = res_groups(p.rb_count[2], 4), ng5 = res_groups(p.rb_count[3], 2);
   const int n = ng5 + ng4 + ng3 + ng2;
   if (!n) return;
-  if (hbd) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_residual_both<uint16_t>), dim3(n), dim3(64 * RES_WPG), 0, st, p, ng5 + ng4, ng5, ng3);
-  else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_residual_both<uint8_t>), dim3(n), dim3(64 * RES_WPG), 0, st, p, ng5 + ng4, ng5, ng3);
+  if (hbd && m355_res32(p.pp)) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_residual_both<uint16_t, true>), dim3(n), dim3(64 * RES_WPG), 0, st, p, ng5 + ng4, ng5, ng3);
+  else if (hbd) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_residual_both<uint16_t, false>), dim3(n), dim3(64 * RES_WPG), 0, st, p, ng5 + ng4, ng5, ng3);
+  else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_residual_both<uint8_t, false>), dim3(n), dim3(64 * RES_WPG), 0, st, p, ng5 + ng4, ng5, ng3);
 }
 
-template <class PIX>
+template <class PIX, bool W16>
 static void launch_res_tu_plan(const DevPic& p, int n_res, int n_big, int ng5, int ng3, int nb_tu, int n_plan, int n_parts, hipStream_t st)
 {
   const dim3 grid(n_res + nb_tu + n_plan * n_parts), blk(64 * RES_WPG);
   switch (p.pp.chroma_format_idc) {
-    case 0: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_residual_tu_plan<PIX, 0>), grid, blk, 0, st, p, n_res, n_big, ng5, ng3, nb_tu, n_plan, n_parts); break;
-    case 1: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_residual_tu_plan<PIX, 1>), grid, blk, 0, st, p, n_res, n_big, ng5, ng3, nb_tu, n_plan, n_parts); break;
-    case 2: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_residual_tu_plan<PIX, 2>), grid, blk, 0, st, p, n_res, n_big, ng5, ng3, nb_tu, n_plan, n_parts); break;
-    default: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_residual_tu_plan<PIX, 3>), grid, blk, 0, st, p, n_res, n_big, ng5, ng3, nb_tu, n_plan, n_parts); break;
+    case 0: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_residual_tu_plan<PIX, 0, W16>), grid, blk, 0, st, p, n_res, n_big, ng5, ng3, nb_tu, n_plan, n_parts); break;
+    case 1: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_residual_tu_plan<PIX, 1, W16>), grid, blk, 0, st, p, n_res, n_big, ng5, ng3, nb_tu, n_plan, n_parts); break;
+    case 2: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_residual_tu_plan<PIX, 2, W16>), grid, blk, 0, st, p, n_res, n_big, ng5, ng3, nb_tu, n_plan, n_parts); break;
+    default: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_residual_tu_plan<PIX, 3, W16>), grid, blk, 0, st, p, n_res, n_big, ng5, ng3, nb_tu, n_plan, n_parts); break;
   }
 }
 /* residuals (both size classes) + transform edges + border plans: the work m355_launch_residual_both and m355_launch_tu_plan (k_intra.hip) do, as one launch */
@@ -555,8 +568,9 @@ void m355_launch_residual_tu_plan(const DevPic& p, bool hbd, hipStream_t st)
   const int n_plan = (p.intra_dense && p.intra_keeper) ? 0 : p.n_intra_work, n_parts = 4 * (p.intra_dense ? PLAN_SPLIT : 1);
   const int nb_tu = (p.n_tus + 64 * RES_WPG - 1) / (64 * RES_WPG);
   if (!(n_res + nb_tu + n_plan)) return;
-  if (hbd) launch_res_tu_plan<uint16_t>(p, n_res, ng5 + ng4, ng5, ng3, nb_tu, n_plan, n_parts, st);
-  else launch_res_tu_plan<uint8_t>(p, n_res, ng5 + ng4, ng5, ng3, nb_tu, n_plan, n_parts, st);
+  if (hbd && m355_res32(p.pp)) launch_res_tu_plan<uint16_t, true>(p, n_res, ng5 + ng4, ng5, ng3, nb_tu, n_plan, n_parts, st);
+  else if (hbd) launch_res_tu_plan<uint16_t, false>(p, n_res, ng5 + ng4, ng5, ng3, nb_tu, n_plan, n_parts, st);
+  else launch_res_tu_plan<uint8_t, false>(p, n_res, ng5 + ng4, ng5, ng3, nb_tu, n_plan, n_parts, st);
 }
 
 void m355_launch_residual(const DevPic& p, bool hbd, bool big, hipStream_t st)

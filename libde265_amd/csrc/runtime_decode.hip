@@ -88,7 +88,7 @@ int prepare(m355_ctx* c, Resident& r, DevPic& d_out, bool& want_sao_out, hipStre
      against 0.470-0.486 one at a time, C3 0.087 against 0.0805 — profiles/r05_h_fused_order_ab.txt — and left the product.) */
   /* behind the intra residuals: room for the residual tiles of every other block, which a dependent chain's picture leaves there in its front part
      (launch_prediction; with three lanes and more) — block i of size bin s at tile_base[s] + i * nT^2 */
-  const size_t res_intra = ((size_t)pic.res_len + 64) & ~(size_t)63;
+  const size_t res_intra = (((size_t)pic.res_len + 64) & ~(size_t)63) * (m355_res32(pp) ? 2 : 1);     /* (int16 units: int32 entries at 16 bits, k_common.h) */
   size_t res_tiles = 0;
   for (int s = 0; s < 4; s++) { d.res_tile_base[s] = (uint32_t)res_tiles; res_tiles += (size_t)pic.rb_count[s] << (2 * (s + 2)); }
   /* (pictures of a one-stream lane only — up to 4K, launch_prediction: an 8K picture's kernels fill the GPU, its transforms gain nothing in front) */
@@ -554,9 +554,11 @@ int m355_decode_batch(m355_ctx* c, const int* handles, int n)
   if (b.pending) { hipEventSynchronize(b.ev); b.pending = false; }     /* (M355_BATCH_RING batches ago) */
   const hipStream_t st0 = S[0].st;                   /* the batch's stream, or the first lane's */
   int max_work = 0; long total = 0;
+  bool res32 = false;
   for (int k = 0; k < n_ok; k++) {
     b.host[k] = S[k].d;
     max_work = std::max(max_work, S[k].d.n_intra_work); total += S[k].d.n_intra_work;
+    res32 = res32 || m355_res32(S[k].d.pp);
     if (k && !bs) hipStreamWaitEvent(st0, c->batch_ev_pre[k], 0);
   }
   hipMemcpyAsync(b.dev, b.host, sizeof(DevPic) * n_ok, hipMemcpyHostToDevice, st0);
@@ -581,7 +583,7 @@ int m355_decode_batch(m355_ctx* c, const int* handles, int n)
     int widest = 0;
     for (int k = 0; k < n_ok; k++) widest += std::min(S[k].d.ctbH, (S[k].d.ctbW + 1) / 2) + 1;
     const int grid = (int)std::min<long>(std::max<long>(total, 1), grid_env > 0 ? grid_env : std::min(slots, n_streams <= 1 ? slots : std::max(widest, slots / (2 * n_streams))));
-    m355_launch_intra_batch(S[0].d, hbd, b.dev, n_ok, max_work, b.ticket, grid, st0);
+    m355_launch_intra_batch(S[0].d, hbd, res32, b.dev, n_ok, max_work, b.ticket, grid, st0);
   }
   hipEventRecord(b.ev, st0); b.pending = true;
   if (bs) {

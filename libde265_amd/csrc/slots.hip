@@ -117,7 +117,8 @@ __global__ void __launch_bounds__(256) ks_transform(int32_t* res, PIX* dst, cons
     int sum = 0;
     for (int j = 0; j < nT; j++) sum += (is_dst ? cs_dst4[j * 4 + i] : s_dct((fact * j) * (2 * i + 1))) * (int)s_g[y * nT + j];
     const int r = (sum + rnd2) >> bdShift;
-    if (dst) dst[o] = (PIX)d_clip_bd((int)dst[o] + r, bd);
+    /* (the 4x4 DST add clips its output to int16 before the add, fallback-dct.cc:327 — a clip that matters at 16 bits only) */
+    if (dst) dst[o] = (PIX)d_clip_bd((int)dst[o] + (is_dst ? d_clip3(-32768, 32767, r) : r), bd);
     else res[o] = r;
   }
 }

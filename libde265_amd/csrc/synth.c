@@ -20,7 +20,7 @@
 
 typedef struct m355_synth_cfg {
   int32_t width, height;
-  int32_t bit_depth;        /* luma = chroma */
+  int32_t bit_depth;        /* luma (and chroma unless bit_depth_chroma says otherwise) */
   int32_t log2_ctb;         /* 4..6 */
   int32_t tile_cols, tile_rows;
   int32_t intra_pct;        /* 100 = intra picture (config C2), else % of CUs coded intra */
@@ -35,6 +35,10 @@ typedef struct m355_synth_cfg {
                                slice when the picture has tiles, arbitrary CTB runs otherwise) */
   int32_t features;         /* M355_SYN_* bits */
   int32_t chroma_format;    /* 0 or 1 = 4:2:0 (default), 2 = 4:2:2, 3 = 4:4:4, 4 = monochrome */
+  /* (appended; 0 = off: the lists are then byte-identical to those of the generator before these fields) */
+  int32_t bit_depth_chroma; /* 0 = same as luma */
+  int32_t qp_wide;          /* QpY uniform over [-QpBdOffsetY, 51] with each block's qP derived as transform.cc:146-181 does (random pic_cb / cr_qp_offset
+                               in -12..12), instead of qP uniform 22..37 */
 } m355_synth_cfg;
 enum { M355_SYN_CONSTRAINED_INTRA = 1, M355_SYN_TRANSQUANT_BYPASS = 2, M355_SYN_SCALING_LIST = 4, M355_SYN_PCM = 8,
        M355_SYN_PCM_LOOP_FILTER_DISABLE = 16, M355_SYN_CROSS_COMPONENT = 32 /* 4:4:4 only */,
@@ -54,12 +58,18 @@ typedef struct gen {
   int cf;                   /* chroma_format_idc of the picture */
   int ctb_has_bypass;       /* a CU of the CTB being generated uses cu_transquant_bypass */
   int cu_bypass;            /* the CU being generated */
+  int bdc;                  /* chroma bit depth */
+  int qp_c[3];              /* qp_wide: qP'Y / qP'Cb / qP'Cr of the CU being generated */
+  int pic_c_off[2];         /* qp_wide: pic_cb_qp_offset / pic_cr_qp_offset */
 } gen;
 
 static uint32_t rnd(gen* g) { uint32_t s = g->s; s ^= s << 13; s ^= s >> 17; s ^= s << 5; g->s = s; return s; }
 static int rbelow(gen* g, int n) { return (int)(rnd(g) % (uint32_t)n); }
 static int rrange(gen* g, int lo, int hi) { return lo + (int)(rnd(g) % (uint32_t)(hi - lo + 1)); }
 static int pct(gen* g, int p) { return rbelow(g, 100) < p; }
+
+/* qP of a transform block: qp_wide as derived by transform.cc:146-181, else the generator's own rule (chroma 3 below luma) */
+static int tb_qp(const gen* g, int cidx, int qp) { return g->cfg->qp_wide ? g->qp_c[cidx] : (cidx ? (qp > 3 ? qp - 3 : qp) : qp); }
 
 static void* vpush(vec* v, size_t esz)
 {
@@ -115,7 +125,7 @@ static int gen_tb(gen* g, int cidx, int x, int y, int log2, int intra, int mode,
   if (!cbf) return 0;
   m355_rb* rb = (m355_rb*)vpush(&g->rbs[log2 - 2], sizeof(m355_rb));
   rb->x = (uint16_t)x; rb->y = (uint16_t)y; rb->cidx = (uint8_t)cidx; rb->log2_size = (uint8_t)log2;
-  rb->qp = (uint8_t)(cidx ? (qp > 3 ? qp - 3 : qp) : qp);
+  rb->qp = (uint8_t)tb_qp(g, cidx, qp);
   rb->kind = (intra && cidx == 0 && log2 == 2) ? M355_RK_DST : M355_RK_DCT;
   if (log2 == 2 && rbelow(g, 20) == 0) rb->kind = M355_RK_SKIP;   /* transform_skip is Main profile for 4x4 */
   if ((g->cfg->features & M355_SYN_RDPCM) && rbelow(g, 4) == 0) rb->kind = M355_RK_SKIP;   /* log2_max_transform_skip_block_size up to 5 (RExt) */
@@ -192,7 +202,7 @@ static void gen_tu(gen* g, int x, int y, int log2, int intra, int lmode, int cmo
         /* gen_tb pushed no block (cbf 0): list an empty one.  For intra blocks gen_tb has pushed the ib already. */
         m355_rb* rb = (m355_rb*)vpush(&g->rbs[log2 - 2], sizeof(m355_rb));
         rb->x = (uint16_t)x; rb->y = (uint16_t)y; rb->cidx = (uint8_t)c; rb->log2_size = (uint8_t)log2;
-        rb->qp = (uint8_t)(qp > 3 ? qp - 3 : qp); rb->kind = g->cu_bypass ? M355_RK_BYPASS : M355_RK_DCT;
+        rb->qp = (uint8_t)tb_qp(g, c, qp); rb->kind = g->cu_bypass ? M355_RK_BYPASS : M355_RK_DCT;
         rb->coeff_ofs = (uint32_t)g->coeffs.n; rb->ncoeff = 0;
         if (g->cfg->features & M355_SYN_SCALING_LIST) rb->matrix_id = (uint8_t)((log2 == 5 ? 0 : c) + (intra ? 0 : (log2 < 5 ? 3 : 1)));
         if (intra) {
@@ -250,15 +260,15 @@ static void gen_pb(gen* g, int x, int y, int w, int h)
   if (pct(g, c->weighted_pct)) {
     pb->flags |= M355_PBF_WEIGHTED;
     const int denom_l = rbelow(g, 8), denom_c = rbelow(g, 8);
-    const int shift1 = 14 - c->bit_depth < 2 ? 2 : 14 - c->bit_depth;
+    const int shift1 = 14 - c->bit_depth < 2 ? 2 : 14 - c->bit_depth, shift1c = 14 - g->bdc < 2 ? 2 : 14 - g->bdc;
     for (int l = 0; l < 2; l++) {
       m355_wt* wt = (m355_wt*)vpush(&g->wts, sizeof(m355_wt));
       pb->wt_idx[l] = (uint16_t)((g->wts.n - 1) & 0xFFFF);
       for (int k = 0; k < 3; k++) {
         wt->w[k] = (int16_t)((1 << (k ? denom_c : denom_l)) + rrange(g, -128, 127));
-        wt->o[k] = (int16_t)(rrange(g, -128, 127) * (1 << (c->bit_depth - 8)));
+        wt->o[k] = (int16_t)(rrange(g, -128, 127) * (1 << ((k ? g->bdc : c->bit_depth) - 8)));
       }
-      wt->log2wd_luma = (uint8_t)(denom_l + shift1); wt->log2wd_chroma = (uint8_t)(denom_c + shift1);
+      wt->log2wd_luma = (uint8_t)(denom_l + shift1); wt->log2wd_chroma = (uint8_t)(denom_c + shift1c);
     }
     if (g->wts.n > 65000) { pb->flags &= (uint8_t)~M355_PBF_WEIGHTED; g->wts.n -= 2; }
   }
@@ -269,7 +279,19 @@ static void gen_cu(gen* g, int x, int y, int log2)
   const m355_synth_cfg* c = g->cfg;
   m355_cu* cu = (m355_cu*)vpush(&g->cus, sizeof(m355_cu));
   const int intra = c->n_refs == 0 || pct(g, c->intra_pct);
-  const int qp = rrange(g, 22, 37);
+  const int qp = c->qp_wide ? rrange(g, -6 * (c->bit_depth - 8), 51) : rrange(g, 22, 37);
+  if (c->qp_wide) {
+    /* transform.cc:146-181 (no slice / CU chroma offsets): qP'Y = QpY + QpBdOffsetY; chroma through table 8-22 in 4:2:0, clipped, + QpBdOffsetC */
+    static const int tab8_22[13] = {29, 30, 31, 32, 33, 33, 34, 34, 35, 35, 36, 36, 37};
+    const int qpbd_c = 6 * (g->bdc - 8);
+    g->qp_c[0] = qp + 6 * (c->bit_depth - 8);
+    for (int k = 0; k < 2; k++) {
+      int qpi = qp + g->pic_c_off[k];
+      qpi = qpi < -qpbd_c ? -qpbd_c : (qpi > 57 ? 57 : qpi);
+      const int qpc = g->cf != 1 ? qpi : (qpi < 30 ? qpi : (qpi >= 43 ? qpi - 6 : tab8_22[qpi - 30]));
+      g->qp_c[1 + k] = qpc + qpbd_c < 0 ? 0 : qpc + qpbd_c;
+    }
+  }
   const int size = 1 << log2;
   cu->x = (uint16_t)x; cu->y = (uint16_t)y; cu->log2_size = (uint8_t)log2; cu->qp_y = (int8_t)qp;
   g->cu_bypass = (c->features & M355_SYN_TRANSQUANT_BYPASS) && rbelow(g, 12) == 0;
@@ -282,12 +304,13 @@ static void gen_cu(gen* g, int x, int y, int log2)
       /* square raw blocks: 4:2:2 chroma (half width, full height) is two stacked squares */
       const int subw = (cidx && (g->cf == 1 || g->cf == 2)) ? 1 : 0, subh = (cidx && g->cf == 1) ? 1 : 0;
       const int l2 = log2 - subw, nblk = (subw && !subh) ? 2 : 1, n = 1 << (2 * l2);
-      const int pcm_bits = c->bit_depth - rbelow(g, 3);           /* PcmBitDepth <= BitDepth: samples << (BitDepth - PcmBitDepth) */
+      const int bdk = cidx ? g->bdc : c->bit_depth;
+      const int pcm_bits = bdk - rbelow(g, 3);                    /* PcmBitDepth <= BitDepth: samples << (BitDepth - PcmBitDepth) */
       for (int b = 0; b < nblk; b++) {
         m355_ib* ib = (m355_ib*)vpush(&g->ibs, sizeof(m355_ib));
         ib->x = (uint16_t)(x >> subw); ib->y = (uint16_t)((y >> subh) + b * (1 << l2)); ib->cidx = (uint8_t)cidx; ib->log2_size = (uint8_t)l2;
         ib->mode = 1; ib->flags = M355_IBF_PCM; ib->res_ofs = (uint32_t)g->pcm.n;
-        for (int i = 0; i < n; i++) *(uint16_t*)vpush(&g->pcm, 2) = (uint16_t)(rbelow(g, 1 << pcm_bits) << (c->bit_depth - pcm_bits));
+        for (int i = 0; i < n; i++) *(uint16_t*)vpush(&g->pcm, 2) = (uint16_t)(rbelow(g, 1 << pcm_bits) << (bdk - pcm_bits));
       }
     }
     m355_tu* tu = (m355_tu*)vpush(&g->tus, sizeof(m355_tu));
@@ -366,9 +389,14 @@ __attribute__((visibility("default"))) int m355_synth_picture(const m355_synth_c
   m355_pic_params* pp = &pic->pp;
   g.cf = cfg->chroma_format == 0 ? 1 : (cfg->chroma_format == 4 ? 0 : cfg->chroma_format);
   pp->width = cfg->width; pp->height = cfg->height; pp->chroma_format_idc = (uint8_t)g.cf;
-  pp->bit_depth_luma = pp->bit_depth_chroma = (uint8_t)cfg->bit_depth;
+  g.bdc = cfg->bit_depth_chroma ? cfg->bit_depth_chroma : cfg->bit_depth;
+  pp->bit_depth_luma = (uint8_t)cfg->bit_depth; pp->bit_depth_chroma = (uint8_t)g.bdc;
   pp->log2_ctb_size = (uint8_t)cfg->log2_ctb; pp->log2_min_tb_size = 2; pp->log2_min_cb_size = 3;
   pp->pic_cb_qp_offset = 1; pp->pic_cr_qp_offset = -1;
+  if (cfg->qp_wide) {
+    g.pic_c_off[0] = rrange(&g, -12, 12); g.pic_c_off[1] = rrange(&g, -12, 12);
+    pp->pic_cb_qp_offset = (int8_t)g.pic_c_off[0]; pp->pic_cr_qp_offset = (int8_t)g.pic_c_off[1];
+  }
   pp->flags = M355_PF_STRONG_INTRA_SMOOTHING | (cfg->sao ? M355_PF_SAO_ENABLED : 0) | (cfg->deblock ? M355_PF_DEBLOCK_ENABLED : 0) |
               (cfg->lf_across_tiles ? M355_PF_LF_ACROSS_TILES : 0) |
               ((cfg->features & M355_SYN_CONSTRAINED_INTRA) ? M355_PF_CONSTRAINED_INTRA_PRED : 0) |
@@ -432,8 +460,8 @@ __attribute__((visibility("default"))) int m355_synth_picture(const m355_synth_c
             ctb->sao_type = (uint8_t)(typ_l | (typ_c << 2) | (typ_c << 4));
             const int cl = tl >= 2 ? tl - 2 : 0, cc = tc >= 2 ? tc - 2 : 0;
             ctb->sao_eo_class = (uint8_t)(cl | (cc << 2) | (cc << 4));
-            const int lim = cfg->bit_depth <= 8 ? 7 : 31;
             for (int k = 0; k < 3; k++) {
+              const int lim = (k ? g.bdc : cfg->bit_depth) <= 8 ? 7 : 31;
               ctb->sao_band_pos[k] = (uint8_t)rbelow(&g, 32);
               for (int j = 0; j < 4; j++) ctb->sao_offset[k][j] = (int8_t)rrange(&g, -lim, lim);
             }

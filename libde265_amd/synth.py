@@ -16,7 +16,8 @@ class SynthCfg(ctypes.Structure):
                 ("width", "height", "bit_depth", "log2_ctb", "tile_cols", "tile_rows", "intra_pct", "bipred_pct",
                  "weighted_pct", "oob_mv_pct", "cbf_pct", "deblock", "sao", "n_refs", "lf_across_tiles")] + \
                [("seed", ctypes.c_uint32), ("fixed_cu_log2", ctypes.c_int32), ("n_slices", ctypes.c_int32),
-                ("features", ctypes.c_int32), ("chroma_format", ctypes.c_int32)]
+                ("features", ctypes.c_int32), ("chroma_format", ctypes.c_int32),
+                ("bit_depth_chroma", ctypes.c_int32), ("qp_wide", ctypes.c_int32)]   # (appended, 0 = off: csrc/synth.c)
 
 SYN_CONSTRAINED_INTRA, SYN_TRANSQUANT_BYPASS, SYN_SCALING_LIST, SYN_PCM, SYN_PCM_LOOP_FILTER_DISABLE, SYN_CROSS_COMPONENT = 1, 2, 4, 8, 16, 32   # SynthCfg.features bits (csrc/synth.c)
 SYN_RDPCM, SYN_ROTATE, SYN_MISSING_REF, SYN_DEQUANTIZED = 64, 128, 256, 512
@@ -75,7 +76,7 @@ CONFIGS = {
 def make_cfg(**kw):
     d = dict(width=416, height=240, bit_depth=8, log2_ctb=6, tile_cols=1, tile_rows=1, intra_pct=10, bipred_pct=50,
              weighted_pct=10, oob_mv_pct=2, cbf_pct=60, deblock=1, sao=1, n_refs=2, lf_across_tiles=1, seed=1,
-             fixed_cu_log2=0, n_slices=0, features=0, chroma_format=0)
+             fixed_cu_log2=0, n_slices=0, features=0, chroma_format=0, bit_depth_chroma=0, qp_wide=0)
     d.update(kw)
     c = SynthCfg()
     for k, v in d.items():
@@ -121,13 +122,15 @@ def picture(**kw):
     return p
 
 
-def ref_planes(seed, width, height, chroma_format_idc, bit_depth):
+def ref_planes(seed, width, height, chroma_format_idc, bit_depth, bit_depth_chroma=None):
+    """bit_depth_chroma: the chroma planes' depth (default: bit_depth); samples are uint16 unless the luma depth is 8."""
+    bdc = bit_depth if bit_depth_chroma is None else bit_depth_chroma
     out = []
     for c, (w, h) in enumerate(worklist.plane_dims(width, height, chroma_format_idc)):
         if w == 0:
             continue
         a = np.zeros((h, w), np.uint8 if bit_depth <= 8 else np.uint16)
-        _lib().m355_synth_ref_plane((seed * 3 + c + 1) & 0xFFFFFFFF, w, h, bit_depth, a.ctypes.data)
+        _lib().m355_synth_ref_plane((seed * 3 + c + 1) & 0xFFFFFFFF, w, h, bdc if c else bit_depth, a.ctypes.data)
         out.append(a)
     return out
 

@@ -482,7 +482,7 @@ typedef struct pic_state {
   uint8_t* edge;              /* per 4x4: bit0 TU-edge V, bit1 TU-edge H, bit2 PB-edge V, bit3 PB-edge H, bit4 nonzero */
   uint32_t* pb_of;            /* per 4x4: index into pbs[] (+1; 0 = none) */
   uint8_t* bs;                /* per 4x4 boundary strength of the current pass */
-  int16_t* resbuf;
+  int32_t* resbuf;            /* deferred residuals of intra blocks (int32: exact at 16 bits) */
 } pic_state;
 
 enum { E_TU_V = 1, E_TU_H = 2, E_PB_V = 4, E_PB_H = 8, E_NONZERO = 16 };
@@ -537,7 +537,7 @@ static int build_state(pic_state* s) {
   s->edge = (uint8_t*)calloc((size_t)s->w4 * s->h4, 1);
   s->pb_of = (uint32_t*)calloc((size_t)s->w4 * s->h4, 4);
   s->bs = (uint8_t*)calloc((size_t)s->w4 * s->h4, 1);
-  s->resbuf = (int16_t*)calloc((size_t)pic->res_len + 1, 2);
+  s->resbuf = (int32_t*)calloc((size_t)pic->res_len + 1, 4);
   /* 6.5.1 (pps.cc:589-606) */
   uint32_t ts = 0; int tidx = 0;
   for (int ty = 0; ty < pp->num_tile_rows; ty++)
@@ -713,7 +713,11 @@ static void do_residual(pic_state* s) {
       }
     }
     if (rb->flags & M355_RBF_DEFERRED) {
-      for (int k = 0; k < nT * nT; k++) s->resbuf[rb->res_ofs + k] = (int16_t)clip3(-32768, 32767, r[k]);
+      /* the reference adds an intra block's residual as it comes out of the transform (transform_add, add_residual: int32), except
+         the 4x4 DST add, which clips it to int16 first (fallback-dct.cc:269-336) — a clip that matters at 16 bits per sample only.
+         With cross-component prediction the DST goes through transform_idst_4x4 + add_residual (transform.cc:611-616): no clip. */
+      const int clip16 = rb->kind == M355_RK_DST && !(pp->flags & M355_PF_CROSS_COMPONENT_PRED);
+      for (int k = 0; k < nT * nT; k++) s->resbuf[rb->res_ofs + k] = clip16 ? clip3(-32768, 32767, r[k]) : r[k];
     } else {
       uint16_t* d = s->dst->p[rb->cidx] + (ptrdiff_t)rb->y * s->dst->stride[rb->cidx] + rb->x;
       add_res(d, s->dst->stride[rb->cidx], 2, r, nT, bd);
@@ -840,7 +844,7 @@ static void do_intra_block(pic_state* s, const m355_ib* ib) {
     o_intra_pred_angular(dstp, stride, 2, bd, (ib->flags & M355_IBF_DISABLE_BOUNDARY_FILTER) != 0, ib->mode, nT, c,
                          border);
   if (ib->flags & M355_IBF_HAS_RESIDUAL) {
-    const int16_t* r = s->resbuf + ib->res_ofs;
+    const int32_t* r = s->resbuf + ib->res_ofs;
     for (int y = 0; y < nT; y++)
       for (int x = 0; x < nT; x++) dstp[y * stride + x] = (uint16_t)clip_bd(dstp[y * stride + x] + r[y * nT + x], bd);
   }

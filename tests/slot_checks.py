@@ -12,7 +12,7 @@ from util import XorShift32, pixel_dtype, ptr, ptr_at
 
 
 def _bds(quick):
-    return [8, 10] if quick else [8, 9, 10, 12]
+    return [8, 10] if quick else [8, 9, 10, 12, 14, 16]
 
 
 def check_weighted(tab, oracle, quick):

@@ -10,7 +10,7 @@ def make_case(**cfgkw):
     pp = pic.pp[0]
     n_refs = pic.meta["cfg"]["n_refs"]
     refs = [synth.ref_planes(pic.meta["cfg"]["seed"] + 17 * i, int(pp["width"]), int(pp["height"]),
-                             int(pp["chroma_format_idc"]), int(pp["bit_depth_luma"])) for i in range(n_refs)]
+                             int(pp["chroma_format_idc"]), int(pp["bit_depth_luma"]), int(pp["bit_depth_chroma"])) for i in range(n_refs)]
     return pic, refs
 
 

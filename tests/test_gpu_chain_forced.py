@@ -130,6 +130,8 @@ elif what == "suites":
     ctx = capi.Context(lib, 0)
     cases = [("small %%d" %% i, c) for i, c in enumerate(SMALL)] + [(n, dict(synth.CONFIGS[n])) for n in ("c2_1080p_intra", "c3_4k_inter", "c4_4k_4tiles", "c5_8k10_8tiles")]
     cases += [("random %%d" %% s, random_case(s)) for s in range(50)]
+    from test_gpu_depths import CHAIN_CASES           # 15 bits (front-part residuals, packed SAO) and 16 (neither; int32 deferred residuals)
+    cases += [("depths %%d" %% i, c) for i, c in enumerate(CHAIN_CASES)]
     n = 0
     for name, case in cases:
         try:

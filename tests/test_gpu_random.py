@@ -51,9 +51,20 @@ def random_case(seed):
                 features=feats, chroma_format=cf, seed=9000 + seed)
 
 
-@pytest.mark.parametrize("seed", range(200))
-def test_random_pictures_bit_exact(ctx, oracle, seed):
+def random_case_deep(seed):
+    """seeds 200 on: random_case's draws, then every bit depth 8..16, luma and chroma apart (never 8-bit beside a deeper one, which
+    m355_frame_create refuses), and QpY over [-QpBdOffsetY, 51] half the time"""
     case = random_case(seed)
+    rng = np.random.default_rng(17000 + seed)
+    bd = int(rng.integers(8, 17))
+    bdc = bd if bd == 8 or rng.random() < 0.5 else int(rng.integers(9, 17))
+    case.update(bit_depth=bd, bit_depth_chroma=bdc, qp_wide=int(rng.random() < 0.5))
+    return case
+
+
+@pytest.mark.parametrize("seed", range(240))
+def test_random_pictures_bit_exact(ctx, oracle, seed):
+    case = random_case(seed) if seed < 200 else random_case_deep(seed)
     try:
         pic, refs = make_case(**case)
     except RuntimeError as e:              # a combination the generator does not build (it says so) is not a test failure

@@ -11,7 +11,7 @@ import pytest
 
 from util import XorShift32, pixel_dtype, ptr, ptr_at
 
-BIT_DEPTHS = [8, 9, 10, 12]
+BIT_DEPTHS = [8, 9, 10, 12, 14, 16]
 
 
 def coeff_scenarios(rng, n, scenario):

@@ -1,7 +1,7 @@
 """Second pin of the CPU oracle: whole synthetic pictures replayed through the REAL reference functions
 (oracle/ref_replay.cc -> generate_inter_prediction_samples, scale_coefficients, decode_intra_prediction,
 apply_deblocking_filter, apply_sample_adaptive_offset_sequential of /root/reference, scalar AND SSE/AVX tables)
-must equal oracle/hevc_oracle.c bit for bit — tiles with and without filtering across them, 8/10/12-bit, CTB
+must equal oracle/hevc_oracle.c bit for bit — tiles with and without filtering across them, 8..16-bit (luma and chroma apart too), CTB
 16/32/64, every CU/TU size, explicit weights, MVs far outside the picture, transform skip, intra-only pictures,
 several slices with their own filter flags, constrained intra prediction, cu_transquant_bypass, scaling lists.
 (The first pin is the recorded girlshy stream, tests/test_girlshy_oracle.py.)  Needs oracle/_ref (built from
@@ -64,11 +64,43 @@ CASES = [
     # blocks that carry already-scaled levels (M355_RBF_DEQUANTIZED): the reference entered below its dequantiser
     dict(width=256, height=192, bit_depth=8, seed=131, features=512, intra_pct=30, cbf_pct=90),
     dict(width=256, height=192, bit_depth=10, seed=132, features=512 + 64 + 128, intra_pct=50, cbf_pct=90),
+] + [
+    # bit depths 11 and 13..16 (the oracle's deferred residuals: int16 only while a sample needs no more than 15 bits), each with
+    # an all-intra picture and a mixed one carrying residuals in every block, the residual tools, PCM and scaling lists, the other chroma
+    # formats, weights and out-of-picture vectors, and QpY over the whole range the depth allows (qp_wide)
+    dict(width=128, height=64, bit_depth=bd, seed=1000 + 10 * bd + k, **kw) for bd in (11, 13, 14, 15, 16) for k, kw in enumerate([
+        dict(intra_pct=100, n_refs=0, cbf_pct=100),
+        dict(intra_pct=50, cbf_pct=100, weighted_pct=30, oob_mv_pct=20),
+        dict(intra_pct=50, cbf_pct=90, features=64 + 128 + 2),
+        dict(intra_pct=60, features=8 + 16 + 4, n_slices=2),
+        dict(intra_pct=40, cbf_pct=100, chroma_format=2, features=31),
+        dict(intra_pct=30, cbf_pct=100, chroma_format=3, features=32 + 2),
+        dict(intra_pct=50, cbf_pct=100, chroma_format=4),
+        dict(intra_pct=50, cbf_pct=100, qp_wide=1, features=4),
+        dict(intra_pct=100, n_refs=0, cbf_pct=100, qp_wide=1, chroma_format=3, features=32),
+    ])
+] + [
+    # luma and chroma of different depths: k_inter_jobs with unequal tables (10/12), k_inter_generic (12/13, 16/9), 4:4:4 with
+    # cross-component prediction (whose (rY << BitDepthC) >> BitDepthY scales between the two)
+    dict(width=128, height=64, bit_depth=10, bit_depth_chroma=12, seed=1201, intra_pct=30, cbf_pct=100, weighted_pct=30, oob_mv_pct=10),
+    dict(width=128, height=64, bit_depth=12, bit_depth_chroma=9, seed=1202, intra_pct=30, cbf_pct=100, chroma_format=3, features=32 + 2),
+    dict(width=128, height=64, bit_depth=9, bit_depth_chroma=12, seed=1203, intra_pct=30, cbf_pct=100, chroma_format=3, features=32 + 8),
+    dict(width=128, height=64, bit_depth=12, bit_depth_chroma=13, seed=1204, intra_pct=30, cbf_pct=100, weighted_pct=30, qp_wide=1),
+    dict(width=128, height=64, bit_depth=16, bit_depth_chroma=9, seed=1205, intra_pct=50, cbf_pct=100, chroma_format=2, qp_wide=1),
+    dict(width=128, height=64, bit_depth=9, bit_depth_chroma=16, seed=1206, intra_pct=100, n_refs=0, cbf_pct=100, chroma_format=3, features=32),
+    # qp_wide at the usual depths: negative QpY at 9 / 10 / 12 bits, chroma through table 8-22 with picture offsets
+    dict(width=128, height=64, bit_depth=10, seed=1207, intra_pct=30, cbf_pct=100, qp_wide=1, n_slices=2),
+    dict(width=128, height=64, bit_depth=12, seed=1208, intra_pct=100, n_refs=0, cbf_pct=100, qp_wide=1, features=64 + 2),
 ]
 STAGES = [W.STAGE_ALL, W.STAGE_INTER | W.STAGE_RESIDUAL | W.STAGE_INTRA, W.STAGE_ALL & ~W.STAGE_SAO, W.STAGE_INTER]
 
 
-@pytest.mark.parametrize("case", CASES, ids=lambda c: "%dx%d_%dbit_seed%d" % (c["width"], c["height"], c["bit_depth"], c["seed"]))
+def case_id(c):
+    bd = "%d" % c["bit_depth"] + ("_%d" % c["bit_depth_chroma"] if c.get("bit_depth_chroma") else "")
+    return "%dx%d_%sbit_seed%d" % (c["width"], c["height"], bd, c["seed"])
+
+
+@pytest.mark.parametrize("case", CASES, ids=case_id)
 def test_oracle_equals_reference_replay(oracle, ref, case):
     o = Oracle(oracle)
     pic, refs = make_case(**case)
