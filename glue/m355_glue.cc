@@ -126,7 +126,10 @@ enum { FEAT_PCM_CU, FEAT_WEIGHTED_PB, FEAT_BYPASS_RB, FEAT_SKIP_RB, FEAT_RDPCM_R
        FEAT_MULTI_SLICE_PIC, FEAT_WEIGHTED_PB_LATER_SLICE, FEAT_NO_BOUNDARY_FILTER_IB, FEAT_FILL_PB, FEAT_CHROMA_422_RB, FEAT_CHROMA_444_RB,
        FEAT_MONO_PIC, FEAT_DEBLOCK_OFF_SLICE, M355_GLUE_N_FEATURES };
 std::atomic<long long> g_feat[M355_GLUE_N_FEATURES];
+std::atomic<long long> g_narrow_rbs(0);      /* residual blocks recorded as 16-bit entries (M355_GLUE_NARROW=1; m355_glue_narrow_blocks) */
 enum { RBF_ROTATE_PENDING = 0x80 };   /* m355_rb.flags bit the recorder alone uses (scale_coefficients): never reaches the library */
+/* words of coeffs[] a residual block occupies: a narrow block (M355_RBF_NARROW, M355_GLUE_NARROW=1) holds two entries per word */
+static inline uint32_t rb_words(const m355_rb& rb) { return (rb.flags & M355_RBF_NARROW) ? (rb.ncoeff + 1u) / 2 : rb.ncoeff; }
 
 struct Run { uint32_t ctb, start, count; };
 
@@ -144,11 +147,13 @@ struct ThreadRec {
   int luma_rb = -1;                 /* cross-component prediction: the transform unit's luma block in its size bin */
   int skipped_pbs = 0;              /* prediction units the reference leaves unwritten (motion.cc warnings) */
   bool any_weighted = false;
+  bool narrow = false;              /* the decoder records blocks that allow it as 16-bit entries (Glue::narrow) */
+  long long narrow_rbs = 0;         /* ... and how many of this thread's blocks did */
   long long feat[M355_GLUE_N_FEATURES] = {};   /* which recorder branches this thread's blocks took (m355_glue_feature_counts) */
   void clear()
   {
     pbs.clear(); for (auto& v : rbs) v.clear(); ibs.clear(); coeffs.clear(); runs.clear();
-    res_len = 0; last_ib = -1; luma_rb = -1; skipped_pbs = 0; any_weighted = false; img_id = 0xFFFFFFFFu; owner = nullptr; thread = nullptr;
+    res_len = 0; last_ib = -1; luma_rb = -1; skipped_pbs = 0; any_weighted = false; narrow_rbs = 0; img_id = 0xFFFFFFFFu; owner = nullptr; thread = nullptr;
     for (long long& f : feat) f = 0;
   }
 };
@@ -219,6 +224,7 @@ struct Glue {
   std::condition_variable job_cv, idle_cv;
   std::deque<Job> jobs;
   bool busy = false, stop = false, sync_submit = false;
+  bool narrow = false;              /* M355_GLUE_NARROW=1 when the decoder was created: scale_coefficients writes M355_RBF_NARROW blocks */
   uint32_t busy_id = 0xFFFFFFFFu;
   uint32_t busy_dpb_id[M355_MAX_REF_FRAMES];    /* the DPB snapshot of the job the worker is running */
   /* DE265_DECODER_PARAM_DISABLE_SAO as the application set it.  The decoder's own param_disable_sao is kept TRUE: that is what
@@ -298,7 +304,7 @@ ThreadRec* rec_for(de265_image* img)
   ThreadRec* r;
   if (!g->pool.empty()) { r = g->pool.back(); g->pool.pop_back(); }
   else r = new ThreadRec;           /* never freed before process exit: other threads may still hold the pointer */
-  r->owner = d; r->img_id = img->get_ID(); r->thread = &t_token;
+  r->owner = d; r->img_id = img->get_ID(); r->thread = &t_token; r->narrow = g->narrow;
   g->recs.push_back(r);
   t_rec = r;
   return r;
@@ -629,7 +635,7 @@ int submit_sharded(Glue* g, const m355_picture& pic, int dslot)
       for (int i = 0; i < pic.n_pbs; i++) c.pbs += own(pic.pbs[i].x, pic.pbs[i].y) == r;
       const m355_rb* src = pic.rbs;
       for (int s = 0; s < 4; s++)
-        for (int i = 0; i < pic.rb_count[s]; i++, src++) if (own_rb(*src) == r) { c.rbs[s]++; c.coeffs += src->ncoeff; }
+        for (int i = 0; i < pic.rb_count[s]; i++, src++) if (own_rb(*src) == r) { c.rbs[s]++; c.coeffs += rb_words(*src); }
       for (int ci = 0; ci < pic.n_ctbs; ci++) if (owner[(size_t)ci] == r) c.ibs += (int)pic.ctbs[ci].ib_count;
     });
     std::vector<m355_picture> rp((size_t)N);
@@ -670,8 +676,8 @@ int submit_sharded(Glue* g, const m355_picture& pic, int dslot)
           if (own_rb(*src) == r) {
             m355_rb rb = *src;
             rb.coeff_ofs = nco;
-            memcpy(co + nco, pic.coeffs + src->coeff_ofs, 4 * (size_t)src->ncoeff);
-            nco += src->ncoeff;
+            memcpy(co + nco, pic.coeffs + src->coeff_ofs, 4 * (size_t)rb_words(*src));
+            nco += rb_words(*src);
             dst[kept++] = rb;
           }
         q.rb_count[s] = kept;
@@ -717,7 +723,7 @@ int submit_sharded(Glue* g, const m355_picture& pic, int dslot)
         if (own_rb(*src) == r) {
           m355_rb rb = *src;
           rb.coeff_ofs = (uint32_t)l.coeffs.size();
-          l.coeffs.insert(l.coeffs.end(), pic.coeffs + src->coeff_ofs, pic.coeffs + src->coeff_ofs + src->ncoeff);
+          l.coeffs.insert(l.coeffs.end(), pic.coeffs + src->coeff_ofs, pic.coeffs + src->coeff_ofs + rb_words(*src));
           l.rbs.push_back(rb); kept++;
         }
       l.rb_count[s] = kept;
@@ -882,6 +888,7 @@ bool submit_picture(Glue* g, Glue::Job& job)
   bool any_weighted = false;
   for (ThreadRec* r : recs) any_weighted = any_weighted || r->any_weighted;
   for (ThreadRec* r : recs) for (int k = 0; k < M355_GLUE_N_FEATURES; k++) if (r->feat[k]) g_feat[k] += r->feat[k];
+  for (ThreadRec* r : recs) if (r->narrow_rbs) g_narrow_rbs += r->narrow_rbs;
   g_feat[FEAT_PCM_CU] += (long long)pcm_cus.size();
   if (slices.size() > 1) g_feat[FEAT_MULTI_SLICE_PIC]++;
   if (sps.chroma_format_idc == 0) g_feat[FEAT_MONO_PIC]++;
@@ -1299,7 +1306,19 @@ void scale_coefficients(thread_context* tctx, int xT, int yT, int x0, int y0, in
   rb.ncoeff = (uint16_t)n;
   const int16_t* lvl = tctx->coeffList[cIdx];
   const int16_t* pos = tctx->coeffPos[cIdx];
-  for (int i = 0; i < n; i++) r->coeffs.push_back((uint32_t)(uint16_t)pos[i] | ((uint32_t)(uint16_t)lvl[i] << 16));
+  /* M355_GLUE_NARROW=1 (read when the decoder is created): a block whose positions are all below 256 and whose levels all fit eight bits is written as 16-bit entries, two per word
+     (M355_RBF_NARROW) — half the bytes of the picture's largest list.  Unset: every block in the 32-bit form. */
+  bool narrow = r->narrow && n > 0;
+  for (int i = 0; i < n && narrow; i++) narrow = (uint16_t)pos[i] < 256 && lvl[i] >= -128 && lvl[i] <= 127;
+  if (narrow) {
+    rb.flags |= M355_RBF_NARROW; r->narrow_rbs++;
+    for (int i = 0; i < n; i += 2) {
+      const uint32_t lo = (uint32_t)(uint8_t)pos[i] | ((uint32_t)(uint8_t)lvl[i] << 8);
+      const uint32_t hi = i + 1 < n ? (uint32_t)(uint8_t)pos[i + 1] | ((uint32_t)(uint8_t)lvl[i + 1] << 8) : 0;
+      r->coeffs.push_back(lo | (hi << 16));
+    }
+  } else
+    for (int i = 0; i < n; i++) r->coeffs.push_back((uint32_t)(uint16_t)pos[i] | ((uint32_t)(uint16_t)lvl[i] << 16));
   if (intra && r->last_ib >= 0) {
     m355_ib& ib = r->ibs[r->last_ib];
     if (ib.cidx == rb.cidx && ib.x == rb.x && ib.y == rb.y && ib.log2_size == rb.log2_size && !(ib.flags & M355_IBF_HAS_RESIDUAL)) {
@@ -1505,6 +1524,7 @@ LIBDE265_API de265_decoder_context* de265_new_decoder()
   if (const char* e = getenv("M355_PIPELINE_DEPTH")) depth = atoi(e);
   if (depth >= 1 && depth <= 16) for (m355_ctx* x : g->rctx) A->m355_set_pipeline_depth(x, g->n_ranks > 1 ? std::min(depth, 3) : depth);
   g->sync_submit = getenv("M355_GLUE_SYNC") != nullptr;
+  g->narrow = getenv("M355_GLUE_NARROW") && atoi(getenv("M355_GLUE_NARROW")) != 0;
   if (!g->sync_submit) g->worker = std::thread(worker_main, g);
   install_traps(g->dctx->acceleration);
   de265_image_allocation alloc = {glue_get_buffer, glue_release_buffer};
@@ -1590,6 +1610,8 @@ LIBDE265_API int m355_glue_feature_counts(long long* out, int n)
   for (int k = 0; k < n && k < M355_GLUE_N_FEATURES; k++) out[k] = g_feat[k].load();
   return M355_GLUE_N_FEATURES;
 }
+/* residual blocks the recorder wrote as 16-bit entries since the process started (M355_GLUE_NARROW=1) */
+LIBDE265_API long long m355_glue_narrow_blocks(void) { return g_narrow_rbs.load(); }
 /* output pictures whose download was started behind their decode (before the application asked) */
 LIBDE265_API long long m355_glue_prefetched_pictures(de265_decoder_context* c) { Glue* g = glue_of((decoder_context*)c); if (g) wait_submitted(g, 0xFFFFFFFFu); return g ? g->n_prefetched : -1; }
 LIBDE265_API long long m355_glue_hashed_pictures(de265_decoder_context* c) { Glue* g = glue_of((decoder_context*)c); if (g) wait_submitted(g, 0xFFFFFFFFu); return g ? g->n_hashed : -1; }

@@ -326,8 +326,10 @@ enum {
   M355_RBF_RDPCM_H   = 1 << 1,     /* rdpcmMode 1 */
   M355_RBF_RDPCM_V   = 1 << 2,     /* rdpcmMode 2 */
   M355_RBF_ROTATE    = 1 << 3,     /* transform_skip_rotation (transform.cc:400-402) */
-  M355_RBF_DEQUANTIZED = 1 << 4    /* coeffs[] levels are already scaled (what the table slots
+  M355_RBF_DEQUANTIZED = 1 << 4,   /* coeffs[] levels are already scaled (what the table slots
                                       transform_add / transform_skip_residual receive): skip dequant */
+  M355_RBF_NARROW    = 1 << 5      /* the block's entries are 16-bit: pos:u8 | level:i8 << 8, two per word of coeffs[], low half
+                                      first — (ncoeff + 1) / 2 words from coeff_ofs (m355_picture below, m355_pack_narrow) */
 };
 typedef struct m355_rb {
   uint16_t x, y;                   /* position in component samples */
@@ -343,8 +345,8 @@ typedef struct m355_rb {
                                       three blocks of a 4:4:4 transform unit have one size, so they sit next to each other
                                       in their size bin.  A chroma block with cbf 0 but ResScaleVal != 0 is listed with
                                       ncoeff 0 (slice.cc:3512-3523). */
-  uint16_t ncoeff;
-  uint32_t coeff_ofs;              /* first entry in coeffs[] */
+  uint16_t ncoeff;                 /* entries; they occupy ncoeff words of coeffs[], (ncoeff + 1) / 2 with M355_RBF_NARROW */
+  uint32_t coeff_ofs;              /* first word of the block in coeffs[] (a word offset, whatever the entry width) */
   uint32_t res_ofs;                /* int16 offset in the residual buffer (DEFERRED) */
 } m355_rb;                         /* 20 bytes */
 
@@ -366,6 +368,11 @@ typedef struct m355_ib {
 /* One picture's complete work description. All pointers are HOST pointers owned by the caller;
  * m355_submit_picture() copies what it needs before returning. Lists:
  *   coeffs[i] = (uint16 pos) | (int16 level << 16)  with pos = xC + yC*nT (slice.cc:3441-3447)
+ *     A block with M355_RBF_NARROW packs two entries per word instead: entry k is the 16-bit half (k & 1) of word
+ *     coeff_ofs + k / 2, low half first, each (uint8 pos) | (int8 level << 8), the level sign-extended.  The spare half of a
+ *     block with an odd count is never read.  Only blocks whose positions are all < 256 and whose levels all fit 8 bits can
+ *     take the form; narrow and wide blocks mix freely in one picture and one size bin.  n_coeffs and coeff_ofs count words:
+ *     a block must satisfy coeff_ofs + words <= n_coeffs, words = ncoeff or (ncoeff + 1) / 2.
  *   rbs[] is grouped by log2_size: rb_count[s] entries of size (s+2), concatenated 4x4,8x8,16,32.
  *   scaling_factors: [sizeId 0..3][matrixID 0..5][y][x] uint8 (sps.h:61-64), 6*(16+64+256+1024) B. */
 typedef struct m355_picture {
@@ -461,6 +468,18 @@ typedef struct m355_arena_caps {
   m355_rb* rb_bin[4];              /* out: where the residual blocks of each size go */
 } m355_arena_caps;
 M355_API int m355_arena_begin(m355_ctx* ctx, m355_arena_caps* caps, m355_picture* pic);
+/* Host only (no GPU call, no context): a copy of the residual records and their coefficient list in which every block that can
+ * take the 16-bit form has it (M355_RBF_NARROW: all positions < 256, all levels in [-128, 127]) and the others are copied as they
+ * are.  A block without entries stays wide; a block that is already narrow is copied unchanged.
+ * The list is compacted: each block's own range is copied, the blocks in the order they have in coeffs_in (equal offsets: the
+ * order of the records).  The records are binned by size while the list is in decode order, so this order is what makes widening
+ * the result again give coeffs_in back word for word.  The luma block a cross-component chroma block re-reads keeps its own range
+ * and flag.
+ * coeffs_out needs room for n_coeffs_in words and must not be coeffs_in; rbs_out may be rbs_in.  *n_coeffs_out = the words written.
+ * M355_ERR_INVALID when a block's range leaves coeffs_in, or when blocks overlap so far that the copies of their ranges would
+ * outgrow n_coeffs_in. */
+M355_API int m355_pack_narrow(const m355_rb* rbs_in, int n_rbs, const uint32_t* coeffs_in, uint32_t n_coeffs_in,
+                              m355_rb* rbs_out, uint32_t* coeffs_out, uint32_t* n_coeffs_out);
 /* Blocks until all submitted work finished; returns M355_ERR_TIMEOUT if a device spin bound hit, M355_ERR_INVALID if a picture
  * recorded in place was rejected by the device-side list validation (the message names the picture's serial and the record; the
  * next call reports the next rejected picture, if any). */

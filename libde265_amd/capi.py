@@ -71,6 +71,8 @@ class Library:
         L.m355_arena_begin.argtypes = [vp, vp, vp]
         if hasattr(L, "m355_picture_arena_begin"):      # (absent from older builds loaded through M355_LIB for an A/B)
             L.m355_picture_arena_begin.argtypes = [vp, i, vp, vp, vp]
+        if hasattr(L, "m355_pack_narrow"):
+            L.m355_pack_narrow.argtypes = [vp, i, vp, ctypes.c_uint32, vp, vp, ctypes.POINTER(ctypes.c_uint32)]
         L.m355_frame_download_async.argtypes = [vp, i, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_ssize_t)]
         L.m355_frame_download_wait.argtypes = [vp, i]
         L.m355_host_alloc.argtypes = [ctypes.c_size_t]
@@ -129,6 +131,17 @@ class Library:
 
     def device_count(self):
         return self.lib.m355_device_count()
+
+    def pack_narrow(self, pic):
+        """m355_pack_narrow on a picture's residual records and coefficient list (host only; worklist.pack_narrow is the numpy
+        statement of the same): a copy with every block that fits in the 16-bit entry form (worklist.RBF_NARROW)"""
+        out = pic.copy()
+        rbs = np.ascontiguousarray(pic.rbs, dtype=worklist.RB)
+        co = np.ascontiguousarray(pic.coeffs, dtype=np.dtype("<u4"))
+        out.rbs, co_out, n = np.zeros(len(rbs), worklist.RB), np.zeros(len(co), np.dtype("<u4")), ctypes.c_uint32(0)
+        self.check(self.lib.m355_pack_narrow(rbs.ctypes.data, len(rbs), co.ctypes.data, len(co), out.rbs.ctypes.data, co_out.ctypes.data, ctypes.byref(n)))
+        out.coeffs = co_out[:n.value].copy()
+        return out
 
 
 class Context:

@@ -424,7 +424,7 @@ __global__ void __launch_bounds__(256) k_validate(DevPic p, uint32_t n_total)
     const int n = 1 << (sb + 2);
     const int Wc = rb.cidx ? W / p.sw : W, Hc = rb.cidx ? H / p.sh : H;
     bad = rb.log2_size != sb + 2 || rb.cidx > 2 || rb.kind > 3 || rb.x + n > Wc || rb.y + n > Hc ||
-          (unsigned long long)rb.coeff_ofs + rb.ncoeff > p.n_coeffs ||
+          (unsigned long long)rb.coeff_ofs + ((rb.flags & M355_RBF_NARROW) ? (rb.ncoeff + 1u) / 2 : rb.ncoeff) > p.n_coeffs ||
           ((rb.flags & M355_RBF_DEFERRED) && (unsigned long long)rb.res_ofs + (unsigned)(n * n) > p.res_len) ||
           ((pp.flags & M355_PF_SCALING_LIST) && (rb.matrix_id & 7) > 5) || (rb.kind == M355_RK_DST && sb != 0);
   } else {

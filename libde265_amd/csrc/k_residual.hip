@@ -65,9 +65,41 @@ __device__ __forceinline__ uint32_t d_sel_u(uint32_t mask, uint32_t a, uint32_t 
 #define RES_WPG 1
 #define RES_LDS_DWORDS (2 * RES_WPG * (1024 + 32))   /* 32x32: 2 blocks per wave, nT^2/2 coefficient pairs + nT * (nT/2+1) first-stage pairs each */
 
+#define RES_GB 8   /* (pos, level) pairs a lane fetches per batch */
+/* A batch of RES_GB entries of block rb's coefficient list: entries k0, k0 + NT, ..., each as the pair pos | level << 16 that scatter
+ * consumes, 0xFFFFFFFF (pos 65535: skipped) past the block's last entry.
+ *  - One unconditional 32-bit load per entry from a CLAMPED index, everything else afterwards: a load under a per-lane condition is
+ *    a branch and a wait of its own (eight dependent round trips instead of one).
+ *  - A wide block's entry k is word k.  A narrow one's (M355_RBF_NARROW) is half k & 1 of word k >> 1, pos:u8 | level:i8 << 8.  The
+ *    flag differs from lane group to lane group within a wave: it is a shift count of the index and, for the widening, a per-lane
+ *    byte selector and shift — never a per-lane branch.
+ *  - The widening as a whole sits behind the loads under a WAVE-uniform test (any_narrow = d_res_any_narrow, taken where the wave is
+ *    converged — the batch loop is not): a wave without a narrow block, i.e. every wave of a picture that uses none, pays one shift
+ *    per entry and a scalar branch per batch.  Widening on every wave cost wide pictures time: profiles/narrow_entries_bench.txt.
+ *  - The flag is that of the record whose list is read: a cross-component chroma block follows its luma block's. */
+__device__ __forceinline__ bool d_res_any_narrow(const m355_rb& rb) { return __any((rb.flags & M355_RBF_NARROW) != 0) != 0; }
+template <int NT>
+__device__ __forceinline__ void d_res_fetch(const DevPic& p, const m355_rb& rb, bool any_narrow, int k0, uint32_t* eb)
+{
+  static_assert(M355_RBF_NARROW == 1 << 5, "the shift below");
+  const uint32_t nar = (rb.flags >> 5) & 1u;
+  const int last = max((int)rb.ncoeff - 1, 0);
+#pragma unroll
+  for (int j = 0; j < RES_GB; j++) eb[j] = p.coeffs[rb.coeff_ofs + ((uint32_t)min(k0 + j * NT, last) >> nar)];
+  if (any_narrow) {
+    /* every entry of the batch sits in the same half as entry k0 (NT is even; a clamped index may not, its entry is replaced below):
+       bytes (pos, 0, level, 0) of that half, then the level's sign into the top byte; a wide block's word passes unchanged */
+    const uint32_t sel = nar ? ((k0 & 1) ? 0x0C030C02u : 0x0C010C00u) : 0x03020100u;
+    const int sh = nar ? 8 : 0;
+#pragma unroll
+    for (int j = 0; j < RES_GB; j++) eb[j] = (uint32_t)((int)(d_perm(eb[j], eb[j], sel) << sh) >> sh);
+  }
+#pragma unroll
+  for (int j = 0; j < RES_GB; j++) eb[j] = k0 + j * NT < rb.ncoeff ? eb[j] : 0xFFFFFFFFu;
+}
+
 /* Residual of one block per lane group (all lanes of the wave call this together): res[] = row `c` of the block,
  * NT adjacent samples, before it is added to the picture / stored.  smem pointers are the lane group's tile. */
-#define RES_GB 8   /* (pos, level) pairs a lane fetches per batch */
 template <int LOG2, bool PRE = false>
 __device__ __forceinline__ void d_rb_compute(const DevPic& p, const m355_rb& rb, bool active, int c, uint32_t* cfp, int* res, const uint32_t* eb0 = nullptr)
 {
@@ -102,6 +134,7 @@ __device__ __forceinline__ void d_rb_compute(const DevPic& p, const m355_rb& rb,
     /* the (pos, level) pairs are fetched eight per lane at a time: a dense 32x32 block holds 1024 of them, and one
        dependent load -> scatter step per pair (32 memory round trips per lane) was what the whole launch waited for */
     constexpr int GB = RES_GB;
+    const bool any_narrow = d_res_any_narrow(rb);
     auto scatter = [&](const uint32_t* eb) {
 #pragma unroll
       for (int j = 0; j < GB; j++) {
@@ -125,12 +158,7 @@ __device__ __forceinline__ void d_rb_compute(const DevPic& p, const m355_rb& rb,
     if (PRE) scatter(eb0);       /* the first batch was requested an iteration ago (d_res_issue) */
     for (int k0 = c + (PRE ? NT * GB : 0); k0 < rb.ncoeff; k0 += NT * GB) {
       uint32_t eb[GB];
-#pragma unroll
-      for (int j = 0; j < GB; j++) {
-        const int k = k0 + j * NT;
-        const uint32_t v = p.coeffs[rb.coeff_ofs + (uint32_t)min(k, max((int)rb.ncoeff - 1, 0))];   /* (clamped: no branch in front of a load) */
-        eb[j] = k < rb.ncoeff ? v : 0xFFFFFFFFu;   /* pos 65535: skipped below */
-      }
+      d_res_fetch<NT>(p, rb, any_narrow, k0, eb);
       scatter(eb);
     }
   }
@@ -271,16 +299,7 @@ __device__ __forceinline__ void d_res_issue(const DevPic& p, const m355_rb& rb, 
       else w[0] = d_ldg4(d);
     }
   }
-  if (PRE) {
-#pragma unroll
-    for (int j = 0; j < RES_GB; j++) {
-      /* from a CLAMPED index, selected afterwards: a load under a per-lane condition is a branch and a wait of its own (eight
-         dependent round trips instead of one) */
-      const int k = c + j * NT;
-      const uint32_t v = p.coeffs[rb.coeff_ofs + (uint32_t)min(k, max((int)rb.ncoeff - 1, 0))];
-      eb[j] = k < rb.ncoeff ? v : 0xFFFFFFFFu;
-    }
-  }
+  if (PRE) d_res_fetch<NT>(p, rb, d_res_any_narrow(rb), c, eb);
 }
 
 /* a row of residuals added to the lane's destination row (w: read earlier) and written back: NT samples as 16-byte (NT >= 8) or 8-byte vectors — blocks are

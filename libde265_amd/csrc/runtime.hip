@@ -575,6 +575,45 @@ int m355_arena_begin(m355_ctx* c, m355_arena_caps* k, m355_picture* pic)
   return arena_into(c, c->transient[c->next_transient], k, 0, false, pic);   /* the arena the next m355_submit_picture uses */
 }
 
+/* residual records + coefficient list with every block that fits in the 16-bit entry form (M355_RBF_NARROW); host only.  rbs_out may be rbs_in. */
+int m355_pack_narrow(const m355_rb* rbs_in, int n_rbs, const uint32_t* co_in, uint32_t n_in, m355_rb* rbs_out, uint32_t* co_out, uint32_t* n_out)
+{
+  if (n_rbs < 0 || (n_rbs && (!rbs_in || !rbs_out)) || (n_in && (!co_in || !co_out)) || !n_out) return fail(M355_ERR_INVALID, "m355_pack_narrow: bad arguments");
+  /* the blocks keep the order they have in the list (records are binned by size, the list is in decode order): unpacking gives the input back word for word */
+  std::vector<int> order((size_t)n_rbs);
+  for (int i = 0; i < n_rbs; i++) order[i] = i;
+  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return rbs_in[a].coeff_ofs < rbs_in[b].coeff_ofs; });
+  uint64_t o = 0;
+  for (int i : order) {
+    m355_rb rb = rbs_in[i];
+    const uint32_t n = rb.ncoeff, words_in = (rb.flags & M355_RBF_NARROW) ? (n + 1) / 2 : n;
+    if ((uint64_t)rb.coeff_ofs + words_in > n_in) return fail(M355_ERR_INVALID, "m355_pack_narrow: rb %d: coefficient range", i);
+    const uint32_t* src = co_in + rb.coeff_ofs;
+    bool fits = n > 0 && !(rb.flags & M355_RBF_NARROW);
+    for (uint32_t k = 0; k < n && fits; k++) {
+      const int lvl = (int16_t)(src[k] >> 16);
+      fits = (src[k] & 0xFFFFu) < 256 && lvl >= -128 && lvl <= 127;
+    }
+    const uint32_t words_out = fits ? (n + 1) / 2 : words_in;
+    /* (only lists whose blocks overlap can grow past their own length) */
+    if (o + words_out > n_in) return fail(M355_ERR_INVALID, "m355_pack_narrow: rb %d: blocks share coefficients, the packed list would outgrow the input", i);
+    uint32_t* dst = co_out + o;
+    if (fits) {
+      for (uint32_t k = 0; k < n; k += 2) {
+        const uint32_t lo = (src[k] & 0xFFu) | ((src[k] >> 8) & 0xFF00u);
+        const uint32_t hi = k + 1 < n ? (src[k + 1] & 0xFFu) | ((src[k + 1] >> 8) & 0xFF00u) : 0;     /* (the spare half of an odd block: never read) */
+        dst[k >> 1] = lo | (hi << 16);
+      }
+      rb.flags |= M355_RBF_NARROW;
+    } else if (words_out) memcpy(dst, src, 4 * (size_t)words_out);
+    rb.coeff_ofs = (uint32_t)o;
+    rbs_out[i] = rb;
+    o += words_out;
+  }
+  *n_out = (uint32_t)o;
+  return M355_OK;
+}
+
 /* the same for the arenas of a RESIDENT picture (tile-sharded contexts decode from handles): handle -1 makes one */
 int m355_picture_arena_begin(m355_ctx* c, int h, m355_arena_caps* k, const m355_pic_params* pp, m355_picture* pic)
 {

@@ -228,7 +228,8 @@ static int validate(const m355_picture* pic, const m355_rb* const* rb_bin_in, bo
     const int n = 1 << (s + 2);
     const int W = rb.cidx ? pp.width / sw : pp.width, H = rb.cidx ? pp.height / sh : pp.height;
     if (rb.log2_size != s + 2 || rb.cidx > 2 || rb.kind > 3 || rb.x + n > W || rb.y + n > H) return "malformed";
-    if ((uint64_t)rb.coeff_ofs + rb.ncoeff > pic->n_coeffs) return "coefficient range";
+    /* (words, not entries: a narrow block holds two entries per word) */
+    if ((uint64_t)rb.coeff_ofs + ((rb.flags & M355_RBF_NARROW) ? (rb.ncoeff + 1u) / 2 : rb.ncoeff) > pic->n_coeffs) return "coefficient range";
     if ((rb.flags & M355_RBF_DEFERRED) && (uint64_t)rb.res_ofs + n * n > pic->res_len) return "residual range";
     if ((pp.flags & M355_PF_SCALING_LIST) && (rb.matrix_id & 7) > 5) return "matrix id";
     if (rb.kind == M355_RK_DST && s != 0) return "DST only exists for 4x4";

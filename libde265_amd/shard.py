@@ -72,7 +72,7 @@ def shard_picture(pic, rank, nranks):
         bins = np.repeat(np.arange(4), pic.rb_count)
         out.rb_count = [int(np.count_nonzero(keep & (bins == s))) for s in range(4)]
         rbs = pic.rbs[keep].copy()
-        n = rbs["ncoeff"].astype(np.int64)
+        n = worklist.rb_words(rbs)                          # words, not entries: a narrow block holds two entries per word
         new_ofs = np.concatenate([[0], np.cumsum(n)[:-1]]) if len(rbs) else np.zeros(0, np.int64)
         idx = np.repeat(rbs["coeff_ofs"].astype(np.int64) - new_ofs, n) + np.arange(int(n.sum()))
         out.coeffs = pic.coeffs[idx] if len(idx) else np.zeros(0, np.dtype("<u4"))

@@ -33,7 +33,7 @@ CUF_PCM, CUF_TRANSQUANT_BYPASS = 1, 2
 TUF_NONZERO_COEFF = 1
 PBF_PRED_L0, PBF_PRED_L1, PBF_MC_L0, PBF_MC_L1, PBF_WEIGHTED, PBF_FILL_L0, PBF_FILL_L1 = 1, 2, 4, 8, 16, 32, 64
 RK_DCT, RK_DST, RK_SKIP, RK_BYPASS = 0, 1, 2, 3
-RBF_DEFERRED, RBF_RDPCM_H, RBF_RDPCM_V, RBF_ROTATE, RBF_DEQUANTIZED = 1, 2, 4, 8, 16
+RBF_DEFERRED, RBF_RDPCM_H, RBF_RDPCM_V, RBF_ROTATE, RBF_DEQUANTIZED, RBF_NARROW = 1, 2, 4, 8, 16, 32
 IBF_HAS_RESIDUAL, IBF_DISABLE_BOUNDARY_FILTER, IBF_PCM = 1, 2, 4
 STAGE_INTER, STAGE_RESIDUAL, STAGE_INTRA, STAGE_DEBLOCK, STAGE_SAO, STAGE_ALL = 1, 2, 4, 8, 16, 31
 
@@ -105,6 +105,17 @@ class Picture:
         self.res_len = 0
         self.scaling_factors = None
         self.meta = {}          # free-form (poc, expected md5 ...), not part of the ABI
+
+    def copy(self):
+        """A picture of its own: every list copied."""
+        p = Picture()
+        p.pp = self.pp.copy()
+        p.dst_frame, p.ref_frames = self.dst_frame, list(self.ref_frames)
+        for name, dt in _LISTS:
+            setattr(p, name, np.array(getattr(self, name), dtype=dt))
+        p.rb_count, p.res_len, p.meta = list(self.rb_count), self.res_len, dict(self.meta)
+        p.scaling_factors = None if self.scaling_factors is None else np.array(self.scaling_factors, dtype=np.uint8)
+        return p
 
     # ---- geometry helpers ----
     @property
@@ -191,6 +202,70 @@ class Picture:
         if c[14]:
             p.scaling_factors = np.frombuffer(buf, np.uint8, SCALING_BYTES, o).copy(); o += SCALING_BYTES
         return p, o
+
+
+# ---- 16-bit coefficient entries (M355_RBF_NARROW, include/de265_mi355x.h) ----
+def rb_words(rbs):
+    """Words of coeffs[] each residual block occupies: ncoeff, or (ncoeff + 1) // 2 for a narrow block."""
+    n = rbs["ncoeff"].astype(np.int64)
+    return np.where((rbs["flags"] & RBF_NARROW) != 0, (n + 1) // 2, n)
+
+
+def _wide_entries(pic):
+    """Every block's entries in the wide form (pos | level << 16), concatenated in record order -> (entries, entries per block)."""
+    rbs = pic.rbs
+    n = rbs["ncoeff"].astype(np.int64)
+    k = np.arange(int(n.sum())) - np.repeat(np.cumsum(n) - n, n)                 # entry index inside its block
+    nar = np.repeat((rbs["flags"] & RBF_NARROW) != 0, n)
+    w = np.asarray(pic.coeffs, dtype=np.uint32)[np.repeat(rbs["coeff_ofs"].astype(np.int64), n) + np.where(nar, k >> 1, k)]
+    h = (w >> ((k & 1) * 16).astype(np.uint32)) & 0xFFFF
+    lvl = (h >> 8).astype(np.uint8).view(np.int8).astype(np.int32)              # sign-extended
+    return np.where(nar, (h & 0xFF) | ((lvl & 0xFFFF).astype(np.uint32) << 16), w).astype(np.uint32), n
+
+
+def _relayout(pic, entries, n, narrow):
+    """A copy of `pic` in which block i is stored narrow where narrow[i], wide elsewhere.  The list is compacted: every block's own range,
+    the blocks in the order they have in pic.coeffs (equal offsets: record order).  The spare half of an odd narrow block is 0."""
+    out = pic.copy()
+    words = np.where(narrow, (n + 1) // 2, n)
+    order = np.argsort(pic.rbs["coeff_ofs"], kind="stable")
+    new_ofs = np.zeros(len(n), np.int64)
+    new_ofs[order] = np.cumsum(words[order]) - words[order]
+    co = np.zeros(int(words.sum()), np.dtype("<u4"))
+    k = np.arange(int(n.sum())) - np.repeat(np.cumsum(n) - n, n)
+    nar, base = np.repeat(narrow, n), np.repeat(new_ofs, n)
+    co[(base + k)[~nar]] = entries[~nar]
+    e = entries[nar]
+    co.view("<u2")[(2 * base + k)[nar]] = ((e & 0xFF) | ((e >> 8) & 0xFF00)).astype(np.uint16)   # half k & 1 of word k >> 1, low half first
+    out.coeffs = co
+    out.rbs["coeff_ofs"] = new_ofs.astype(np.uint32)
+    out.rbs["flags"] = np.where(narrow, out.rbs["flags"] | RBF_NARROW, out.rbs["flags"] & ~np.uint8(RBF_NARROW)).astype(np.uint8)
+    return out
+
+
+def narrow_fits(pic):
+    """Per residual block: it has entries, and all of them have pos < 256 and -128 <= level <= 127."""
+    entries, n = _wide_entries(pic)
+    lvl = (entries >> 16).astype(np.uint16).view(np.int16)
+    bad = ((entries & 0xFFFF) >= 256) | (lvl < -128) | (lvl > 127)
+    return (np.bincount(np.repeat(np.arange(len(n)), n), weights=bad, minlength=len(n)) == 0) & (n > 0)
+
+
+def pack_narrow(pic, blocks=None):
+    """A packed copy of the picture (what m355_pack_narrow makes of its lists): every residual block whose entries all fit the 16-bit
+    form carries RBF_NARROW and half the words, the others stay wide.  `blocks` (a boolean array over pic.rbs) restricts the choice."""
+    entries, n = _wide_entries(pic)
+    fits = narrow_fits(pic)
+    if blocks is not None:
+        fits &= np.asarray(blocks, dtype=bool)
+    return _relayout(pic, entries, n, fits | ((pic.rbs["flags"] & RBF_NARROW) != 0))
+
+
+def unpack_narrow(pic, blocks=None):
+    """The inverse of pack_narrow: every narrow block (or those of the boolean array `blocks`) back in the wide form."""
+    entries, n = _wide_entries(pic)
+    narrow = (pic.rbs["flags"] & RBF_NARROW) != 0
+    return _relayout(pic, entries, n, narrow & ~np.asarray(blocks, dtype=bool) if blocks is not None else np.zeros(len(n), bool))
 
 
 def plane_dims(width, height, chroma_format_idc):
