@@ -80,7 +80,7 @@ namespace {
   X(m355_last_error) X(m355_device_count) X(m355_create) X(m355_destroy) X(m355_frame_create) X(m355_frame_destroy) \
   X(m355_frame_upload) X(m355_frame_download) X(m355_submit_picture) X(m355_wait) X(m355_set_pipeline_depth) \
   X(m355_host_alloc) X(m355_host_free) X(m355_frame_hash) X(m355_arena_begin) X(m355_last_serial) X(m355_decode_status) \
-  X(m355_frame_download_async) X(m355_frame_download_wait) \
+  X(m355_frame_download_async) X(m355_frame_download_wait) X(m355_frame_export) X(m355_frame_export_order) \
   X(m355_group_create) X(m355_group_destroy) X(m355_group_decode) X(m355_picture_upload) X(m355_picture_replace) X(m355_shard_owner_of_tile) \
   X(m355_picture_arena_begin)
 
@@ -1600,6 +1600,44 @@ LIBDE265_API const uint8_t* de265_get_image_plane(const struct de265_image* img,
   }
   return m355ref_de265_get_image_plane(img, channel, stride);
 }
+
+/* The other way out of the decoder, for a consumer on the same GPU (not part of de265.h, which stays as it is): the picture's DEVICE frame
+ * exported into device memory of the caller (m355_frame_export: layout / samples = M355_EXPORT_*; rect = {x0, y0, width, height} in luma
+ * samples, NULL: the image's conformance window), and the consumer's stream ordered behind the export (m355_frame_export_order).  Nothing
+ * waits for the GPU here — the only wait is for the glue's worker thread to have enqueued the picture's decode —, and an image taken this
+ * way and never read through de265_get_image_plane is never downloaded.  -> M355_OK or an M355_ERR_* code (M355_ERR_INVALID also for an
+ * image the backend holds no frame of, and for a decoder that shards its pictures over several ranks: their frames are complete only
+ * behind the gather). */
+LIBDE265_API int m355_glue_export_image(const struct de265_image* img, int layout, int samples, const int rect[4], void* const dst[3],
+                                        const int64_t pitch[3], void* consumer_stream)
+{
+  Api* A = api();
+  if (!A) return M355_ERR_NO_DEVICE;
+  if (!img || !img->decctx || !dst || !pitch) return M355_ERR_INVALID;
+  Glue* g = glue_of(img->decctx);
+  if (!g || g->n_ranks > 1) return M355_ERR_INVALID;
+  wait_submitted(g, img->get_ID());
+  std::lock_guard<std::mutex> api_lock(g->api_mu);
+  const int slot = slot_of(g->dctx, img);
+  if (slot < 0 || g->frame_of_slot[slot] < 0 || g->dev_id[slot] != img->get_ID()) return M355_ERR_INVALID;
+  m355_export_desc d;
+  memset(&d, 0, sizeof(d));
+  d.layout = layout; d.samples = samples;
+  if (rect) { d.x0 = rect[0]; d.y0 = rect[1]; d.width = rect[2]; d.height = rect[3]; }
+  else {
+    const seq_parameter_set& sps = img->get_sps();               /* (window offsets count chroma samples: sps.cc, conformance_window_flag) */
+    d.x0 = sps.SubWidthC * sps.conf_win_left_offset; d.y0 = sps.SubHeightC * sps.conf_win_top_offset;
+    d.width = sps.pic_width_in_luma_samples - sps.SubWidthC * (sps.conf_win_left_offset + sps.conf_win_right_offset);
+    d.height = sps.pic_height_in_luma_samples - sps.SubHeightC * (sps.conf_win_top_offset + sps.conf_win_bottom_offset);
+  }
+  for (int c = 0; c < 3; c++) { d.dst[c] = dst[c]; d.pitch[c] = pitch[c]; }
+  int rc = A->m355_frame_export(g->mctx, g->frame_of_slot[slot], &d);
+  if (rc == M355_OK) rc = A->m355_frame_export_order(g->mctx, g->frame_of_slot[slot], consumer_stream);
+  if (rc != M355_OK) g->error = A->m355_last_error();
+  return rc;
+}
+/* the backend context behind a decoder, for the m355_device_* calls that go with the export (device memory without a second HIP runtime) */
+LIBDE265_API void* m355_glue_backend_context(de265_decoder_context* c) { Glue* g = glue_of((decoder_context*)c); return g ? (void*)g->mctx : nullptr; }
 
 /* test / diagnostics hooks of this build (not part of de265.h) */
 LIBDE265_API long long m355_glue_cpu_pixel_calls(void) { return g_cpu_pixel_calls.load(); }

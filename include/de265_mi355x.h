@@ -422,6 +422,46 @@ M355_API int m355_frame_download_async(m355_ctx* ctx, int frame, void* const dst
 M355_API int m355_frame_download_wait(m355_ctx* ctx, int frame);
 M355_API int m355_frame_fill(m355_ctx* ctx, int frame, int value_luma, int value_chroma);
 
+/* Export into DEVICE memory, for a consumer on the same GPU (an encoder, a renderer, an inference pipeline): the frame's conformance
+ * window — any rectangle — instead of the coded-size planes with their 128-byte pitch, planar or semi-planar (NV12 / NV16 / NV24 shapes,
+ * P010 / P016 with M355_EXPORT_MSB16), optionally rounded to 8 bits.  One kernel for all planes, integer-exact: no colour conversion, no
+ * scaling.  What lands is a closed-form function of the samples m355_frame_download returns:
+ *   rectangle   luma samples [x0, x0 + width) x [y0, y0 + height), chroma the same divided by SubWidthC / SubHeightC
+ *   NATIVE      s            MSB16  (uint16)(s << (16 - bit_depth))            U8  bit_depth 8: s, else min(255, (s + (1 << (bit_depth - 9))) >> (bit_depth - 8))
+ * with the bit depth of the plane (bit_depth_luma / bit_depth_chroma).  A monochrome frame exports luma only (dst[1], dst[2] and their
+ * pitches are ignored in both layouts).  Destination bytes of a row beyond the exported row are never written.
+ * M355_ERR_INVALID (nothing is enqueued, no destination byte written): a rectangle that leaves the frame or is not aligned to the chroma
+ * grid, a null destination for a plane that exists, a pitch below the row's bytes, unknown layout / samples values.
+ * Asynchronous, and a READER of the frame: the kernel is queued behind the decode that writes the frame (on that lane's stream, beside the
+ * host and the other lanes' decodes), and a later picture decoded into the frame waits for it in front of its first write.  An export
+ * behind a decode whose lists were rejected writes nothing, like that decode (m355_decode_status).  The destination stays the caller's:
+ * the library never frees it and does not track the consumer's reads.
+ *   m355_frame_export_wait    the host blocks until this frame's last export has landed (m355_wait also waits for every export)
+ *   m355_frame_export_order   the consumer's stream waits for it instead; the host does not.  m355_stream() cannot stand for this:
+ *                             consecutive pictures go round several lanes, each with streams of its own */
+#define M355_EXPORT_PLANAR      0   /* dst[0..2] = Y, Cb, Cr */
+#define M355_EXPORT_SEMIPLANAR  1   /* dst[0] = Y, dst[1] = Cb,Cr interleaved (NV12/NV16/NV24 shapes by chroma format) */
+#define M355_EXPORT_NATIVE      0   /* element type and values of the frame (u8, or u16 LSB-aligned) */
+#define M355_EXPORT_MSB16       1   /* u16, value << (16 - bit_depth)  (P010/P016 convention; 8-bit sources too) */
+#define M355_EXPORT_U8          2   /* u8: bit_depth 8 -> s; else min(255, (s + (1 << (bd-9))) >> (bd-8)) */
+typedef struct m355_export_desc {
+  int32_t layout, samples;
+  int32_t x0, y0, width, height;    /* luma rectangle; width == 0: the whole frame. Multiples of SubWidthC / SubHeightC */
+  void*   dst[3];                   /* device memory, or m355_host_alloc memory (device-addressable) */
+  int64_t pitch[3];                 /* BYTES per destination row, >= the row's bytes */
+} m355_export_desc;
+M355_API int   m355_frame_export(m355_ctx* ctx, int frame, const m355_export_desc* desc);       /* asynchronous */
+M355_API int   m355_frame_export_wait(m355_ctx* ctx, int frame);
+M355_API int   m355_frame_export_order(m355_ctx* ctx, int frame, void* consumer_hipStream);
+/* Device memory for export destinations and blocking copies out of / into it, for applications (and the tests) that keep a second HIP
+ * runtime out of the process.  m355_device_alloc: NULL on failure, contents undefined;
+ * m355_device_free waits for the context's work first.  m355_device_read / _write block until all work of the context (exports included) has
+ * finished and copy through the context's pinned staging buffer. */
+M355_API void* m355_device_alloc(m355_ctx* ctx, size_t bytes);
+M355_API void  m355_device_free(m355_ctx* ctx, void* p);
+M355_API int   m355_device_read(m355_ctx* ctx, const void* dev_src, void* host_dst, size_t bytes);
+M355_API int   m355_device_write(m355_ctx* ctx, void* dev_dst, const void* host_src, size_t bytes);
+
 /* Diagnostic (bench.py's roofline): the device-to-device copy rate this box reaches — `bytes` read + `bytes` written per launch of a float4 copy
  * kernel, the median of `iters` launches timed with events on the context's stream, in GB/s (read + written bytes / time).  The achievable
  * ceiling next to the 8 TB/s specification ("measure the real ceiling with a device-to-device copy kernel on the box"). */

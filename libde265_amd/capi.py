@@ -37,6 +37,18 @@ class PictureHash(ctypes.Structure):
     _fields_ = [("md5", (ctypes.c_uint8 * 16) * 3), ("crc", ctypes.c_uint16 * 3), ("checksum", ctypes.c_uint32 * 3)]
 
 
+EXPORT_PLANAR, EXPORT_SEMIPLANAR = 0, 1
+EXPORT_NATIVE, EXPORT_MSB16, EXPORT_U8 = 0, 1, 2
+DEVICE_FILL = 0xA5          # the sentinel byte this harness fills export destinations with before an export (Context.device_alloc)
+
+
+class ExportDesc(ctypes.Structure):
+    """m355_export_desc (include/de265_mi355x.h)"""
+    _fields_ = [("layout", ctypes.c_int32), ("samples", ctypes.c_int32),
+                ("x0", ctypes.c_int32), ("y0", ctypes.c_int32), ("width", ctypes.c_int32), ("height", ctypes.c_int32),
+                ("dst", ctypes.c_void_p * 3), ("pitch", ctypes.c_int64 * 3)]
+
+
 class ArenaCaps(ctypes.Structure):
     """m355_arena_caps (include/de265_mi355x.h)"""
     _fields_ = [(n, ctypes.c_int32) for n in ("n_slices", "n_ctbs", "n_cus", "n_tus", "n_pbs", "n_wts", "n_ibs")] + \
@@ -75,6 +87,16 @@ class Library:
             L.m355_pack_narrow.argtypes = [vp, i, vp, ctypes.c_uint32, vp, vp, ctypes.POINTER(ctypes.c_uint32)]
         L.m355_frame_download_async.argtypes = [vp, i, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_ssize_t)]
         L.m355_frame_download_wait.argtypes = [vp, i]
+        if hasattr(L, "m355_frame_export"):             # (absent from older builds loaded through M355_LIB for an A/B)
+            L.m355_frame_export.argtypes = [vp, i, ctypes.POINTER(ExportDesc)]
+            L.m355_frame_export_wait.argtypes = [vp, i]
+            L.m355_frame_export_order.argtypes = [vp, i, vp]
+            L.m355_device_alloc.argtypes = [vp, ctypes.c_size_t]
+            L.m355_device_alloc.restype = vp
+            L.m355_device_free.argtypes = [vp, vp]
+            L.m355_device_free.restype = None
+            L.m355_device_read.argtypes = [vp, vp, vp, ctypes.c_size_t]
+            L.m355_device_write.argtypes = [vp, vp, vp, ctypes.c_size_t]
         L.m355_host_alloc.argtypes = [ctypes.c_size_t]
         L.m355_host_alloc.restype = vp
         L.m355_host_free.argtypes = [vp]
@@ -256,6 +278,97 @@ class Context:
         for p in bufs:
             self.L.lib.m355_host_free(p)
         return out
+
+    # ---- export into device memory (m355_frame_export) ----
+    def device_alloc(self, nbytes, fill=DEVICE_FILL):
+        """device memory (m355_device_alloc), every byte set to `fill` through m355_device_write (None: left as it comes) -> pointer"""
+        p = self.L.lib.m355_device_alloc(self.h, nbytes)
+        if not p:
+            raise M355Error(4, self.L.error())       # M355_ERR_NOMEM
+        if fill is not None:
+            a = np.full(nbytes, fill, np.uint8)
+            rc = self.L.lib.m355_device_write(self.h, p, a.ctypes.data, nbytes)
+            if rc:
+                self.L.lib.m355_device_free(self.h, p)
+                self.L.check(rc)
+        return p
+
+    def device_free(self, p):
+        self.L.lib.m355_device_free(self.h, p)
+
+    def device_read(self, p, nbytes):
+        """blocking copy of device memory (m355_device_read) -> uint8 array"""
+        a = np.zeros(nbytes, np.uint8)
+        self.L.check(self.L.lib.m355_device_read(self.h, p, a.ctypes.data, nbytes))
+        return a
+
+    def export_shapes(self, f, layout, samples, rect=None):
+        """the destination planes of an export of frame f: [(rows, elements per row, dtype)] — semi-planar: Y, then Cb and Cr interleaved"""
+        w, h, cf, bdl, bdc = self._geom[f]
+        if rect is not None:
+            w, h = rect[2], rect[3]
+        out = []
+        for c, (pw, ph) in enumerate(worklist.plane_dims(w, h, cf)):
+            if pw == 0 or (layout == EXPORT_SEMIPLANAR and c == 2):
+                continue
+            native = np.uint8 if (bdl if c == 0 else bdc) <= 8 else np.uint16
+            dt = native if samples == EXPORT_NATIVE else (np.uint16 if samples == EXPORT_MSB16 else np.uint8)
+            out.append((ph, pw * (2 if layout == EXPORT_SEMIPLANAR and c == 1 else 1), np.dtype(dt)))
+        return out
+
+    def frame_export(self, f, layout, samples, rect=None, host=False, pad=20):
+        """start m355_frame_export of frame f (rect = (x0, y0, width, height) in luma samples, None: the whole frame) into buffers of its
+        own — device memory, or with host=True pinned host memory —, every byte of which holds DEVICE_FILL beforehand; the pitch is `pad`
+        bytes LARGER than the row, so rows start at addresses that are no multiple of a vector.  -> token for frame_export_finish"""
+        shapes = self.export_shapes(f, layout, samples, rect)
+        desc = ExportDesc(layout=layout, samples=samples)
+        if rect is not None:
+            desc.x0, desc.y0, desc.width, desc.height = rect
+        bufs = []
+        try:
+            for k, (rows, n, dt) in enumerate(shapes):
+                pitch = n * dt.itemsize + pad
+                if host:
+                    p = self.L.lib.m355_host_alloc(rows * pitch)
+                    if not p:
+                        raise M355Error(4, self.L.error())
+                    ctypes.memset(p, DEVICE_FILL, rows * pitch)
+                else:
+                    p = self.device_alloc(rows * pitch)
+                bufs.append(p)
+                desc.dst[k] = p; desc.pitch[k] = pitch
+            self.L.check(self.L.lib.m355_frame_export(self.h, f, ctypes.byref(desc)))
+        except Exception:
+            for p in bufs:
+                self.L.lib.m355_host_free(p) if host else self.device_free(p)
+            raise
+        return (f, shapes, bufs, [int(desc.pitch[k]) for k in range(len(shapes))], host)
+
+    def frame_export_finish(self, token, raw=False):
+        """the planes of a frame_export, read back (device buffers: m355_device_read, which waits for the context's work; pinned host buffers:
+        behind m355_frame_export_wait) and freed -> list of numpy planes; raw=True: (planes, the whole buffers as (rows, pitch) byte arrays)"""
+        f, shapes, bufs, pitches, host = token
+        if host:
+            self.L.check(self.L.lib.m355_frame_export_wait(self.h, f))
+        planes, raws = [], []
+        for (rows, n, dt), p, pitch in zip(shapes, bufs, pitches):
+            if host:
+                b = np.ctypeslib.as_array(ctypes.cast(p, ctypes.POINTER(ctypes.c_uint8)), (rows * pitch,)).copy()
+                self.L.lib.m355_host_free(p)
+            else:
+                b = self.device_read(p, rows * pitch)
+                self.device_free(p)
+            b = b.reshape(rows, pitch)
+            raws.append(b)
+            planes.append(np.ascontiguousarray(b[:, :n * dt.itemsize]).view(dt))
+        return (planes, raws) if raw else planes
+
+    def frame_export_wait(self, f):
+        self.L.check(self.L.lib.m355_frame_export_wait(self.h, f))
+
+    def frame_export_order(self, f, stream):
+        """the consumer's stream (a hipStream_t as an integer) waits for frame f's last export (m355_frame_export_order)"""
+        self.L.check(self.L.lib.m355_frame_export_order(self.h, f, stream))
 
     def frame_fill(self, f, luma, chroma):
         self.L.check(self.L.lib.m355_frame_fill(self.h, f, luma, chroma))

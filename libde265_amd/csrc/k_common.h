@@ -261,6 +261,22 @@ template <class PP> __host__ __device__ static inline bool m355_res32(const PP& 
 struct TileCopyArgs { char* plane[3]; size_t pitch[3]; TileCopyRect r[M355_TILE_COPY_RECTS]; };
 void m355_launch_tiles_copy(const TileCopyArgs& a, int n, void* xbuf, bool to_slot, hipStream_t st);
 
+/* one m355_frame_export (k_export.hip): the planes of the launch (semi-planar: plane 1 = Cb and Cr interleaved, read from src[1] and src[2]).
+   src[] points at the rectangle's first sample; pitches and row_bytes in BYTES, row_bytes = the DESTINATION row.  A wavefront converts one
+   64-lane chunk (1024 destination bytes) of one row: unit_end[k] = the chunks of planes 0..k, chunks[k] = chunks per row of plane k.
+   shift[k]: MSB16 16 - bit depth, U8 bit depth - 8, else 0.  timeout / epoch: the gate of the decode that wrote the frame (M355_GATE). */
+struct ExportArgs {
+  const uint8_t* src[3];
+  uint8_t* dst[3];
+  long long src_pitch[3], dst_pitch[3];
+  uint32_t row_bytes[3], chunks[3], unit_end[3];
+  int32_t shift[3];
+  const uint32_t* timeout;
+  uint32_t epoch;
+};
+/* src_bytes / dst_bytes: 1 or 2 per sample (2 -> 1: round and clip to 8 bits; 1 -> 2: the 8-bit sample in the high byte) */
+void m355_launch_export(const ExportArgs& a, int src_bytes, int dst_bytes, bool semiplanar, hipStream_t st);
+
 /* first statement of every kernel of a decode: a picture whose lists k_validate rejected is never acted upon */
 /* Element `c` (0..2, per lane) of a three-entry table of the kernel arguments (plane pointers, pitches, ...): all three entries are
  * read as scalars and the lane selects — indexing the argument segment with a per-lane value is a VECTOR memory load from it, i.e. one

@@ -402,6 +402,120 @@ int m355_frame_download_wait(m355_ctx* c, int h)
   f->dl_pending = false;
   return M355_OK;
 }
+/* The frame, or a rectangle of it, converted into memory of the caller (k_export.hip): one launch for all planes, queued — like the copies of
+ * m355_frame_download_async above, and for the reason given there — on the stream of the lane that wrote the frame.  The export is a READER
+ * of the frame: the mark behind it is what the next decode into the frame waits for (dst_hazards), what m355_frame_export_wait blocks on
+ * and what m355_frame_export_order makes a consumer's stream wait for. */
+int m355_frame_export(m355_ctx* c, int h, const m355_export_desc* e)
+{
+  Frame* f = get_frame(c, h);
+  if (!f || !e) return fail(M355_ERR_INVALID, "bad frame handle %d / null descriptor", h);
+  if (e->layout != M355_EXPORT_PLANAR && e->layout != M355_EXPORT_SEMIPLANAR) return fail(M355_ERR_INVALID, "m355_frame_export: unknown layout %d", e->layout);
+  if (e->samples != M355_EXPORT_NATIVE && e->samples != M355_EXPORT_MSB16 && e->samples != M355_EXPORT_U8) return fail(M355_ERR_INVALID, "m355_frame_export: unknown sample format %d", e->samples);
+  const int sw = (f->cf == 1 || f->cf == 2) ? 2 : 1, sh = f->cf == 1 ? 2 : 1;
+  int x0 = 0, y0 = 0, w = f->w, hgt = f->h;
+  if (e->width != 0) {
+    x0 = e->x0; y0 = e->y0; w = e->width; hgt = e->height;
+    if (x0 < 0 || y0 < 0 || w <= 0 || hgt <= 0 || x0 > f->w - w || y0 > f->h - hgt) return fail(M355_ERR_INVALID, "m355_frame_export: rectangle %d,%d %dx%d leaves the %dx%d frame", x0, y0, w, hgt, f->w, f->h);
+    if (f->cf && ((x0 | w) % sw || (y0 | hgt) % sh)) return fail(M355_ERR_INVALID, "m355_frame_export: rectangle %d,%d %dx%d is not aligned to the chroma grid (%dx%d luma samples)", x0, y0, w, hgt, sw, sh);
+  }
+  const bool semi = e->layout == M355_EXPORT_SEMIPLANAR && f->cf != 0;
+  const int np = f->cf == 0 ? 1 : (semi ? 2 : 3);
+  ExportArgs a = {};
+  uint32_t units = 0;
+  for (int p = 0; p < 3; p++) {
+    if (p < np) {
+      const int bd = p ? f->bdc : f->bdl, sb = f->bpp[p];
+      const int db = e->samples == M355_EXPORT_NATIVE ? sb : (e->samples == M355_EXPORT_MSB16 ? 2 : 1);
+      const int pw = p ? w / sw : w, ph = p ? hgt / sh : hgt, px = p ? x0 / sw : x0, py = p ? y0 / sh : y0;
+      const int64_t rb = (int64_t)pw * db * (semi && p ? 2 : 1);
+      if (!e->dst[p]) return fail(M355_ERR_INVALID, "m355_frame_export: no destination for plane %d", p);
+      if (e->pitch[p] < rb) return fail(M355_ERR_INVALID, "m355_frame_export: pitch %lld of plane %d is below its row of %lld bytes", (long long)e->pitch[p], p, (long long)rb);
+      a.dst[p] = (uint8_t*)e->dst[p]; a.dst_pitch[p] = e->pitch[p];
+      a.src_pitch[p] = (long long)f->stride[p] * sb;
+      a.row_bytes[p] = (uint32_t)rb; a.chunks[p] = (uint32_t)((rb + 1023) / 1024);
+      a.shift[p] = e->samples == M355_EXPORT_MSB16 ? 16 - bd : (e->samples == M355_EXPORT_U8 ? bd - 8 : 0);
+      units += a.chunks[p] * (uint32_t)ph;
+      for (int q = p; q < (semi && p ? 3 : p + 1); q++) a.src[q] = (const uint8_t*)f->plane[q] + (size_t)py * a.src_pitch[p] + (size_t)px * sb;
+    }
+    a.unit_end[p] = units;
+  }
+  hipSetDevice(c->device);
+  hipStream_t cs = f->wr_stream ? f->wr_stream : lane(c).stream;                /* (no decode of this context wrote it: uploads and fills are synchronous) */
+  if (!f->wr_stream) ev_wait(c, cs, f->wr);
+  ev_wait(c, cs, f->ex);                                                        /* (an earlier export on another stream: the one mark kept stands for both) */
+  if (f->wr_stream && f->wr_gate) { a.timeout = f->wr_gate; a.epoch = f->wr_epoch; }
+  else {                                                                        /* no decode to be gated by: an epoch of its own, which no gate word holds */
+    a.timeout = lane(c).timeout; a.epoch = ++c->epoch;
+    if (a.epoch == 0) a.epoch = ++c->epoch;
+  }
+  m355_launch_export(a, f->bpp[0], e->samples == M355_EXPORT_NATIVE ? f->bpp[0] : (e->samples == M355_EXPORT_MSB16 ? 2 : 1), semi, cs);
+  HIPCHK(hipGetLastError());
+  return ev_mark(c, cs, &f->ex);
+}
+/* the host waits until this frame's last export has landed */
+int m355_frame_export_wait(m355_ctx* c, int h)
+{
+  Frame* f = get_frame(c, h);
+  if (!f) return fail(M355_ERR_INVALID, "bad frame handle %d", h);
+  hipSetDevice(c->device);
+  HIPCHK(ev_sync(c, f->ex));
+  f->ex = EvRef();
+  return M355_OK;
+}
+/* the consumer's stream continues behind this frame's last export (nothing to enqueue when that has long passed: its mark has left the ring) */
+int m355_frame_export_order(m355_ctx* c, int h, void* consumer)
+{
+  Frame* f = get_frame(c, h);
+  if (!f) return fail(M355_ERR_INVALID, "bad frame handle %d", h);
+  hipSetDevice(c->device);
+  ev_wait(c, (hipStream_t)consumer, f->ex);
+  return M355_OK;
+}
+/* Device memory for the destinations of m355_frame_export, for applications (and tests) that have no HIP runtime of their own in the process */
+void* m355_device_alloc(m355_ctx* c, size_t bytes)
+{
+  if (!c) { fail(M355_ERR_INVALID, "m355_device_alloc: no context"); return nullptr; }
+  hipSetDevice(c->device);
+  void* p = nullptr;
+  if (hipMalloc(&p, bytes ? bytes : 1) != hipSuccess) { fail(M355_ERR_NOMEM, "hipMalloc(%zu) failed", bytes); return nullptr; }
+  return p;
+}
+void m355_device_free(m355_ctx* c, void* p)
+{
+  if (!c || !p) return;
+  hipSetDevice(c->device);
+  sync_all(c);                                              /* (an export into it may still be running) */
+  hipFree(p);
+}
+int m355_device_read(m355_ctx* c, const void* src, void* dst, size_t bytes)
+{
+  if (!c || (bytes && (!src || !dst))) return fail(M355_ERR_INVALID, "m355_device_read: bad arguments");
+  if (!bytes) return M355_OK;
+  hipSetDevice(c->device);
+  HIPCHK(sync_all(c));                                      /* whichever lane's export wrote the memory */
+  int rc = stage_reserve(c, bytes);
+  if (rc) return rc;
+  const hipStream_t st = lane(c).stream;
+  HIPCHK(hipMemcpyAsync(c->stage, src, bytes, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  memcpy(dst, c->stage, bytes);
+  return M355_OK;
+}
+int m355_device_write(m355_ctx* c, void* dst, const void* src, size_t bytes)
+{
+  if (!c || (bytes && (!src || !dst))) return fail(M355_ERR_INVALID, "m355_device_write: bad arguments");
+  if (!bytes) return M355_OK;
+  hipSetDevice(c->device);
+  HIPCHK(sync_all(c));                                      /* (an export into the memory, on whichever lane) */
+  int rc = stage_reserve(c, bytes);
+  if (rc) return rc;
+  memcpy(c->stage, src, bytes);
+  const hipStream_t st = lane(c).stream;
+  HIPCHK(hipMemcpyAsync(dst, c->stage, bytes, hipMemcpyHostToDevice, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return M355_OK;
+}
 int m355_frame_fill(m355_ctx* c, int h, int vl, int vc)
 {
   Frame* f = get_frame(c, h);
@@ -661,7 +775,7 @@ int m355_wait(m355_ctx* c)
 {
   hipSetDevice(c->device);
   HIPCHK(sync_all(c));
-  for (auto& f : c->frames) { f.wr = EvRef(); f.dl_pending = false; for (int k = 0; k < M355_MAX_LANES; k++) f.rd[k] = EvRef(); }   /* everything is complete */
+  for (auto& f : c->frames) { f.wr = EvRef(); f.ex = EvRef(); f.dl_pending = false; for (int k = 0; k < M355_MAX_LANES; k++) f.rd[k] = EvRef(); }   /* everything is complete */
   uint32_t t = 0;
   for (const Lane& l : c->lanes)
     if (l.timeout) { uint32_t t2 = 0; HIPCHK(hipMemcpy(&t2, l.timeout, 4, hipMemcpyDeviceToHost)); t |= t2; }

@@ -287,18 +287,21 @@ hipStream_t launch_prediction(m355_ctx* c, const Resident& r, const DevPic& d, b
    stage when SAO runs (everything before writes this lane's working planes), else the first stage */
 void dst_hazards(m355_ctx* c, Frame* dstf, bool piped, hipStream_t st) {
   if (dstf->dl_pending) hipStreamWaitEvent(st, dstf->ev_dl, 0);     /* (stays pending for the HOST until m355_frame_download_wait / m355_wait) */
+  ev_wait(c, st, dstf->ex);                                          /* an export of the frame's previous picture (queued on that picture's stream) */
   if (!piped) return;
   ev_wait(c, st, dstf->wr);
   for (int k = 0; k < M355_MAX_LANES; k++) ev_wait(c, st, dstf->rd[k]);
 }
 
 /* ONE mark behind the last kernel on `st` into the lists (their arenas), the destination frame (its next reader / writer) and the lane
-   (its next decode, which may run on the lane's other stream): -> r.done */
-int mark_done(m355_ctx* c, Resident& r, Frame* dstf, hipStream_t st) {
+   (its next decode, which may run on the lane's other stream): -> r.done.  d: the decode's record — its gate travels with the frame (m355_frame_export); the phases of a
+   sharded picture pass none: their lists are checked on the host, no decode of theirs is ever gated */
+int mark_done(m355_ctx* c, Resident& r, Frame* dstf, hipStream_t st, const DevPic* d) {
   const int rc = ev_mark(c, st, &r.done);
   if (rc) return rc;
   r.fresh = false;
   dstf->wr_stream = st; dstf->wr = r.done;
+  dstf->wr_gate = d ? d->timeout : nullptr; dstf->wr_epoch = d ? d->epoch : 0;
   lane(c).last = r.done; lane(c).last_stream = st;
   return M355_OK;
 }
@@ -411,7 +414,7 @@ static int decode_post(m355_ctx* c, Resident& r, DecodeState& S, bool filters = 
   /* ONE mark behind the decode's last kernel for everything that has to know when it is over: the lists' arenas, the destination
      frame's next reader / writer, the reference frames' next writer, the lane's next decode, the status slot */
   {
-    const int rcm = mark_done(c, r, dstf, st);
+    const int rcm = mark_done(c, r, dstf, st, &d);
     if (rcm) return rcm;
   }
   const EvRef done = r.done;

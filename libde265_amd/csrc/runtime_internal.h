@@ -84,7 +84,12 @@ struct Frame {
   /* a download in flight on the context's copy stream (m355_frame_download_async): the next writer of the frame waits for it */
   hipEvent_t ev_dl = nullptr;
   bool dl_pending = false;
-  hipStream_t wr_stream = nullptr;         /* the stream that last wrote the frame (its downloads are queued on that stream) */
+  hipStream_t wr_stream = nullptr;         /* the stream that last wrote the frame (its downloads and exports are queued on that stream) */
+  /* the gate of the decode that last wrote the frame (its lane's gate words, its epoch): an export queued behind a decode whose lists were
+     rejected does nothing, like that decode's own kernels (M355_GATE) */
+  const uint32_t* wr_gate = nullptr; uint32_t wr_epoch = 0;
+  /* the last export in flight (m355_frame_export, a reader of the frame): the next writer waits for it in front of its first write */
+  EvRef ex;
 };
 
 static void frame_geometry(Frame& f, int w, int h, int cf, int bdl, int bdc)
@@ -121,6 +126,7 @@ static void frame_free(Frame& f)
   f.wr = EvRef();
   for (int k = 0; k < M355_MAX_LANES; k++) f.rd[k] = EvRef();
   f.ev_dl = nullptr; f.dl_pending = false; f.wr_stream = nullptr;
+  f.wr_gate = nullptr; f.wr_epoch = 0; f.ex = EvRef();
   f.used = false;
 }
 
@@ -309,7 +315,7 @@ int lane_class_priority(int index);
 int lane_priorities_mode();
 hipStream_t launch_prediction(m355_ctx* c, const Resident& r, const DevPic& d, bool hbd, hipStream_t st, hipEvent_t* ev, bool with_intra = true, hipStream_t chain = nullptr, Frame* hazard_dst = nullptr);
 void make_layout(const m355_arena_caps& k, int nCtb, int halo_units, bool sharded, bool with_ib_input, Lay& L);
-int mark_done(m355_ctx* c, Resident& r, Frame* dstf, hipStream_t st);
+int mark_done(m355_ctx* c, Resident& r, Frame* dstf, hipStream_t st, const DevPic* d = nullptr);
 int prepare(m355_ctx* c, Resident& r, DevPic& d_out, bool& want_sao_out, hipStream_t st);
 size_t slot_bytes(const m355_pic_params& pp, int nranks);
 int status_of(m355_ctx* c, m355_ctx::Status& s);

@@ -1,0 +1,135 @@
+#!/usr/bin/env python3
+"""What m355_frame_export costs at the C5 frame geometry (7680x4320, 10-bit, 4:2:0), timed with events on the context's stream in one process:
+
+  (a) three hipMemcpy2DAsync device-to-device plane copies on that stream, between buffers with the frame's pitch — what an application
+      could do today if it had the plane pointers
+  (b) m355_frame_export NATIVE planar, whole frame
+  (c) MSB16 semi-planar, the frame minus an 8-sample border (x0 = y0 = 8: misaligned source rows)
+  (d) U8 semi-planar, whole frame
+  (e), (f) what separates (c) from (b): MSB16 semi-planar uncropped, NATIVE planar cropped
+
+and, beside them, m355_measure_copy_rate for the frame's byte count.  Every figure is the median of --iters launches; (b) is measured in
+--rounds separate rounds spread over the run, and the spread of their medians is the margin (c) and (d) are held against.  The HIP calls
+of (a) and the events go to the runtime the library itself has loaded (no second runtime in the process).
+
+  python tools/export_bench.py [--out profiles/export_bench.txt]
+"""
+import argparse
+import ctypes
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from libde265_amd import capi  # noqa: E402
+
+W, H, BD = 7680, 4320, 10
+D2D = 3   # hipMemcpyDeviceToDevice
+
+
+def hip_runtime():
+    """the HIP runtime the product library is linked against, as already mapped into this process"""
+    with open("/proc/self/maps") as f:
+        for line in f:
+            if "libamdhip64" in line:
+                return ctypes.CDLL(line.split()[-1])
+    raise RuntimeError("the product library has not loaded a HIP runtime")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=30)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--out", default=None, help="append the result lines to this file")
+    args = ap.parse_args()
+
+    lib = capi.Library()
+    ctx = capi.Context(lib, 0)
+    hip = hip_runtime()
+    vp = ctypes.c_void_p
+    hip.hipEventCreate.argtypes = [ctypes.POINTER(vp)]
+    hip.hipEventRecord.argtypes = [vp, vp]
+    hip.hipEventSynchronize.argtypes = [vp]
+    hip.hipEventElapsedTime.argtypes = [ctypes.POINTER(ctypes.c_float), vp, vp]
+    hip.hipMemcpy2DAsync.argtypes = [vp, ctypes.c_size_t, vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int, vp]
+    e0, e1 = vp(), vp()
+    assert hip.hipEventCreate(ctypes.byref(e0)) == 0 and hip.hipEventCreate(ctypes.byref(e1)) == 0
+
+    frame = ctx.frame_create(W, H, 1, BD, BD)
+    ctx.frame_fill(frame, 600, 500)
+    stream = ctx.stream()          # the frame was written by no decode: its exports run on the active lane's stream
+    planes = [(W, H), (W // 2, H // 2), (W // 2, H // 2)]
+    frame_bytes = sum(w * h * 2 for w, h in planes)
+    pitch = [(w * 2 + 127) // 128 * 128 for w, h in planes]
+    src = [ctx.device_alloc(p * h + 256, fill=0x5A) for p, (w, h) in zip(pitch, planes)]
+    # one set of destinations, large enough for every variant
+    dst = [ctx.device_alloc(n, fill=None) for n in (W * 2 * H, W * 2 * (H // 2), W * (H // 2))]
+
+    def timed(fn):
+        ms = []
+        for k in range(-3, args.iters):
+            hip.hipEventRecord(e0, stream)
+            fn()
+            hip.hipEventRecord(e1, stream)
+            assert hip.hipEventSynchronize(e1) == 0
+            t = ctypes.c_float()
+            assert hip.hipEventElapsedTime(ctypes.byref(t), e0, e1) == 0
+            if k >= 0:
+                ms.append(t.value)
+        return statistics.median(ms)
+
+    def copies():
+        for k, (w, h) in enumerate(planes):
+            assert hip.hipMemcpy2DAsync(dst[k], w * 2, src[k], pitch[k], w * 2, h, D2D, stream) == 0
+
+    def export(layout, samples, rect, elem):
+        d = capi.ExportDesc(layout=layout, samples=samples)
+        if rect:
+            d.x0, d.y0, d.width, d.height = rect
+        w = rect[2] if rect else W
+        rows = [w * elem, w * elem if layout else w // 2 * elem, w // 2 * elem]
+        for k in range(3):
+            d.dst[k] = dst[k]; d.pitch[k] = rows[k]
+        return lambda: lib.check(lib.lib.m355_frame_export(ctx.h, frame, ctypes.byref(d)))
+
+    variants = {
+        "a_memcpy2d_x3": copies,
+        "b_native_planar": export(capi.EXPORT_PLANAR, capi.EXPORT_NATIVE, None, 2),
+        "c_msb16_semiplanar_crop8": export(capi.EXPORT_SEMIPLANAR, capi.EXPORT_MSB16, (8, 8, W - 16, H - 16), 2),
+        "d_u8_semiplanar": export(capi.EXPORT_SEMIPLANAR, capi.EXPORT_U8, None, 1),
+        # beside the four: (c) without its crop (aligned source rows, interleaved stores) and (b) with it (misaligned rows, plain stores)
+        "e_msb16_semiplanar": export(capi.EXPORT_SEMIPLANAR, capi.EXPORT_MSB16, None, 2),
+        "f_native_planar_crop8": export(capi.EXPORT_PLANAR, capi.EXPORT_NATIVE, (8, 8, W - 16, H - 16), 2),
+    }
+    ms = {n: [] for n in variants}
+    for _ in range(args.rounds):
+        for n, fn in variants.items():
+            ms[n].append(timed(fn))
+    ctx.wait()
+    res = {n: statistics.median(v) for n, v in ms.items()}
+    b = ms["b_native_planar"]
+    spread = max(b) - min(b)
+    out = {
+        "geometry": "%dx%d %d-bit 4:2:0, %d bytes per frame" % (W, H, BD, frame_bytes),
+        "iters": args.iters, "rounds": args.rounds,
+        "ms_median": res, "ms_rounds": ms, "b_spread_ms": spread,
+        "GBps_read_plus_written": {"a_memcpy2d_x3": 2 * frame_bytes / res["a_memcpy2d_x3"] / 1e6, "b_native_planar": 2 * frame_bytes / res["b_native_planar"] / 1e6},
+        "copy_rate_GBps_same_bytes": ctx.measure_copy_rate(frame_bytes, 9),
+        "bars": {"b_le_a": res["b_native_planar"] <= res["a_memcpy2d_x3"],
+                 "c_le_b_plus_spread": res["c_msb16_semiplanar_crop8"] <= res["b_native_planar"] + spread,
+                 "d_le_b_plus_spread": res["d_u8_semiplanar"] <= res["b_native_planar"] + spread},
+    }
+    line = json.dumps(out)
+    print(line)
+    if args.out:
+        with open(args.out, "a") as f:
+            f.write(line + "\n")
+    for p in src + dst:
+        ctx.device_free(p)
+    ctx.close()
+
+
+if __name__ == "__main__":
+    main()
