@@ -11,8 +11,10 @@
  *   generate_inter_prediction_samples   motion.cc:288      -> record one m355_pb with the host-side decisions
  *   decoder_context::run_postprocessing_filters_sequential / _parallel   decctx.cc:1783 / 1811
  *                                                          -> walk the picture's metadata, m355_submit_picture()
- *   process_sei                         sei.cc:436         -> decoded picture hash SEIs are checked against the DEVICE frame (m355_frame_hash)
+ *   process_sei                         sei.cc:436         -> decoded picture hash SEIs are checked against the DEVICE frame (m355_frame_hash;
+ *                                                             M355_GLUE_ASYNC_HASH=1: m355_frame_hash_async, the verdict when the picture leaves the decoder)
  *   de265_new_decoder / de265_free_decoder / de265_get_image_plane   de265.cc:254-281, 729-738 (renamed in de265.o, wrapped here)
+ *   de265_get_next_picture / de265_peek_next_picture / de265_flush_data / de265_reset   (likewise: where pending hash verdicts are taken)
  *                                                          -> backend context; a picture is downloaded when its samples are asked for
  * deblock.cc, sao.cc, fallback-*.cc and x86/*.cc are not compiled at all (the entry points the parser's objects still name
  * exist here as traps; init_acceleration_functions_fallback fills the decoder's table with counting traps).
@@ -70,6 +72,10 @@ de265_error m355ref_de265_free_decoder(de265_decoder_context*);
 const uint8_t* m355ref_de265_get_image_plane(const struct de265_image*, int, int*);
 void m355ref_de265_set_parameter_bool(de265_decoder_context*, enum de265_param, int);
 int m355ref_de265_get_parameter_bool(de265_decoder_context*, enum de265_param);
+const struct de265_image* m355ref_de265_get_next_picture(de265_decoder_context*);
+const struct de265_image* m355ref_de265_peek_next_picture(de265_decoder_context*);
+de265_error m355ref_de265_flush_data(de265_decoder_context*);
+void m355ref_de265_reset(de265_decoder_context*);
 }
 
 namespace {
@@ -82,7 +88,7 @@ namespace {
   X(m355_host_alloc) X(m355_host_free) X(m355_frame_hash) X(m355_arena_begin) X(m355_last_serial) X(m355_decode_status) \
   X(m355_frame_download_async) X(m355_frame_download_wait) X(m355_frame_export) X(m355_frame_export_order) \
   X(m355_group_create) X(m355_group_destroy) X(m355_group_decode) X(m355_picture_upload) X(m355_picture_replace) X(m355_shard_owner_of_tile) \
-  X(m355_picture_arena_begin)
+  X(m355_picture_arena_begin) X(m355_frame_hash_async) X(m355_frame_hash_result)
 
 struct Api {
   void* handle = nullptr;
@@ -225,6 +231,11 @@ struct Glue {
   std::deque<Job> jobs;
   bool busy = false, stop = false, sync_submit = false;
   bool narrow = false;              /* M355_GLUE_NARROW=1 when the decoder was created: scale_coefficients writes M355_RBF_NARROW blocks */
+  /* M355_GLUE_ASYNC_HASH=1 when the decoder was created (one rank only): process_sei enqueues the picture's hash behind its decode
+     (m355_frame_hash_async) and returns; the verdict is taken when the picture leaves the decoder (hash_verdicts).  Under api_mu. */
+  bool async_hash = false;
+  struct PendingHash { unsigned long long ticket; uint32_t img_id; int type, n; sei_decoded_picture_hash want; };
+  std::deque<PendingHash> hash_pending;
   uint32_t busy_id = 0xFFFFFFFFu;
   uint32_t busy_dpb_id[M355_MAX_REF_FRAMES];    /* the DPB snapshot of the job the worker is running */
   /* DE265_DECODER_PARAM_DISABLE_SAO as the application set it.  The decoder's own param_disable_sao is kept TRUE: that is what
@@ -279,6 +290,7 @@ Glue* glue_of(const decoder_context* d)
 void install_traps(acceleration_functions& a);
 void wait_submitted(Glue* g, uint32_t id, bool also_as_reference = false);
 void flush_warnings(Glue* g);
+void hash_verdicts(Glue* g, uint32_t id, bool decoder_thread);
 
 /* the calling thread's lists for the picture `img` */
 ThreadRec* rec_for(de265_image* img)
@@ -372,6 +384,7 @@ void glue_release_buffer(de265_decoder_context* ctx, de265_image* img, void* use
   Glue* g = (Glue*)userdata;
   wait_submitted(g, img->get_ID(), true);         /* the DPB recycles the image (dpb.cc:206-216): the worker may still be walking its metadata,
                                                      or reading it as a reference of a later picture's job */
+  hash_verdicts(g, img->get_ID(), false);         /* a picture with a hash request pending that the application never fetched */
   {
     /* a download started behind the picture's decode that nobody waited for (the application never looked at the picture): it must
        have landed before the planes go back to the pool — the next image's parser may write PCM samples into them */
@@ -487,6 +500,36 @@ void download_if_needed(Glue* g, de265_image* img)
   g->host_id[slot] = img->get_ID();
   g->n_downloads++;
   g->ms_download += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+/* M355_GLUE_ASYNC_HASH=1: collect one request and compare (api_mu held; blocks for that request's mark only).  A mismatch, or a hash that
+   could not be made (the picture's lists were rejected), is DE265_ERROR_CHECKSUM_MISMATCH on the decoder's warning queue. */
+void take_verdict(Glue* g, const Glue::PendingHash& p)
+{
+  m355_picture_hash got; memset(&got, 0, sizeof(got));
+  bool ok = api()->m355_frame_hash_result(g->mctx, p.ticket, 1, &got) == M355_OK;
+  if (!ok) fprintf(stderr, "libde265 (MI355X glue): picture hash: %s\n", api()->m355_last_error());
+  g->n_hashed++;
+  for (int c = 0; ok && c < p.n; c++) {
+    if (p.type == M355_HASH_MD5) ok = memcmp(got.md5[c], p.want.md5[c], 16) == 0;
+    else if (p.type == M355_HASH_CRC) ok = got.crc[c] == p.want.crc[c];
+    else ok = got.checksum[c] == p.want.checksum[c];
+  }
+  if (!ok) { std::lock_guard<std::mutex> lk(g->job_mu); g->deferred_warnings.push_back(DE265_ERROR_CHECKSUM_MISMATCH); }
+}
+/* the verdicts of picture `id` (0xFFFFFFFF: of every picture); on the decoder's own thread they reach its warning queue at once */
+void hash_verdicts(Glue* g, uint32_t id, bool decoder_thread)
+{
+  if (!g->async_hash) return;
+  {
+    std::lock_guard<std::mutex> api_lock(g->api_mu);
+    for (auto it = g->hash_pending.begin(); it != g->hash_pending.end();) {
+      if (id != 0xFFFFFFFFu && it->img_id != id) { ++it; continue; }
+      take_verdict(g, *it);
+      it = g->hash_pending.erase(it);
+    }
+  }
+  if (decoder_thread) flush_warnings(g);
 }
 
 /* ------------------------------------------------------------------ picture submission ----------- */
@@ -1446,9 +1489,23 @@ de265_error process_sei(const sei_message* sei, de265_image* img)
   std::lock_guard<std::mutex> api_lock(g->api_mu);
   const int slot = slot_of(g->dctx, img);
   if (slot < 0 || g->frame_of_slot[slot] < 0 || g->dev_id[slot] != img->get_ID()) return DE265_OK;   /* not a picture the backend decoded */
-  collect_status(g, slot);                                                    /* waits for its decode; a rejected picture is reported there */
   const sei_decoded_picture_hash* want = &sei->data.decoded_picture_hash;
   const int type = want->hash_type == sei_decoded_picture_hash_type_MD5 ? M355_HASH_MD5 : (want->hash_type == sei_decoded_picture_hash_type_CRC ? M355_HASH_CRC : M355_HASH_CHECKSUM);
+  if (g->async_hash) {
+    /* nothing is waited for: the request runs behind the picture's decode, the pictures in flight on the other lanes go on; the verdict is
+       taken when the picture leaves the decoder (de265_get_next_picture / de265_peek_next_picture below, the release hook, flush, reset) */
+    if (want->hash_type > sei_decoded_picture_hash_type_checksum) return DE265_OK;
+    if (g->hash_pending.size() >= M355_HASH_REQUESTS) { take_verdict(g, g->hash_pending.front()); g->hash_pending.pop_front(); }
+    Glue::PendingHash p;
+    p.img_id = img->get_ID(); p.type = type; p.n = img->get_sps().chroma_format_idc == 0 ? 1 : 3; p.want = *want;
+    if (api()->m355_frame_hash_async(g->mctx, g->frame_of_slot[slot], type, &p.ticket) != M355_OK) {
+      fprintf(stderr, "libde265 (MI355X glue): picture hash: %s\n", api()->m355_last_error());
+      return DE265_ERROR_CHECKSUM_MISMATCH;
+    }
+    g->hash_pending.push_back(p);
+    return DE265_OK;
+  }
+  collect_status(g, slot);                                                    /* waits for its decode; a rejected picture is reported there */
   if (want->hash_type > sei_decoded_picture_hash_type_checksum) return DE265_OK;
   m355_picture_hash got; memset(&got, 0, sizeof(got));
   if (api()->m355_frame_hash(g->mctx, g->frame_of_slot[slot], type, &got) != M355_OK) {
@@ -1525,6 +1582,7 @@ LIBDE265_API de265_decoder_context* de265_new_decoder()
   if (depth >= 1 && depth <= 16) for (m355_ctx* x : g->rctx) A->m355_set_pipeline_depth(x, g->n_ranks > 1 ? std::min(depth, 3) : depth);
   g->sync_submit = getenv("M355_GLUE_SYNC") != nullptr;
   g->narrow = getenv("M355_GLUE_NARROW") && atoi(getenv("M355_GLUE_NARROW")) != 0;
+  g->async_hash = g->n_ranks == 1 && getenv("M355_GLUE_ASYNC_HASH") && atoi(getenv("M355_GLUE_ASYNC_HASH")) != 0;   /* (a sharded context takes no hash requests) */
   if (!g->sync_submit) g->worker = std::thread(worker_main, g);
   install_traps(g->dctx->acceleration);
   de265_image_allocation alloc = {glue_get_buffer, glue_release_buffer};
@@ -1559,6 +1617,7 @@ LIBDE265_API de265_error de265_free_decoder(de265_decoder_context* c)
   }
   if (g) {
     wait_submitted(g, 0xFFFFFFFFu);
+    hash_verdicts(g, 0xFFFFFFFFu, false);
     std::lock_guard<std::mutex> api_lock(g->api_mu);
     collect_status(g, -1);
     for (size_t r = 1; r < g->rctx.size(); r++) api()->m355_wait(g->rctx[r]);
@@ -1587,6 +1646,31 @@ LIBDE265_API de265_error de265_free_decoder(de265_decoder_context* c)
     delete g;                                                /* ThreadRecs stay allocated (see rec_for) */
   }
   return e;
+}
+
+/* M355_GLUE_ASYNC_HASH=1: the picture about to be handed to the application has its hash verdict taken first (de265.cc:676-712), so a mismatch
+ * is on the warning queue no later than the picture is in the application's hands; flush and reset take every pending verdict. */
+LIBDE265_API const struct de265_image* de265_peek_next_picture(de265_decoder_context* c)
+{
+  const struct de265_image* img = m355ref_de265_peek_next_picture(c);
+  Glue* g = img ? glue_of((decoder_context*)c) : nullptr;
+  if (g) hash_verdicts(g, img->get_ID(), true);
+  return img;
+}
+LIBDE265_API const struct de265_image* de265_get_next_picture(de265_decoder_context* c)
+{
+  de265_peek_next_picture(c);
+  return m355ref_de265_get_next_picture(c);
+}
+LIBDE265_API de265_error de265_flush_data(de265_decoder_context* c)
+{
+  if (Glue* g = glue_of((decoder_context*)c)) { if (g->async_hash) wait_submitted(g, 0xFFFFFFFFu); hash_verdicts(g, 0xFFFFFFFFu, true); }
+  return m355ref_de265_flush_data(c);
+}
+LIBDE265_API void de265_reset(de265_decoder_context* c)
+{
+  if (Glue* g = glue_of((decoder_context*)c)) { if (g->async_hash) wait_submitted(g, 0xFFFFFFFFu); hash_verdicts(g, 0xFFFFFFFFu, true); }
+  m355ref_de265_reset(c);
 }
 
 /* The application touches a decoded picture's samples through this call (de265.cc:729-738; dec265's writer, a player's

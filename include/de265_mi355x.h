@@ -477,7 +477,9 @@ M355_API void  m355_host_free(void* p);
  * Replaces compute_MD5 / compute_CRC_8bit_fast / compute_checksum (sei.cc:161-258) as called by
  * process_sei_decoded_picture_hash (sei.cc:276-356); hash_type and the result fields are those of
  * sei_decoded_picture_hash (sei.h:57-70).  Only the field of the requested type is written, for plane 0 (monochrome)
- * or planes 0..2.  Synchronous: waits for the pictures in flight.  CRC and checksum run on the device (the frame is not
+ * or planes 0..2.  Synchronous: waits for the pictures in flight — for EVERY picture on every lane, not only for the frame's own:
+ * a caller that hashes every picture decodes one picture at a time, whatever m355_set_pipeline_depth says (m355_frame_hash_async
+ * below does not).  CRC and checksum run on the device (the frame is not
  * copied back); MD5 is one serial chain per plane, so the planes are downloaded and hashed on host threads. */
 #define M355_HASH_MD5      0
 #define M355_HASH_CRC      1
@@ -488,6 +490,24 @@ typedef struct m355_picture_hash {
   uint32_t checksum[3];
 } m355_picture_hash;
 M355_API int m355_frame_hash(m355_ctx* ctx, int frame, int hash_type, m355_picture_hash* out);
+/* The same hash as a REQUEST queued behind the frame's decode: m355_frame_hash_async enqueues the hash of the frame as its last writer
+ * leaves it and returns without waiting for anything; the pictures in flight on the other lanes go on.  The request is a reader of the
+ * frame, like m355_frame_export: it runs on the stream of the decode that wrote the frame, and the next decode INTO the frame waits
+ * for it in front of its first write — hash a frame, then decode the next picture into it, and the value is the earlier picture's.
+ * CRC / checksum: one kernel launch that reduces the planes and writes the values into pinned memory of the request.  MD5: the planes
+ * are copied into pinned planes of the request behind the decode and hashed on host threads when the result is collected.
+ * *ticket counts 1, 2, ... per context.  At most M355_HASH_REQUESTS requests may be outstanding (enqueued and not yet collected):
+ * one more returns M355_ERR_BUSY and enqueues nothing.  M355_ERR_INVALID (nothing enqueued): bad frame handle, bad hash type, null
+ * ticket, or a tile-sharded context (its frames are complete only behind the gather).
+ * m355_frame_hash_result collects a request and frees its slot: block = 0 -> M355_ERR_BUSY while the request has not finished
+ * (nothing is waited for, the request stays), block = 1 -> the host waits for THAT request only.  M355_OK: the field of the requested
+ * type is filled as by m355_frame_hash, bit for bit.  M355_ERR_INVALID: an unknown or already collected ticket; or — the request is
+ * collected all the same — a hash queued behind a decode whose lists were rejected on the device (m355_decode_status): like an
+ * export behind such a decode it has produced nothing.  m355_wait completes every request and collects none; a frame may be
+ * destroyed with requests pending (they are completed first and stay collectable). */
+#define M355_HASH_REQUESTS 16
+M355_API int m355_frame_hash_async(m355_ctx* ctx, int frame, int hash_type, unsigned long long* ticket);
+M355_API int m355_frame_hash_result(m355_ctx* ctx, unsigned long long ticket, int block, m355_picture_hash* out);
 
 /* Replaces (deferred): decode_TU (slice.cc:3460), decode_prediction_unit (motion.cc:2190) and
  * run_postprocessing_filters_sequential/_parallel (decctx.cc:1783/1811) for one picture. Asynchronous:

@@ -101,6 +101,9 @@ class Library:
         L.m355_host_alloc.restype = vp
         L.m355_host_free.argtypes = [vp]
         L.m355_frame_hash.argtypes = [vp, i, i, vp]
+        if hasattr(L, "m355_frame_hash_async"):         # (absent from older builds loaded through M355_LIB for an A/B)
+            L.m355_frame_hash_async.argtypes = [vp, i, i, ctypes.POINTER(ctypes.c_ulonglong)]
+            L.m355_frame_hash_result.argtypes = [vp, ctypes.c_ulonglong, i, vp]
         L.m355_submit_picture.argtypes = [vp, vp]
         L.m355_wait.argtypes = [vp]
         L.m355_last_serial.argtypes = [vp]
@@ -175,6 +178,7 @@ class Context:
         self.L.check(self.L.lib.m355_create(device, ctypes.byref(h)))
         self.h = h
         self._geom = {}
+        self._hash_reqs = {}            # ticket -> (hash type, planes) of the requests not collected yet
 
     def close(self):
         if self.h:
@@ -385,6 +389,26 @@ class Context:
         self.L.check(self.L.lib.m355_frame_hash(self.h, f, hash_type, ctypes.addressof(out)))
         w, h, cf, bdl, bdc = self._geom[f]
         n = 3 if cf else 1
+        if hash_type == HASH_MD5:
+            return [bytes(out.md5[c]) for c in range(n)]
+        return [int((out.crc if hash_type == HASH_CRC else out.checksum)[c]) for c in range(n)]
+
+    def frame_hash_async(self, f, hash_type):
+        """enqueue the hash of the frame as its last writer leaves it (m355_frame_hash_async; nothing is waited for) -> ticket"""
+        t = ctypes.c_ulonglong(0)
+        self.L.check(self.L.lib.m355_frame_hash_async(self.h, f, hash_type, ctypes.byref(t)))
+        self._hash_reqs[t.value] = (hash_type, 3 if self._geom[f][2] else 1)
+        return int(t.value)
+
+    def frame_hash_result(self, ticket, block=True):
+        """collect a request (m355_frame_hash_result): the list frame_hash returns; None while it has not finished (block=False);
+        raises M355Error for an unknown / collected ticket and for a hash queued behind a rejected decode"""
+        out = PictureHash()
+        rc = self.L.lib.m355_frame_hash_result(self.h, ticket, 1 if block else 0, ctypes.addressof(out))
+        if rc == 6 and not block:                               # M355_ERR_BUSY
+            return None
+        self.L.check(rc)
+        hash_type, n = self._hash_reqs.pop(ticket)
         if hash_type == HASH_MD5:
             return [bytes(out.md5[c]) for c in range(n)]
         return [int((out.crc if hash_type == HASH_CRC else out.checksum)[c]) for c in range(n)]

@@ -182,6 +182,29 @@ int m355_device_count(void)
   return n;
 }
 
+/* the slots of m355_frame_hash_async: device records (zeroed here, once: every request leaves its record zero), pinned result records, marks */
+static int hash_requests_create(m355_ctx* c)
+{
+  hipStream_t st = c->lanes[0].stream;
+  HIPCHK(hipMalloc(&c->hash_rec, M355_HASH_REQUESTS * HASH_REC_WORDS * sizeof(uint32_t)));
+  HIPCHK(hipMemsetAsync(c->hash_rec, 0, M355_HASH_REQUESTS * HASH_REC_WORDS * sizeof(uint32_t), st));
+  HIPCHK(hipStreamSynchronize(st));
+  HIPCHK(hipHostMalloc(&c->hash_res, M355_HASH_REQUESTS * HASH_RES_WORDS * sizeof(uint32_t), hipHostMallocDefault));
+  memset(c->hash_res, 0, M355_HASH_REQUESTS * HASH_RES_WORDS * sizeof(uint32_t));
+  for (auto& s : c->hash_slot) HIPCHK(hipEventCreateWithFlags(&s.ev, hipEventDisableTiming));
+  return M355_OK;
+}
+/* (behind sync_all: nothing is in flight; requests nobody collected are dropped) */
+static void hash_requests_destroy(m355_ctx* c)
+{
+  for (auto& s : c->hash_slot) { if (s.ev) hipEventDestroy(s.ev); if (s.planes) hipHostFree(s.planes); s = m355_ctx::HashSlot(); }
+  for (auto& b : c->hash_pool) hipHostFree(b.first);
+  c->hash_pool.clear();
+  if (c->hash_rec) hipFree(c->hash_rec);
+  if (c->hash_res) hipHostFree(c->hash_res);
+  c->hash_rec = c->hash_res = nullptr;
+}
+
 int m355_create(int device, m355_ctx** out)
 {
   *out = nullptr;
@@ -192,7 +215,8 @@ int m355_create(int device, m355_ctx** out)
   m355_ctx* c = new m355_ctx;
   c->device = device;
   int rc = lane_create(c, c->lanes[0], 0);
-  if (rc) { lane_destroy(c->lanes[0]); delete c; return rc; }
+  if (rc == M355_OK) rc = hash_requests_create(c);
+  if (rc) { hash_requests_destroy(c); lane_destroy(c->lanes[0]); delete c; return rc; }
   *out = c;
   return M355_OK;
 }
@@ -231,6 +255,7 @@ void m355_destroy(m355_ctx* c)
   for (auto& t : c->transient) resident_free(t);
   for (hipEvent_t e : c->evs) hipEventDestroy(e);
   if (c->hash_acc) hipFree(c->hash_acc);
+  hash_requests_destroy(c);
   for (auto& e : c->inter_tabs) hipFree(e.second);
   for (auto& b : c->batch) { if (b.host) hipHostFree(b.host); if (b.dev) hipFree(b.dev); if (b.ev) hipEventDestroy(b.ev); }
   for (hipEvent_t e : c->batch_ev_pre) if (e) hipEventDestroy(e);
@@ -640,6 +665,161 @@ int m355_frame_hash(m355_ctx* c, int h, int type, m355_picture_hash* out)
   return M355_OK;
 }
 
+/* ---- hash requests (m355_frame_hash_async / m355_frame_hash_result) ---- */
+
+static m355_ctx::HashSlot* hash_slot_of(m355_ctx* c, unsigned long long ticket)
+{
+  if (ticket) for (auto& s : c->hash_slot) if (s.ticket == ticket) return &s;
+  return nullptr;
+}
+/* `st` continues behind the frame's last hash request (a reader of the frame): nothing to enqueue when the request runs on `st` itself or has been
+   collected — a request is collected behind its mark, so that mark has passed */
+void hash_reader_wait(m355_ctx* c, hipStream_t st, const Frame* f) {
+  if (!f->hs || f->hs_stream == st) return;
+  if (const m355_ctx::HashSlot* s = hash_slot_of(c, f->hs)) hipStreamWaitEvent(st, s->ev, 0);
+}
+/* an MD5 request's pinned planes: the smallest idle buffer that fits, else a new one (nothing is freed here: hipHostFree may wait for the device —
+   a buffer smaller than the largest one made is freed when its request is collected, hash_slot_free) */
+static int hash_planes_take(m355_ctx* c, m355_ctx::HashSlot& s, size_t bytes)
+{
+  int best = -1;
+  for (int k = 0; k < (int)c->hash_pool.size(); k++)
+    if (c->hash_pool[k].second >= bytes && (best < 0 || c->hash_pool[k].second < c->hash_pool[best].second)) best = k;
+  if (best < 0) {
+    void* p = nullptr;
+    const size_t want = (bytes + ((size_t)1 << 20) - 1) & ~(((size_t)1 << 20) - 1);
+    if (hipHostMalloc(&p, want, hipHostMallocDefault) != hipSuccess) return fail(M355_ERR_NOMEM, "pinned planes of %zu bytes for an MD5 request", want);
+    s.planes = (uint8_t*)p; s.planes_cap = want;
+    return M355_OK;
+  }
+  s.planes = c->hash_pool[best].first; s.planes_cap = c->hash_pool[best].second;
+  c->hash_pool.erase(c->hash_pool.begin() + best);
+  return M355_OK;
+}
+static void hash_slot_free(m355_ctx* c, m355_ctx::HashSlot& s)
+{
+  if (s.planes) {
+    /* the pool grows to the largest frame seen: smaller buffers of earlier, smaller frames are idle pinned memory, and they go here — where the caller
+       has just waited for its request anyway — first the pool's, then this one if a larger one exists */
+    size_t largest = s.planes_cap;
+    for (const auto& x : c->hash_slot) largest = std::max(largest, x.planes_cap);
+    for (const auto& b : c->hash_pool) largest = std::max(largest, b.second);
+    for (size_t k = c->hash_pool.size(); k-- > 0;) if (c->hash_pool[k].second < largest) { hipHostFree(c->hash_pool[k].first); c->hash_pool.erase(c->hash_pool.begin() + k); }
+    if (s.planes_cap < largest) hipHostFree(s.planes);
+    else c->hash_pool.push_back(std::make_pair(s.planes, s.planes_cap));
+  }
+  s.planes = nullptr; s.planes_cap = 0;
+  s.ticket = 0;
+}
+
+/* Enqueue only: the host waits for nothing here.  A READER of the frame, queued like m355_frame_export on the stream of the decode that wrote the frame, behind
+   the frame's earlier readers where those run on another stream; the next decode into the frame waits for the request's mark (dst_hazards -> hash_reader_wait). */
+int m355_frame_hash_async(m355_ctx* c, int h, int type, unsigned long long* ticket)
+{
+  Frame* f = get_frame(c, h);
+  if (!f || !ticket) return fail(M355_ERR_INVALID, "m355_frame_hash_async: bad frame handle %d / null ticket", h);
+  if (type != M355_HASH_MD5 && type != M355_HASH_CRC && type != M355_HASH_CHECKSUM) return fail(M355_ERR_INVALID, "m355_frame_hash_async: bad hash type %d", type);
+  if (c->shard_n > 0) return fail(M355_ERR_INVALID, "m355_frame_hash_async: not on a tile-sharded context (its frames are complete only behind the gather)");
+  m355_ctx::HashSlot* s = nullptr;
+  for (auto& x : c->hash_slot) if (!x.ticket) { s = &x; break; }
+  if (!s) return fail(M355_ERR_BUSY, "m355_frame_hash_async: %d requests outstanding (collect one: m355_frame_hash_result)", M355_HASH_REQUESTS);
+  const int slot = (int)(s - c->hash_slot);
+  hipSetDevice(c->device);
+  s->type = type; s->np = f->pw[1] ? 3 : 1;
+  size_t plane_ofs[3] = {0, 0, 0}, bytes = 0;
+  for (int cc = 0; cc < 3; cc++) {
+    s->row_bytes[cc] = cc < s->np ? f->pw[cc] * f->bpp[cc] : 0;
+    s->rows[cc] = cc < s->np ? f->ph[cc] : 0;
+    plane_ofs[cc] = bytes;
+    bytes += ((size_t)s->row_bytes[cc] * s->rows[cc] + 255) & ~(size_t)255;
+  }
+  if (type == M355_HASH_MD5) { int rc = hash_planes_take(c, *s, bytes); if (rc) return rc; }
+  HashReq q = {};
+  q.rec = c->hash_rec + slot * HASH_REC_WORDS;
+  q.res = c->hash_res + slot * HASH_RES_WORDS;
+  q.seq = (uint32_t)(c->hash_ticket + 1);
+  q.res[3] = HASH_RES_NONE;                                                     /* (the slot is idle: nothing in flight writes its record) */
+  hipStream_t cs = f->wr_stream ? f->wr_stream : lane(c).stream;                /* (no decode of this context wrote it: uploads and fills are synchronous) */
+  if (!f->wr_stream) ev_wait(c, cs, f->wr);
+  ev_wait(c, cs, f->ex);
+  hash_reader_wait(c, cs, f);                                                   /* (an earlier request on another stream: the one mark kept stands for both) */
+  if (f->wr_stream && f->wr_gate) { q.timeout = f->wr_gate; q.epoch = f->wr_epoch; }
+  else {                                                                        /* no decode to be gated by: an epoch of its own, which no gate word holds */
+    q.timeout = lane(c).timeout; q.epoch = ++c->epoch;
+    if (q.epoch == 0) q.epoch = ++c->epoch;
+  }
+  HashArgs a = {};
+  a.out = q.rec;
+  if (type == M355_HASH_MD5) {
+    /* (behind a rejected decode the copies bring an older picture's planes: the verdict says so, the result is never made of them) */
+    for (int cc = 0; cc < s->np; cc++)
+      if (hipMemcpy2DAsync(s->planes + plane_ofs[cc], (size_t)s->row_bytes[cc], f->plane[cc], (size_t)f->stride[cc] * f->bpp[cc], (size_t)s->row_bytes[cc], s->rows[cc],
+                           hipMemcpyDeviceToHost, cs) != hipSuccess) { hash_slot_free(c, *s); return fail(M355_ERR_HIP, "m355_frame_hash_async: copy of plane %d failed", cc); }
+  } else {
+    int rows = 0, nw = 0;
+    for (int cc = 0; cc < s->np; cc++) rows += f->ph[cc];
+    a.rows_per_wave = std::max(1, rows / 4096);                                 /* as m355_frame_hash */
+    for (int cc = 0; cc < 3; cc++) {
+      a.first[cc] = nw;
+      if (cc >= s->np) continue;
+      a.pl[cc].base = (const uint8_t*)f->plane[cc];
+      a.pl[cc].pitch = (size_t)f->stride[cc] * f->bpp[cc];
+      a.pl[cc].row_bytes = s->row_bytes[cc];
+      a.pl[cc].h = f->ph[cc];
+      a.pl[cc].bpp = f->bpp[cc];
+      nw += (f->ph[cc] + a.rows_per_wave - 1) / a.rows_per_wave;
+    }
+    a.first[3] = nw;
+  }
+  m355_launch_frame_hash_req(a, q, type, cs);
+  if (hipGetLastError() != hipSuccess || hipEventRecord(s->ev, cs) != hipSuccess) { hash_slot_free(c, *s); return fail(M355_ERR_HIP, "m355_frame_hash_async: launch failed"); }
+  s->ticket = ++c->hash_ticket;
+  f->hs = s->ticket; f->hs_stream = cs;
+  *ticket = s->ticket;
+  return M355_OK;
+}
+
+int m355_frame_hash_result(m355_ctx* c, unsigned long long ticket, int block, m355_picture_hash* out)
+{
+  m355_ctx::HashSlot* s = hash_slot_of(c, ticket);
+  if (!s) return fail(M355_ERR_INVALID, "m355_frame_hash_result: ticket %llu is unknown or was collected", ticket);
+  if (!out) return fail(M355_ERR_INVALID, "m355_frame_hash_result: null result");
+  hipSetDevice(c->device);
+  if (block) HIPCHK(hipEventSynchronize(s->ev));                                /* this request's mark only */
+  else {
+    const hipError_t e = hipEventQuery(s->ev);
+    if (e == hipErrorNotReady) return M355_ERR_BUSY;
+    if (e != hipSuccess) return fail(M355_ERR_HIP, "hipEventQuery failed: %s", hipGetErrorString(e));
+  }
+  const uint32_t* res = c->hash_res + (s - c->hash_slot) * HASH_RES_WORDS;
+  const uint32_t state = res[3], seq = res[4];
+  if (state == HASH_RES_GATED && seq == (uint32_t)ticket) {
+    hash_slot_free(c, *s);
+    return fail(M355_ERR_INVALID, "hash request %llu was queued behind a decode whose lists were rejected: no value", ticket);
+  }
+  if (state != HASH_RES_VALID || seq != (uint32_t)ticket) {
+    hash_slot_free(c, *s);
+    return fail(M355_ERR_HIP, "hash request %llu finished without a result (state %u, sequence %u)", ticket, state, seq);
+  }
+  if (s->type == M355_HASH_MD5) {
+    std::vector<std::thread> th;
+    size_t ofs = 0;
+    for (int cc = 0; cc < s->np; cc++) {
+      const uint8_t* p = s->planes + ofs;
+      const int rb = s->row_bytes[cc], rows = s->rows[cc];
+      th.emplace_back([=] { m355_md5_rows(p, (size_t)rb, rb, rows, out->md5[cc]); });
+      ofs += ((size_t)rb * rows + 255) & ~(size_t)255;
+    }
+    for (auto& t : th) t.join();
+  } else
+    for (int cc = 0; cc < s->np; cc++) {
+      if (s->type == M355_HASH_CRC) out->crc[cc] = (uint16_t)(res[cc] ^ m355_crc_init_term((uint64_t)s->row_bytes[cc] * s->rows[cc]));
+      else out->checksum[cc] = res[cc];
+    }
+  hash_slot_free(c, *s);
+  return M355_OK;
+}
+
 /* room for `k` entries per list in the arenas of `r` (grown when it does not fit), list pointers into its pinned half */
 static int arena_into(m355_ctx* c, Resident& r, m355_arena_caps* k, int halo_units, bool sharded, m355_picture* pic)
 {
@@ -775,7 +955,7 @@ int m355_wait(m355_ctx* c)
 {
   hipSetDevice(c->device);
   HIPCHK(sync_all(c));
-  for (auto& f : c->frames) { f.wr = EvRef(); f.ex = EvRef(); f.dl_pending = false; for (int k = 0; k < M355_MAX_LANES; k++) f.rd[k] = EvRef(); }   /* everything is complete */
+  for (auto& f : c->frames) { f.wr = EvRef(); f.ex = EvRef(); f.hs = 0; f.dl_pending = false; for (int k = 0; k < M355_MAX_LANES; k++) f.rd[k] = EvRef(); }   /* everything is complete */
   uint32_t t = 0;
   for (const Lane& l : c->lanes)
     if (l.timeout) { uint32_t t2 = 0; HIPCHK(hipMemcpy(&t2, l.timeout, 4, hipMemcpyDeviceToHost)); t |= t2; }

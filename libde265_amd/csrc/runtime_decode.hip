@@ -288,6 +288,7 @@ hipStream_t launch_prediction(m355_ctx* c, const Resident& r, const DevPic& d, b
 void dst_hazards(m355_ctx* c, Frame* dstf, bool piped, hipStream_t st) {
   if (dstf->dl_pending) hipStreamWaitEvent(st, dstf->ev_dl, 0);     /* (stays pending for the HOST until m355_frame_download_wait / m355_wait) */
   ev_wait(c, st, dstf->ex);                                          /* an export of the frame's previous picture (queued on that picture's stream) */
+  hash_reader_wait(c, st, dstf);                                     /* ... a hash request on it (m355_frame_hash_async) */
   if (!piped) return;
   ev_wait(c, st, dstf->wr);
   for (int k = 0; k < M355_MAX_LANES; k++) ev_wait(c, st, dstf->rd[k]);

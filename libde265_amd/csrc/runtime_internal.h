@@ -90,6 +90,9 @@ struct Frame {
   const uint32_t* wr_gate = nullptr; uint32_t wr_epoch = 0;
   /* the last export in flight (m355_frame_export, a reader of the frame): the next writer waits for it in front of its first write */
   EvRef ex;
+  /* the last hash request in flight on the frame (m355_frame_hash_async, a reader like the export): its ticket and the stream it runs on;
+     the mark itself is the request's own event (hash_reader_wait) */
+  unsigned long long hs = 0; hipStream_t hs_stream = nullptr;
 };
 
 static void frame_geometry(Frame& f, int w, int h, int cf, int bdl, int bdc)
@@ -127,6 +130,7 @@ static void frame_free(Frame& f)
   for (int k = 0; k < M355_MAX_LANES; k++) f.rd[k] = EvRef();
   f.ev_dl = nullptr; f.dl_pending = false; f.wr_stream = nullptr;
   f.wr_gate = nullptr; f.wr_epoch = 0; f.ex = EvRef();
+  f.hs = 0; f.hs_stream = nullptr;
   f.used = false;
 }
 
@@ -240,6 +244,18 @@ struct m355_ctx {
   bool timed = false;
   bool timing_on = false;      /* between m355_timing_reset and m355_timing_collect: decodes record their seven stage events */
   uint32_t* hash_acc = nullptr; /* m355_frame_hash accumulators */
+  /* m355_frame_hash_async: M355_HASH_REQUESTS slots, each with a device record (zero between requests: the kernel leaves it so), a pinned
+     result record and the event that is the request's mark; all allocated when the context is created.  ticket == 0: the slot is free. */
+  struct HashSlot {
+    unsigned long long ticket = 0; int type = 0, np = 0;
+    int row_bytes[3] = {0, 0, 0}, rows[3] = {0, 0, 0};
+    hipEvent_t ev = nullptr;
+    uint8_t* planes = nullptr; size_t planes_cap = 0;   /* MD5: pinned copy of the planes, taken from hash_pool */
+  };
+  HashSlot hash_slot[M355_HASH_REQUESTS];
+  unsigned long long hash_ticket = 0;
+  uint32_t *hash_rec = nullptr, *hash_res = nullptr;    /* HASH_REC_WORDS (device) / HASH_RES_WORDS (pinned) per slot */
+  std::vector<std::pair<uint8_t*, size_t>> hash_pool;   /* idle pinned plane buffers of MD5 requests: they grow to the largest frame seen */
   /* pinned staging buffer of the blocking frame transfers (m355_frame_upload / _download / _fill, MD5 of m355_frame_hash): the copy itself is queued on the
      stream that last wrote the frame, between pinned memory and the frame (frame_stage_* in runtime.hip) */
   void* stage = nullptr; size_t stage_bytes = 0;
@@ -305,6 +321,7 @@ void clear_target(m355_ctx* c, const DevPic& d, Frame* tgt, bool gated, hipStrea
 int copy_tiles(m355_ctx* c, const m355_pic_params& pp, Frame* f, int k0, int k1, int skip, int nranks, char* xbuf, size_t slot, bool to_slot);
 int decode(m355_ctx* c, Resident& r, bool rotate = true);
 void dst_hazards(m355_ctx* c, Frame* dstf, bool piped, hipStream_t st);
+void hash_reader_wait(m355_ctx* c, hipStream_t st, const Frame* f);
 int ev_mark(m355_ctx* c, hipStream_t st, EvRef* out);
 hipError_t ev_query(m355_ctx* c, const EvRef& r);
 hipError_t ev_sync(m355_ctx* c, const EvRef& r);
