@@ -103,93 +103,8 @@ __device__ __forceinline__ void d_load16(const uint8_t* row, int o, int n, uint3
     for (int k = 0; k < n; k++) w[k >> 2] |= (uint32_t)row[o + k] << (8 * (k & 3));
 }
 
-/* one wave per (plane, span of rows); wave index -> plane by the prefix counts in a.first[] */
-template <int TYPE>
-__global__ void __launch_bounds__(256) k_frame_hash(HashArgs a)
-{
-  const int lane = threadIdx.x & 63;
-  const int wv = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (wv >= a.first[3]) return;
-  const int c = wv >= a.first[2] ? 2 : (wv >= a.first[1] ? 1 : 0);
-  const HashPlane pl = a.pl[c];
-  const int y0 = (wv - a.first[c]) * a.rows_per_wave, y1 = min(y0 + a.rows_per_wave, pl.h);
-
-  if (TYPE == M355_HASH_CRC) {
-    uint32_t acc = 0;
-    for (int y = y0; y < y1; y++) {
-      const uint8_t* row = pl.base + (size_t)y * pl.pitch;
-      for (int o = 0; o < pl.row_bytes; o += HASH_BLOCK) {
-        const int len = min(HASH_BLOCK, pl.row_bytes - o);
-        const int lo = lane * 16, n = d_clip3(0, 16, len - lo);
-        uint32_t w[4];
-        d_load16(row, o + lo, n, w);
-        uint32_t crc = 0;
-#pragma unroll
-        for (int k = 0; k < 16; k++)
-          if (k < n) crc = d_crc_byte(crc, (w[k >> 2] >> (8 * (k & 3))) & 0xFFu);
-        uint32_t mult, step;
-        if (len == HASH_BLOCK) { mult = c_hash.after[lane]; step = c_hash.blk; }
-        else { mult = d_pow_x8((uint64_t)max(len - lo - n, 0)); step = d_pow_x8((uint64_t)len); }   /* last block of a row */
-        const uint32_t blk = d_wave_xor(n > 0 ? gf_mul(crc, mult) : 0u);
-        acc = gf_mul(acc, step) ^ blk;
-      }
-    }
-    const uint64_t after = (uint64_t)(pl.h - y1) * (uint64_t)pl.row_bytes;
-    const uint32_t v = gf_mul(acc, d_pow_x8(after));
-    if (lane == 0 && y1 > y0) atomicXor(&a.out[c], v);
-  } else {
-    uint32_t sum = 0;
-    for (int y = y0; y < y1; y++) {
-      const uint8_t* row = pl.base + (size_t)y * pl.pitch;
-      const uint32_t my = (uint32_t)((y & 0xFF) ^ (y >> 8));
-      for (int o = lane * 16; o < pl.row_bytes; o += HASH_BLOCK) {
-        const int n = min(16, pl.row_bytes - o);
-        uint32_t w[4];
-        d_load16(row, o, n, w);
-#pragma unroll
-        for (int k = 0; k < 16; k++)
-          if (k < n) {
-            const int x = (o + k) >> (pl.bpp - 1);            /* sample column: both bytes of a 16-bit sample share the mask */
-            const uint32_t m = (my ^ (uint32_t)(x & 0xFF) ^ (uint32_t)(x >> 8)) & 0xFFu;
-            sum += ((w[k >> 2] >> (8 * (k & 3))) & 0xFFu) ^ m;
-          }
-      }
-    }
-    sum = d_wave_add(sum);
-    if (lane == 0 && y1 > y0) atomicAdd(&a.out[c], sum);
-  }
-}
-
-void m355_launch_frame_hash(const HashArgs& a, int type, hipStream_t st)
-{
-  const int nw = a.first[3];
-  if (!nw) return;
-  if (type == M355_HASH_CRC) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_frame_hash<M355_HASH_CRC>), dim3((nw + 3) / 4), dim3(256), 0, st, a);
-  else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_frame_hash<M355_HASH_CHECKSUM>), dim3((nw + 3) / 4), dim3(256), 0, st, a);
-}
-
-/* ---- the request form (m355_frame_hash_async): one launch, no fill in front of it, no copy behind it ----
- *
- * The arithmetic is k_frame_hash's (same spans, same Horner chain, same factors — restated here so that kernel stays as it is); what differs is
- * where the values go.  Every wavefront with a span XORs / adds its value into the request slot's device record q.rec[0..2], then draws an
- * arrival ticket from q.rec[3]; the wavefront that draws the last ticket takes the three values out of the record, writes them with the
- * verdict into the slot's pinned record q.res and leaves q.rec zero for the slot's next request.
- *
- * ORDERING (the part only the hardware can get wrong).  Every access to q.rec is an agent-scope atomic read-modify-write, performed where such
- * atomics are performed for the whole device — no lane ever holds a word of the record in its CU's L1 or its XCD's L2, so there is no copy to go
- * stale — and the arrival counter carries the order between them:
- *   - a wavefront's accumulator atomic is sequenced before its ticket fetch_add, which is a RELEASE at agent scope: the accumulator atomic has
- *     been performed (the wait the release puts in front of the fetch_add) before the ticket becomes visible;
- *   - the same fetch_add is an ACQUIRE, and read-modify-writes continue a release sequence: the wavefront that reads first[3] - 1 from the
- *     counter synchronises with EVERY earlier ticket, hence every other wavefront's accumulator atomic happens before its own later accesses;
- *   - it reads the accumulators with atomicExch(…, 0) — again an agent-scope read-modify-write, ordered behind the acquire — which returns the
- *     complete value and zeroes the word in one step; the counter is zeroed by an agent-scope atomic store.  Nobody else touches the record any
- *     more in this launch (all tickets are drawn), and the slot's NEXT launch is enqueued only after the host has seen this request's mark pass
- *     (a slot is free again when its result was collected), so the zeroes are in place before that launch starts;
- *   - the pinned record is written with ordinary vector stores by that one lane and read by the host only behind the request's mark
- *     (hipEventQuery / hipEventSynchronize on an event recorded behind the launch): the end of the kernel releases them to the system.
- * A gated launch (the decode that wrote the frame was rejected: its planes hold an older picture) writes the verdict from one lane of its first
- * workgroup and touches nothing else: the device record stays zero. */
+/* the value of rows [y0, y1) of a plane, computed by one wavefront (the same in every lane): the CRC state of the span from state 0, times x^(8 * bytes of the
+   plane that follow the span) — or the checksum of its bytes.  Both kernels below XOR / add these values per plane. */
 template <int TYPE>
 __device__ __forceinline__ uint32_t d_span_hash(const HashPlane& pl, int y0, int y1, int lane)
 {
@@ -226,7 +141,7 @@ __device__ __forceinline__ uint32_t d_span_hash(const HashPlane& pl, int y0, int
 #pragma unroll
       for (int k = 0; k < 16; k++)
         if (k < n) {
-          const int x = (o + k) >> (pl.bpp - 1);
+          const int x = (o + k) >> (pl.bpp - 1);            /* sample column: both bytes of a 16-bit sample share the mask */
           const uint32_t m = (my ^ (uint32_t)(x & 0xFF) ^ (uint32_t)(x >> 8)) & 0xFFu;
           sum += ((w[k >> 2] >> (8 * (k & 3))) & 0xFFu) ^ m;
         }
@@ -235,6 +150,51 @@ __device__ __forceinline__ uint32_t d_span_hash(const HashPlane& pl, int y0, int
   return d_wave_add(sum);
 }
 
+/* one wave per (plane, span of rows); wave index -> plane by the prefix counts in a.first[] */
+template <int TYPE>
+__global__ void __launch_bounds__(256) k_frame_hash(HashArgs a)
+{
+  const int lane = threadIdx.x & 63;
+  const int wv = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (wv >= a.first[3]) return;
+  const int c = wv >= a.first[2] ? 2 : (wv >= a.first[1] ? 1 : 0);
+  const HashPlane pl = a.pl[c];
+  const int y0 = (wv - a.first[c]) * a.rows_per_wave, y1 = min(y0 + a.rows_per_wave, pl.h);
+  const uint32_t v = d_span_hash<TYPE>(pl, y0, y1, lane);
+  if (lane != 0 || y1 <= y0) return;
+  if (TYPE == M355_HASH_CRC) atomicXor(&a.out[c], v);
+  else atomicAdd(&a.out[c], v);
+}
+
+void m355_launch_frame_hash(const HashArgs& a, int type, hipStream_t st)
+{
+  const int nw = a.first[3];
+  if (!nw) return;
+  if (type == M355_HASH_CRC) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_frame_hash<M355_HASH_CRC>), dim3((nw + 3) / 4), dim3(256), 0, st, a);
+  else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_frame_hash<M355_HASH_CHECKSUM>), dim3((nw + 3) / 4), dim3(256), 0, st, a);
+}
+
+/* ---- the request form (m355_frame_hash_async): one launch, no fill in front of it, no copy behind it ----
+ *
+ * The arithmetic is k_frame_hash's (same spans, d_span_hash); what differs is where the values go.  Every wavefront with a span XORs / adds its value into the request slot's device record q.rec[0..2], then draws an
+ * arrival ticket from q.rec[3]; the wavefront that draws the last ticket takes the three values out of the record, writes them with the
+ * verdict into the slot's pinned record q.res and leaves q.rec zero for the slot's next request.
+ *
+ * ORDERING (the part only the hardware can get wrong).  Every access to q.rec is an agent-scope atomic read-modify-write, performed where such
+ * atomics are performed for the whole device — no lane ever holds a word of the record in its CU's L1 or its XCD's L2, so there is no copy to go
+ * stale — and the arrival counter carries the order between them:
+ *   - a wavefront's accumulator atomic is sequenced before its ticket fetch_add, which is a RELEASE at agent scope: the accumulator atomic has
+ *     been performed (the wait the release puts in front of the fetch_add) before the ticket becomes visible;
+ *   - the same fetch_add is an ACQUIRE, and read-modify-writes continue a release sequence: the wavefront that reads first[3] - 1 from the
+ *     counter synchronises with EVERY earlier ticket, hence every other wavefront's accumulator atomic happens before its own later accesses;
+ *   - it reads the accumulators with atomicExch(…, 0) — again an agent-scope read-modify-write, ordered behind the acquire — which returns the
+ *     complete value and zeroes the word in one step; the counter is zeroed by an agent-scope atomic store.  Nobody else touches the record any
+ *     more in this launch (all tickets are drawn), and the slot's NEXT launch is enqueued only after the host has seen this request's mark pass
+ *     (a slot is free again when its result was collected), so the zeroes are in place before that launch starts;
+ *   - the pinned record is written with ordinary vector stores by that one lane and read by the host only behind the request's mark
+ *     (hipEventQuery / hipEventSynchronize on an event recorded behind the launch): the end of the kernel releases them to the system.
+ * A gated launch (the decode that wrote the frame was rejected: its planes hold an older picture) writes the verdict from one lane of its first
+ * workgroup and touches nothing else: the device record stays zero. */
 __device__ __forceinline__ void d_hash_verdict(const HashReq& q, uint32_t v0, uint32_t v1, uint32_t v2, uint32_t state)
 {
   q.res[0] = v0; q.res[1] = v1; q.res[2] = v2;

@@ -50,6 +50,29 @@ hipError_t ev_query(m355_ctx* c, const EvRef& r) {
   return e.ticket == r.ticket ? hipEventQuery(e.ev) : hipSuccess;
 }
 
+/* A READER of frame `f` (Frame::reader) is queued on the stream this returns: the stream of the decode that wrote the frame, right behind it — measured
+ * (tests/test_gpu_pipeline.py, profiles/r03_y_*) a copy on a stream of its own, ordered behind the writer by an event (even with the host waiting for that event
+ * first), now and then read a half-written picture: the writer's last stores were not yet visible to the copy engine; queued on the writer's own stream it never
+ * did.  It still runs beside the host and beside the other lanes' decodes.  gate / epoch: what a gated kernel of the reader is launched with. */
+hipStream_t reader_begin(m355_ctx* c, Frame* f, int kind, const uint32_t** gate, uint32_t* epoch) {
+  const hipStream_t st = f->wr_stream ? f->wr_stream : lane(c).stream;
+  if (!f->wr_stream) ev_wait(c, st, f->wr);                 /* no decode of this context wrote it (uploads and fills are synchronous): its zero fill at creation */
+  ev_wait(c, st, f->reader[kind]);                          /* (an earlier reader of the kind on another stream: the one mark kept stands for both) */
+  if (!gate) return st;
+  if (f->wr_stream && f->wr_gate) { *gate = f->wr_gate; *epoch = f->wr_epoch; }
+  else {                                                    /* no decode to be gated by: an epoch of its own, which no gate word holds */
+    *gate = lane(c).timeout; *epoch = ++c->epoch;
+    if (*epoch == 0) *epoch = ++c->epoch;
+  }
+  return st;
+}
+/* the mark behind the reader: what the next decode into the frame and the host's wait for this kind of reader go by */
+int reader_end(m355_ctx* c, Frame* f, int kind, hipStream_t st) { return ev_mark(c, st, &f->reader[kind]); }
+/* `st` (the next decode into the frame) continues behind the frame's readers */
+void readers_wait(m355_ctx* c, hipStream_t st, const Frame* f) {
+  for (const EvRef& m : f->reader) ev_wait(c, st, m);
+}
+
 /* The HIP runtime multiplexes its streams onto a few hardware queues PER STREAM PRIORITY (GPU_MAX_HW_QUEUES, default 4), and
  * kernels of different streams that share a hardware queue mostly run one after the other.  Three lanes (six streams) do well on
  * the default priority's queues.  Every further group of three lanes belongs to the next priority class, whose streams have
@@ -182,7 +205,7 @@ int m355_device_count(void)
   return n;
 }
 
-/* the slots of m355_frame_hash_async: device records (zeroed here, once: every request leaves its record zero), pinned result records, marks */
+/* the slots of m355_frame_hash_async: device records (zeroed here, once: every request leaves its record zero), pinned result records */
 static int hash_requests_create(m355_ctx* c)
 {
   hipStream_t st = c->lanes[0].stream;
@@ -191,13 +214,12 @@ static int hash_requests_create(m355_ctx* c)
   HIPCHK(hipStreamSynchronize(st));
   HIPCHK(hipHostMalloc(&c->hash_res, M355_HASH_REQUESTS * HASH_RES_WORDS * sizeof(uint32_t), hipHostMallocDefault));
   memset(c->hash_res, 0, M355_HASH_REQUESTS * HASH_RES_WORDS * sizeof(uint32_t));
-  for (auto& s : c->hash_slot) HIPCHK(hipEventCreateWithFlags(&s.ev, hipEventDisableTiming));
   return M355_OK;
 }
 /* (behind sync_all: nothing is in flight; requests nobody collected are dropped) */
 static void hash_requests_destroy(m355_ctx* c)
 {
-  for (auto& s : c->hash_slot) { if (s.ev) hipEventDestroy(s.ev); if (s.planes) hipHostFree(s.planes); s = m355_ctx::HashSlot(); }
+  for (auto& s : c->hash_slot) { if (s.planes) hipHostFree(s.planes); s = m355_ctx::HashSlot(); }
   for (auto& b : c->hash_pool) hipHostFree(b.first);
   c->hash_pool.clear();
   if (c->hash_rec) hipFree(c->hash_rec);
@@ -264,7 +286,6 @@ void m355_destroy(m355_ctx* c)
   for (auto& e_ : c->evring) if (e_.ev) hipEventDestroy(e_.ev);
   if (c->status_words) hipHostFree(c->status_words);
   if (c->stage) hipHostFree(c->stage);
-  for (hipEvent_t e : c->dl_evs) if (e) hipEventDestroy(e);
   for (Lane& l : c->lanes) lane_destroy(l);
   delete c;
 }
@@ -379,57 +400,35 @@ int m355_frame_download(m355_ctx* c, int h, int cidx, void* dst, ptrdiff_t strid
   HIPCHK(sync_all(c));
   return frame_stage_down(c, f, cidx, dst, (size_t)stride * f->bpp[cidx]);
 }
-/* The download of a whole frame, asynchronous: the copies run on the context's own copy stream, behind the frame's last writer and
- * beside the decodes of later pictures; the next picture written into the frame waits for them.  dst planes should be pinned
- * (m355_host_alloc), else the copies are staged by the runtime and block. */
+/* The download of a whole frame, asynchronous: a READER of the frame (reader_begin) — the copies run behind the frame's last writer and beside the
+ * decodes of later pictures; the next picture written into the frame waits for them.  dst planes should be pinned (m355_host_alloc), else the
+ * copies are staged by the runtime and block. */
 int m355_frame_download_async(m355_ctx* c, int h, void* const dst[3], const ptrdiff_t stride[3])
 {
   Frame* f = get_frame(c, h);
   if (!f || !dst || !stride) return fail(M355_ERR_INVALID, "bad frame / destination");
+  for (int cc = 0; cc < 3; cc++) if (f->pw[cc] && !dst[cc]) return fail(M355_ERR_INVALID, "no destination for plane %d", cc);
   hipSetDevice(c->device);
-  /* The copies go on the stream of the lane that wrote the frame, right behind the decode: measured (tests/test_gpu_pipeline.py,
-     profiles/r03_y_*) a copy on a stream of its own, ordered behind the writer by an event (even with the host waiting for that event
-     first), now and then read a half-written picture — the writer's last stores were not yet visible to the copy engine; queued on
-     the writer's own stream it never did.  They still run beside the host and beside the other lanes' decodes; the lane's next
-     picture waits for them. */
-  if (c->dl_evs.empty()) {
-    std::vector<hipEvent_t> evs(128, nullptr);              /* installed only when every event exists */
-    for (auto& e : evs)
-      if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) {
-        for (hipEvent_t x : evs) if (x) hipEventDestroy(x);
-        return fail(M355_ERR_HIP, "hipEventCreate failed");
-      }
-    c->dl_evs.swap(evs);
-  }
-  hipEvent_t ev_done = c->dl_evs[c->dl_ev_next];            /* (a ring: never re-recorded while an earlier record may still be waited for) */
-  c->dl_ev_next = (c->dl_ev_next + 1) % (int)c->dl_evs.size();
-  hipStream_t cs = f->wr_stream ? f->wr_stream : lane(c).stream;                /* (no decode of this context wrote it: uploads and fills are synchronous) */
-  if (!f->wr_stream) ev_wait(c, cs, f->wr);
+  const hipStream_t cs = reader_begin(c, f, RD_DOWNLOAD);
   for (int cc = 0; cc < 3; cc++) {
     if (!f->pw[cc]) continue;
-    if (!dst[cc]) return fail(M355_ERR_INVALID, "no destination for plane %d", cc);
     HIPCHK(hipMemcpy2DAsync(dst[cc], (size_t)stride[cc] * f->bpp[cc], f->plane[cc], (size_t)f->stride[cc] * f->bpp[cc],
                             (size_t)f->pw[cc] * f->bpp[cc], f->ph[cc], hipMemcpyDeviceToHost, cs));
   }
-  HIPCHK(hipEventRecord(ev_done, cs));
-  f->ev_dl = ev_done;                                                           /* (the ring's: not the frame's to destroy) */
-  f->dl_pending = true;
-  return M355_OK;
+  return reader_end(c, f, RD_DOWNLOAD, cs);
 }
 /* wait (this frame's download only) until the planes handed to m355_frame_download_async hold the picture */
 int m355_frame_download_wait(m355_ctx* c, int h)
 {
   Frame* f = get_frame(c, h);
   if (!f) return fail(M355_ERR_INVALID, "bad frame handle %d", h);
-  if (!f->dl_pending) return M355_OK;
   hipSetDevice(c->device);
-  HIPCHK(hipEventSynchronize(f->ev_dl));
-  f->dl_pending = false;
+  HIPCHK(ev_sync(c, f->reader[RD_DOWNLOAD]));
+  f->reader[RD_DOWNLOAD] = EvRef();
   return M355_OK;
 }
-/* The frame, or a rectangle of it, converted into memory of the caller (k_export.hip): one launch for all planes, queued — like the copies of
- * m355_frame_download_async above, and for the reason given there — on the stream of the lane that wrote the frame.  The export is a READER
- * of the frame: the mark behind it is what the next decode into the frame waits for (dst_hazards), what m355_frame_export_wait blocks on
+/* The frame, or a rectangle of it, converted into memory of the caller (k_export.hip): one launch for all planes.  The export is a READER of the
+ * frame (reader_begin): the mark behind it is what the next decode into the frame waits for (dst_hazards), what m355_frame_export_wait blocks on
  * and what m355_frame_export_order makes a consumer's stream wait for. */
 int m355_frame_export(m355_ctx* c, int h, const m355_export_desc* e)
 {
@@ -466,17 +465,10 @@ int m355_frame_export(m355_ctx* c, int h, const m355_export_desc* e)
     a.unit_end[p] = units;
   }
   hipSetDevice(c->device);
-  hipStream_t cs = f->wr_stream ? f->wr_stream : lane(c).stream;                /* (no decode of this context wrote it: uploads and fills are synchronous) */
-  if (!f->wr_stream) ev_wait(c, cs, f->wr);
-  ev_wait(c, cs, f->ex);                                                        /* (an earlier export on another stream: the one mark kept stands for both) */
-  if (f->wr_stream && f->wr_gate) { a.timeout = f->wr_gate; a.epoch = f->wr_epoch; }
-  else {                                                                        /* no decode to be gated by: an epoch of its own, which no gate word holds */
-    a.timeout = lane(c).timeout; a.epoch = ++c->epoch;
-    if (a.epoch == 0) a.epoch = ++c->epoch;
-  }
+  const hipStream_t cs = reader_begin(c, f, RD_EXPORT, &a.timeout, &a.epoch);
   m355_launch_export(a, f->bpp[0], e->samples == M355_EXPORT_NATIVE ? f->bpp[0] : (e->samples == M355_EXPORT_MSB16 ? 2 : 1), semi, cs);
   HIPCHK(hipGetLastError());
-  return ev_mark(c, cs, &f->ex);
+  return reader_end(c, f, RD_EXPORT, cs);
 }
 /* the host waits until this frame's last export has landed */
 int m355_frame_export_wait(m355_ctx* c, int h)
@@ -484,8 +476,8 @@ int m355_frame_export_wait(m355_ctx* c, int h)
   Frame* f = get_frame(c, h);
   if (!f) return fail(M355_ERR_INVALID, "bad frame handle %d", h);
   hipSetDevice(c->device);
-  HIPCHK(ev_sync(c, f->ex));
-  f->ex = EvRef();
+  HIPCHK(ev_sync(c, f->reader[RD_EXPORT]));
+  f->reader[RD_EXPORT] = EvRef();
   return M355_OK;
 }
 /* the consumer's stream continues behind this frame's last export (nothing to enqueue when that has long passed: its mark has left the ring) */
@@ -494,7 +486,7 @@ int m355_frame_export_order(m355_ctx* c, int h, void* consumer)
   Frame* f = get_frame(c, h);
   if (!f) return fail(M355_ERR_INVALID, "bad frame handle %d", h);
   hipSetDevice(c->device);
-  ev_wait(c, (hipStream_t)consumer, f->ex);
+  ev_wait(c, (hipStream_t)consumer, f->reader[RD_EXPORT]);
   return M355_OK;
 }
 /* Device memory for the destinations of m355_frame_export, for applications (and tests) that have no HIP runtime of their own in the process */
@@ -610,36 +602,14 @@ void* m355_host_alloc(size_t bytes)
 }
 void m355_host_free(void* p) { if (p) hipHostFree(p); }
 
-int m355_frame_hash(m355_ctx* c, int h, int type, m355_picture_hash* out)
+/* the launch arguments of the hash kernels for the frame's planes (a.out / the request stay with the caller) */
+static void hash_args_fill(const Frame* f, HashArgs& a)
 {
-  Frame* f = get_frame(c, h);
-  if (!f || !out) return fail(M355_ERR_INVALID, "bad frame handle %d / null result", h);
-  if (type != M355_HASH_MD5 && type != M355_HASH_CRC && type != M355_HASH_CHECKSUM) return fail(M355_ERR_INVALID, "bad hash type %d", type);
-  hipSetDevice(c->device);
-  HIPCHK(sync_all(c));
   const int np = f->pw[1] ? 3 : 1;
-  if (type == M355_HASH_MD5) {
-    std::vector<uint8_t> host[3];
-    std::vector<std::thread> th;
-    for (int cc = 0; cc < np; cc++) {
-      const size_t rb = (size_t)f->pw[cc] * f->bpp[cc];
-      host[cc].resize(rb * f->ph[cc]);
-      { int rc = frame_stage_down(c, f, cc, host[cc].data(), rb); if (rc) { for (auto& t : th) t.join(); return rc; } }
-      th.emplace_back([&, cc, rb] { m355_md5_rows(host[cc].data(), rb, (int)rb, f->ph[cc], out->md5[cc]); });
-    }
-    for (auto& t : th) t.join();
-    return M355_OK;
-  }
-  if (!c->hash_acc) HIPCHK(hipMalloc(&c->hash_acc, 4 * sizeof(uint32_t)));
-  HashArgs a = {};
-  a.out = c->hash_acc;
-  {
-    /* enough waves to fill 1024 SIMDs a few times over, each still covering >= 1 row */
-    int rows = 0;
-    for (int cc = 0; cc < np; cc++) rows += f->ph[cc];
-    a.rows_per_wave = std::max(1, rows / 4096);
-  }
-  int nw = 0;
+  /* enough waves to fill 1024 SIMDs a few times over, each still covering >= 1 row */
+  int rows = 0, nw = 0;
+  for (int cc = 0; cc < np; cc++) rows += f->ph[cc];
+  a.rows_per_wave = std::max(1, rows / 4096);
   for (int cc = 0; cc < 3; cc++) {
     a.first[cc] = nw;
     if (cc >= np) continue;
@@ -651,6 +621,41 @@ int m355_frame_hash(m355_ctx* c, int h, int type, m355_picture_hash* out)
     nw += (f->ph[cc] + a.rows_per_wave - 1) / a.rows_per_wave;
   }
   a.first[3] = nw;
+}
+/* MD5 of `np` planes in host memory (rows packed: pitch = row_bytes), one thread per plane: each is one serial chain (k_hash.hip) */
+static void md5_planes(int np, const uint8_t* const base[3], const int row_bytes[3], const int rows[3], m355_picture_hash* out)
+{
+  std::vector<std::thread> th;
+  for (int cc = 0; cc < np; cc++) th.emplace_back([=] { m355_md5_rows(base[cc], (size_t)row_bytes[cc], row_bytes[cc], rows[cc], out->md5[cc]); });
+  for (auto& t : th) t.join();
+}
+
+int m355_frame_hash(m355_ctx* c, int h, int type, m355_picture_hash* out)
+{
+  Frame* f = get_frame(c, h);
+  if (!f || !out) return fail(M355_ERR_INVALID, "bad frame handle %d / null result", h);
+  if (type != M355_HASH_MD5 && type != M355_HASH_CRC && type != M355_HASH_CHECKSUM) return fail(M355_ERR_INVALID, "bad hash type %d", type);
+  hipSetDevice(c->device);
+  HIPCHK(sync_all(c));
+  const int np = f->pw[1] ? 3 : 1;
+  if (type == M355_HASH_MD5) {
+    std::vector<uint8_t> host[3];
+    const uint8_t* base[3] = {nullptr, nullptr, nullptr};
+    int row_bytes[3] = {0, 0, 0};
+    for (int cc = 0; cc < np; cc++) {
+      row_bytes[cc] = f->pw[cc] * f->bpp[cc];
+      host[cc].resize((size_t)row_bytes[cc] * f->ph[cc]);
+      const int rc = frame_stage_down(c, f, cc, host[cc].data(), (size_t)row_bytes[cc]);
+      if (rc) return rc;
+      base[cc] = host[cc].data();
+    }
+    md5_planes(np, base, row_bytes, f->ph, out);
+    return M355_OK;
+  }
+  if (!c->hash_acc) HIPCHK(hipMalloc(&c->hash_acc, 4 * sizeof(uint32_t)));
+  HashArgs a = {};
+  a.out = c->hash_acc;
+  hash_args_fill(f, a);
   uint32_t acc[4] = {0, 0, 0, 0};
   const hipStream_t st = lane(c).stream;
   HIPCHK(hipMemsetAsync(c->hash_acc, 0, 4 * sizeof(uint32_t), st));
@@ -671,12 +676,6 @@ static m355_ctx::HashSlot* hash_slot_of(m355_ctx* c, unsigned long long ticket)
 {
   if (ticket) for (auto& s : c->hash_slot) if (s.ticket == ticket) return &s;
   return nullptr;
-}
-/* `st` continues behind the frame's last hash request (a reader of the frame): nothing to enqueue when the request runs on `st` itself or has been
-   collected — a request is collected behind its mark, so that mark has passed */
-void hash_reader_wait(m355_ctx* c, hipStream_t st, const Frame* f) {
-  if (!f->hs || f->hs_stream == st) return;
-  if (const m355_ctx::HashSlot* s = hash_slot_of(c, f->hs)) hipStreamWaitEvent(st, s->ev, 0);
 }
 /* an MD5 request's pinned planes: the smallest idle buffer that fits, else a new one (nothing is freed here: hipHostFree may wait for the device —
    a buffer smaller than the largest one made is freed when its request is collected, hash_slot_free) */
@@ -709,11 +708,16 @@ static void hash_slot_free(m355_ctx* c, m355_ctx::HashSlot& s)
     else c->hash_pool.push_back(std::make_pair(s.planes, s.planes_cap));
   }
   s.planes = nullptr; s.planes_cap = 0;
+  /* a request is collected behind its mark: the next decode into its frame has nothing to wait for (a wait packet saved where the request is collected before
+     the frame is recycled: about 2 us, profiles/r04_aj_stage_events_ab.txt) — if the frame's mark is still this request's: handles are reused, tickets are not */
+  Frame* f = get_frame(c, s.frame);
+  if (f && s.mark.ticket && f->reader[RD_HASH].ticket == s.mark.ticket) f->reader[RD_HASH] = EvRef();
+  s.mark = EvRef(); s.frame = -1;
   s.ticket = 0;
 }
 
-/* Enqueue only: the host waits for nothing here.  A READER of the frame, queued like m355_frame_export on the stream of the decode that wrote the frame, behind
-   the frame's earlier readers where those run on another stream; the next decode into the frame waits for the request's mark (dst_hazards -> hash_reader_wait). */
+/* Enqueue only: the host waits for nothing here.  A READER of the frame (reader_begin), like m355_frame_export: the next decode into the frame waits for the
+   request's mark (dst_hazards), which the slot remembers for m355_frame_hash_result. */
 int m355_frame_hash_async(m355_ctx* c, int h, int type, unsigned long long* ticket)
 {
   Frame* f = get_frame(c, h);
@@ -739,42 +743,18 @@ int m355_frame_hash_async(m355_ctx* c, int h, int type, unsigned long long* tick
   q.res = c->hash_res + slot * HASH_RES_WORDS;
   q.seq = (uint32_t)(c->hash_ticket + 1);
   q.res[3] = HASH_RES_NONE;                                                     /* (the slot is idle: nothing in flight writes its record) */
-  hipStream_t cs = f->wr_stream ? f->wr_stream : lane(c).stream;                /* (no decode of this context wrote it: uploads and fills are synchronous) */
-  if (!f->wr_stream) ev_wait(c, cs, f->wr);
-  ev_wait(c, cs, f->ex);
-  hash_reader_wait(c, cs, f);                                                   /* (an earlier request on another stream: the one mark kept stands for both) */
-  if (f->wr_stream && f->wr_gate) { q.timeout = f->wr_gate; q.epoch = f->wr_epoch; }
-  else {                                                                        /* no decode to be gated by: an epoch of its own, which no gate word holds */
-    q.timeout = lane(c).timeout; q.epoch = ++c->epoch;
-    if (q.epoch == 0) q.epoch = ++c->epoch;
-  }
   HashArgs a = {};
   a.out = q.rec;
-  if (type == M355_HASH_MD5) {
-    /* (behind a rejected decode the copies bring an older picture's planes: the verdict says so, the result is never made of them) */
-    for (int cc = 0; cc < s->np; cc++)
-      if (hipMemcpy2DAsync(s->planes + plane_ofs[cc], (size_t)s->row_bytes[cc], f->plane[cc], (size_t)f->stride[cc] * f->bpp[cc], (size_t)s->row_bytes[cc], s->rows[cc],
-                           hipMemcpyDeviceToHost, cs) != hipSuccess) { hash_slot_free(c, *s); return fail(M355_ERR_HIP, "m355_frame_hash_async: copy of plane %d failed", cc); }
-  } else {
-    int rows = 0, nw = 0;
-    for (int cc = 0; cc < s->np; cc++) rows += f->ph[cc];
-    a.rows_per_wave = std::max(1, rows / 4096);                                 /* as m355_frame_hash */
-    for (int cc = 0; cc < 3; cc++) {
-      a.first[cc] = nw;
-      if (cc >= s->np) continue;
-      a.pl[cc].base = (const uint8_t*)f->plane[cc];
-      a.pl[cc].pitch = (size_t)f->stride[cc] * f->bpp[cc];
-      a.pl[cc].row_bytes = s->row_bytes[cc];
-      a.pl[cc].h = f->ph[cc];
-      a.pl[cc].bpp = f->bpp[cc];
-      nw += (f->ph[cc] + a.rows_per_wave - 1) / a.rows_per_wave;
-    }
-    a.first[3] = nw;
-  }
+  if (type != M355_HASH_MD5) hash_args_fill(f, a);
+  const hipStream_t cs = reader_begin(c, f, RD_HASH, &q.timeout, &q.epoch);
+  /* (MD5: behind a rejected decode the copies bring an older picture's planes: the verdict says so, the result is never made of them) */
+  for (int cc = 0; type == M355_HASH_MD5 && cc < s->np; cc++)
+    if (hipMemcpy2DAsync(s->planes + plane_ofs[cc], (size_t)s->row_bytes[cc], f->plane[cc], (size_t)f->stride[cc] * f->bpp[cc], (size_t)s->row_bytes[cc], s->rows[cc],
+                         hipMemcpyDeviceToHost, cs) != hipSuccess) { hash_slot_free(c, *s); return fail(M355_ERR_HIP, "m355_frame_hash_async: copy of plane %d failed", cc); }
   m355_launch_frame_hash_req(a, q, type, cs);
-  if (hipGetLastError() != hipSuccess || hipEventRecord(s->ev, cs) != hipSuccess) { hash_slot_free(c, *s); return fail(M355_ERR_HIP, "m355_frame_hash_async: launch failed"); }
+  if (hipGetLastError() != hipSuccess || reader_end(c, f, RD_HASH, cs) != M355_OK) { hash_slot_free(c, *s); return fail(M355_ERR_HIP, "m355_frame_hash_async: launch failed"); }
+  s->mark = f->reader[RD_HASH]; s->frame = h;
   s->ticket = ++c->hash_ticket;
-  f->hs = s->ticket; f->hs_stream = cs;
   *ticket = s->ticket;
   return M355_OK;
 }
@@ -785,9 +765,9 @@ int m355_frame_hash_result(m355_ctx* c, unsigned long long ticket, int block, m3
   if (!s) return fail(M355_ERR_INVALID, "m355_frame_hash_result: ticket %llu is unknown or was collected", ticket);
   if (!out) return fail(M355_ERR_INVALID, "m355_frame_hash_result: null result");
   hipSetDevice(c->device);
-  if (block) HIPCHK(hipEventSynchronize(s->ev));                                /* this request's mark only */
+  if (block) HIPCHK(ev_sync(c, s->mark));                                       /* this request's mark only */
   else {
-    const hipError_t e = hipEventQuery(s->ev);
+    const hipError_t e = ev_query(c, s->mark);
     if (e == hipErrorNotReady) return M355_ERR_BUSY;
     if (e != hipSuccess) return fail(M355_ERR_HIP, "hipEventQuery failed: %s", hipGetErrorString(e));
   }
@@ -802,15 +782,9 @@ int m355_frame_hash_result(m355_ctx* c, unsigned long long ticket, int block, m3
     return fail(M355_ERR_HIP, "hash request %llu finished without a result (state %u, sequence %u)", ticket, state, seq);
   }
   if (s->type == M355_HASH_MD5) {
-    std::vector<std::thread> th;
-    size_t ofs = 0;
-    for (int cc = 0; cc < s->np; cc++) {
-      const uint8_t* p = s->planes + ofs;
-      const int rb = s->row_bytes[cc], rows = s->rows[cc];
-      th.emplace_back([=] { m355_md5_rows(p, (size_t)rb, rb, rows, out->md5[cc]); });
-      ofs += ((size_t)rb * rows + 255) & ~(size_t)255;
-    }
-    for (auto& t : th) t.join();
+    const uint8_t* base[3] = {s->planes, nullptr, nullptr};
+    for (int cc = 1; cc < s->np; cc++) base[cc] = base[cc - 1] + (((size_t)s->row_bytes[cc - 1] * s->rows[cc - 1] + 255) & ~(size_t)255);
+    md5_planes(s->np, base, s->row_bytes, s->rows, out);
   } else
     for (int cc = 0; cc < s->np; cc++) {
       if (s->type == M355_HASH_CRC) out->crc[cc] = (uint16_t)(res[cc] ^ m355_crc_init_term((uint64_t)s->row_bytes[cc] * s->rows[cc]));
@@ -955,7 +929,7 @@ int m355_wait(m355_ctx* c)
 {
   hipSetDevice(c->device);
   HIPCHK(sync_all(c));
-  for (auto& f : c->frames) { f.wr = EvRef(); f.ex = EvRef(); f.hs = 0; f.dl_pending = false; for (int k = 0; k < M355_MAX_LANES; k++) f.rd[k] = EvRef(); }   /* everything is complete */
+  for (auto& f : c->frames) { f.wr = EvRef(); for (EvRef& m : f.reader) m = EvRef(); for (int k = 0; k < M355_MAX_LANES; k++) f.rd[k] = EvRef(); }   /* everything is complete */
   uint32_t t = 0;
   for (const Lane& l : c->lanes)
     if (l.timeout) { uint32_t t2 = 0; HIPCHK(hipMemcpy(&t2, l.timeout, 4, hipMemcpyDeviceToHost)); t |= t2; }

@@ -164,11 +164,6 @@ int prepare(m355_ctx* c, Resident& r, DevPic& d_out, bool& want_sao_out, hipStre
   return M355_OK;
 }
 
-hipError_t frame_event(hipEvent_t* e) {
-  if (*e) return hipSuccess;
-  return hipEventCreateWithFlags(e, hipEventDisableTiming);
-}
-
 /* The prediction half of a decode on the active lane, enqueued on `st`: the metadata planes (read first by k_intra) are rasterised on the side
  * stream while the main stream runs job list -> inter prediction, which do not read them; the residual stage then runs in two
  * launches side by side — 32x32 + 16x16 blocks on the main stream, 8x8 + 4x4 on the side stream — and k_intra follows the join.
@@ -286,9 +281,7 @@ hipStream_t launch_prediction(m355_ctx* c, const Resident& r, const DevPic& d, b
 /* write-after-write / write-after-read on the destination: waited for right before the first kernel that writes it — the SAO
    stage when SAO runs (everything before writes this lane's working planes), else the first stage */
 void dst_hazards(m355_ctx* c, Frame* dstf, bool piped, hipStream_t st) {
-  if (dstf->dl_pending) hipStreamWaitEvent(st, dstf->ev_dl, 0);     /* (stays pending for the HOST until m355_frame_download_wait / m355_wait) */
-  ev_wait(c, st, dstf->ex);                                          /* an export of the frame's previous picture (queued on that picture's stream) */
-  hash_reader_wait(c, st, dstf);                                     /* ... a hash request on it (m355_frame_hash_async) */
+  readers_wait(c, st, dstf);                                         /* downloads, exports, hash requests of the frame's previous picture (queued on that picture's stream) */
   if (!piped) return;
   ev_wait(c, st, dstf->wr);
   for (int k = 0; k < M355_MAX_LANES; k++) ev_wait(c, st, dstf->rd[k]);
@@ -423,7 +416,6 @@ static int decode_post(m355_ctx* c, Resident& r, DecodeState& S, bool filters = 
     Frame* f = r.hdr.ref_frames[i] >= 0 ? get_frame(c, r.hdr.ref_frames[i]) : nullptr;
     if (f) f->rd[c->active] = done;
   }
-  if (ev) c->timed = true;
   {
     /* this decode's status slot; a device-validated decode also brings its lane's gate words back — behind the mark the dependent
        decodes wait on, with a mark of its own: nobody waits for this copy but m355_decode_status / m355_wait */

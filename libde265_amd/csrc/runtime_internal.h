@@ -74,6 +74,7 @@ constexpr int intra_class_first_lane = 3;
 struct EvRef { unsigned long long ticket = 0; hipStream_t stream = nullptr; };
 #define M355_EV_RING 256
 
+enum ReaderKind { RD_DOWNLOAD, RD_EXPORT, RD_HASH, RD_KINDS };
 struct Frame {
   bool used = false;
   int w = 0, h = 0, cf = 0, bdl = 0, bdc = 0;
@@ -81,18 +82,16 @@ struct Frame {
   void* plane[3] = {nullptr, nullptr, nullptr};
   /* pictures in flight on different lanes (m355_set_pipeline_depth): last writer / last readers per lane */
   EvRef wr, rd[M355_MAX_LANES];
-  /* a download in flight on the context's copy stream (m355_frame_download_async): the next writer of the frame waits for it */
-  hipEvent_t ev_dl = nullptr;
-  bool dl_pending = false;
-  hipStream_t wr_stream = nullptr;         /* the stream that last wrote the frame (its downloads and exports are queued on that stream) */
-  /* the gate of the decode that last wrote the frame (its lane's gate words, its epoch): an export queued behind a decode whose lists were
+  hipStream_t wr_stream = nullptr;         /* the stream that last wrote the frame */
+  /* the gate of the decode that last wrote the frame (its lane's gate words, its epoch): a reader's kernel queued behind a decode whose lists were
      rejected does nothing, like that decode's own kernels (M355_GATE) */
   const uint32_t* wr_gate = nullptr; uint32_t wr_epoch = 0;
-  /* the last export in flight (m355_frame_export, a reader of the frame): the next writer waits for it in front of its first write */
-  EvRef ex;
-  /* the last hash request in flight on the frame (m355_frame_hash_async, a reader like the export): its ticket and the stream it runs on;
-     the mark itself is the request's own event (hash_reader_wait) */
-  unsigned long long hs = 0; hipStream_t hs_stream = nullptr;
+  /* READERS queued behind the decode that wrote the frame — a download (m355_frame_download_async), an export (m355_frame_export), a hash request
+     (m355_frame_hash_async): per kind the mark behind the LAST one.  reader_begin picks the stream (the writer's, so stream order stands for the wait for the
+     picture) and lets it continue behind the kind's earlier mark, so that the one mark kept stands for both; reader_end marks; the next decode into the frame
+     waits for every kind in front of its first write (readers_wait, from dst_hazards).  The kinds are separate because the HOST waits per kind
+     (m355_frame_download_wait, m355_frame_export_wait, m355_frame_hash_result), and a finished wait clears its mark: readers of different kinds need no order. */
+  EvRef reader[RD_KINDS];
 };
 
 static void frame_geometry(Frame& f, int w, int h, int cf, int bdl, int bdc)
@@ -128,9 +127,8 @@ static void frame_free(Frame& f)
   for (int c = 0; c < 3; c++) { if (f.plane[c]) hipFree(f.plane[c]); f.plane[c] = nullptr; }
   f.wr = EvRef();
   for (int k = 0; k < M355_MAX_LANES; k++) f.rd[k] = EvRef();
-  f.ev_dl = nullptr; f.dl_pending = false; f.wr_stream = nullptr;
-  f.wr_gate = nullptr; f.wr_epoch = 0; f.ex = EvRef();
-  f.hs = 0; f.hs_stream = nullptr;
+  for (EvRef& m : f.reader) m = EvRef();
+  f.wr_stream = nullptr; f.wr_gate = nullptr; f.wr_epoch = 0;
   f.used = false;
 }
 
@@ -211,8 +209,6 @@ struct m355_ctx {
   struct EvSlot { hipEvent_t ev = nullptr; unsigned long long ticket = 0; };
   EvSlot evring[M355_EV_RING];
   unsigned long long ev_ticket = 0;
-  std::vector<hipEvent_t> dl_evs;          /* m355_frame_download_async: ring of completion events */
-  int dl_ev_next = 0;
   std::vector<Frame> frames;
   std::vector<Resident> resident;
   /* m355_submit_picture: rotating staging arenas, so the host prepares picture k+1 while k decodes; a slot is free again when the
@@ -241,15 +237,14 @@ struct m355_ctx {
   int xchg_h = -1, xchg_k = -1;      /* m355_decode_sharded: the picture handle / exchange the callbacks are being called for */
   std::vector<hipEvent_t> evs;  /* 7 events per timed decode (ring grows on demand) */
   int ev_used = 0;             /* decodes recorded since the last m355_timing_reset */
-  bool timed = false;
   bool timing_on = false;      /* between m355_timing_reset and m355_timing_collect: decodes record their seven stage events */
   uint32_t* hash_acc = nullptr; /* m355_frame_hash accumulators */
-  /* m355_frame_hash_async: M355_HASH_REQUESTS slots, each with a device record (zero between requests: the kernel leaves it so), a pinned
-     result record and the event that is the request's mark; all allocated when the context is created.  ticket == 0: the slot is free. */
+  /* m355_frame_hash_async: M355_HASH_REQUESTS slots, each with a device record (zero between requests: the kernel leaves it so) and a pinned
+     result record, allocated when the context is created, and the mark behind its request.  ticket == 0: the slot is free. */
   struct HashSlot {
     unsigned long long ticket = 0; int type = 0, np = 0;
     int row_bytes[3] = {0, 0, 0}, rows[3] = {0, 0, 0};
-    hipEvent_t ev = nullptr;
+    EvRef mark; int frame = -1;                         /* the request's mark and the frame it reads (collecting it clears that frame's mark, if still this one) */
     uint8_t* planes = nullptr; size_t planes_cap = 0;   /* MD5: pinned copy of the planes, taken from hash_pool */
   };
   HashSlot hash_slot[M355_HASH_REQUESTS];
@@ -321,12 +316,14 @@ void clear_target(m355_ctx* c, const DevPic& d, Frame* tgt, bool gated, hipStrea
 int copy_tiles(m355_ctx* c, const m355_pic_params& pp, Frame* f, int k0, int k1, int skip, int nranks, char* xbuf, size_t slot, bool to_slot);
 int decode(m355_ctx* c, Resident& r, bool rotate = true);
 void dst_hazards(m355_ctx* c, Frame* dstf, bool piped, hipStream_t st);
-void hash_reader_wait(m355_ctx* c, hipStream_t st, const Frame* f);
 int ev_mark(m355_ctx* c, hipStream_t st, EvRef* out);
 hipError_t ev_query(m355_ctx* c, const EvRef& r);
 hipError_t ev_sync(m355_ctx* c, const EvRef& r);
 void ev_wait(m355_ctx* c, hipStream_t st, const EvRef& r);
 Frame* get_frame(m355_ctx* c, int h);
+hipStream_t reader_begin(m355_ctx* c, Frame* f, int kind, const uint32_t** gate = nullptr, uint32_t* epoch = nullptr);
+int reader_end(m355_ctx* c, Frame* f, int kind, hipStream_t st);
+void readers_wait(m355_ctx* c, hipStream_t st, const Frame* f);
 void halo_layout(const m355_pic_params& pp, HaloLayout& h);
 int lane_class_priority(int index);
 int lane_priorities_mode();
@@ -338,7 +335,6 @@ size_t slot_bytes(const m355_pic_params& pp, int nranks);
 int status_of(m355_ctx* c, m355_ctx::Status& s);
 hipError_t sync_all(m355_ctx* c);
 int upload(m355_ctx* c, Resident& r, const m355_picture* pic);
-hipError_t frame_event(hipEvent_t* e);
 }
 
 #endif

@@ -5,7 +5,7 @@ into the frame is checked where launches are asynchronous (tests/test_gpu_hash_a
 (tests/hash_async_util.py).
 
 One property cannot be observed from outside and is kept by reading the code: m355_frame_hash_async and what it calls
-(hash_reader_wait, hash_planes_take, ev_wait, m355_launch_frame_hash_req) contain no sync_all, hipStreamSynchronize,
+(reader_begin, reader_end, hash_planes_take, ev_wait, ev_mark, m355_launch_frame_hash_req) contain no sync_all, hipStreamSynchronize,
 hipEventSynchronize or hipDeviceSynchronize."""
 import pytest
 
