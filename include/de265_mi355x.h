@@ -548,7 +548,10 @@ M355_API int m355_wait(m355_ctx* ctx);
  * ahead of the picture's kernels: m355_submit_picture has returned M355_OK long before a rejection is known.  Every decode gets
  * a serial (1, 2, ...); m355_decode_status(serial) is non-blocking: M355_ERR_BUSY while the decode runs, M355_OK when it finished,
  * M355_ERR_INVALID when its lists were rejected — none of its kernels acted on them, the destination frame was NOT written
- * (m355_last_error names the record).  Kept for the last 64 decodes (an older serial: M355_ERR_STALE — distinct from a rejection, which M355_ERR_INVALID stays for; a
+ * (m355_last_error names the record: the same checks and list names as for lists the library copies, which
+ * m355_submit_picture rejects itself.  Two lists are numbered differently on the two paths: a residual block rejected at the submit is
+ * numbered across the four size bins concatenated, one rejected on the device inside its own bin; and the device checks its sorted copy of
+ * ibs, so an intra block's number there need not be the caller's).  Kept for the last 64 decodes (an older serial: M355_ERR_STALE — distinct from a rejection, which M355_ERR_INVALID stays for; a
  * rejection that left the ring unreported is still reported by the next m355_wait).  The caller marks the picture and whatever references it
  * as damaged (the reference does the same bookkeeping with de265_image::integrity, image.h:347). */
 M355_API unsigned long long m355_last_serial(m355_ctx* ctx);      /* of the decode the last submit / decode call enqueued */

@@ -100,7 +100,7 @@ int prepare(m355_ctx* c, Resident& r, DevPic& d_out, bool& want_sao_out, hipStre
   if ((rc = grow(&L.sao_nb, &L.cap_sao, (size_t)d.nCtb * 3, st, false))) return rc;
   {
     /* inter jobs of 4 x 8 luma samples: a list of disjoint prediction blocks makes at most one per 16 luma samples (8x4 blocks),
-       and at most one per 32 plus eight per block; the counts themselves are made on the device (k_job_count / k_job_scan) */
+       and at most one per 32 plus eight per block; the counts themselves are made on the device (k_job_count / k_meta_pb) */
     const size_t area = (size_t)pp.width * pp.height;
     const size_t cap = pic.n_pbs > 0 ? std::min(area / 16, area / 32 + 8 * (size_t)pic.n_pbs) + 256 : 1;
     const size_t n_chunks = ((size_t)(pic.n_pbs > 0 ? pic.n_pbs : 0) + 255) / 256;

@@ -3,6 +3,7 @@
  * (dependency levels, exec records, work list) and upload(): lists -> one pinned arena -> the device.
  */
 #include "runtime_internal.h"
+#include "record_checks.h"
 
 extern "C" {
 /* ----------------------------------------------------------------------- validation ----------- */
@@ -125,21 +126,6 @@ template <class F> static void parallel_ranges(size_t n, size_t min_per_thread, 
   if (!g.owns_lock()) { f((size_t)0, n); return; }
   host_pool().run(T, part);
 }
-/* check(i) -> nullptr or a message; the LOWEST failing index is reported as "<what> <i>: <message>" */
-template <class F> static int check_all(const char* what, size_t n, F check)
-{
-  std::atomic<size_t> first(n);
-  std::atomic<const char*> msg(nullptr);
-  std::mutex mu;
-  parallel_ranges(n, 32768, [&](size_t b, size_t e) {
-    for (size_t i = b; i < e && i < first.load(std::memory_order_relaxed); i++) {
-      const char* m = check(i);
-      if (m) { std::lock_guard<std::mutex> g(mu); if (i < first.load()) { first.store(i); msg.store(m); } return; }
-    }
-  });
-  if (first.load() < n) return fail(M355_ERR_INVALID, "%s %zu: %s", what, first.load(), msg.load());
-  return M355_OK;
-}
 static void parallel_memcpy(void* dst, const void* src, size_t bytes)
 {
   parallel_ranges(bytes, (size_t)1 << 20, [=](size_t b, size_t e) { memcpy((char*)dst + b, (const char*)src + b, e - b); });
@@ -173,7 +159,6 @@ static int validate(const m355_picture* pic, const m355_rb* const* rb_bin_in, bo
   if ((pp.flags & M355_PF_SCALING_LIST) && !pic->scaling_factors) return fail(M355_ERR_INVALID, "scaling list enabled but no factors");
   if (pic->n_cus < 0 || pic->n_tus < 0 || pic->n_pbs < 0 || pic->n_wts < 0 || pic->n_ibs < 0) return fail(M355_ERR_INVALID, "negative list length");
   const int sw = (pp.chroma_format_idc == 1 || pp.chroma_format_idc == 2) ? 2 : 1, sh = pp.chroma_format_idc == 1 ? 2 : 1;
-  int rc;
   uint32_t ibsum = 0;
   for (int i = 0; i < pic->n_ctbs; i++) {
     const m355_ctb& c = pic->ctbs[i];
@@ -185,6 +170,8 @@ static int validate(const m355_picture* pic, const m355_rb* const* rb_bin_in, bo
   size_t nrb = 0, bin_end[4];
   for (int s = 0; s < 4; s++) { if (pic->rb_count[s] < 0) return fail(M355_ERR_INVALID, "negative rb_count"); nrb += (size_t)pic->rb_count[s]; bin_end[s] = nrb; }
   /* every record of every list, as ONE parallel sweep over their concatenation (one thread start-up per picture) */
+  /* each CTB's intra blocks lie inside it: host only, for lists recorded in place too — the host's own schedules (intra_schedule)
+     index by a block's position inside its CTB */
   auto chk_ctb = [&](size_t i) -> const char* {
     const m355_ctb& c = pic->ctbs[i];
     const int cx = (int)i % ctbW, cy = (int)i / ctbW;
@@ -197,59 +184,23 @@ static int validate(const m355_picture* pic, const m355_rb* const* rb_bin_in, bo
     }
     return nullptr;
   };
-  auto chk_cu = [&](size_t i) -> const char* {
-    const m355_cu& cu = pic->cus[i];
-    return (cu.log2_size < pp.log2_min_cb_size || cu.log2_size > pp.log2_ctb_size || cu.x >= pp.width || cu.y >= pp.height || cu.pred_mode > 2 || cu.part_mode > 7) ? "malformed" : nullptr;
-  };
-  auto chk_tu = [&](size_t i) -> const char* {
-    const m355_tu& tu = pic->tus[i];
-    return (tu.log2_size < 2 || tu.log2_size > 6 || tu.x >= pp.width || tu.y >= pp.height) ? "malformed" : nullptr;
-  };
-  auto chk_pb = [&](size_t i) -> const char* {
-    const m355_pb& pb = pic->pbs[i];
-    if (pb.w < 4 || pb.h < 4 || pb.w > 64 || pb.h > 64 || (pb.w & 3) || (pb.h & 3) || pb.x + pb.w > pp.width || pb.y + pb.h > pp.height) return "geometry";
-    if (!(pb.flags & (M355_PBF_MC_L0 | M355_PBF_MC_L1))) return "no list selected";
-    for (int l = 0; l < 2 && !records_on_device; l++) {
-      if (!(pb.flags & (M355_PBF_MC_L0 << l))) continue;
-      if (!(pb.flags & (M355_PBF_FILL_L0 << l)) && (pb.ref_slot[l] < 0 || pb.ref_slot[l] >= M355_MAX_REF_FRAMES || pic->ref_frames[pb.ref_slot[l]] < 0)) return "reference slot invalid";
-      if ((pb.flags & M355_PBF_WEIGHTED) && pb.wt_idx[l] >= pic->n_wts) return "weight index";
-    }
-    return nullptr;
-  };
-  auto chk_wt = [&](size_t i) -> const char* {
-    return (pic->wts[i].log2wd_luma < 1 || pic->wts[i].log2wd_luma > 31 || (pp.chroma_format_idc && (pic->wts[i].log2wd_chroma < 1 || pic->wts[i].log2wd_chroma > 31))) ? "log2WD out of range" : nullptr;
-  };
+  /* the record checks proper: record_checks.h, shared with k_validate */
+  M355RecLimits lim = {pp.width, pp.height, sw, sh, pp.chroma_format_idc, pp.log2_min_cb_size, pp.log2_ctb_size, pic->n_wts,
+                       pp.flags, pic->n_coeffs, pic->res_len, pic->n_pcm, 0};
+  for (int i = 0; i < M355_MAX_REF_FRAMES; i++) if (pic->ref_frames[i] >= 0) lim.ref_mask |= 1u << i;
   /* the four size bins: consecutive in rbs[], or (lists recorded in place) in the regions m355_arena_begin handed out */
   const m355_rb* rb_bin[4];
   for (int b = 0; b < 4; b++) rb_bin[b] = rb_bin_in ? rb_bin_in[b] : pic->rbs + (b ? bin_end[b - 1] : 0);
-  auto chk_rb = [&](size_t k) -> const char* {
+  auto chk_rb = [&](size_t k) {          /* (numbered across the four bins concatenated) */
     const int s = k < bin_end[0] ? 0 : (k < bin_end[1] ? 1 : (k < bin_end[2] ? 2 : 3));
-    const m355_rb& rb = rb_bin[s][k - (s ? bin_end[s - 1] : 0)];
-    const int n = 1 << (s + 2);
-    const int W = rb.cidx ? pp.width / sw : pp.width, H = rb.cidx ? pp.height / sh : pp.height;
-    if (rb.log2_size != s + 2 || rb.cidx > 2 || rb.kind > 3 || rb.x + n > W || rb.y + n > H) return "malformed";
-    /* (words, not entries: a narrow block holds two entries per word) */
-    if ((uint64_t)rb.coeff_ofs + ((rb.flags & M355_RBF_NARROW) ? (rb.ncoeff + 1u) / 2 : rb.ncoeff) > pic->n_coeffs) return "coefficient range";
-    if ((rb.flags & M355_RBF_DEFERRED) && (uint64_t)rb.res_ofs + n * n > pic->res_len) return "residual range";
-    if ((pp.flags & M355_PF_SCALING_LIST) && (rb.matrix_id & 7) > 5) return "matrix id";
-    if (rb.kind == M355_RK_DST && s != 0) return "DST only exists for 4x4";
-    return nullptr;
-  };
-  auto chk_ib = [&](size_t i) -> const char* {
-    const m355_ib& ib = pic->ibs[i];
-    const int n = 1 << ib.log2_size;
-    const int W = ib.cidx ? pp.width / sw : pp.width, H = ib.cidx ? pp.height / sh : pp.height;
-    if (ib.log2_size < 2 || ib.log2_size > 5 || ib.cidx > 2 || ib.mode > 34 || ib.x + n > W || ib.y + n > H) return "malformed";
-    if ((ib.flags & M355_IBF_HAS_RESIDUAL) && (uint64_t)ib.res_ofs + n * n > pic->res_len) return "residual range";
-    if ((ib.flags & M355_IBF_PCM) && (uint64_t)ib.res_ofs + n * n > pic->n_pcm) return "pcm range";
-    return nullptr;
+    return m355_check_rb(rb_bin[s][k - (s ? bin_end[s - 1] : 0)], s, lim);
   };
   const char* const names[7] = {"ctb", "cu", "tu", "pb", "weight", "rb", "ib"};
   /* records_on_device: only what the host's own schedules index by is checked here — the CTB table with each CTB's intra blocks;
      every record check runs in k_validate before any kernel acts on the lists, and the inter job counts are made on the device
-     (k_job_count / k_job_scan): the host does not read the PB list at all */
-  const size_t cnts[7] = {(size_t)pic->n_ctbs, records_on_device ? 0 : (size_t)pic->n_cus, records_on_device ? 0 : (size_t)pic->n_tus, records_on_device ? 0 : (size_t)pic->n_pbs,
-                          records_on_device ? 0 : (size_t)pic->n_wts, records_on_device ? 0 : nrb, records_on_device ? 0 : (size_t)pic->n_ibs};
+     (k_job_count / k_meta_pb): the host does not read the PB list at all */
+  const size_t rec = records_on_device ? 0 : 1;
+  const size_t cnts[7] = {(size_t)pic->n_ctbs, rec * pic->n_cus, rec * pic->n_tus, rec * pic->n_pbs, rec * pic->n_wts, rec * nrb, rec * pic->n_ibs};
   size_t ofs[8];
   ofs[0] = 0;
   for (int q = 0; q < 7; q++) ofs[q + 1] = ofs[q] + cnts[q];
@@ -266,15 +217,15 @@ static int validate(const m355_picture* pic, const m355_rb* const* rb_bin_in, bo
       size_t bad = hi;
       const char* m = nullptr;
       const size_t base = ofs[q];
-#define SWEEP(chk) for (size_t g = lo; g < hi; g++) if ((m = chk(g - base)) != nullptr) { bad = g; break; }
-      switch (q) {
-        case 0: SWEEP(chk_ctb) break;
-        case 1: SWEEP(chk_cu) break;
-        case 2: SWEEP(chk_tu) break;
-        case 3: SWEEP(chk_pb) break;
-        case 4: SWEEP(chk_wt) break;
-        case 5: SWEEP(chk_rb) break;
-        default: SWEEP(chk_ib) break;
+#define SWEEP(check, text) for (size_t g = lo; g < hi; g++) { const size_t i = g - base; if (auto r = (check)) { bad = g; m = (text); break; } }
+      switch (q) {                                           /* (a reason code becomes its message where a record fails) */
+        case 0: SWEEP(chk_ctb(i), r) break;
+        case 1: SWEEP(m355_check_cu(pic->cus[i], lim), m355_rc_text[r]) break;
+        case 2: SWEEP(m355_check_tu(pic->tus[i], lim), m355_rc_text[r]) break;
+        case 3: SWEEP(m355_check_pb(pic->pbs[i], lim), m355_rc_text[r]) break;
+        case 4: SWEEP(m355_check_wt(pic->wts[i], lim), m355_rc_text[r]) break;
+        case 5: SWEEP(chk_rb(i), m355_rc_text[r]) break;
+        default: SWEEP(m355_check_ib(pic->ibs[i], lim), m355_rc_text[r]) break;
       }
 #undef SWEEP
       if (bad < hi) { std::lock_guard<std::mutex> gd(mu); if (bad < first.load()) { first.store(bad); first_msg.store(m); } return; }
@@ -285,7 +236,6 @@ static int validate(const m355_picture* pic, const m355_rb* const* rb_bin_in, bo
     while (first.load() >= ofs[q + 1]) q++;
     return fail(M355_ERR_INVALID, "%s %zu: %s", names[q], first.load() - ofs[q], first_msg.load());
   }
-  (void)rc;
   *ctbW_out = ctbW; *ctbH_out = ctbH;
   return M355_OK;
 }
