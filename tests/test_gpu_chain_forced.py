@@ -132,10 +132,13 @@ elif what == "suites":
     cases += [("random %%d" %% s, random_case(s)) for s in range(50)]
     from test_gpu_depths import CHAIN_CASES           # 15 bits (front-part residuals, packed SAO) and 16 (neither; int32 deferred residuals)
     cases += [("depths %%d" %% i, c) for i, c in enumerate(CHAIN_CASES)]
+    from test_deblock_smooth import CHAIN_CASES as SMOOTH_CASES   # smoothed references: the luma deblocking filters at work (10 / 12 / 15 / 16 bits)
+    from deblock_content import make_smooth_case
+    cases += [("smooth %%d" %% i, c) for i, c in enumerate(SMOOTH_CASES)]
     n = 0
     for name, case in cases:
         try:
-            pic, refs = make_case(**case)
+            pic, refs = (make_smooth_case if name.startswith("smooth") else make_case)(**case)
         except RuntimeError:
             continue
         want = oracle_decode(Oracle(o), pic, refs)
