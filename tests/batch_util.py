@@ -11,11 +11,12 @@ def intra_pictures(n, **cfg):
     return [synth.picture(**dict(cfg, intra_pct=100, n_refs=0, seed=cfg["seed"] + 37 * k)) for k in range(n)]
 
 
-def check_batches(lib, o, cfg, depth, batches, sizes=None, stages=worklist.STAGE_ALL):
+def check_batches(lib, o, cfg, depth, batches, sizes=None, stages=worklist.STAGE_ALL, pics=None):
     """decode `batches` = lists of picture indices, one m355_decode_batch each and no wait in between (frames are recycled from
-    batch to batch: hazards across batches), then compare every picture's last decode"""
+    batch to batch: hazards across batches), then compare every picture's last decode.  pics: the caller's own intra pictures
+    (of one chroma format and one sample type, any depths) instead of intra_pictures(n, **cfg)"""
     n = 1 + max(max(b) for b in batches)
-    pics = intra_pictures(n, **cfg)
+    pics = intra_pictures(n, **cfg) if pics is None else pics
     if sizes:                                   # pictures of different sizes in one batch: ragged work lists
         for k, (w, h) in sizes.items():
             pics[k] = synth.picture(**dict(cfg, intra_pct=100, n_refs=0, seed=cfg["seed"] + 37 * k, width=w, height=h))
