@@ -88,7 +88,7 @@ namespace {
   X(m355_host_alloc) X(m355_host_free) X(m355_frame_hash) X(m355_arena_begin) X(m355_last_serial) X(m355_decode_status) \
   X(m355_frame_download_async) X(m355_frame_download_wait) X(m355_frame_export) X(m355_frame_export_order) \
   X(m355_group_create) X(m355_group_destroy) X(m355_group_decode) X(m355_picture_upload) X(m355_picture_replace) X(m355_shard_owner_of_tile) \
-  X(m355_picture_arena_begin) X(m355_frame_hash_async) X(m355_frame_hash_result)
+  X(m355_picture_arena_begin) X(m355_frame_hash_async) X(m355_frame_hash_result) X(m355_frame_measure_async) X(m355_frame_measure_result)
 
 struct Api {
   void* handle = nullptr;
@@ -1685,6 +1685,22 @@ LIBDE265_API const uint8_t* de265_get_image_plane(const struct de265_image* img,
   return m355ref_de265_get_image_plane(img, channel, stride);
 }
 
+/* the device frame behind an image the application holds (-1: the backend holds none of it) and the luma rectangle a call on it means: rect = {x0, y0, width,
+   height}, NULL: the image's conformance window.  With g->api_mu held, behind wait_submitted for the image. */
+static int frame_and_rect(Glue* g, const de265_image* img, const int rect[4], int out[4])
+{
+  const int slot = slot_of(g->dctx, img);
+  if (slot < 0 || g->frame_of_slot[slot] < 0 || g->dev_id[slot] != img->get_ID()) return -1;
+  if (rect) { for (int k = 0; k < 4; k++) out[k] = rect[k]; }
+  else {
+    const seq_parameter_set& sps = img->get_sps();               /* (window offsets count chroma samples: sps.cc, conformance_window_flag) */
+    out[0] = sps.SubWidthC * sps.conf_win_left_offset; out[1] = sps.SubHeightC * sps.conf_win_top_offset;
+    out[2] = sps.pic_width_in_luma_samples - sps.SubWidthC * (sps.conf_win_left_offset + sps.conf_win_right_offset);
+    out[3] = sps.pic_height_in_luma_samples - sps.SubHeightC * (sps.conf_win_top_offset + sps.conf_win_bottom_offset);
+  }
+  return g->frame_of_slot[slot];
+}
+
 /* The other way out of the decoder, for a consumer on the same GPU (not part of de265.h, which stays as it is): the picture's DEVICE frame
  * exported into device memory of the caller (m355_frame_export: layout / samples = M355_EXPORT_*; rect = {x0, y0, width, height} in luma
  * samples, NULL: the image's conformance window), and the consumer's stream ordered behind the export (m355_frame_export_order).  Nothing
@@ -1702,21 +1718,44 @@ LIBDE265_API int m355_glue_export_image(const struct de265_image* img, int layou
   if (!g || g->n_ranks > 1) return M355_ERR_INVALID;
   wait_submitted(g, img->get_ID());
   std::lock_guard<std::mutex> api_lock(g->api_mu);
-  const int slot = slot_of(g->dctx, img);
-  if (slot < 0 || g->frame_of_slot[slot] < 0 || g->dev_id[slot] != img->get_ID()) return M355_ERR_INVALID;
+  int r[4];
+  const int frame = frame_and_rect(g, img, rect, r);
+  if (frame < 0) return M355_ERR_INVALID;
   m355_export_desc d;
   memset(&d, 0, sizeof(d));
   d.layout = layout; d.samples = samples;
-  if (rect) { d.x0 = rect[0]; d.y0 = rect[1]; d.width = rect[2]; d.height = rect[3]; }
-  else {
-    const seq_parameter_set& sps = img->get_sps();               /* (window offsets count chroma samples: sps.cc, conformance_window_flag) */
-    d.x0 = sps.SubWidthC * sps.conf_win_left_offset; d.y0 = sps.SubHeightC * sps.conf_win_top_offset;
-    d.width = sps.pic_width_in_luma_samples - sps.SubWidthC * (sps.conf_win_left_offset + sps.conf_win_right_offset);
-    d.height = sps.pic_height_in_luma_samples - sps.SubHeightC * (sps.conf_win_top_offset + sps.conf_win_bottom_offset);
-  }
+  d.x0 = r[0]; d.y0 = r[1]; d.width = r[2]; d.height = r[3];
   for (int c = 0; c < 3; c++) { d.dst[c] = dst[c]; d.pitch[c] = pitch[c]; }
-  int rc = A->m355_frame_export(g->mctx, g->frame_of_slot[slot], &d);
-  if (rc == M355_OK) rc = A->m355_frame_export_order(g->mctx, g->frame_of_slot[slot], consumer_stream);
+  int rc = A->m355_frame_export(g->mctx, frame, &d);
+  if (rc == M355_OK) rc = A->m355_frame_export_order(g->mctx, frame, consumer_stream);
+  if (rc != M355_OK) g->error = A->m355_last_error();
+  return rc;
+}
+/* The picture COMPARED with another one on the device — what dec265 -m YUV does with MSE() of quality.cc on downloaded planes (dec265.cc:388-419); this call is
+ * what a -m implementation on this backend calls.  ref / pitch: the reference picture's planes for the rectangle (rect = {x0, y0, width, height} in luma
+ * samples, NULL: the image's conformance window) in device or m355_host_alloc memory, element type of the image's planes (m355_measure_desc).  Preconditions
+ * of m355_glue_export_image.  The request is enqueued behind the picture's decode and collected with block = 1: the call waits for THIS request only — not for the
+ * pictures in flight on the other lanes —, and nothing is downloaded.  -> M355_OK with *out filled, or an M355_ERR_* code. */
+LIBDE265_API int m355_glue_measure_image(const struct de265_image* img, const int rect[4], const void* const ref[3], const int64_t pitch[3], m355_measure* out)
+{
+  Api* A = api();
+  if (!A) return M355_ERR_NO_DEVICE;
+  if (!img || !img->decctx || !ref || !pitch || !out) return M355_ERR_INVALID;
+  Glue* g = glue_of(img->decctx);
+  if (!g || g->n_ranks > 1) return M355_ERR_INVALID;
+  wait_submitted(g, img->get_ID());
+  std::lock_guard<std::mutex> api_lock(g->api_mu);
+  int r[4];
+  const int frame = frame_and_rect(g, img, rect, r);
+  if (frame < 0) return M355_ERR_INVALID;
+  m355_measure_desc d;
+  memset(&d, 0, sizeof(d));
+  d.ref_frame = -1;
+  d.x0 = r[0]; d.y0 = r[1]; d.width = r[2]; d.height = r[3];
+  for (int c = 0; c < 3; c++) { d.ref[c] = ref[c]; d.pitch[c] = pitch[c]; }
+  unsigned long long ticket = 0;
+  int rc = A->m355_frame_measure_async(g->mctx, frame, &d, &ticket);
+  if (rc == M355_OK) rc = A->m355_frame_measure_result(g->mctx, ticket, 1, out);
   if (rc != M355_OK) g->error = A->m355_last_error();
   return rc;
 }

@@ -509,6 +509,48 @@ M355_API int m355_frame_hash(m355_ctx* ctx, int frame, int hash_type, m355_pictu
 M355_API int m355_frame_hash_async(m355_ctx* ctx, int frame, int hash_type, unsigned long long* ticket);
 M355_API int m355_frame_hash_result(m355_ctx* ctx, unsigned long long ticket, int block, m355_picture_hash* out);
 
+/* A frame COMPARED with another picture where both lie — what libde265/quality.cc (SSD, SAD, MSE) computes on host planes and `dec265 -m`
+ * prints per picture, without either side crossing PCIe — as a request queued behind the frame's decode, under the contract of
+ * m355_frame_hash_async.  The other picture is a frame of the same context (ref_frame >= 0) or planes in memory of the caller (ref_frame == -1).
+ * Per plane of the rectangle, with a = the frame's element values as stored, b = the reference's, d = a - b:
+ *   row_ssd[y] = sum_x d^2    ssd = sum_y row_ssd[y]    sad = sum |d|    n_diff = #{d != 0}    max_abs = max |d|
+ *   first_x, first_y = the first sample with d != 0 in raster order, in PLANE COORDINATES OF THE FRAME (-1, -1: none)
+ *   mse = MSE() of quality.cc:71-95 — from 0.0, plus (double)row_ssd[y] / width for each row in row order, then divided by height, in IEEE
+ *         double (the host does this sum at collection, from per-row sums the kernel left in pinned memory).
+ * All but mse are exact integers; PSNR stays with the caller (the peak value is the caller's: the reference's PSNR() hard-codes 255).
+ * Planes a monochrome frame does not have read 0 / -1 / 0.0.  ref_frame == frame is legal (all zero).
+ * The request is a READER of the frame, and of ref_frame when given: queued on the stream of the frame's last writer, ordered behind
+ * ref_frame's last writer the way a decode waits for the writers of its reference frames, and a later decode into either frame waits for it
+ * in front of its first write; the host waits for nothing at enqueue.  ref[] memory must be complete when the call is made: ordering
+ * against a producer's stream is not provided.  *ticket counts 1, 2, ... per context (a count of its own, not the hash requests'); at most
+ * M355_MEASURE_REQUESTS requests may be outstanding: one more returns M355_ERR_BUSY and enqueues nothing.
+ * M355_ERR_INVALID, nothing enqueued: bad handles, null descriptor or ticket; a rectangle that leaves the frame or is not aligned to the
+ * chroma grid (the rules of m355_export_desc); a ref_frame whose chroma format, bit depths or element size differ or which does not contain
+ * the rectangle; a null ref[p] for a plane that exists, a pitch below the row's bytes, a pointer or pitch that is no multiple of the element
+ * size; a tile-sharded context.
+ * m355_frame_measure_result collects a request and frees its slot: block = 0 -> M355_ERR_BUSY while it runs (the request stays), block = 1 ->
+ * the host waits for THAT request only.  M355_ERR_INVALID: an unknown or collected ticket; or — the request is collected all the same — a
+ * request queued behind a decode whose lists were rejected, for either frame: it has read nothing.  (The gate is the lane's: a request whose
+ * ref_frame was written on another lane sees that decode's verdict as long as no LATER decode of that lane has been rejected meanwhile:
+ * then it returns M355_OK with values of the frame's older content — DESIGN.md section 3 states this limit of the per-lane gate.)
+ * m355_wait completes every request and collects none; a frame may be destroyed with requests pending. */
+#define M355_MEASURE_REQUESTS 16
+typedef struct m355_measure_desc {
+  int32_t     ref_frame;              /* >= 0: compare with this frame of the same context; -1: with ref[] below */
+  int32_t     x0, y0, width, height;  /* luma rectangle, rules of m355_export_desc (width == 0: whole frame; chroma-grid aligned) */
+  const void* ref[3];                 /* ref_frame == -1: the RECTANGLE's planes, planar, element type of the frame's plane
+                                         (u8, or u16 LSB-aligned), device memory or m355_host_alloc memory */
+  int64_t     pitch[3];               /* BYTES per row of ref[]; >= the row's bytes; pointer and pitch multiples of the element size */
+} m355_measure_desc;
+typedef struct m355_measure {
+  uint64_t ssd[3], sad[3], n_diff[3];
+  uint32_t max_abs[3];
+  int32_t  first_x[3], first_y[3];    /* plane coordinates IN THE FRAME of the first differing sample in raster order; -1, -1: none */
+  double   mse[3];
+} m355_measure;
+M355_API int m355_frame_measure_async(m355_ctx* ctx, int frame, const m355_measure_desc* desc, unsigned long long* ticket);
+M355_API int m355_frame_measure_result(m355_ctx* ctx, unsigned long long ticket, int block, m355_measure* out);
+
 /* Replaces (deferred): decode_TU (slice.cc:3460), decode_prediction_unit (motion.cc:2190) and
  * run_postprocessing_filters_sequential/_parallel (decctx.cc:1783/1811) for one picture. Asynchronous:
  * returns after the work is enqueued on the context's stream. */

@@ -49,6 +49,18 @@ class ExportDesc(ctypes.Structure):
                 ("dst", ctypes.c_void_p * 3), ("pitch", ctypes.c_int64 * 3)]
 
 
+class MeasureDesc(ctypes.Structure):
+    """m355_measure_desc (include/de265_mi355x.h)"""
+    _fields_ = [("ref_frame", ctypes.c_int32), ("x0", ctypes.c_int32), ("y0", ctypes.c_int32), ("width", ctypes.c_int32), ("height", ctypes.c_int32),
+                ("ref", ctypes.c_void_p * 3), ("pitch", ctypes.c_int64 * 3)]
+
+
+class Measure(ctypes.Structure):
+    """m355_measure (include/de265_mi355x.h)"""
+    _fields_ = [("ssd", ctypes.c_uint64 * 3), ("sad", ctypes.c_uint64 * 3), ("n_diff", ctypes.c_uint64 * 3), ("max_abs", ctypes.c_uint32 * 3),
+                ("first_x", ctypes.c_int32 * 3), ("first_y", ctypes.c_int32 * 3), ("mse", ctypes.c_double * 3)]
+
+
 class ArenaCaps(ctypes.Structure):
     """m355_arena_caps (include/de265_mi355x.h)"""
     _fields_ = [(n, ctypes.c_int32) for n in ("n_slices", "n_ctbs", "n_cus", "n_tus", "n_pbs", "n_wts", "n_ibs")] + \
@@ -104,6 +116,9 @@ class Library:
         if hasattr(L, "m355_frame_hash_async"):         # (absent from older builds loaded through M355_LIB for an A/B)
             L.m355_frame_hash_async.argtypes = [vp, i, i, ctypes.POINTER(ctypes.c_ulonglong)]
             L.m355_frame_hash_result.argtypes = [vp, ctypes.c_ulonglong, i, vp]
+        if hasattr(L, "m355_frame_measure_async"):      # (absent from older builds loaded through M355_LIB for an A/B)
+            L.m355_frame_measure_async.argtypes = [vp, i, ctypes.POINTER(MeasureDesc), ctypes.POINTER(ctypes.c_ulonglong)]
+            L.m355_frame_measure_result.argtypes = [vp, ctypes.c_ulonglong, i, ctypes.POINTER(Measure)]
         L.m355_submit_picture.argtypes = [vp, vp]
         L.m355_wait.argtypes = [vp]
         L.m355_last_serial.argtypes = [vp]
@@ -179,6 +194,7 @@ class Context:
         self.h = h
         self._geom = {}
         self._hash_reqs = {}            # ticket -> (hash type, planes) of the requests not collected yet
+        self._measure_reqs = {}         # ticket -> (planes, reference buffers to free, host?) of the comparison requests not collected yet
 
     def close(self):
         if self.h:
@@ -412,6 +428,78 @@ class Context:
         if hash_type == HASH_MD5:
             return [bytes(out.md5[c]) for c in range(n)]
         return [int((out.crc if hash_type == HASH_CRC else out.checksum)[c]) for c in range(n)]
+
+    # ---- comparison with another picture on the device (m355_frame_measure_async) ----
+    def measure_reference(self, planes, host=False, pad=None):
+        """the reference planes of a comparison (numpy arrays of the frame's element type, the RECTANGLE's planes) copied into device memory
+        (m355_device_*; host=True: pinned host memory) at a pitch `pad` bytes above the row (default 6 for u8, 10 for u16: every row of the
+        reference starts at another alignment than the frame's).  m355_device_write waits for the context's work, so a caller that must not wait
+        between two enqueues prepares the reference beforehand -> token for frame_measure_async(ref_planes=...), which owns it from then on"""
+        bufs, pitches = [], []
+        try:
+            for a in planes:
+                a = np.ascontiguousarray(a)
+                pitch = a.shape[1] * a.itemsize + ((6 if a.itemsize == 1 else 10) if pad is None else pad)
+                raw = np.full((a.shape[0], pitch), DEVICE_FILL, np.uint8)
+                raw[:, :a.shape[1] * a.itemsize] = a.view(np.uint8).reshape(a.shape[0], -1)
+                if host:
+                    p = self.L.lib.m355_host_alloc(raw.size)
+                    if not p:
+                        raise M355Error(4, self.L.error())
+                    bufs.append(p)
+                    ctypes.memmove(p, raw.ctypes.data, raw.size)
+                else:
+                    p = self.device_alloc(raw.size, fill=None)
+                    bufs.append(p)
+                    self.L.check(self.L.lib.m355_device_write(self.h, p, raw.ctypes.data, raw.size))
+                pitches.append(pitch)
+        except Exception:
+            self._measure_free(bufs, host)
+            raise
+        return ("measure_reference", bufs, pitches, host)
+
+    def frame_measure_async(self, f, ref_frame=None, ref_planes=None, rect=None, host=False, pad=None):
+        """enqueue the comparison of frame f (rect = (x0, y0, width, height) in luma samples, None: the whole frame) with frame `ref_frame`, or
+        with `ref_planes`: a token of measure_reference, or numpy planes, which go through measure_reference(host, pad) first.  Nothing is
+        waited for behind the enqueue -> ticket for frame_measure_result, which frees the reference's buffers"""
+        desc = MeasureDesc(ref_frame=-1 if ref_frame is None else ref_frame)
+        if rect is not None:
+            desc.x0, desc.y0, desc.width, desc.height = rect
+        if ref_planes is not None and not (isinstance(ref_planes, tuple) and ref_planes[:1] == ("measure_reference",)):
+            ref_planes = self.measure_reference(ref_planes, host, pad)
+        _, bufs, pitches, host = ref_planes or (None, [], [], False)
+        for k, (p, pitch) in enumerate(zip(bufs, pitches)):
+            desc.ref[k] = p; desc.pitch[k] = pitch
+        t = ctypes.c_ulonglong(0)
+        rc = self.L.lib.m355_frame_measure_async(self.h, f, ctypes.byref(desc), ctypes.byref(t))
+        if rc:
+            text = self.L.error()
+            self._measure_free(bufs, host)
+            raise M355Error(rc, text)
+        self._measure_reqs[t.value] = (3 if self._geom[f][2] else 1, bufs, host)
+        return int(t.value)
+
+    def _measure_free(self, bufs, host):
+        for p in bufs:
+            self.L.lib.m355_host_free(p) if host else self.device_free(p)
+
+    def frame_measure_result(self, ticket, block=True):
+        """collect a request (m355_frame_measure_result) -> one dict per plane of the frame: ssd, sad, n_diff, max_abs, first (x, y) or None, mse;
+        None while it has not finished (block=False); raises M355Error for an unknown / collected ticket and behind a rejected decode"""
+        out = Measure()
+        rc = self.L.lib.m355_frame_measure_result(self.h, ticket, 1 if block else 0, ctypes.byref(out))
+        if rc == 6 and not block:                               # M355_ERR_BUSY
+            return None
+        if rc:
+            text = self.L.error()
+            if rc == 3:                                         # M355_ERR_INVALID: collected without a value (behind a rejected decode), or no such request
+                self._measure_free(*self._measure_reqs.pop(ticket, (3, [], False))[1:])
+            # (any other failure — the wait itself failed — may leave the request outstanding and reading the reference's buffers: they stay)
+            raise M355Error(rc, text)
+        n, bufs, host = self._measure_reqs.pop(ticket)
+        self._measure_free(bufs, host)                          # (collected: nothing reads the buffers any more)
+        return [dict(ssd=int(out.ssd[c]), sad=int(out.sad[c]), n_diff=int(out.n_diff[c]), max_abs=int(out.max_abs[c]),
+                     first=None if out.first_x[c] < 0 else (int(out.first_x[c]), int(out.first_y[c])), mse=float(out.mse[c])) for c in range(n)]
 
     # ---- pictures ----
     def submit(self, pic):

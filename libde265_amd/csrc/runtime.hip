@@ -227,6 +227,27 @@ static void hash_requests_destroy(m355_ctx* c)
   c->hash_rec = c->hash_res = nullptr;
 }
 
+/* the slots of m355_frame_measure_async: the same two kinds of record, 64-bit words */
+static int measure_requests_create(m355_ctx* c)
+{
+  hipStream_t st = c->lanes[0].stream;
+  HIPCHK(hipMalloc(&c->meas_rec, M355_MEASURE_REQUESTS * MEAS_REC_WORDS * sizeof(unsigned long long)));
+  HIPCHK(hipMemsetAsync(c->meas_rec, 0, M355_MEASURE_REQUESTS * MEAS_REC_WORDS * sizeof(unsigned long long), st));
+  HIPCHK(hipStreamSynchronize(st));
+  HIPCHK(hipHostMalloc(&c->meas_res, M355_MEASURE_REQUESTS * MEAS_RES_WORDS * sizeof(unsigned long long), hipHostMallocDefault));
+  memset(c->meas_res, 0, M355_MEASURE_REQUESTS * MEAS_RES_WORDS * sizeof(unsigned long long));
+  return M355_OK;
+}
+static void measure_requests_destroy(m355_ctx* c)
+{
+  for (auto& s : c->meas_slot) { if (s.rows) hipHostFree(s.rows); s = m355_ctx::MeasSlot(); }
+  for (auto& b : c->meas_pool) hipHostFree(b.first);
+  c->meas_pool.clear();
+  if (c->meas_rec) hipFree(c->meas_rec);
+  if (c->meas_res) hipHostFree(c->meas_res);
+  c->meas_rec = c->meas_res = nullptr;
+}
+
 int m355_create(int device, m355_ctx** out)
 {
   *out = nullptr;
@@ -238,7 +259,8 @@ int m355_create(int device, m355_ctx** out)
   c->device = device;
   int rc = lane_create(c, c->lanes[0], 0);
   if (rc == M355_OK) rc = hash_requests_create(c);
-  if (rc) { hash_requests_destroy(c); lane_destroy(c->lanes[0]); delete c; return rc; }
+  if (rc == M355_OK) rc = measure_requests_create(c);
+  if (rc) { measure_requests_destroy(c); hash_requests_destroy(c); lane_destroy(c->lanes[0]); delete c; return rc; }
   *out = c;
   return M355_OK;
 }
@@ -278,6 +300,7 @@ void m355_destroy(m355_ctx* c)
   for (hipEvent_t e : c->evs) hipEventDestroy(e);
   if (c->hash_acc) hipFree(c->hash_acc);
   hash_requests_destroy(c);
+  measure_requests_destroy(c);
   for (auto& e : c->inter_tabs) hipFree(e.second);
   for (auto& b : c->batch) { if (b.host) hipHostFree(b.host); if (b.dev) hipFree(b.dev); if (b.ev) hipEventDestroy(b.ev); }
   for (hipEvent_t e : c->batch_ev_pre) if (e) hipEventDestroy(e);
@@ -791,6 +814,177 @@ int m355_frame_hash_result(m355_ctx* c, unsigned long long ticket, int block, m3
       else out->checksum[cc] = res[cc];
     }
   hash_slot_free(c, *s);
+  return M355_OK;
+}
+
+/* ---- comparison requests (m355_frame_measure_async / m355_frame_measure_result): the hash requests' machinery with another kernel (k_measure.hip),
+   a second frame to read, and a pinned row array per request ---- */
+
+static m355_ctx::MeasSlot* meas_slot_of(m355_ctx* c, unsigned long long ticket)
+{
+  if (ticket) for (auto& s : c->meas_slot) if (s.ticket == ticket) return &s;
+  return nullptr;
+}
+/* a request's pinned row array (one 64-bit sum per row of every plane: 69 KB for an 8K 4:2:0 frame): the smallest idle one that fits, else a new one.  Nothing
+   is freed here: hipHostFree may wait for the device, and the enqueue waits for nothing (hash_planes_take) — arrays smaller than the largest one made go when a
+   request is collected, meas_slot_free */
+static int meas_rows_take(m355_ctx* c, m355_ctx::MeasSlot& s, size_t entries)
+{
+  int best = -1;
+  for (int k = 0; k < (int)c->meas_pool.size(); k++)
+    if (c->meas_pool[k].second >= entries && (best < 0 || c->meas_pool[k].second < c->meas_pool[best].second)) best = k;
+  if (best < 0) {
+    void* p = nullptr;
+    const size_t want = (entries + 8191) & ~(size_t)8191;
+    if (hipHostMalloc(&p, want * sizeof(unsigned long long), hipHostMallocDefault) != hipSuccess) return fail(M355_ERR_NOMEM, "pinned row array of %zu entries for a comparison request", want);
+    s.rows = (unsigned long long*)p; s.rows_cap = want;
+    return M355_OK;
+  }
+  s.rows = c->meas_pool[best].first; s.rows_cap = c->meas_pool[best].second;
+  c->meas_pool.erase(c->meas_pool.begin() + best);
+  return M355_OK;
+}
+static void meas_slot_free(m355_ctx* c, m355_ctx::MeasSlot& s)
+{
+  if (s.rows) {
+    /* the arrays grow to the tallest frame seen; smaller ones of earlier, shorter frames go here, where the caller has just waited for its request anyway
+       (hash_slot_free): first the pool's, then this one if a larger one exists */
+    size_t largest = s.rows_cap;
+    for (const auto& x : c->meas_slot) largest = std::max(largest, x.rows_cap);
+    for (const auto& b : c->meas_pool) largest = std::max(largest, b.second);
+    for (size_t k = c->meas_pool.size(); k-- > 0;) if (c->meas_pool[k].second < largest) { hipHostFree(c->meas_pool[k].first); c->meas_pool.erase(c->meas_pool.begin() + k); }
+    if (s.rows_cap < largest) hipHostFree(s.rows);
+    else c->meas_pool.push_back(std::make_pair(s.rows, s.rows_cap));
+  }
+  s.rows = nullptr; s.rows_cap = 0;
+  /* collected behind its mark: the next decode into either frame has nothing to wait for, if the frame's mark is still this request's (hash_slot_free) */
+  for (int k = 0; k < 2; k++) {
+    Frame* f = get_frame(c, s.frame[k]);
+    if (f && s.mark.ticket && f->reader[RD_MEASURE].ticket == s.mark.ticket) f->reader[RD_MEASURE] = EvRef();
+    s.frame[k] = -1;
+  }
+  s.mark = EvRef();
+  s.ticket = 0;
+}
+
+/* Enqueue only: the host waits for nothing here.  A READER of the frame (reader_begin) and of the reference frame: the kernel runs on the stream of the frame's
+   last writer, which first continues behind the reference frame's last writer (as a decode waits for the writers of its reference frames) and behind that frame's
+   earlier comparison mark; ONE mark behind the launch is kept by both frames and by the slot. */
+int m355_frame_measure_async(m355_ctx* c, int h, const m355_measure_desc* e, unsigned long long* ticket)
+{
+  Frame* f = c ? get_frame(c, h) : nullptr;
+  if (!f || !e || !ticket) return fail(M355_ERR_INVALID, "m355_frame_measure_async: bad frame handle %d / null descriptor / null ticket", h);
+  if (c->shard_n > 0) return fail(M355_ERR_INVALID, "m355_frame_measure_async: not on a tile-sharded context (its frames are complete only behind the gather)");
+  const int sw = (f->cf == 1 || f->cf == 2) ? 2 : 1, sh = f->cf == 1 ? 2 : 1;
+  int x0 = 0, y0 = 0, w = f->w, hgt = f->h;
+  if (e->width != 0) {
+    x0 = e->x0; y0 = e->y0; w = e->width; hgt = e->height;
+    if (x0 < 0 || y0 < 0 || w <= 0 || hgt <= 0 || x0 > f->w - w || y0 > f->h - hgt) return fail(M355_ERR_INVALID, "m355_frame_measure_async: rectangle %d,%d %dx%d leaves the %dx%d frame", x0, y0, w, hgt, f->w, f->h);
+    if (f->cf && ((x0 | w) % sw || (y0 | hgt) % sh)) return fail(M355_ERR_INVALID, "m355_frame_measure_async: rectangle %d,%d %dx%d is not aligned to the chroma grid (%dx%d luma samples)", x0, y0, w, hgt, sw, sh);
+  }
+  Frame* r = nullptr;
+  if (e->ref_frame != -1) {
+    r = get_frame(c, e->ref_frame);
+    if (!r) return fail(M355_ERR_INVALID, "m355_frame_measure_async: bad reference frame handle %d", e->ref_frame);
+    if (r->cf != f->cf || r->bdl != f->bdl || r->bdc != f->bdc || r->bpp[0] != f->bpp[0]) return fail(M355_ERR_INVALID, "m355_frame_measure_async: the reference frame's chroma format / bit depths differ from the frame's");
+    if (x0 > r->w - w || y0 > r->h - hgt) return fail(M355_ERR_INVALID, "m355_frame_measure_async: the %dx%d reference frame does not contain the rectangle %d,%d %dx%d", r->w, r->h, x0, y0, w, hgt);
+  }
+  const int np = f->cf == 0 ? 1 : 3;
+  MeasArgs a = {};
+  int rows = 0, nw = 0;
+  for (int p = 0; p < np; p++) rows += p ? hgt / sh : hgt;
+  a.rows_per_wave = std::max(1, rows / 4096);                                   /* (hash_args_fill: enough waves to fill 1024 SIMDs a few times over) */
+  m355_ctx::MeasSlot geom;
+  for (int p = 0, row0 = 0; p < 3; p++) {
+    a.first[p] = nw;
+    if (p >= np) continue;
+    const int sb = f->bpp[p];
+    const int pw = p ? w / sw : w, ph = p ? hgt / sh : hgt, px = p ? x0 / sw : x0, py = p ? y0 / sh : y0;
+    MeasPlane& m = a.pl[p];
+    m.pitch_a = (long long)f->stride[p] * sb;
+    m.a = (const uint8_t*)f->plane[p] + (size_t)py * m.pitch_a + (size_t)px * sb;
+    if (r) {
+      m.pitch_b = (long long)r->stride[p] * sb;
+      m.b = (const uint8_t*)r->plane[p] + (size_t)py * m.pitch_b + (size_t)px * sb;
+    } else {
+      if (!e->ref[p]) return fail(M355_ERR_INVALID, "m355_frame_measure_async: no reference for plane %d", p);
+      if (e->pitch[p] < (int64_t)pw * sb) return fail(M355_ERR_INVALID, "m355_frame_measure_async: pitch %lld of plane %d is below its row of %lld bytes", (long long)e->pitch[p], p, (long long)pw * sb);
+      if (((uintptr_t)e->ref[p] | (uintptr_t)e->pitch[p]) & (uintptr_t)(sb - 1)) return fail(M355_ERR_INVALID, "m355_frame_measure_async: pointer / pitch of plane %d is no multiple of the %d-byte element", p, sb);
+      m.pitch_b = e->pitch[p];
+      m.b = (const uint8_t*)e->ref[p];
+    }
+    m.row_bytes = pw * sb; m.h = ph; m.px = px; m.py = py; m.row0 = row0;
+    geom.pw[p] = pw; geom.ph[p] = ph; geom.row0[p] = row0;
+    row0 += ph;
+    nw += (ph + a.rows_per_wave - 1) / a.rows_per_wave;
+  }
+  a.first[3] = nw;
+  m355_ctx::MeasSlot* s = nullptr;
+  for (auto& x : c->meas_slot) if (!x.ticket) { s = &x; break; }
+  if (!s) return fail(M355_ERR_BUSY, "m355_frame_measure_async: %d requests outstanding (collect one: m355_frame_measure_result)", M355_MEASURE_REQUESTS);
+  const int slot = (int)(s - c->meas_slot);
+  hipSetDevice(c->device);
+  int rc = meas_rows_take(c, *s, (size_t)rows);
+  if (rc) return rc;
+  s->np = np;
+  for (int p = 0; p < 3; p++) { s->pw[p] = geom.pw[p]; s->ph[p] = geom.ph[p]; s->row0[p] = geom.row0[p]; }
+  MeasReq q = {};
+  q.rec = c->meas_rec + slot * MEAS_REC_WORDS;
+  q.res = c->meas_res + slot * MEAS_RES_WORDS;
+  q.rows = s->rows;
+  q.seq = (uint32_t)(c->meas_ticket + 1);
+  q.res[15] = MEAS_RES_NONE;                                                    /* (the slot is idle: nothing in flight writes its record) */
+  const hipStream_t cs = reader_begin(c, f, RD_MEASURE, &q.timeout[0], &q.epoch[0]);
+  q.timeout[1] = q.timeout[0]; q.epoch[1] = q.epoch[0];
+  if (r && r != f) {
+    ev_wait(c, cs, r->wr);                                                      /* the reference frame's last writer (nothing to enqueue when that ran on `cs`) */
+    ev_wait(c, cs, r->reader[RD_MEASURE]);                                      /* ... and its earlier comparison on another stream: the one mark kept stands for both */
+    if (r->wr_stream && r->wr_gate) { q.timeout[1] = r->wr_gate; q.epoch[1] = r->wr_epoch; }
+  }
+  m355_launch_measure(a, q, f->bpp[0], cs);
+  if (hipGetLastError() != hipSuccess || reader_end(c, f, RD_MEASURE, cs) != M355_OK) { meas_slot_free(c, *s); return fail(M355_ERR_HIP, "m355_frame_measure_async: launch failed"); }
+  s->mark = f->reader[RD_MEASURE]; s->frame[0] = h; s->frame[1] = -1;
+  if (r && r != f) { r->reader[RD_MEASURE] = s->mark; s->frame[1] = e->ref_frame; }
+  s->ticket = ++c->meas_ticket;
+  *ticket = s->ticket;
+  return M355_OK;
+}
+
+int m355_frame_measure_result(m355_ctx* c, unsigned long long ticket, int block, m355_measure* out)
+{
+  m355_ctx::MeasSlot* s = c ? meas_slot_of(c, ticket) : nullptr;
+  if (!s) return fail(M355_ERR_INVALID, "m355_frame_measure_result: ticket %llu is unknown or was collected", ticket);
+  if (!out) return fail(M355_ERR_INVALID, "m355_frame_measure_result: null result");
+  hipSetDevice(c->device);
+  if (block) HIPCHK(ev_sync(c, s->mark));                                       /* this request's mark only */
+  else {
+    const hipError_t e = ev_query(c, s->mark);
+    if (e == hipErrorNotReady) return M355_ERR_BUSY;
+    if (e != hipSuccess) return fail(M355_ERR_HIP, "hipEventQuery failed: %s", hipGetErrorString(e));
+  }
+  const unsigned long long* res = c->meas_res + (s - c->meas_slot) * MEAS_RES_WORDS;
+  const unsigned long long state = res[15], seq = res[16];
+  if (state == MEAS_RES_GATED && seq == (uint32_t)ticket) {
+    meas_slot_free(c, *s);
+    return fail(M355_ERR_INVALID, "comparison request %llu was queued behind a decode whose lists were rejected: no value", ticket);
+  }
+  if (state != MEAS_RES_VALID || seq != (uint32_t)ticket) {
+    meas_slot_free(c, *s);
+    return fail(M355_ERR_HIP, "comparison request %llu finished without a result (state %llu, sequence %llu)", ticket, state, seq);
+  }
+  memset(out, 0, sizeof(*out));
+  for (int p = 0; p < 3; p++) {
+    out->first_x[p] = out->first_y[p] = -1;
+    if (p >= s->np) continue;
+    const unsigned long long* v = res + p * MEAS_PER_PLANE;
+    out->ssd[p] = v[MEAS_SSD]; out->sad[p] = v[MEAS_SAD]; out->n_diff[p] = v[MEAS_NDIFF]; out->max_abs[p] = (uint32_t)v[MEAS_MAX];
+    if (v[MEAS_FIRST]) { const unsigned long long pos = ~v[MEAS_FIRST]; out->first_x[p] = (int32_t)(pos & 0xFFFFFFFFu); out->first_y[p] = (int32_t)(pos >> 32); }
+    /* MSE() of quality.cc:71-95, in its order of operations */
+    double sum = 0.0;
+    for (int y = 0; y < s->ph[p]; y++) sum += ((double)s->rows[s->row0[p] + y]) / s->pw[p];
+    out->mse[p] = sum / s->ph[p];
+  }
+  meas_slot_free(c, *s);
   return M355_OK;
 }
 

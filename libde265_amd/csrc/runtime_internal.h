@@ -29,6 +29,7 @@
 #include <pthread.h>
 #include "k_common.h"
 #include "k_hash.h"
+#include "k_measure.h"
 
 
 extern thread_local std::string g_err;
@@ -74,7 +75,7 @@ constexpr int intra_class_first_lane = 3;
 struct EvRef { unsigned long long ticket = 0; hipStream_t stream = nullptr; };
 #define M355_EV_RING 256
 
-enum ReaderKind { RD_DOWNLOAD, RD_EXPORT, RD_HASH, RD_KINDS };
+enum ReaderKind { RD_DOWNLOAD, RD_EXPORT, RD_HASH, RD_MEASURE, RD_KINDS };
 struct Frame {
   bool used = false;
   int w = 0, h = 0, cf = 0, bdl = 0, bdc = 0;
@@ -87,10 +88,10 @@ struct Frame {
      rejected does nothing, like that decode's own kernels (M355_GATE) */
   const uint32_t* wr_gate = nullptr; uint32_t wr_epoch = 0;
   /* READERS queued behind the decode that wrote the frame — a download (m355_frame_download_async), an export (m355_frame_export), a hash request
-     (m355_frame_hash_async): per kind the mark behind the LAST one.  reader_begin picks the stream (the writer's, so stream order stands for the wait for the
+     (m355_frame_hash_async), a comparison (m355_frame_measure_async, which reads two frames and marks both): per kind the mark behind the LAST one.  reader_begin picks the stream (the writer's, so stream order stands for the wait for the
      picture) and lets it continue behind the kind's earlier mark, so that the one mark kept stands for both; reader_end marks; the next decode into the frame
      waits for every kind in front of its first write (readers_wait, from dst_hazards).  The kinds are separate because the HOST waits per kind
-     (m355_frame_download_wait, m355_frame_export_wait, m355_frame_hash_result), and a finished wait clears its mark: readers of different kinds need no order. */
+     (m355_frame_download_wait, m355_frame_export_wait, m355_frame_hash_result, m355_frame_measure_result), and a finished wait clears its mark: readers of different kinds need no order. */
   EvRef reader[RD_KINDS];
 };
 
@@ -251,6 +252,19 @@ struct m355_ctx {
   unsigned long long hash_ticket = 0;
   uint32_t *hash_rec = nullptr, *hash_res = nullptr;    /* HASH_REC_WORDS (device) / HASH_RES_WORDS (pinned) per slot */
   std::vector<std::pair<uint8_t*, size_t>> hash_pool;   /* idle pinned plane buffers of MD5 requests: they grow to the largest frame seen */
+  /* m355_frame_measure_async: M355_MEASURE_REQUESTS slots like the hash slots — a device record the kernel leaves zero, a pinned result record — and a
+     pinned row array (the rows' sums of squared differences, which the host adds in row order at collection) taken from meas_pool, sized at the request.
+     frame[1] / the second mark's frame: the reference frame of a frame-against-frame request, -1 otherwise. */
+  struct MeasSlot {
+    unsigned long long ticket = 0;
+    int np = 0, pw[3] = {0, 0, 0}, ph[3] = {0, 0, 0}, row0[3] = {0, 0, 0};
+    EvRef mark; int frame[2] = {-1, -1};
+    unsigned long long* rows = nullptr; size_t rows_cap = 0;
+  };
+  MeasSlot meas_slot[M355_MEASURE_REQUESTS];
+  unsigned long long meas_ticket = 0;
+  unsigned long long *meas_rec = nullptr, *meas_res = nullptr;   /* MEAS_REC_WORDS (device) / MEAS_RES_WORDS (pinned) per slot */
+  std::vector<std::pair<unsigned long long*, size_t>> meas_pool; /* idle pinned row arrays (entries) */
   /* pinned staging buffer of the blocking frame transfers (m355_frame_upload / _download / _fill, MD5 of m355_frame_hash): the copy itself is queued on the
      stream that last wrote the frame, between pinned memory and the frame (frame_stage_* in runtime.hip) */
   void* stage = nullptr; size_t stage_bytes = 0;
