@@ -86,7 +86,7 @@ namespace {
   X(m355_last_error) X(m355_device_count) X(m355_create) X(m355_destroy) X(m355_frame_create) X(m355_frame_destroy) \
   X(m355_frame_upload) X(m355_frame_download) X(m355_submit_picture) X(m355_wait) X(m355_set_pipeline_depth) \
   X(m355_host_alloc) X(m355_host_free) X(m355_frame_hash) X(m355_arena_begin) X(m355_last_serial) X(m355_decode_status) \
-  X(m355_frame_download_async) X(m355_frame_download_wait) X(m355_frame_export) X(m355_frame_export_order) \
+  X(m355_frame_download_async) X(m355_frame_download_wait) X(m355_frame_export) X(m355_frame_export_scaled) X(m355_frame_export_order) \
   X(m355_group_create) X(m355_group_destroy) X(m355_group_decode) X(m355_picture_upload) X(m355_picture_replace) X(m355_shard_owner_of_tile) \
   X(m355_picture_arena_begin) X(m355_frame_hash_async) X(m355_frame_hash_result) X(m355_frame_measure_async) X(m355_frame_measure_result)
 
@@ -1708,8 +1708,8 @@ static int frame_and_rect(Glue* g, const de265_image* img, const int rect[4], in
  * way and never read through de265_get_image_plane is never downloaded.  -> M355_OK or an M355_ERR_* code (M355_ERR_INVALID also for an
  * image the backend holds no frame of, and for a decoder that shards its pictures over several ranks: their frames are complete only
  * behind the gather). */
-LIBDE265_API int m355_glue_export_image(const struct de265_image* img, int layout, int samples, const int rect[4], void* const dst[3],
-                                        const int64_t pitch[3], void* consumer_stream)
+static int export_image(const struct de265_image* img, int layout, int samples, const int rect[4], int log2_scale, void* const dst[3],
+                        const int64_t pitch[3], void* consumer_stream)
 {
   Api* A = api();
   if (!A) return M355_ERR_NO_DEVICE;
@@ -1726,10 +1726,23 @@ LIBDE265_API int m355_glue_export_image(const struct de265_image* img, int layou
   d.layout = layout; d.samples = samples;
   d.x0 = r[0]; d.y0 = r[1]; d.width = r[2]; d.height = r[3];
   for (int c = 0; c < 3; c++) { d.dst[c] = dst[c]; d.pitch[c] = pitch[c]; }
-  int rc = A->m355_frame_export(g->mctx, frame, &d);
+  int rc = log2_scale ? A->m355_frame_export_scaled(g->mctx, frame, &d, log2_scale) : A->m355_frame_export(g->mctx, frame, &d);
   if (rc == M355_OK) rc = A->m355_frame_export_order(g->mctx, frame, consumer_stream);
   if (rc != M355_OK) g->error = A->m355_last_error();
   return rc;
+}
+LIBDE265_API int m355_glue_export_image(const struct de265_image* img, int layout, int samples, const int rect[4], void* const dst[3],
+                                        const int64_t pitch[3], void* consumer_stream)
+{
+  return export_image(img, layout, samples, rect, 0, dst, pitch, consumer_stream);
+}
+/* The same, downscaled on the device by 1 << log2_scale in both directions (m355_frame_export_scaled: an exact box average per plane; 0 is the call
+ * above).  A NULL rectangle is the conformance window, which must then be a multiple of the scale on every plane's grid like any rectangle. */
+LIBDE265_API int m355_glue_export_image_scaled(const struct de265_image* img, int layout, int samples, const int rect[4], int log2_scale,
+                                               void* const dst[3], const int64_t pitch[3], void* consumer_stream)
+{
+  if (log2_scale < 0 || log2_scale > 3) return M355_ERR_INVALID;
+  return export_image(img, layout, samples, rect, log2_scale, dst, pitch, consumer_stream);
 }
 /* The picture COMPARED with another one on the device — what dec265 -m YUV does with MSE() of quality.cc on downloaded planes (dec265.cc:388-419); this call is
  * what a -m implementation on this backend calls.  ref / pitch: the reference picture's planes for the rectangle (rect = {x0, y0, width, height} in luma

@@ -451,6 +451,21 @@ typedef struct m355_export_desc {
   int64_t pitch[3];                 /* BYTES per destination row, >= the row's bytes */
 } m355_export_desc;
 M355_API int   m355_frame_export(m355_ctx* ctx, int frame, const m355_export_desc* desc);       /* asynchronous */
+/* The same export, downscaled on the device by f = 1 << log2_scale in both directions, every plane on its own grid: an exact integer box average.
+ * log2_scale 0 is m355_frame_export itself; 1, 2 and 3 take a kernel of their own (k_export_scaled.hip); anything else is M355_ERR_INVALID.
+ * desc keeps its meaning.  In addition to the rules above, the rectangle's width must be a multiple of f * SubWidthC and its height a multiple
+ * of f * SubHeightC (monochrome: f and f); a whole-frame request (width == 0) on a frame whose size is no such multiple is M355_ERR_INVALID like
+ * any other misfit: nothing is cropped implicitly.  Plane p of the rectangle, pw x ph samples, becomes pw / f x ph / f samples; a semi-planar
+ * chroma row interleaves the scaled Cb and Cr samples; a pitch is checked against the SCALED row's bytes, and bytes beyond a scaled row are never
+ * written.  With k = log2_scale, n = f * f, bd the plane's bit depth and S(x, y) the sum of the f x f source block of output sample (x, y):
+ *   NATIVE      a = (S + n / 2) >> 2k, in the frame's element type
+ *   MSB16       (uint16)(a << (16 - bd))
+ *   U8          min(255, (S + (1 << (2k + bd - 9))) >> (2k + bd - 8))     — ONE rounding from the sum, not a rounding of a; for bd = 8 it equals a
+ * Siting: an output sample sits at the centre of its block, on each plane's own grid — for 4:2:0 content with left-sited chroma the scaled chroma
+ * therefore lies (f - 1) / (2f) output luma samples off its nominal position; there is no siting correction and no other filter.
+ * Errors, ordering and the gate are those of m355_frame_export: a rejected call enqueues nothing and writes nothing; the call is asynchronous and a
+ * reader of the frame of the same kind, so m355_frame_export_wait and m355_frame_export_order cover it. */
+M355_API int   m355_frame_export_scaled(m355_ctx* ctx, int frame, const m355_export_desc* desc, int log2_scale);   /* asynchronous */
 M355_API int   m355_frame_export_wait(m355_ctx* ctx, int frame);
 M355_API int   m355_frame_export_order(m355_ctx* ctx, int frame, void* consumer_hipStream);
 /* Device memory for export destinations and blocking copies out of / into it, for applications (and the tests) that keep a second HIP

@@ -109,6 +109,8 @@ class Library:
             L.m355_device_free.restype = None
             L.m355_device_read.argtypes = [vp, vp, vp, ctypes.c_size_t]
             L.m355_device_write.argtypes = [vp, vp, vp, ctypes.c_size_t]
+        if hasattr(L, "m355_frame_export_scaled"):      # (absent from older builds loaded through M355_LIB for an A/B)
+            L.m355_frame_export_scaled.argtypes = [vp, i, ctypes.POINTER(ExportDesc), i]
         L.m355_host_alloc.argtypes = [ctypes.c_size_t]
         L.m355_host_alloc.restype = vp
         L.m355_host_free.argtypes = [vp]
@@ -322,8 +324,9 @@ class Context:
         self.L.check(self.L.lib.m355_device_read(self.h, p, a.ctypes.data, nbytes))
         return a
 
-    def export_shapes(self, f, layout, samples, rect=None):
-        """the destination planes of an export of frame f: [(rows, elements per row, dtype)] — semi-planar: Y, then Cb and Cr interleaved"""
+    def export_shapes(self, f, layout, samples, rect=None, log2_scale=0):
+        """the destination planes of an export of frame f: [(rows, elements per row, dtype)] — semi-planar: Y, then Cb and Cr interleaved;
+        log2_scale: every plane's size divided by 1 << log2_scale (m355_frame_export_scaled)"""
         w, h, cf, bdl, bdc = self._geom[f]
         if rect is not None:
             w, h = rect[2], rect[3]
@@ -331,16 +334,18 @@ class Context:
         for c, (pw, ph) in enumerate(worklist.plane_dims(w, h, cf)):
             if pw == 0 or (layout == EXPORT_SEMIPLANAR and c == 2):
                 continue
+            pw, ph = pw >> log2_scale, ph >> log2_scale
             native = np.uint8 if (bdl if c == 0 else bdc) <= 8 else np.uint16
             dt = native if samples == EXPORT_NATIVE else (np.uint16 if samples == EXPORT_MSB16 else np.uint8)
             out.append((ph, pw * (2 if layout == EXPORT_SEMIPLANAR and c == 1 else 1), np.dtype(dt)))
         return out
 
-    def frame_export(self, f, layout, samples, rect=None, host=False, pad=20):
+    def frame_export(self, f, layout, samples, rect=None, host=False, pad=20, log2_scale=0, scaled_entry=False):
         """start m355_frame_export of frame f (rect = (x0, y0, width, height) in luma samples, None: the whole frame) into buffers of its
         own — device memory, or with host=True pinned host memory —, every byte of which holds DEVICE_FILL beforehand; the pitch is `pad`
-        bytes LARGER than the row, so rows start at addresses that are no multiple of a vector.  -> token for frame_export_finish"""
-        shapes = self.export_shapes(f, layout, samples, rect)
+        bytes LARGER than the row, so rows start at addresses that are no multiple of a vector.  log2_scale != 0: downscaled by 1 << log2_scale
+        (m355_frame_export_scaled; scaled_entry=True takes that entry point for log2_scale 0 too).  -> token for frame_export_finish"""
+        shapes = self.export_shapes(f, layout, samples, rect, log2_scale)
         desc = ExportDesc(layout=layout, samples=samples)
         if rect is not None:
             desc.x0, desc.y0, desc.width, desc.height = rect
@@ -357,7 +362,10 @@ class Context:
                     p = self.device_alloc(rows * pitch)
                 bufs.append(p)
                 desc.dst[k] = p; desc.pitch[k] = pitch
-            self.L.check(self.L.lib.m355_frame_export(self.h, f, ctypes.byref(desc)))
+            if log2_scale or scaled_entry:
+                self.L.check(self.L.lib.m355_frame_export_scaled(self.h, f, ctypes.byref(desc), log2_scale))
+            else:
+                self.L.check(self.L.lib.m355_frame_export(self.h, f, ctypes.byref(desc)))
         except Exception:
             for p in bufs:
                 self.L.lib.m355_host_free(p) if host else self.device_free(p)

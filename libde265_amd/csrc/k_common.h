@@ -277,6 +277,23 @@ struct ExportArgs {
 /* src_bytes / dst_bytes: 1 or 2 per sample (2 -> 1: round and clip to 8 bits; 1 -> 2: the 8-bit sample in the high byte) */
 void m355_launch_export(const ExportArgs& a, int src_bytes, int dst_bytes, bool semiplanar, hipStream_t st);
 
+/* one m355_frame_export_scaled (k_export_scaled.hip), planes as in ExportArgs.  Units follow the SOURCE: a wavefront reduces one 64-lane chunk
+   (1024 source bytes of each of the f = 1 << log2_scale source rows) of one OUTPUT row: chunks[k] = chunks per row of plane k, unit_end[k] = the
+   chunks of planes 0..k, out_w[k] = output samples per row (of each plane of an interleaved row).  An output sample is
+   min(clip, (block sum + (1 << (rshift - 1))) >> rshift) << lshift, clip = 255 for 8-bit destinations: rshift[k] = 2 log2_scale (U8: + bit depth - 8),
+   lshift[k] = 16 - bit depth for MSB16, else 0.  timeout / epoch: the gate of the decode that wrote the frame (M355_GATE). */
+struct ExportScaledArgs {
+  const uint8_t* src[3];
+  uint8_t* dst[3];
+  long long src_pitch[3], dst_pitch[3];
+  uint32_t out_w[3], chunks[3], unit_end[3];
+  int32_t rshift[3], lshift[3];
+  const uint32_t* timeout;
+  uint32_t epoch;
+};
+/* src_bytes / dst_bytes: 1 or 2 per sample; log2_scale: 1, 2 or 3 */
+void m355_launch_export_scaled(const ExportScaledArgs& a, int src_bytes, int dst_bytes, bool semiplanar, int log2_scale, hipStream_t st);
+
 /* first statement of every kernel of a decode: a picture whose lists k_validate rejected is never acted upon */
 /* Element `c` (0..2, per lane) of a three-entry table of the kernel arguments (plane pointers, pitches, ...): all three entries are
  * read as scalars and the lane selects — indexing the argument segment with a per-lane value is a VECTOR memory load from it, i.e. one

@@ -450,48 +450,109 @@ int m355_frame_download_wait(m355_ctx* c, int h)
   f->reader[RD_DOWNLOAD] = EvRef();
   return M355_OK;
 }
+/* What m355_frame_export and m355_frame_export_scaled share: the argument checks and, per plane of the launch (semi-planar: plane 1 = Cb and Cr
+ * interleaved), where the rectangle starts in the frame, its size and where it goes.  log2_scale = k: the rectangle must divide into blocks of 1 << k
+ * samples on every plane's grid, and row_bytes / the pitch check are those of the SCALED row. */
+struct ExportPlane {
+  const uint8_t* src[2];            /* the rectangle's first sample (src[1]: the Cr plane of an interleaved row) */
+  uint8_t* dst;
+  long long src_pitch, dst_pitch;   /* bytes */
+  int pw, ph, bd, sb, db;           /* the rectangle on this plane (source samples), bit depth, bytes per source / destination sample */
+  int64_t row_bytes;                /* of a destination row */
+};
+struct ExportPlan { Frame* f; int np; bool semi; ExportPlane p[3]; };
+static int export_plan(m355_ctx* c, int h, const m355_export_desc* e, int k, const char* who, ExportPlan& P)
+{
+  Frame* f = get_frame(c, h);
+  if (!f || !e) return fail(M355_ERR_INVALID, "bad frame handle %d / null descriptor", h);
+  if (e->layout != M355_EXPORT_PLANAR && e->layout != M355_EXPORT_SEMIPLANAR) return fail(M355_ERR_INVALID, "%s: unknown layout %d", who, e->layout);
+  if (e->samples != M355_EXPORT_NATIVE && e->samples != M355_EXPORT_MSB16 && e->samples != M355_EXPORT_U8) return fail(M355_ERR_INVALID, "%s: unknown sample format %d", who, e->samples);
+  const int sw = (f->cf == 1 || f->cf == 2) ? 2 : 1, sh = f->cf == 1 ? 2 : 1, fs = 1 << k;
+  int x0 = 0, y0 = 0, w = f->w, hgt = f->h;
+  if (e->width != 0) {
+    x0 = e->x0; y0 = e->y0; w = e->width; hgt = e->height;
+    if (x0 < 0 || y0 < 0 || w <= 0 || hgt <= 0 || x0 > f->w - w || y0 > f->h - hgt) return fail(M355_ERR_INVALID, "%s: rectangle %d,%d %dx%d leaves the %dx%d frame", who, x0, y0, w, hgt, f->w, f->h);
+    if (f->cf && ((x0 | w) % sw || (y0 | hgt) % sh)) return fail(M355_ERR_INVALID, "%s: rectangle %d,%d %dx%d is not aligned to the chroma grid (%dx%d luma samples)", who, x0, y0, w, hgt, sw, sh);
+  }
+  if (k && (w % (fs * sw) || hgt % (fs * sh))) return fail(M355_ERR_INVALID, "%s: %dx%d is no multiple of %dx%d luma samples (scale %d on every plane)", who, w, hgt, fs * sw, fs * sh, fs);
+  P.f = f;
+  P.semi = e->layout == M355_EXPORT_SEMIPLANAR && f->cf != 0;
+  P.np = f->cf == 0 ? 1 : (P.semi ? 2 : 3);
+  for (int p = 0; p < P.np; p++) {
+    ExportPlane& q = P.p[p];
+    q.bd = p ? f->bdc : f->bdl; q.sb = f->bpp[p];
+    q.db = e->samples == M355_EXPORT_NATIVE ? q.sb : (e->samples == M355_EXPORT_MSB16 ? 2 : 1);
+    q.pw = p ? w / sw : w; q.ph = p ? hgt / sh : hgt;
+    const int px = p ? x0 / sw : x0, py = p ? y0 / sh : y0;
+    q.row_bytes = (int64_t)(q.pw >> k) * q.db * (P.semi && p ? 2 : 1);
+    if (!e->dst[p]) return fail(M355_ERR_INVALID, "%s: no destination for plane %d", who, p);
+    if (e->pitch[p] < q.row_bytes) return fail(M355_ERR_INVALID, "%s: pitch %lld of plane %d is below its row of %lld bytes", who, (long long)e->pitch[p], p, (long long)q.row_bytes);
+    q.dst = (uint8_t*)e->dst[p]; q.dst_pitch = e->pitch[p];
+    q.src_pitch = (long long)f->stride[p] * q.sb;
+    for (int j = 0; j < (P.semi && p ? 2 : 1); j++) q.src[j] = (const uint8_t*)f->plane[p + j] + (size_t)py * q.src_pitch + (size_t)px * q.sb;
+  }
+  return M355_OK;
+}
+
 /* The frame, or a rectangle of it, converted into memory of the caller (k_export.hip): one launch for all planes.  The export is a READER of the
  * frame (reader_begin): the mark behind it is what the next decode into the frame waits for (dst_hazards), what m355_frame_export_wait blocks on
  * and what m355_frame_export_order makes a consumer's stream wait for. */
 int m355_frame_export(m355_ctx* c, int h, const m355_export_desc* e)
 {
-  Frame* f = get_frame(c, h);
-  if (!f || !e) return fail(M355_ERR_INVALID, "bad frame handle %d / null descriptor", h);
-  if (e->layout != M355_EXPORT_PLANAR && e->layout != M355_EXPORT_SEMIPLANAR) return fail(M355_ERR_INVALID, "m355_frame_export: unknown layout %d", e->layout);
-  if (e->samples != M355_EXPORT_NATIVE && e->samples != M355_EXPORT_MSB16 && e->samples != M355_EXPORT_U8) return fail(M355_ERR_INVALID, "m355_frame_export: unknown sample format %d", e->samples);
-  const int sw = (f->cf == 1 || f->cf == 2) ? 2 : 1, sh = f->cf == 1 ? 2 : 1;
-  int x0 = 0, y0 = 0, w = f->w, hgt = f->h;
-  if (e->width != 0) {
-    x0 = e->x0; y0 = e->y0; w = e->width; hgt = e->height;
-    if (x0 < 0 || y0 < 0 || w <= 0 || hgt <= 0 || x0 > f->w - w || y0 > f->h - hgt) return fail(M355_ERR_INVALID, "m355_frame_export: rectangle %d,%d %dx%d leaves the %dx%d frame", x0, y0, w, hgt, f->w, f->h);
-    if (f->cf && ((x0 | w) % sw || (y0 | hgt) % sh)) return fail(M355_ERR_INVALID, "m355_frame_export: rectangle %d,%d %dx%d is not aligned to the chroma grid (%dx%d luma samples)", x0, y0, w, hgt, sw, sh);
-  }
-  const bool semi = e->layout == M355_EXPORT_SEMIPLANAR && f->cf != 0;
-  const int np = f->cf == 0 ? 1 : (semi ? 2 : 3);
+  ExportPlan P;
+  int rc = export_plan(c, h, e, 0, "m355_frame_export", P);
+  if (rc) return rc;
   ExportArgs a = {};
   uint32_t units = 0;
   for (int p = 0; p < 3; p++) {
-    if (p < np) {
-      const int bd = p ? f->bdc : f->bdl, sb = f->bpp[p];
-      const int db = e->samples == M355_EXPORT_NATIVE ? sb : (e->samples == M355_EXPORT_MSB16 ? 2 : 1);
-      const int pw = p ? w / sw : w, ph = p ? hgt / sh : hgt, px = p ? x0 / sw : x0, py = p ? y0 / sh : y0;
-      const int64_t rb = (int64_t)pw * db * (semi && p ? 2 : 1);
-      if (!e->dst[p]) return fail(M355_ERR_INVALID, "m355_frame_export: no destination for plane %d", p);
-      if (e->pitch[p] < rb) return fail(M355_ERR_INVALID, "m355_frame_export: pitch %lld of plane %d is below its row of %lld bytes", (long long)e->pitch[p], p, (long long)rb);
-      a.dst[p] = (uint8_t*)e->dst[p]; a.dst_pitch[p] = e->pitch[p];
-      a.src_pitch[p] = (long long)f->stride[p] * sb;
-      a.row_bytes[p] = (uint32_t)rb; a.chunks[p] = (uint32_t)((rb + 1023) / 1024);
-      a.shift[p] = e->samples == M355_EXPORT_MSB16 ? 16 - bd : (e->samples == M355_EXPORT_U8 ? bd - 8 : 0);
-      units += a.chunks[p] * (uint32_t)ph;
-      for (int q = p; q < (semi && p ? 3 : p + 1); q++) a.src[q] = (const uint8_t*)f->plane[q] + (size_t)py * a.src_pitch[p] + (size_t)px * sb;
+    if (p < P.np) {
+      const ExportPlane& q = P.p[p];
+      a.dst[p] = q.dst; a.dst_pitch[p] = q.dst_pitch;
+      a.src_pitch[p] = q.src_pitch;
+      a.row_bytes[p] = (uint32_t)q.row_bytes; a.chunks[p] = (uint32_t)((q.row_bytes + 1023) / 1024);
+      a.shift[p] = e->samples == M355_EXPORT_MSB16 ? 16 - q.bd : (e->samples == M355_EXPORT_U8 ? q.bd - 8 : 0);
+      units += a.chunks[p] * (uint32_t)q.ph;
+      a.src[p] = q.src[0];
+      if (P.semi && p) a.src[2] = q.src[1];
     }
     a.unit_end[p] = units;
   }
   hipSetDevice(c->device);
-  const hipStream_t cs = reader_begin(c, f, RD_EXPORT, &a.timeout, &a.epoch);
-  m355_launch_export(a, f->bpp[0], e->samples == M355_EXPORT_NATIVE ? f->bpp[0] : (e->samples == M355_EXPORT_MSB16 ? 2 : 1), semi, cs);
+  const hipStream_t cs = reader_begin(c, P.f, RD_EXPORT, &a.timeout, &a.epoch);
+  m355_launch_export(a, P.f->bpp[0], P.p[0].db, P.semi, cs);
   HIPCHK(hipGetLastError());
-  return reader_end(c, f, RD_EXPORT, cs);
+  return reader_end(c, P.f, RD_EXPORT, cs);
+}
+/* The same, downscaled by 1 << log2_scale in both directions (k_export_scaled.hip): a reader of the same kind, so that m355_frame_export_wait and
+ * m355_frame_export_order cover it and the next decode into the frame waits for it. */
+int m355_frame_export_scaled(m355_ctx* c, int h, const m355_export_desc* e, int log2_scale)
+{
+  if (log2_scale == 0) return m355_frame_export(c, h, e);
+  if (log2_scale < 0 || log2_scale > 3) return fail(M355_ERR_INVALID, "m355_frame_export_scaled: log2_scale %d is not 0..3", log2_scale);
+  ExportPlan P;
+  int rc = export_plan(c, h, e, log2_scale, "m355_frame_export_scaled", P);
+  if (rc) return rc;
+  ExportScaledArgs a = {};
+  uint32_t units = 0;
+  for (int p = 0; p < 3; p++) {
+    if (p < P.np) {
+      const ExportPlane& q = P.p[p];
+      a.dst[p] = q.dst; a.dst_pitch[p] = q.dst_pitch;
+      a.src_pitch[p] = q.src_pitch;
+      a.out_w[p] = (uint32_t)(q.pw >> log2_scale); a.chunks[p] = (uint32_t)(((int64_t)q.pw * q.sb + 1023) / 1024);
+      a.rshift[p] = 2 * log2_scale + (e->samples == M355_EXPORT_U8 ? q.bd - 8 : 0);
+      a.lshift[p] = e->samples == M355_EXPORT_MSB16 ? 16 - q.bd : 0;
+      units += a.chunks[p] * (uint32_t)(q.ph >> log2_scale);
+      a.src[p] = q.src[0];
+      if (P.semi && p) a.src[2] = q.src[1];
+    }
+    a.unit_end[p] = units;
+  }
+  hipSetDevice(c->device);
+  const hipStream_t cs = reader_begin(c, P.f, RD_EXPORT, &a.timeout, &a.epoch);
+  m355_launch_export_scaled(a, P.f->bpp[0], P.p[0].db, P.semi, log2_scale, cs);
+  HIPCHK(hipGetLastError());
+  return reader_end(c, P.f, RD_EXPORT, cs);
 }
 /* the host waits until this frame's last export has landed */
 int m355_frame_export_wait(m355_ctx* c, int h)

@@ -7,9 +7,12 @@
   (c) MSB16 semi-planar, the frame minus an 8-sample border (x0 = y0 = 8: misaligned source rows)
   (d) U8 semi-planar, whole frame
   (e), (f) what separates (c) from (b): MSB16 semi-planar uncropped, NATIVE planar cropped
+  (g), (h), (i) m355_frame_export_scaled NATIVE planar, whole frame, downscaled 2x, 4x, 8x
+  (j) U8 semi-planar downscaled 4x: the 8K to 1080p NV12 proxy
 
 and, beside them, m355_measure_copy_rate for the frame's byte count.  Every figure is the median of --iters launches; (b) is measured in
---rounds separate rounds spread over the run, and the spread of their medians is the margin (c) and (d) are held against.  The HIP calls
+--rounds separate rounds spread over the run, and the spread of their medians is the margin (c), (d) and (g)-(j) are held against: a scaled export reads exactly (b)'s source bytes and writes at most a
+quarter of (b)'s destination bytes, so it should not be slower than (b).  Beside each scaled row: its source bytes / time.  The HIP calls
 of (a) and the events go to the runtime the library itself has loaded (no second runtime in the process).
 
   python tools/export_bench.py [--out profiles/export_bench.txt]
@@ -84,14 +87,16 @@ def main():
         for k, (w, h) in enumerate(planes):
             assert hip.hipMemcpy2DAsync(dst[k], w * 2, src[k], pitch[k], w * 2, h, D2D, stream) == 0
 
-    def export(layout, samples, rect, elem):
+    def export(layout, samples, rect, elem, log2_scale=0):
         d = capi.ExportDesc(layout=layout, samples=samples)
         if rect:
             d.x0, d.y0, d.width, d.height = rect
-        w = rect[2] if rect else W
+        w = (rect[2] if rect else W) >> log2_scale
         rows = [w * elem, w * elem if layout else w // 2 * elem, w // 2 * elem]
         for k in range(3):
             d.dst[k] = dst[k]; d.pitch[k] = rows[k]
+        if log2_scale:
+            return lambda: lib.check(lib.lib.m355_frame_export_scaled(ctx.h, frame, ctypes.byref(d), log2_scale))
         return lambda: lib.check(lib.lib.m355_frame_export(ctx.h, frame, ctypes.byref(d)))
 
     variants = {
@@ -102,7 +107,12 @@ def main():
         # beside the four: (c) without its crop (aligned source rows, interleaved stores) and (b) with it (misaligned rows, plain stores)
         "e_msb16_semiplanar": export(capi.EXPORT_SEMIPLANAR, capi.EXPORT_MSB16, None, 2),
         "f_native_planar_crop8": export(capi.EXPORT_PLANAR, capi.EXPORT_NATIVE, (8, 8, W - 16, H - 16), 2),
+        "g_native_planar_2x": export(capi.EXPORT_PLANAR, capi.EXPORT_NATIVE, None, 2, 1),
+        "h_native_planar_4x": export(capi.EXPORT_PLANAR, capi.EXPORT_NATIVE, None, 2, 2),
+        "i_native_planar_8x": export(capi.EXPORT_PLANAR, capi.EXPORT_NATIVE, None, 2, 3),
+        "j_u8_semiplanar_4x": export(capi.EXPORT_SEMIPLANAR, capi.EXPORT_U8, None, 1, 2),
     }
+    scaled = [n for n in variants if n[0] in "ghij"]
     ms = {n: [] for n in variants}
     for _ in range(args.rounds):
         for n, fn in variants.items():
@@ -116,10 +126,12 @@ def main():
         "iters": args.iters, "rounds": args.rounds,
         "ms_median": res, "ms_rounds": ms, "b_spread_ms": spread,
         "GBps_read_plus_written": {"a_memcpy2d_x3": 2 * frame_bytes / res["a_memcpy2d_x3"] / 1e6, "b_native_planar": 2 * frame_bytes / res["b_native_planar"] / 1e6},
+        "scaled_GBps_source_read": {n: frame_bytes / res[n] / 1e6 for n in scaled},
         "copy_rate_GBps_same_bytes": ctx.measure_copy_rate(frame_bytes, 9),
         "bars": {"b_le_a": res["b_native_planar"] <= res["a_memcpy2d_x3"],
                  "c_le_b_plus_spread": res["c_msb16_semiplanar_crop8"] <= res["b_native_planar"] + spread,
-                 "d_le_b_plus_spread": res["d_u8_semiplanar"] <= res["b_native_planar"] + spread},
+                 "d_le_b_plus_spread": res["d_u8_semiplanar"] <= res["b_native_planar"] + spread,
+                 **{n[0] + "_le_b_plus_spread": res[n] <= res["b_native_planar"] + spread for n in scaled}},
     }
     line = json.dumps(out)
     print(line)
