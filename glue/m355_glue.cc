@@ -86,7 +86,7 @@ namespace {
   X(m355_last_error) X(m355_device_count) X(m355_create) X(m355_destroy) X(m355_frame_create) X(m355_frame_destroy) \
   X(m355_frame_upload) X(m355_frame_download) X(m355_submit_picture) X(m355_wait) X(m355_set_pipeline_depth) \
   X(m355_host_alloc) X(m355_host_free) X(m355_frame_hash) X(m355_arena_begin) X(m355_last_serial) X(m355_decode_status) \
-  X(m355_frame_download_async) X(m355_frame_download_wait) X(m355_frame_export) X(m355_frame_export_scaled) X(m355_frame_export_order) \
+  X(m355_frame_download_async) X(m355_frame_download_wait) X(m355_frame_export) X(m355_frame_export_scaled) X(m355_frame_export_rgb) X(m355_frame_export_order) \
   X(m355_group_create) X(m355_group_destroy) X(m355_group_decode) X(m355_picture_upload) X(m355_picture_replace) X(m355_shard_owner_of_tile) \
   X(m355_picture_arena_begin) X(m355_frame_hash_async) X(m355_frame_hash_result) X(m355_frame_measure_async) X(m355_frame_measure_result)
 
@@ -1743,6 +1743,42 @@ LIBDE265_API int m355_glue_export_image_scaled(const struct de265_image* img, in
 {
   if (log2_scale < 0 || log2_scale > 3) return M355_ERR_INVALID;
   return export_image(img, layout, samples, rect, log2_scale, dst, pitch, consumer_stream);
+}
+/* The picture as R'G'B' (m355_frame_export_rgb: layout / samples = M355_RGB_*, one chroma reconstruction filter, integer-exact), with the waiting
+ * behaviour of m355_glue_export_image: the only wait is for the worker to have enqueued the picture.  matrix = M355_MATRIX_*, or -1: what the stream
+ * signals (de265_get_image_matrix_coefficients: 1 -> BT.709; 5, 6 -> BT.601; 9 -> BT.2020 non-constant luminance; 2, unspecified -> BT.709; anything
+ * else is M355_ERR_INVALID: there is no integer matrix for it here).  full_range = 0 / 1, or -1: de265_get_image_full_range_flag.  PACKED uses dst[0]
+ * and pitch[0] only. */
+LIBDE265_API int m355_glue_export_image_rgb(const struct de265_image* img, int layout, int samples, int matrix, int full_range, const int rect[4],
+                                            void* const dst[3], const int64_t pitch[3], void* consumer_stream)
+{
+  Api* A = api();
+  if (!A) return M355_ERR_NO_DEVICE;
+  if (!img || !img->decctx || !dst || !pitch) return M355_ERR_INVALID;
+  Glue* g = glue_of(img->decctx);
+  if (!g || g->n_ranks > 1) return M355_ERR_INVALID;
+  if (matrix == -1) {
+    const int mc = de265_get_image_matrix_coefficients(img);
+    if (mc == 1 || mc == 2) matrix = M355_MATRIX_BT709;
+    else if (mc == 5 || mc == 6) matrix = M355_MATRIX_BT601;
+    else if (mc == 9) matrix = M355_MATRIX_BT2020;
+    else return M355_ERR_INVALID;
+  }
+  if (full_range == -1) full_range = de265_get_image_full_range_flag(img) ? 1 : 0;
+  wait_submitted(g, img->get_ID());
+  std::lock_guard<std::mutex> api_lock(g->api_mu);
+  int r[4];
+  const int frame = frame_and_rect(g, img, rect, r);
+  if (frame < 0) return M355_ERR_INVALID;
+  m355_rgb_desc d;
+  memset(&d, 0, sizeof(d));
+  d.layout = layout; d.samples = samples; d.matrix = matrix; d.full_range = full_range;
+  d.x0 = r[0]; d.y0 = r[1]; d.width = r[2]; d.height = r[3];
+  for (int c = 0; c < 3; c++) { d.dst[c] = dst[c]; d.pitch[c] = pitch[c]; }
+  int rc = A->m355_frame_export_rgb(g->mctx, frame, &d);
+  if (rc == M355_OK) rc = A->m355_frame_export_order(g->mctx, frame, consumer_stream);
+  if (rc != M355_OK) g->error = A->m355_last_error();
+  return rc;
 }
 /* The picture COMPARED with another one on the device — what dec265 -m YUV does with MSE() of quality.cc on downloaded planes (dec265.cc:388-419); this call is
  * what a -m implementation on this backend calls.  ref / pitch: the reference picture's planes for the rectangle (rect = {x0, y0, width, height} in luma

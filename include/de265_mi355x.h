@@ -466,6 +466,50 @@ M355_API int   m355_frame_export(m355_ctx* ctx, int frame, const m355_export_des
  * Errors, ordering and the gate are those of m355_frame_export: a rejected call enqueues nothing and writes nothing; the call is asynchronous and a
  * reader of the frame of the same kind, so m355_frame_export_wait and m355_frame_export_order cover it. */
 M355_API int   m355_frame_export_scaled(m355_ctx* ctx, int frame, const m355_export_desc* desc, int log2_scale);   /* asynchronous */
+/* The frame, or a rectangle of it, as R'G'B' (k_export_rgb.hip): for a model or a compositor on the same GPU.  Integer arithmetic only, so that
+ * what lands is a closed-form function of the samples m355_frame_download returns, the same on every build.  m355_rgb_coefficients is the one
+ * place the constants are made (the runtime calls it for the launch); with 64-bit integers, rdiv(a, b) = (2a + b) / (2b), D = 8 or 16 (samples),
+ * M = 2^D - 1, F = 29 - D, Kr / Kb of the matrix in 1/10000, Kg = 10000 - Kr - Kb, bdY / bdC the bit depths:
+ *   limited range  y0 = 16 << (bdY - 8)   ys = 219 << (bdY - 8)   cs = 224 << (bdC - 8)
+ *   full range     y0 = 0                 ys = 2^bdY - 1          cs = 2^bdC - 1                  c0 = 1 << (bdC - 1) in both
+ *   cy  = rdiv(M << F, ys)
+ *   crv = rdiv(2 (10000 - Kr) (M << F), 10000 cs)             cbu = rdiv(2 (10000 - Kb) (M << F), 10000 cs)
+ *   cgu = rdiv(2 Kb (10000 - Kb) (M << F), 10000 Kg cs)       cgv = rdiv(2 Kr (10000 - Kr) (M << F), 10000 Kg cs)
+ * Per pixel, y = Y - y0, u = Cb' - c0, v = Cr' - c0, H = 1 << (F - 1), sums in signed 32 bits, >> an arithmetic shift:
+ *   R = clip(0, M, (cy y + crv v + H) >> F)    G = clip(0, M, (cy y - cgu u - cgv v + H) >> F)    B = clip(0, M, (cy y + cbu u + H) >> F)
+ * (within 0.5 + 0.5 (|y| + |u| + |v|) / 2^F output LSB of the real-valued conversion: below 1 LSB for 8..12-bit sources, up to 3.2 at 16 -> U16).
+ * A monochrome frame has u = v = 0.  M355_RGB_U16 is full scale 0..65535, not the frame's bit depth MSB-aligned.
+ * Cb', Cr' are the chroma samples AT THE LUMA POSITION.  There is ONE reconstruction filter, the bilinear one for chroma sample location type 0
+ * (horizontally co-sited, vertically midway); no other siting is offered.  It works on the FRAME's chroma plane C of CW x CH samples with indices
+ * clamped to that plane — samples outside the rectangle but inside the frame are read as they are, so an exported rectangle equals the same
+ * rectangle cut from a whole-frame export — and its result is a sample of the chroma bit depth, rounded BEFORE the matrix.  For luma (X, Y):
+ *   4:4:4  C[Y][X]
+ *   4:2:2  i = X >> 1;  X even: C[Y][i];  X odd: (C[Y][i] + C[Y][min(i + 1, CW - 1)] + 1) >> 1
+ *   4:2:0  j = Y >> 1, jn = max(j - 1, 0) for even Y, min(j + 1, CH - 1) for odd Y, T[i] = 3 C[j][i] + C[jn][i];
+ *          X even: (T[i] + 2) >> 2;  X odd: (T[i] + T[min(i + 1, CW - 1)] + 4) >> 3
+ * M355_ERR_INVALID (nothing is enqueued, no destination byte written): whatever m355_frame_export rejects for the frame handle and the rectangle;
+ * an unknown layout, samples or matrix value, full_range not 0 or 1; a null dst for a plane the layout uses; a pitch below the row's bytes (width * 3 *
+ * element bytes packed, width * element bytes planar); for U16 a pointer or a pitch that is no multiple of 2.  m355_rgb_coefficients rejects the same
+ * matrix / full_range / samples values, bit depths outside 8..16 and a null `out`.
+ * Ordering, the gate and sharded contexts are those of m355_frame_export: asynchronous, a reader of the frame of the same kind — m355_frame_export_wait
+ * and m355_frame_export_order cover it, the next decode into the frame waits for it —, nothing is written behind a rejected decode, and destination
+ * bytes beyond a row are never written. */
+#define M355_RGB_PACKED  0   /* dst[0]: R,G,B,R,G,B,... three elements per pixel */
+#define M355_RGB_PLANAR  1   /* dst[0..2] = R, G, B planes (CHW) */
+#define M355_RGB_U8      0   /* D = 8 */
+#define M355_RGB_U16     1   /* D = 16, full scale 0..65535 (not MSB-aligned bit-depth samples) */
+#define M355_MATRIX_BT601 0  /* Kr, Kb = 2990, 1140 (in 1/10000) */
+#define M355_MATRIX_BT709 1  /*          2126,  722 */
+#define M355_MATRIX_BT2020 2 /*          2627,  593  (non-constant luminance) */
+typedef struct m355_rgb_desc {
+  int32_t layout, samples, matrix, full_range;
+  int32_t x0, y0, width, height;    /* as m355_export_desc: luma rectangle, width == 0 = whole frame, multiples of SubWidthC / SubHeightC */
+  void*   dst[3];                   /* device memory, or m355_host_alloc memory; PACKED uses [0] only */
+  int64_t pitch[3];                 /* BYTES per destination row, >= the row's bytes */
+} m355_rgb_desc;
+M355_API int   m355_frame_export_rgb(m355_ctx* ctx, int frame, const m355_rgb_desc* desc);      /* asynchronous */
+typedef struct m355_rgb_coeffs { int32_t F, y0, c0, cy, crv, cgu, cgv, cbu; } m355_rgb_coeffs;
+M355_API int   m355_rgb_coefficients(int matrix, int full_range, int bit_depth_luma, int bit_depth_chroma, int samples, m355_rgb_coeffs* out);
 M355_API int   m355_frame_export_wait(m355_ctx* ctx, int frame);
 M355_API int   m355_frame_export_order(m355_ctx* ctx, int frame, void* consumer_hipStream);
 /* Device memory for export destinations and blocking copies out of / into it, for applications (and the tests) that keep a second HIP

@@ -49,6 +49,23 @@ class ExportDesc(ctypes.Structure):
                 ("dst", ctypes.c_void_p * 3), ("pitch", ctypes.c_int64 * 3)]
 
 
+RGB_PACKED, RGB_PLANAR = 0, 1
+RGB_U8, RGB_U16 = 0, 1
+MATRIX_BT601, MATRIX_BT709, MATRIX_BT2020 = 0, 1, 2
+
+
+class RgbDesc(ctypes.Structure):
+    """m355_rgb_desc (include/de265_mi355x.h)"""
+    _fields_ = [("layout", ctypes.c_int32), ("samples", ctypes.c_int32), ("matrix", ctypes.c_int32), ("full_range", ctypes.c_int32),
+                ("x0", ctypes.c_int32), ("y0", ctypes.c_int32), ("width", ctypes.c_int32), ("height", ctypes.c_int32),
+                ("dst", ctypes.c_void_p * 3), ("pitch", ctypes.c_int64 * 3)]
+
+
+class RgbCoeffs(ctypes.Structure):
+    """m355_rgb_coeffs (include/de265_mi355x.h)"""
+    _fields_ = [(n, ctypes.c_int32) for n in ("F", "y0", "c0", "cy", "crv", "cgu", "cgv", "cbu")]
+
+
 class MeasureDesc(ctypes.Structure):
     """m355_measure_desc (include/de265_mi355x.h)"""
     _fields_ = [("ref_frame", ctypes.c_int32), ("x0", ctypes.c_int32), ("y0", ctypes.c_int32), ("width", ctypes.c_int32), ("height", ctypes.c_int32),
@@ -111,6 +128,9 @@ class Library:
             L.m355_device_write.argtypes = [vp, vp, vp, ctypes.c_size_t]
         if hasattr(L, "m355_frame_export_scaled"):      # (absent from older builds loaded through M355_LIB for an A/B)
             L.m355_frame_export_scaled.argtypes = [vp, i, ctypes.POINTER(ExportDesc), i]
+        if hasattr(L, "m355_frame_export_rgb"):         # (absent from older builds loaded through M355_LIB for an A/B)
+            L.m355_frame_export_rgb.argtypes = [vp, i, ctypes.POINTER(RgbDesc)]
+            L.m355_rgb_coefficients.argtypes = [i, i, i, i, i, ctypes.POINTER(RgbCoeffs)]
         L.m355_host_alloc.argtypes = [ctypes.c_size_t]
         L.m355_host_alloc.restype = vp
         L.m355_host_free.argtypes = [vp]
@@ -173,6 +193,12 @@ class Library:
 
     def device_count(self):
         return self.lib.m355_device_count()
+
+    def rgb_coefficients(self, matrix, full_range, bit_depth_luma, bit_depth_chroma, samples):
+        """the integers of the R'G'B' conversion (m355_rgb_coefficients; host only) -> dict F, y0, c0, cy, crv, cgu, cgv, cbu"""
+        k = RgbCoeffs()
+        self.check(self.lib.m355_rgb_coefficients(matrix, full_range, bit_depth_luma, bit_depth_chroma, samples, ctypes.byref(k)))
+        return {n: int(getattr(k, n)) for n, _ in RgbCoeffs._fields_}
 
     def pack_narrow(self, pic):
         """m355_pack_narrow on a picture's residual records and coefficient list (host only; worklist.pack_narrow is the numpy
@@ -366,6 +392,42 @@ class Context:
                 self.L.check(self.L.lib.m355_frame_export_scaled(self.h, f, ctypes.byref(desc), log2_scale))
             else:
                 self.L.check(self.L.lib.m355_frame_export(self.h, f, ctypes.byref(desc)))
+        except Exception:
+            for p in bufs:
+                self.L.lib.m355_host_free(p) if host else self.device_free(p)
+            raise
+        return (f, shapes, bufs, [int(desc.pitch[k]) for k in range(len(shapes))], host)
+
+    def rgb_coefficients(self, matrix, full_range, bit_depth_luma, bit_depth_chroma, samples):
+        """the integers of the R'G'B' conversion (m355_rgb_coefficients) -> dict F, y0, c0, cy, crv, cgu, cgv, cbu"""
+        return self.L.rgb_coefficients(matrix, full_range, bit_depth_luma, bit_depth_chroma, samples)
+
+    def frame_export_rgb(self, f, layout, samples, matrix, full_range, rect=None, host=False, pad=20):
+        """start m355_frame_export_rgb of frame f (rect = (x0, y0, width, height) in luma samples, None: the whole frame) into buffers of its own,
+        made as frame_export makes them: every byte holds DEVICE_FILL beforehand, the pitch is `pad` bytes larger than the row.  Packed: one plane
+        of 3 * width elements per row; planar: R, G, B.  -> token for frame_export_finish"""
+        w, h = self._geom[f][:2]
+        if rect is not None:
+            w, h = rect[2], rect[3]
+        dt = np.dtype(np.uint16 if samples == RGB_U16 else np.uint8)
+        shapes = [(h, 3 * w, dt)] if layout == RGB_PACKED else [(h, w, dt)] * 3
+        desc = RgbDesc(layout=layout, samples=samples, matrix=matrix, full_range=full_range)
+        if rect is not None:
+            desc.x0, desc.y0, desc.width, desc.height = rect
+        bufs = []
+        try:
+            for k, (rows, n, _) in enumerate(shapes):
+                pitch = n * dt.itemsize + pad
+                if host:
+                    p = self.L.lib.m355_host_alloc(rows * pitch)
+                    if not p:
+                        raise M355Error(4, self.L.error())
+                    ctypes.memset(p, DEVICE_FILL, rows * pitch)
+                else:
+                    p = self.device_alloc(rows * pitch)
+                bufs.append(p)
+                desc.dst[k] = p; desc.pitch[k] = pitch
+            self.L.check(self.L.lib.m355_frame_export_rgb(self.h, f, ctypes.byref(desc)))
         except Exception:
             for p in bufs:
                 self.L.lib.m355_host_free(p) if host else self.device_free(p)

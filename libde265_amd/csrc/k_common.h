@@ -294,6 +294,24 @@ struct ExportScaledArgs {
 /* src_bytes / dst_bytes: 1 or 2 per sample; log2_scale: 1, 2 or 3 */
 void m355_launch_export_scaled(const ExportScaledArgs& a, int src_bytes, int dst_bytes, bool semiplanar, int log2_scale, hipStream_t st);
 
+/* one m355_frame_export_rgb (k_export_rgb.hip).  src[] are the FRAME's planes (the chroma filter reads neighbours outside the rectangle and clamps
+   to the frame: cw x ch chroma samples), x0, y0, width, height the luma rectangle; pitches in BYTES (src_pitch[0] luma, [1] both chroma planes).
+   dst[0] alone for the packed layout, else R, G, B.  A wavefront converts one 64-lane chunk (64 * 16 / source sample bytes pixels) of one row:
+   chunks per row, units = chunks * height.  k: the integers of m355_rgb_coefficients.  timeout / epoch: the gate of the decode that wrote the
+   frame (M355_GATE). */
+struct ExportRgbArgs {
+  const uint8_t* src[3];
+  uint8_t* dst[3];
+  long long src_pitch[2], dst_pitch[3];
+  uint32_t x0, y0, width, height, cw, ch;
+  uint32_t chunks, units;
+  m355_rgb_coeffs k;
+  const uint32_t* timeout;
+  uint32_t epoch;
+};
+/* src_bytes / dst_bytes: 1 or 2 per sample / channel; chroma_format: 0..3 */
+void m355_launch_export_rgb(const ExportRgbArgs& a, int src_bytes, int dst_bytes, bool planar, int chroma_format, hipStream_t st);
+
 /* first statement of every kernel of a decode: a picture whose lists k_validate rejected is never acted upon */
 /* Element `c` (0..2, per lane) of a three-entry table of the kernel arguments (plane pointers, pitches, ...): all three entries are
  * read as scalars and the lane selects — indexing the argument segment with a per-lane value is a VECTOR memory load from it, i.e. one

@@ -1,0 +1,185 @@
+/*
+ * k_export_rgb.hip — a decoded frame (or a rectangle of it) into memory of the caller as R'G'B', packed or planar, 8 or 16 bits per channel
+ * (m355_frame_export_rgb, include/de265_mi355x.h).  Integer-exact: chroma is brought to the luma positions by the one bilinear filter of the
+ * header (chroma sample location type 0), then the eight integers of m355_rgb_coefficients are applied in signed 32-bit arithmetic.
+ *
+ * ONE launch per export.  The destination is the larger side of the traffic, so units follow destination rows: a wavefront converts one
+ * 64-lane chunk of one row of the rectangle — row and chunk are decided once per wavefront, in scalar registers —, a lane the NP = 16 / SB
+ * pixels behind ONE 16-byte luma vector.  All of a lane's loads are issued before the first use: its luma vector and, per chroma plane,
+ * one 16-byte vector from each chroma row it needs (4:2:0: rows j and jn; 4:2:2 / 4:4:4: the one row), starting at the chroma sample of its
+ * first pixel.  A subsampled lane needs NP / 2 chroma samples and the one to their right: the vector holds NP, so the right neighbour comes
+ * with the same load — neither a neighbour lane nor an extra load is needed —, and where the frame's plane ends inside the vector the sample
+ * of column CW - 1 stands for it (the clamp of the definition).  No LDS, no atomics.
+ * Arithmetic: 4:2:0 sums T = 3 C[j] + C[jn] and their pairs stay below 2^19 and are kept in 32-bit registers; the offset c0 is folded into
+ * the rounding constant of the filter's shift ((T + 2 - 4 c0) >> 2 = ((T + 2) >> 2) - c0, arithmetic shift), so u and v come out signed.
+ * The matrix is five v_mad_i32_i24 per pixel (coefficients < 2^23, |u|, |v|, Y < 2^16), a shift and a clip per channel.  The luma offset and
+ * the rounding term are one constant (H - cy y0) and sums are accumulated modulo 2^32: whatever a partial sum does, the complete sum is the
+ * one the header defines, which fits a signed 32-bit register (its largest magnitude is 0.54 * 2^31).
+ * Stores are whole vectors: a lane's channels are packed into dwords with v_perm_b32 (8-bit: four values per dword, three perms) and go out
+ * as 16-byte stores (+ one of 8 bytes where the lane's bytes are 24 or 8); the last lane of a row stores its valid bytes only, as dwords and
+ * single bytes (the idiom of k_export.hip's d_export_store for any number of dwords; d_scaled_store's whole-lane sizes end at 32 bytes, a
+ * lane here has up to 96), so nothing beyond the exported row is written.
+ *
+ * No out-of-bounds read.  Every load is 16 bytes from a sample INSIDE a row of the frame's plane: luma column x0 + p0 < W of row y0 + row <
+ * H; chroma column i0 = (x0 + p0) / SubWidthC <= CW - 1 of a row clamped to 0 .. CH - 1.  Rows are padded to 128 bytes and a plane's
+ * allocation ends with a 256-byte tail (runtime_internal.h frame_alloc), so even the vector of the last sample of the last row ends inside
+ * the allocation — half the span k_export.hip argues for.  Bytes of a vector beyond column CW - 1 (padding, or the next row's start) are
+ * loaded and never used: every use is indexed through the clamp.
+ * Roofline: traffic (every luma byte read once, every chroma row once or twice, every destination byte written once) against ~40 VALU
+ * issues per pixel — profiles/export_rgb_bench.txt.
+ */
+#include "k_common.h"
+
+#ifdef SIMT_EMU
+static inline int d_mad24(int a, int b, int c) { return (int)((unsigned)a * (unsigned)b + (unsigned)c); }
+#else
+/* v_mad_i32_i24: a, b within 24 signed bits */
+__device__ __forceinline__ int d_mad24(int a, int b, int c) { return (int)((unsigned)__mul24(a, b) + (unsigned)c); }
+#endif
+
+/* sample k of a 16-byte vector */
+template <int SB> __device__ __forceinline__ int d_rgb_sample(const unsigned* w, int k)
+{
+  return SB == 1 ? (int)((w[k >> 2] >> (8 * (k & 3))) & 0xFFu) : (int)((w[k >> 1] >> (16 * (k & 1))) & 0xFFFFu);
+}
+
+/* the NP chroma samples of one plane at the lane's luma positions, minus c0.  r0 / r1: the vectors of chroma rows j / jn (4:2:0; else r0 only),
+   last = CW - 1 - i0 >= 0: the index inside the vector of the plane's last column */
+template <int SB, int CF>
+__device__ __forceinline__ void d_rgb_chroma(const unsigned* r0, const unsigned* r1, int last, int c0, int* out)
+{
+  constexpr int NP = 16 / SB, NC = NP / 2;
+  if (CF == 3) {
+#pragma unroll
+    for (int k = 0; k < NP; k++) out[k] = d_rgb_sample<SB>(r0, k) - c0;
+    return;
+  }
+  int t[NC + 1];
+#pragma unroll
+  for (int k = 0; k <= NC; k++) {
+    const int s = d_rgb_sample<SB>(r0, k);
+    t[k] = CF == 1 ? 3 * s + d_rgb_sample<SB>(r1, k) : s;
+  }
+  const int ke = CF == 1 ? 2 - 4 * c0 : -c0, ko = CF == 1 ? 4 - 8 * c0 : 1 - 2 * c0;
+#pragma unroll
+  for (int k = 0; k < NC; k++) {
+    const int tn = k < last ? t[k + 1] : t[k];                /* column min(i + 1, CW - 1) */
+    out[2 * k] = CF == 1 ? (t[k] + ke) >> 2 : t[k] + ke;
+    out[2 * k + 1] = (t[k] + tn + ko) >> (CF == 1 ? 3 : 1);
+  }
+}
+
+/* N values of one byte / one 16-bit half each -> N * DB / 4 dwords */
+template <int DB, int N> __device__ __forceinline__ void d_rgb_pack(const unsigned* e, unsigned* o)
+{
+  if (DB == 1) {
+#pragma unroll
+    for (int i = 0; i < N / 4; i++) o[i] = d_pack_lo16(d_perm(e[4 * i + 1], e[4 * i], 0x0c0c0400u), d_perm(e[4 * i + 3], e[4 * i + 2], 0x0c0c0400u));
+  } else {
+#pragma unroll
+    for (int i = 0; i < N / 2; i++) o[i] = d_pack_lo16(e[2 * i], e[2 * i + 1]);
+  }
+}
+
+/* ND dwords (nb >= 4 ND) or the first nb bytes of them to d: whole lanes store vectors, the end of a row goes out as dwords and single bytes */
+template <int ND> __device__ __forceinline__ void d_rgb_store(M355_GLOBAL uint8_t* d, const unsigned* o, uint32_t nb)
+{
+  if (nb >= 4u * ND) {
+#pragma unroll
+    for (int i = 0; i + 4 <= ND; i += 4) d_stg16(d + 4 * i, o + i);
+    if (ND % 4 == 2) d_stg8(d + 4 * (ND - 2), o + ND - 2);
+    return;
+  }
+#pragma unroll
+  for (uint32_t i = 0; i < (uint32_t)ND; i++) {
+    if (4 * i + 4 <= nb) d_stg4(d + 4 * i, o[i]);
+    else for (uint32_t k = 0; k < 3; k++) if (4 * i + k < nb) d[4 * i + k] = (uint8_t)(o[i] >> (8 * k));
+  }
+}
+
+template <int SB, int DB, int PLANAR, int CF>
+__global__ void __launch_bounds__(256) k_export_rgb(ExportRgbArgs a)
+{
+  M355_GATE(a);
+  constexpr int NP = 16 / SB, M = DB == 1 ? 255 : 65535;
+  /* this wavefront's unit: row of the rectangle, position in the row */
+  const uint32_t unit = __builtin_amdgcn_readfirstlane((uint32_t)(blockIdx.x * 4u + (threadIdx.x >> 6)));
+  if (unit >= a.units) return;
+  const uint32_t row = unit / a.chunks, chunk = unit - row * a.chunks;
+  const uint32_t p0 = (chunk * 64u + (threadIdx.x & 63u)) * NP;
+  if (p0 >= a.width) return;
+  const uint32_t n = a.width - p0 < (uint32_t)NP ? a.width - p0 : (uint32_t)NP;
+  const uint32_t X0 = a.x0 + p0, Y = a.y0 + row;
+  unsigned ry[4], rc[2][2][4];
+  d_ldg16((const M355_GLOBAL uint8_t*)a.src[0] + (size_t)Y * a.src_pitch[0] + (size_t)X0 * SB, ry);
+  int last = 0;
+  if (CF != 0) {
+    const uint32_t i0 = CF == 3 ? X0 : X0 >> 1;
+    uint32_t j = Y, jn = Y;
+    if (CF == 1) {
+      j = Y >> 1;
+      jn = (Y & 1u) ? (j + 1 < a.ch ? j + 1 : a.ch - 1) : (j ? j - 1 : 0u);
+    }
+    last = (int)(a.cw - 1u - i0);
+#pragma unroll
+    for (int c = 0; c < 2; c++) {
+      const M355_GLOBAL uint8_t* s = (const M355_GLOBAL uint8_t*)a.src[1 + c] + (size_t)i0 * SB;
+      d_ldg16(s + (size_t)j * a.src_pitch[1], rc[c][0]);
+      if (CF == 1) d_ldg16(s + (size_t)jn * a.src_pitch[1], rc[c][1]);
+    }
+  }
+  /* the constants of the launch (scalar): the rounding term and the luma offset in one */
+  const int F = a.k.F, ky = (int)((1u << (F - 1)) - (unsigned)a.k.cy * (unsigned)a.k.y0);
+  const int cy = a.k.cy, crv = a.k.crv, ncgu = -a.k.cgu, ncgv = -a.k.cgv, cbu = a.k.cbu;
+  int u[NP], v[NP];
+  if (CF != 0) {
+    d_rgb_chroma<SB, CF>(rc[0][0], rc[0][1], last, a.k.c0, u);
+    d_rgb_chroma<SB, CF>(rc[1][0], rc[1][1], last, a.k.c0, v);
+  }
+  unsigned e[3][NP];
+#pragma unroll
+  for (int k = 0; k < NP; k++) {
+    const int base = d_mad24(cy, d_rgb_sample<SB>(ry, k), ky);
+    int r = base, g = base, b = base;
+    if (CF != 0) {
+      r = d_mad24(crv, v[k], base);
+      g = d_mad24(ncgv, v[k], d_mad24(ncgu, u[k], base));
+      b = d_mad24(cbu, u[k], base);
+    }
+    e[0][k] = (unsigned)d_clip3(0, M, r >> F);
+    e[1][k] = (unsigned)d_clip3(0, M, g >> F);
+    e[2][k] = (unsigned)d_clip3(0, M, b >> F);
+  }
+  if (PLANAR) {
+    constexpr int ND = NP * DB / 4;
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+      unsigned o[ND];
+      d_rgb_pack<DB, NP>(e[c], o);
+      d_rgb_store<ND>((M355_GLOBAL uint8_t*)a.dst[c] + (size_t)row * a.dst_pitch[c] + (size_t)p0 * DB, o, n * (uint32_t)DB);
+    }
+  } else {
+    constexpr int ND = 3 * NP * DB / 4;
+    unsigned w[3 * NP], o[ND];
+#pragma unroll
+    for (int k = 0; k < NP; k++) { w[3 * k] = e[0][k]; w[3 * k + 1] = e[1][k]; w[3 * k + 2] = e[2][k]; }
+    d_rgb_pack<DB, 3 * NP>(w, o);
+    d_rgb_store<ND>((M355_GLOBAL uint8_t*)a.dst[0] + (size_t)row * a.dst_pitch[0] + (size_t)p0 * (3 * DB), o, n * (uint32_t)(3 * DB));
+  }
+}
+
+void m355_launch_export_rgb(const ExportRgbArgs& a, int src_bytes, int dst_bytes, bool planar, int chroma_format, hipStream_t st)
+{
+  if (!a.units) return;
+  const dim3 grid((a.units + 3) / 4), block(256);
+#define M355_EXPORT_RGB_CF(SB, DB, PL, CF) \
+  if (chroma_format == CF) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_export_rgb<SB, DB, PL, CF>), grid, block, 0, st, a);
+#define M355_EXPORT_RGB_CASE(SB, DB) \
+  if (src_bytes == SB && dst_bytes == DB) { \
+    if (planar) { M355_EXPORT_RGB_CF(SB, DB, 1, 0) M355_EXPORT_RGB_CF(SB, DB, 1, 1) M355_EXPORT_RGB_CF(SB, DB, 1, 2) M355_EXPORT_RGB_CF(SB, DB, 1, 3) } \
+    else { M355_EXPORT_RGB_CF(SB, DB, 0, 0) M355_EXPORT_RGB_CF(SB, DB, 0, 1) M355_EXPORT_RGB_CF(SB, DB, 0, 2) M355_EXPORT_RGB_CF(SB, DB, 0, 3) } \
+  }
+  M355_EXPORT_RGB_CASE(1, 1) M355_EXPORT_RGB_CASE(1, 2) M355_EXPORT_RGB_CASE(2, 1) M355_EXPORT_RGB_CASE(2, 2)
+#undef M355_EXPORT_RGB_CASE
+#undef M355_EXPORT_RGB_CF
+}

@@ -554,6 +554,69 @@ int m355_frame_export_scaled(m355_ctx* c, int h, const m355_export_desc* e, int 
   HIPCHK(hipGetLastError());
   return reader_end(c, P.f, RD_EXPORT, cs);
 }
+/* The integers of the R'G'B' conversion (de265_mi355x.h states the formulas): 64-bit integer arithmetic only, so every build makes the same ones */
+int m355_rgb_coefficients(int matrix, int full_range, int bdl, int bdc, int samples, m355_rgb_coeffs* out)
+{
+  static const int64_t K[3][2] = {{2990, 1140}, {2126, 722}, {2627, 593}};
+  if (!out) return fail(M355_ERR_INVALID, "m355_rgb_coefficients: null result");
+  if (matrix < 0 || matrix > 2 || (full_range != 0 && full_range != 1) || (samples != M355_RGB_U8 && samples != M355_RGB_U16))
+    return fail(M355_ERR_INVALID, "m355_rgb_coefficients: unknown matrix %d / full_range %d / samples %d", matrix, full_range, samples);
+  if (bdl < 8 || bdl > 16 || bdc < 8 || bdc > 16) return fail(M355_ERR_INVALID, "m355_rgb_coefficients: bit depths %d / %d are not 8..16", bdl, bdc);
+  const auto rdiv = [](int64_t a, int64_t b) { return (2 * a + b) / (2 * b); };
+  const int D = samples == M355_RGB_U8 ? 8 : 16, F = 29 - D;
+  const int64_t kr = K[matrix][0], kb = K[matrix][1], kg = 10000 - kr - kb, mf = (((int64_t)1 << D) - 1) << F;
+  const int64_t ys = full_range ? ((int64_t)1 << bdl) - 1 : (int64_t)219 << (bdl - 8), cs = full_range ? ((int64_t)1 << bdc) - 1 : (int64_t)224 << (bdc - 8);
+  out->F = F;
+  out->y0 = full_range ? 0 : 16 << (bdl - 8);
+  out->c0 = 1 << (bdc - 1);
+  out->cy = (int32_t)rdiv(mf, ys);
+  out->crv = (int32_t)rdiv(2 * (10000 - kr) * mf, 10000 * cs);
+  out->cbu = (int32_t)rdiv(2 * (10000 - kb) * mf, 10000 * cs);
+  out->cgu = (int32_t)rdiv(2 * kb * (10000 - kb) * mf, 10000 * kg * cs);
+  out->cgv = (int32_t)rdiv(2 * kr * (10000 - kr) * mf, 10000 * kg * cs);
+  return M355_OK;
+}
+/* The frame, or a rectangle of it, as R'G'B' (k_export_rgb.hip): the frame handle and the rectangle are checked by export_plan — as a planar NATIVE
+ * export whose destinations cannot fail —, the destinations here.  A reader of the kind RD_EXPORT, like the two above. */
+int m355_frame_export_rgb(m355_ctx* c, int h, const m355_rgb_desc* e)
+{
+  m355_export_desc yuv = {};
+  if (e) {
+    yuv.layout = M355_EXPORT_PLANAR; yuv.samples = M355_EXPORT_NATIVE;
+    yuv.x0 = e->x0; yuv.y0 = e->y0; yuv.width = e->width; yuv.height = e->height;
+    for (int p = 0; p < 3; p++) { yuv.dst[p] = e->dst[0]; yuv.pitch[p] = INT64_MAX; }
+  }
+  ExportPlan P;
+  int rc = export_plan(c, h, e ? &yuv : nullptr, 0, "m355_frame_export_rgb", P);
+  if (rc) return rc;
+  Frame* f = P.f;
+  if (e->layout != M355_RGB_PACKED && e->layout != M355_RGB_PLANAR) return fail(M355_ERR_INVALID, "m355_frame_export_rgb: unknown layout %d", e->layout);
+  ExportRgbArgs a = {};
+  rc = m355_rgb_coefficients(e->matrix, e->full_range, f->bdl, f->bdc, e->samples, &a.k);
+  if (rc) return rc;
+  const bool planar = e->layout == M355_RGB_PLANAR;
+  const int db = e->samples == M355_RGB_U16 ? 2 : 1, sb = f->bpp[0];
+  const int64_t w = P.p[0].pw, row_bytes = w * db * (planar ? 1 : 3);
+  for (int p = 0; p < (planar ? 3 : 1); p++) {
+    if (!e->dst[p]) return fail(M355_ERR_INVALID, "m355_frame_export_rgb: no destination for plane %d", p);
+    if (e->pitch[p] < row_bytes) return fail(M355_ERR_INVALID, "m355_frame_export_rgb: pitch %lld of plane %d is below its row of %lld bytes", (long long)e->pitch[p], p, (long long)row_bytes);
+    if (db == 2 && (((uintptr_t)e->dst[p] | (uint64_t)e->pitch[p]) & 1)) return fail(M355_ERR_INVALID, "m355_frame_export_rgb: 16-bit plane %d at an odd address or pitch", p);
+    a.dst[p] = (uint8_t*)e->dst[p]; a.dst_pitch[p] = e->pitch[p];
+  }
+  for (int p = 0; p < 3; p++) a.src[p] = (const uint8_t*)f->plane[p];
+  a.src_pitch[0] = (long long)f->stride[0] * sb; a.src_pitch[1] = (long long)f->stride[1] * sb;
+  a.x0 = e->width ? (uint32_t)e->x0 : 0u; a.y0 = e->width ? (uint32_t)e->y0 : 0u;
+  a.width = (uint32_t)w; a.height = (uint32_t)P.p[0].ph;
+  a.cw = (uint32_t)f->pw[1]; a.ch = (uint32_t)f->ph[1];
+  const uint32_t per_chunk = 64u * 16u / (uint32_t)sb;
+  a.chunks = (a.width + per_chunk - 1) / per_chunk;
+  a.units = a.chunks * a.height;
+  hipSetDevice(c->device);
+  const hipStream_t cs = reader_begin(c, f, RD_EXPORT, &a.timeout, &a.epoch);
+  m355_launch_export_rgb(a, sb, db, planar, f->cf, cs);
+  HIPCHK(hipGetLastError());
+  return reader_end(c, f, RD_EXPORT, cs);
+}
 /* the host waits until this frame's last export has landed */
 int m355_frame_export_wait(m355_ctx* c, int h)
 {

@@ -9,6 +9,8 @@
   (e), (f) what separates (c) from (b): MSB16 semi-planar uncropped, NATIVE planar cropped
   (g), (h), (i) m355_frame_export_scaled NATIVE planar, whole frame, downscaled 2x, 4x, 8x
   (j) U8 semi-planar downscaled 4x: the 8K to 1080p NV12 proxy
+  (k), (l) m355_frame_export_rgb, whole frame, BT.709 limited range: U8 packed and U16 planar.  (k) reads the frame's 99.5 MB and writes
+      7680 * 4320 * 3 = 99.5 MB — exactly the bytes of (b), which is therefore its traffic floor; the result line has (k) / (b)
 
 and, beside them, m355_measure_copy_rate for the frame's byte count.  Every figure is the median of --iters launches; (b) is measured in
 --rounds separate rounds spread over the run, and the spread of their medians is the margin (c), (d) and (g)-(j) are held against: a scaled export reads exactly (b)'s source bytes and writes at most a
@@ -99,6 +101,14 @@ def main():
             return lambda: lib.check(lib.lib.m355_frame_export_scaled(ctx.h, frame, ctypes.byref(d), log2_scale))
         return lambda: lib.check(lib.lib.m355_frame_export(ctx.h, frame, ctypes.byref(d)))
 
+    rgb_dst = [ctx.device_alloc(n, fill=None) for n in (W * 3 * H, W * 2 * H, W * 2 * H)]
+
+    def export_rgb(layout, samples, elem):
+        d = capi.RgbDesc(layout=layout, samples=samples, matrix=capi.MATRIX_BT709, full_range=0)
+        for k in range(3):
+            d.dst[k] = rgb_dst[k]; d.pitch[k] = W * elem * (1 if layout == capi.RGB_PLANAR else 3)
+        return lambda: lib.check(lib.lib.m355_frame_export_rgb(ctx.h, frame, ctypes.byref(d)))
+
     variants = {
         "a_memcpy2d_x3": copies,
         "b_native_planar": export(capi.EXPORT_PLANAR, capi.EXPORT_NATIVE, None, 2),
@@ -111,6 +121,8 @@ def main():
         "h_native_planar_4x": export(capi.EXPORT_PLANAR, capi.EXPORT_NATIVE, None, 2, 2),
         "i_native_planar_8x": export(capi.EXPORT_PLANAR, capi.EXPORT_NATIVE, None, 2, 3),
         "j_u8_semiplanar_4x": export(capi.EXPORT_SEMIPLANAR, capi.EXPORT_U8, None, 1, 2),
+        "k_rgb_u8_packed": export_rgb(capi.RGB_PACKED, capi.RGB_U8, 1),
+        "l_rgb_u16_planar": export_rgb(capi.RGB_PLANAR, capi.RGB_U16, 2),
     }
     scaled = [n for n in variants if n[0] in "ghij"]
     ms = {n: [] for n in variants}
@@ -127,6 +139,8 @@ def main():
         "ms_median": res, "ms_rounds": ms, "b_spread_ms": spread,
         "GBps_read_plus_written": {"a_memcpy2d_x3": 2 * frame_bytes / res["a_memcpy2d_x3"] / 1e6, "b_native_planar": 2 * frame_bytes / res["b_native_planar"] / 1e6},
         "scaled_GBps_source_read": {n: frame_bytes / res[n] / 1e6 for n in scaled},
+        "rgb": {"k_over_b": res["k_rgb_u8_packed"] / res["b_native_planar"], "l_over_b": res["l_rgb_u16_planar"] / res["b_native_planar"],
+                "k_bytes_read_plus_written": frame_bytes + W * H * 3, "l_bytes_read_plus_written": frame_bytes + W * H * 6},
         "copy_rate_GBps_same_bytes": ctx.measure_copy_rate(frame_bytes, 9),
         "bars": {"b_le_a": res["b_native_planar"] <= res["a_memcpy2d_x3"],
                  "c_le_b_plus_spread": res["c_msb16_semiplanar_crop8"] <= res["b_native_planar"] + spread,
@@ -138,7 +152,7 @@ def main():
     if args.out:
         with open(args.out, "a") as f:
             f.write(line + "\n")
-    for p in src + dst:
+    for p in src + dst + rgb_dst:
         ctx.device_free(p)
     ctx.close()
 
