@@ -86,7 +86,7 @@ namespace {
   X(m355_last_error) X(m355_device_count) X(m355_create) X(m355_destroy) X(m355_frame_create) X(m355_frame_destroy) \
   X(m355_frame_upload) X(m355_frame_download) X(m355_submit_picture) X(m355_wait) X(m355_set_pipeline_depth) \
   X(m355_host_alloc) X(m355_host_free) X(m355_frame_hash) X(m355_arena_begin) X(m355_last_serial) X(m355_decode_status) \
-  X(m355_frame_download_async) X(m355_frame_download_wait) X(m355_frame_export) X(m355_frame_export_scaled) X(m355_frame_export_rgb) X(m355_frame_export_order) \
+  X(m355_frame_download_async) X(m355_frame_download_wait) X(m355_frame_export) X(m355_frame_export_scaled) X(m355_frame_export_rgb) X(m355_frame_export_resized) X(m355_frame_export_order) \
   X(m355_group_create) X(m355_group_destroy) X(m355_group_decode) X(m355_picture_upload) X(m355_picture_replace) X(m355_shard_owner_of_tile) \
   X(m355_picture_arena_begin) X(m355_frame_hash_async) X(m355_frame_hash_result) X(m355_frame_measure_async) X(m355_frame_measure_result)
 
@@ -1776,6 +1776,33 @@ LIBDE265_API int m355_glue_export_image_rgb(const struct de265_image* img, int l
   d.x0 = r[0]; d.y0 = r[1]; d.width = r[2]; d.height = r[3];
   for (int c = 0; c < 3; c++) { d.dst[c] = dst[c]; d.pitch[c] = pitch[c]; }
   int rc = A->m355_frame_export_rgb(g->mctx, frame, &d);
+  if (rc == M355_OK) rc = A->m355_frame_export_order(g->mctx, frame, consumer_stream);
+  if (rc != M355_OK) g->error = A->m355_last_error();
+  return rc;
+}
+/* The picture RESIZED on the device to out_size = {out_width, out_height} luma samples (m355_frame_export_resized: one separable triangle filter,
+ * antialiased when downscaling, integer-exact; layout / samples = M355_EXPORT_*), with the waiting behaviour of m355_glue_export_image: the only wait
+ * is for the worker to have enqueued the picture.  rect = the SOURCE rectangle, NULL: the image's conformance window. */
+LIBDE265_API int m355_glue_export_image_resized(const struct de265_image* img, int layout, int samples, const int rect[4], const int out_size[2],
+                                                void* const dst[3], const int64_t pitch[3], void* consumer_stream)
+{
+  Api* A = api();
+  if (!A) return M355_ERR_NO_DEVICE;
+  if (!img || !img->decctx || !out_size || !dst || !pitch) return M355_ERR_INVALID;
+  Glue* g = glue_of(img->decctx);
+  if (!g || g->n_ranks > 1) return M355_ERR_INVALID;
+  wait_submitted(g, img->get_ID());
+  std::lock_guard<std::mutex> api_lock(g->api_mu);
+  int r[4];
+  const int frame = frame_and_rect(g, img, rect, r);
+  if (frame < 0) return M355_ERR_INVALID;
+  m355_resize_desc d;
+  memset(&d, 0, sizeof(d));
+  d.layout = layout; d.samples = samples;
+  d.x0 = r[0]; d.y0 = r[1]; d.width = r[2]; d.height = r[3];
+  d.out_width = out_size[0]; d.out_height = out_size[1];
+  for (int c = 0; c < 3; c++) { d.dst[c] = dst[c]; d.pitch[c] = pitch[c]; }
+  int rc = A->m355_frame_export_resized(g->mctx, frame, &d);
   if (rc == M355_OK) rc = A->m355_frame_export_order(g->mctx, frame, consumer_stream);
   if (rc != M355_OK) g->error = A->m355_last_error();
   return rc;

@@ -510,6 +510,50 @@ typedef struct m355_rgb_desc {
 M355_API int   m355_frame_export_rgb(m355_ctx* ctx, int frame, const m355_rgb_desc* desc);      /* asynchronous */
 typedef struct m355_rgb_coeffs { int32_t F, y0, c0, cy, crv, cgu, cgv, cbu; } m355_rgb_coeffs;
 M355_API int   m355_rgb_coefficients(int matrix, int full_range, int bit_depth_luma, int bit_depth_chroma, int samples, m355_rgb_coeffs* out);
+/* The frame's rectangle RESIZED to out_width x out_height luma samples (k_export_resized.hip): every plane is resampled on its own grid — chroma to
+ * out_width / SubWidthC x out_height / SubHeightC — and goes to the caller's memory in the layouts and sample formats of m355_frame_export.  ONE
+ * filter: a separable triangle, widened by the downscale ratio — an antialiased bilinear filter when downscaling, plain bilinear when upscaling.
+ * Integer arithmetic only: what lands is a closed-form function of the samples m355_frame_download returns, the same on every build.
+ * One axis of one plane maps sn source samples (the rectangle's, on that plane's grid) to dn output samples.  With 64-bit integers and
+ * rdiv(a, b) = (2a + b) / (2b), for output index i:
+ *   M = 2 max(sn, dn);   C = (2i + 1) sn - dn on a centre-aligned grid, C = 2 i sn on a co-sited grid
+ *   for every integer k with |2 dn k - C| < M (at most 16 inside the ratio limit):  n_k = M - |2 dn k - C|
+ *   N = sum n_k,  P_k = the prefix sum of n over increasing k (0 before the first),  q_k = rdiv(P_k << 14, N) - rdiv(P_(k-1) << 14, N)
+ * so that every q_k >= 0 and the q_k sum to exactly 1 << 14.  k is then clamped to [0, sn - 1] — the RECTANGLE, not the frame: a rectangle's resize
+ * equals the resize of a frame that holds only that rectangle — and coefficients that land on the same index are added.  m355_resize_taps returns this
+ * folded row, which is contiguous (libde265_amd/csrc/resize_taps.h: the one definition, which the kernel calls too).
+ * Grids: luma and every vertical axis are centre-aligned; the horizontal chroma axis of 4:2:0 and 4:2:2 is co-sited (chroma sample location type 0,
+ * the siting m355_frame_export_rgb assumes), so resized chroma stays where type 0 puts it.  No other siting is offered.
+ * Per plane, bd its bit depth, S the rectangle's samples, qy_j / qx_i the rows of the vertical / horizontal axis: the VERTICAL pass first, ONE
+ * rounding to an 18-bit intermediate, then the horizontal pass, everything unsigned:
+ *   u(x, j) = sum_k qy_j[k] S[k][x]                      < 2^(bd + 14)
+ *   t(x, j) = (u + (1 << (bd - 5))) >> (bd - 4)          < 2^18
+ *   v(i, j) = sum_k qx_i[k] t(k, j)                      < 2^32
+ *   NATIVE  a = (v + (1 << (31 - bd))) >> (32 - bd)      (the sum still fits 32 bits)
+ *   MSB16   (uint16)(a << (16 - bd))
+ *   U8      min(255, (v + (1 << 23)) >> 24)              — ONE rounding from v, not a rounding of a; the sum needs 33 bits,
+ *                                                          ((v >> 1) + (1 << 22)) >> 23 is the same value in 32
+ * A constant plane stays constant; out_width == width && out_height == height delivers what m355_frame_export delivers, byte for byte.
+ * M355_ERR_INVALID (nothing is enqueued, no destination byte written): whatever m355_frame_export rejects for the frame handle, the rectangle, the
+ * layout and the samples; out_width not positive or no multiple of SubWidthC, out_height not positive or no multiple of SubHeightC (monochrome: 1
+ * and 1); a ratio outside src <= 8 * out && out <= 8 * src on either axis (at most 8x down or 8x up: it bounds a row at 16 coefficients); a null dst
+ * for a plane that exists; a pitch below the OUTPUT row's bytes.  A monochrome frame exports luma only; bytes beyond an output row are never written.
+ * Ordering, the gate and sharded contexts are those of m355_frame_export: asynchronous, a reader of the frame of the same kind — m355_frame_export_wait
+ * and m355_frame_export_order cover it, the next decode into the frame waits for it —, and nothing is written behind a rejected decode.
+ * Not offered: RGB at the resized size, filters with negative lobes (bicubic, Lanczos: signed sums and clipping), ratios beyond 8, another chroma
+ * siting, resizing into a frame of the decoder. */
+#define M355_RESIZE_MAX_TAPS 16
+typedef struct m355_resize_desc {
+  int32_t layout, samples;          /* M355_EXPORT_PLANAR / _SEMIPLANAR, M355_EXPORT_NATIVE / _MSB16 / _U8 */
+  int32_t x0, y0, width, height;    /* source luma rectangle, exactly as in m355_export_desc (width == 0: whole frame) */
+  int32_t out_width, out_height;    /* luma size of the result */
+  void*   dst[3];
+  int64_t pitch[3];                 /* bytes per destination row, >= the OUTPUT row's bytes */
+} m355_resize_desc;
+M355_API int   m355_frame_export_resized(m355_ctx* ctx, int frame, const m355_resize_desc* desc);   /* asynchronous */
+/* row i of one axis' filter: returns the number of coefficients (1..16), *first = source index of coeff[0]; < 0 on bad arguments (a size below 1,
+ * a ratio outside the limit, i outside [0, dst_n), cosited not 0 or 1, a null pointer) */
+M355_API int   m355_resize_taps(int src_n, int dst_n, int cosited, int i, int32_t* first, int32_t coeff[M355_RESIZE_MAX_TAPS]);
 M355_API int   m355_frame_export_wait(m355_ctx* ctx, int frame);
 M355_API int   m355_frame_export_order(m355_ctx* ctx, int frame, void* consumer_hipStream);
 /* Device memory for export destinations and blocking copies out of / into it, for applications (and the tests) that keep a second HIP

@@ -49,6 +49,17 @@ class ExportDesc(ctypes.Structure):
                 ("dst", ctypes.c_void_p * 3), ("pitch", ctypes.c_int64 * 3)]
 
 
+RESIZE_MAX_TAPS = 16
+
+
+class ResizeDesc(ctypes.Structure):
+    """m355_resize_desc (include/de265_mi355x.h)"""
+    _fields_ = [("layout", ctypes.c_int32), ("samples", ctypes.c_int32),
+                ("x0", ctypes.c_int32), ("y0", ctypes.c_int32), ("width", ctypes.c_int32), ("height", ctypes.c_int32),
+                ("out_width", ctypes.c_int32), ("out_height", ctypes.c_int32),
+                ("dst", ctypes.c_void_p * 3), ("pitch", ctypes.c_int64 * 3)]
+
+
 RGB_PACKED, RGB_PLANAR = 0, 1
 RGB_U8, RGB_U16 = 0, 1
 MATRIX_BT601, MATRIX_BT709, MATRIX_BT2020 = 0, 1, 2
@@ -131,6 +142,9 @@ class Library:
         if hasattr(L, "m355_frame_export_rgb"):         # (absent from older builds loaded through M355_LIB for an A/B)
             L.m355_frame_export_rgb.argtypes = [vp, i, ctypes.POINTER(RgbDesc)]
             L.m355_rgb_coefficients.argtypes = [i, i, i, i, i, ctypes.POINTER(RgbCoeffs)]
+        if hasattr(L, "m355_frame_export_resized"):     # (absent from older builds loaded through M355_LIB for an A/B)
+            L.m355_frame_export_resized.argtypes = [vp, i, ctypes.POINTER(ResizeDesc)]
+            L.m355_resize_taps.argtypes = [i, i, i, i, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]
         L.m355_host_alloc.argtypes = [ctypes.c_size_t]
         L.m355_host_alloc.restype = vp
         L.m355_host_free.argtypes = [vp]
@@ -199,6 +213,12 @@ class Library:
         k = RgbCoeffs()
         self.check(self.lib.m355_rgb_coefficients(matrix, full_range, bit_depth_luma, bit_depth_chroma, samples, ctypes.byref(k)))
         return {n: int(getattr(k, n)) for n, _ in RgbCoeffs._fields_}
+
+    def resize_taps(self, src_n, dst_n, cosited, i):
+        """row i of one axis of the resize filter (m355_resize_taps; host only) -> (first source index, [coefficients]), or None for arguments it rejects"""
+        first, coeff = ctypes.c_int32(), (ctypes.c_int32 * RESIZE_MAX_TAPS)()
+        n = self.lib.m355_resize_taps(src_n, dst_n, cosited, i, ctypes.byref(first), coeff)
+        return None if n < 0 else (int(first.value), [int(coeff[k]) for k in range(n)])
 
     def pack_narrow(self, pic):
         """m355_pack_narrow on a picture's residual records and coefficient list (host only; worklist.pack_narrow is the numpy
@@ -392,6 +412,38 @@ class Context:
                 self.L.check(self.L.lib.m355_frame_export_scaled(self.h, f, ctypes.byref(desc), log2_scale))
             else:
                 self.L.check(self.L.lib.m355_frame_export(self.h, f, ctypes.byref(desc)))
+        except Exception:
+            for p in bufs:
+                self.L.lib.m355_host_free(p) if host else self.device_free(p)
+            raise
+        return (f, shapes, bufs, [int(desc.pitch[k]) for k in range(len(shapes))], host)
+
+    def resize_taps(self, src_n, dst_n, cosited, i):
+        """row i of one axis of the resize filter (m355_resize_taps) -> (first source index, [coefficients]), or None for arguments it rejects"""
+        return self.L.resize_taps(src_n, dst_n, cosited, i)
+
+    def frame_export_resized(self, f, layout, samples, out_size, rect=None, host=False, pad=20):
+        """start m355_frame_export_resized of frame f to out_size = (out_width, out_height) luma samples (rect = the source rectangle (x0, y0, width,
+        height) in luma samples, None: the whole frame) into buffers of its own, made as frame_export makes them: every byte holds DEVICE_FILL
+        beforehand, the pitch is `pad` bytes larger than the row.  -> token for frame_export_finish"""
+        shapes = self.export_shapes(f, layout, samples, (0, 0, out_size[0], out_size[1]))
+        desc = ResizeDesc(layout=layout, samples=samples, out_width=out_size[0], out_height=out_size[1])
+        if rect is not None:
+            desc.x0, desc.y0, desc.width, desc.height = rect
+        bufs = []
+        try:
+            for k, (rows, n, dt) in enumerate(shapes):
+                pitch = n * dt.itemsize + pad
+                if host:
+                    p = self.L.lib.m355_host_alloc(rows * pitch)
+                    if not p:
+                        raise M355Error(4, self.L.error())
+                    ctypes.memset(p, DEVICE_FILL, rows * pitch)
+                else:
+                    p = self.device_alloc(rows * pitch)
+                bufs.append(p)
+                desc.dst[k] = p; desc.pitch[k] = pitch
+            self.L.check(self.L.lib.m355_frame_export_resized(self.h, f, ctypes.byref(desc)))
         except Exception:
             for p in bufs:
                 self.L.lib.m355_host_free(p) if host else self.device_free(p)

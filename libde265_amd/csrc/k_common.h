@@ -312,6 +312,27 @@ struct ExportRgbArgs {
 /* src_bytes / dst_bytes: 1 or 2 per sample / channel; chroma_format: 0..3 */
 void m355_launch_export_rgb(const ExportRgbArgs& a, int src_bytes, int dst_bytes, bool planar, int chroma_format, hipStream_t st);
 
+/* one m355_frame_export_resized (k_export_resized.hip), planes as in ExportArgs (semi-planar: plane 1 = Cb and Cr, read from src[1] and src[2] and
+   stored interleaved).  Plane k maps the rectangle's sn_x[k] x sn_y[k] source samples to dn_x[k] x dn_y[k] output samples; cosited[k]: the
+   horizontal axis is co-sited (4:2:0 / 4:2:2 chroma), every other axis centre-aligned.  A workgroup resizes a tile of tile_w[k] <= M355_RESIZE_TILE_W
+   output columns x M355_RESIZE_TILE_H output rows: tiles_x[k] = tiles per row of tiles, unit_end[k] = the tiles of planes 0..k.  tshift[k] = bit depth - 4
+   (the rounding to the 18-bit intermediate), an output sample is min(clip, ((v >> 1) + (1 << (oshift - 1))) >> oshift) << lshift with
+   oshift[k] = 31 - bit depth (U8: 23, clip = 255), lshift[k] = 16 - bit depth for MSB16, else 0.  timeout / epoch: the gate (M355_GATE). */
+#define M355_RESIZE_TILE_W 256
+#define M355_RESIZE_TILE_H 16
+struct ExportResizedArgs {
+  const uint8_t* src[3];
+  uint8_t* dst[3];
+  long long src_pitch[3], dst_pitch[3];
+  uint32_t sn_x[3], sn_y[3], dn_x[3], dn_y[3], cosited[3];
+  uint32_t tile_w[3], tiles_x[3], unit_end[3];
+  int32_t tshift[3], oshift[3], lshift[3];
+  const uint32_t* timeout;
+  uint32_t epoch;
+};
+/* src_bytes / dst_bytes: 1 or 2 per sample */
+void m355_launch_export_resized(const ExportResizedArgs& a, int src_bytes, int dst_bytes, bool semiplanar, hipStream_t st);
+
 /* first statement of every kernel of a decode: a picture whose lists k_validate rejected is never acted upon */
 /* Element `c` (0..2, per lane) of a three-entry table of the kernel arguments (plane pointers, pitches, ...): all three entries are
  * read as scalars and the lane selects — indexing the argument segment with a per-lane value is a VECTOR memory load from it, i.e. one

@@ -10,6 +10,7 @@
  * is unavailable every entry point fails with M355_ERR_NO_DEVICE.
  */
 #include "runtime_internal.h"
+#include "resize_taps.h"
 
 thread_local std::string g_err;
 int fail(int code, const char* fmt, ...)
@@ -614,6 +615,74 @@ int m355_frame_export_rgb(m355_ctx* c, int h, const m355_rgb_desc* e)
   hipSetDevice(c->device);
   const hipStream_t cs = reader_begin(c, f, RD_EXPORT, &a.timeout, &a.epoch);
   m355_launch_export_rgb(a, sb, db, planar, f->cf, cs);
+  HIPCHK(hipGetLastError());
+  return reader_end(c, f, RD_EXPORT, cs);
+}
+/* row i of one axis of the resize filter (resize_taps.h: the function k_export_resized.hip derives its rows with) */
+int m355_resize_taps(int src_n, int dst_n, int cosited, int i, int32_t* first, int32_t coeff[M355_RESIZE_MAX_TAPS])
+{
+  if (!first || !coeff || (cosited != 0 && cosited != 1) || !m355_resize_ratio_ok(src_n, dst_n) || i < 0 || i >= dst_n) return -1;
+  return m355_resize_row(src_n, dst_n, cosited, i, first, coeff, 1);
+}
+/* The width of k_export_resized's tiles on one plane: 256 output columns, or a few less where that saves a wavefront — the lanes of the vertical pass
+ * own the 16-byte vectors of the tile's source span, and a span of 64 k + a few vectors (256 columns at ratio 4: 129) would run a wavefront for them. */
+static uint32_t resize_tile_w(int64_t sn, int64_t dn, int sb)
+{
+  const int64_t S = 16 / sb, T = m355_resize_max_taps(sn, dn);
+  const auto vectors = [&](int64_t w) { return ((w - 1) * sn / dn + 2 + T + S - 1) / S; };   /* (an upper bound of the span of w columns) */
+  int64_t w = M355_RESIZE_TILE_W;
+  const int64_t nv = vectors(w), k = nv / 64;
+  if (k >= 1 && nv % 64 != 0 && nv % 64 <= 16) while (w > 1 && vectors(w) > 64 * k) w--;
+  return (uint32_t)w;
+}
+/* The frame, or a rectangle of it, resized to out_width x out_height luma samples (k_export_resized.hip): the frame handle, the rectangle, the layout and
+ * the samples are checked by export_plan — with destinations that cannot fail, as for the R'G'B' export —, the output size, the ratio and the destinations
+ * here.  A reader of the kind RD_EXPORT, like the three above. */
+int m355_frame_export_resized(m355_ctx* c, int h, const m355_resize_desc* e)
+{
+  const char* who = "m355_frame_export_resized";
+  m355_export_desc yuv = {};
+  if (e) {
+    yuv.layout = e->layout; yuv.samples = e->samples;
+    yuv.x0 = e->x0; yuv.y0 = e->y0; yuv.width = e->width; yuv.height = e->height;
+    for (int p = 0; p < 3; p++) { yuv.dst[p] = (void*)e; yuv.pitch[p] = INT64_MAX; }
+  }
+  ExportPlan P;
+  int rc = export_plan(c, h, e ? &yuv : nullptr, 0, who, P);
+  if (rc) return rc;
+  Frame* f = P.f;
+  const int sw = (f->cf == 1 || f->cf == 2) ? 2 : 1, sh = f->cf == 1 ? 2 : 1;
+  if (e->out_width <= 0 || e->out_height <= 0 || e->out_width % sw || e->out_height % sh)
+    return fail(M355_ERR_INVALID, "%s: output size %dx%d is not positive or no multiple of %dx%d luma samples", who, e->out_width, e->out_height, sw, sh);
+  if (!m355_resize_ratio_ok(P.p[0].pw, e->out_width) || !m355_resize_ratio_ok(P.p[0].ph, e->out_height))
+    return fail(M355_ERR_INVALID, "%s: %dx%d to %dx%d is more than 8x down or up", who, P.p[0].pw, P.p[0].ph, e->out_width, e->out_height);
+  ExportResizedArgs a = {};
+  uint32_t units = 0;
+  for (int p = 0; p < 3; p++) {
+    if (p < P.np) {
+      const ExportPlane& q = P.p[p];
+      const int ow = p ? e->out_width / sw : e->out_width, oh = p ? e->out_height / sh : e->out_height;
+      const int64_t row_bytes = (int64_t)ow * q.db * (P.semi && p ? 2 : 1);
+      if (!e->dst[p]) return fail(M355_ERR_INVALID, "%s: no destination for plane %d", who, p);
+      if (e->pitch[p] < row_bytes) return fail(M355_ERR_INVALID, "%s: pitch %lld of plane %d is below its row of %lld bytes", who, (long long)e->pitch[p], p, (long long)row_bytes);
+      a.src[p] = q.src[0];
+      if (P.semi && p) a.src[2] = q.src[1];
+      a.dst[p] = (uint8_t*)e->dst[p]; a.dst_pitch[p] = e->pitch[p];
+      a.src_pitch[p] = q.src_pitch;
+      a.sn_x[p] = (uint32_t)q.pw; a.sn_y[p] = (uint32_t)q.ph; a.dn_x[p] = (uint32_t)ow; a.dn_y[p] = (uint32_t)oh;
+      a.cosited[p] = p && sw == 2;
+      a.tile_w[p] = resize_tile_w(q.pw, ow, q.sb);
+      a.tiles_x[p] = ((uint32_t)ow + a.tile_w[p] - 1) / a.tile_w[p];
+      a.tshift[p] = q.bd - 4;
+      a.oshift[p] = e->samples == M355_EXPORT_U8 ? 23 : 31 - q.bd;
+      a.lshift[p] = e->samples == M355_EXPORT_MSB16 ? 16 - q.bd : 0;
+      units += a.tiles_x[p] * (((uint32_t)oh + M355_RESIZE_TILE_H - 1) / M355_RESIZE_TILE_H);
+    }
+    a.unit_end[p] = units;
+  }
+  hipSetDevice(c->device);
+  const hipStream_t cs = reader_begin(c, f, RD_EXPORT, &a.timeout, &a.epoch);
+  m355_launch_export_resized(a, f->bpp[0], P.p[0].db, P.semi, cs);
   HIPCHK(hipGetLastError());
   return reader_end(c, f, RD_EXPORT, cs);
 }

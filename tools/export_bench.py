@@ -11,9 +11,12 @@
   (j) U8 semi-planar downscaled 4x: the 8K to 1080p NV12 proxy
   (k), (l) m355_frame_export_rgb, whole frame, BT.709 limited range: U8 packed and U16 planar.  (k) reads the frame's 99.5 MB and writes
       7680 * 4320 * 3 = 99.5 MB — exactly the bytes of (b), which is therefore its traffic floor; the result line has (k) / (b)
+  (m), (n) m355_frame_export_resized to 1920x1080, NATIVE planar and U8 semi-planar: the output sizes of (h) and (j); the result line has (m) / (h)
+      and (n) / (j), the cost of the triangle over the box at the same traffic
+  (o), (p) m355_frame_export_resized NATIVE planar to 2560x1440 (ratio 3) and to 1280x720 (ratio 6)
 
 and, beside them, m355_measure_copy_rate for the frame's byte count.  Every figure is the median of --iters launches; (b) is measured in
---rounds separate rounds spread over the run, and the spread of their medians is the margin (c), (d) and (g)-(j) are held against: a scaled export reads exactly (b)'s source bytes and writes at most a
+--rounds separate rounds spread over the run, and the spread of their medians is the margin (c), (d), (g)-(j) and (m)-(p) are held against: a scaled or resized export reads exactly (b)'s source bytes and writes at most a
 quarter of (b)'s destination bytes, so it should not be slower than (b).  Beside each scaled row: its source bytes / time.  The HIP calls
 of (a) and the events go to the runtime the library itself has loaded (no second runtime in the process).
 
@@ -101,6 +104,14 @@ def main():
             return lambda: lib.check(lib.lib.m355_frame_export_scaled(ctx.h, frame, ctypes.byref(d), log2_scale))
         return lambda: lib.check(lib.lib.m355_frame_export(ctx.h, frame, ctypes.byref(d)))
 
+    def export_resized(layout, samples, out_size, elem):
+        d = capi.ResizeDesc(layout=layout, samples=samples, out_width=out_size[0], out_height=out_size[1])
+        w = out_size[0]
+        rows = [w * elem, w * elem if layout else w // 2 * elem, w // 2 * elem]
+        for k in range(3):
+            d.dst[k] = dst[k]; d.pitch[k] = rows[k]
+        return lambda: lib.check(lib.lib.m355_frame_export_resized(ctx.h, frame, ctypes.byref(d)))
+
     rgb_dst = [ctx.device_alloc(n, fill=None) for n in (W * 3 * H, W * 2 * H, W * 2 * H)]
 
     def export_rgb(layout, samples, elem):
@@ -123,8 +134,12 @@ def main():
         "j_u8_semiplanar_4x": export(capi.EXPORT_SEMIPLANAR, capi.EXPORT_U8, None, 1, 2),
         "k_rgb_u8_packed": export_rgb(capi.RGB_PACKED, capi.RGB_U8, 1),
         "l_rgb_u16_planar": export_rgb(capi.RGB_PLANAR, capi.RGB_U16, 2),
+        "m_resized_native_planar_1080p": export_resized(capi.EXPORT_PLANAR, capi.EXPORT_NATIVE, (1920, 1080), 2),
+        "n_resized_u8_semiplanar_1080p": export_resized(capi.EXPORT_SEMIPLANAR, capi.EXPORT_U8, (1920, 1080), 1),
+        "o_resized_native_planar_1440p": export_resized(capi.EXPORT_PLANAR, capi.EXPORT_NATIVE, (2560, 1440), 2),
+        "p_resized_native_planar_720p": export_resized(capi.EXPORT_PLANAR, capi.EXPORT_NATIVE, (1280, 720), 2),
     }
-    scaled = [n for n in variants if n[0] in "ghij"]
+    scaled = [n for n in variants if n[0] in "ghijmnop"]
     ms = {n: [] for n in variants}
     for _ in range(args.rounds):
         for n, fn in variants.items():
@@ -141,6 +156,8 @@ def main():
         "scaled_GBps_source_read": {n: frame_bytes / res[n] / 1e6 for n in scaled},
         "rgb": {"k_over_b": res["k_rgb_u8_packed"] / res["b_native_planar"], "l_over_b": res["l_rgb_u16_planar"] / res["b_native_planar"],
                 "k_bytes_read_plus_written": frame_bytes + W * H * 3, "l_bytes_read_plus_written": frame_bytes + W * H * 6},
+        "resized": {"m_over_h": res["m_resized_native_planar_1080p"] / res["h_native_planar_4x"],
+                    "n_over_j": res["n_resized_u8_semiplanar_1080p"] / res["j_u8_semiplanar_4x"]},
         "copy_rate_GBps_same_bytes": ctx.measure_copy_rate(frame_bytes, 9),
         "bars": {"b_le_a": res["b_native_planar"] <= res["a_memcpy2d_x3"],
                  "c_le_b_plus_spread": res["c_msb16_semiplanar_crop8"] <= res["b_native_planar"] + spread,
