@@ -86,7 +86,7 @@ namespace {
   X(m355_last_error) X(m355_device_count) X(m355_create) X(m355_destroy) X(m355_frame_create) X(m355_frame_destroy) \
   X(m355_frame_upload) X(m355_frame_download) X(m355_submit_picture) X(m355_wait) X(m355_set_pipeline_depth) \
   X(m355_host_alloc) X(m355_host_free) X(m355_frame_hash) X(m355_arena_begin) X(m355_last_serial) X(m355_decode_status) \
-  X(m355_frame_download_async) X(m355_frame_download_wait) X(m355_frame_export) X(m355_frame_export_scaled) X(m355_frame_export_rgb) X(m355_frame_export_resized) X(m355_frame_export_order) \
+  X(m355_frame_download_async) X(m355_frame_download_wait) X(m355_frame_export) X(m355_frame_export_scaled) X(m355_frame_export_rgb) X(m355_frame_export_resized) X(m355_frame_export_resized_rgb) X(m355_frame_export_order) \
   X(m355_group_create) X(m355_group_destroy) X(m355_group_decode) X(m355_picture_upload) X(m355_picture_replace) X(m355_shard_owner_of_tile) \
   X(m355_picture_arena_begin) X(m355_frame_hash_async) X(m355_frame_hash_result) X(m355_frame_measure_async) X(m355_frame_measure_result)
 
@@ -1803,6 +1803,42 @@ LIBDE265_API int m355_glue_export_image_resized(const struct de265_image* img, i
   d.out_width = out_size[0]; d.out_height = out_size[1];
   for (int c = 0; c < 3; c++) { d.dst[c] = dst[c]; d.pitch[c] = pitch[c]; }
   int rc = A->m355_frame_export_resized(g->mctx, frame, &d);
+  if (rc == M355_OK) rc = A->m355_frame_export_order(g->mctx, frame, consumer_stream);
+  if (rc != M355_OK) g->error = A->m355_last_error();
+  return rc;
+}
+/* The picture RESIZED to out_size = {out_width, out_height} luma samples and converted to R'G'B' in one launch (m355_frame_export_resized_rgb: the
+ * resized export and the R'G'B' export of the resized picture composed, integer-exact), with the waiting behaviour of m355_glue_export_image.  The frame,
+ * the rectangle (NULL: the image's conformance window), matrix == -1 and full_range == -1 are resolved as in m355_glue_export_image_rgb, out_size as in
+ * m355_glue_export_image_resized.  PACKED uses dst[0] and pitch[0] only. */
+LIBDE265_API int m355_glue_export_image_resized_rgb(const struct de265_image* img, int layout, int samples, int matrix, int full_range, const int rect[4],
+                                                    const int out_size[2], void* const dst[3], const int64_t pitch[3], void* consumer_stream)
+{
+  Api* A = api();
+  if (!A) return M355_ERR_NO_DEVICE;
+  if (!img || !img->decctx || !out_size || !dst || !pitch) return M355_ERR_INVALID;
+  Glue* g = glue_of(img->decctx);
+  if (!g || g->n_ranks > 1) return M355_ERR_INVALID;
+  if (matrix == -1) {
+    const int mc = de265_get_image_matrix_coefficients(img);
+    if (mc == 1 || mc == 2) matrix = M355_MATRIX_BT709;
+    else if (mc == 5 || mc == 6) matrix = M355_MATRIX_BT601;
+    else if (mc == 9) matrix = M355_MATRIX_BT2020;
+    else return M355_ERR_INVALID;
+  }
+  if (full_range == -1) full_range = de265_get_image_full_range_flag(img) ? 1 : 0;
+  wait_submitted(g, img->get_ID());
+  std::lock_guard<std::mutex> api_lock(g->api_mu);
+  int r[4];
+  const int frame = frame_and_rect(g, img, rect, r);
+  if (frame < 0) return M355_ERR_INVALID;
+  m355_resize_rgb_desc d;
+  memset(&d, 0, sizeof(d));
+  d.layout = layout; d.samples = samples; d.matrix = matrix; d.full_range = full_range;
+  d.x0 = r[0]; d.y0 = r[1]; d.width = r[2]; d.height = r[3];
+  d.out_width = out_size[0]; d.out_height = out_size[1];
+  for (int c = 0; c < 3; c++) { d.dst[c] = dst[c]; d.pitch[c] = pitch[c]; }
+  int rc = A->m355_frame_export_resized_rgb(g->mctx, frame, &d);
   if (rc == M355_OK) rc = A->m355_frame_export_order(g->mctx, frame, consumer_stream);
   if (rc != M355_OK) g->error = A->m355_last_error();
   return rc;

@@ -540,8 +540,9 @@ M355_API int   m355_rgb_coefficients(int matrix, int full_range, int bit_depth_l
  * for a plane that exists; a pitch below the OUTPUT row's bytes.  A monochrome frame exports luma only; bytes beyond an output row are never written.
  * Ordering, the gate and sharded contexts are those of m355_frame_export: asynchronous, a reader of the frame of the same kind — m355_frame_export_wait
  * and m355_frame_export_order cover it, the next decode into the frame waits for it —, and nothing is written behind a rejected decode.
- * Not offered: RGB at the resized size, filters with negative lobes (bicubic, Lanczos: signed sums and clipping), ratios beyond 8, another chroma
- * siting, resizing into a frame of the decoder. */
+ * Not offered: filters with negative lobes (bicubic, Lanczos: signed sums and clipping), ratios beyond 8, another chroma siting, resizing into a
+ * frame of the decoder; and of m355_frame_export_resized_rgb below: float / normalised output, another chroma siting, chroma resampled straight onto
+ * the luma grid (it is resized on its own grid, then reconstructed), batches of frames per launch. */
 #define M355_RESIZE_MAX_TAPS 16
 typedef struct m355_resize_desc {
   int32_t layout, samples;          /* M355_EXPORT_PLANAR / _SEMIPLANAR, M355_EXPORT_NATIVE / _MSB16 / _U8 */
@@ -554,6 +555,35 @@ M355_API int   m355_frame_export_resized(m355_ctx* ctx, int frame, const m355_re
 /* row i of one axis' filter: returns the number of coefficients (1..16), *first = source index of coeff[0]; < 0 on bad arguments (a size below 1,
  * a ratio outside the limit, i outside [0, dst_n), cosited not 0 or 1, a null pointer) */
 M355_API int   m355_resize_taps(int src_n, int dst_n, int cosited, int i, int32_t* first, int32_t coeff[M355_RESIZE_MAX_TAPS]);
+/* The frame's rectangle RESIZED to out_width x out_height luma samples AND converted to R'G'B', in one launch (k_export_resized_rgb.hip): what a model
+ * (its input size) or a compositor (its window's size) on the same GPU takes.  The definition is a COMPOSITION and adds no arithmetic, constant or
+ * siting rule of its own:
+ *   let R be the planes m355_frame_export_resized delivers for this rectangle and this output size with M355_EXPORT_PLANAR, M355_EXPORT_NATIVE, and F'
+ *   a frame of out_width x out_height with the source frame's chroma format and bit depths whose samples are R;
+ *   the call delivers, byte for byte, what m355_frame_export_rgb delivers for the whole of F' with the same layout, samples, matrix and full_range.
+ * Spelled out: every plane is resampled on its own grid by the one triangle filter above; each output sample is rounded to a sample of the plane's
+ * bit depth, a = (v + (1 << (31 - bd))) >> (32 - bd); chroma is then brought to the luma positions by the one bilinear filter of m355_frame_export_rgb,
+ * its indices clamped to the RESIZED chroma plane (out_width / SubWidthC x out_height / SubHeightC); then the eight integers of m355_rgb_coefficients are
+ * applied as defined there.  No resized Y, Cb or Cr sample passes through memory.  Consequences:
+ *   out == rectangle == whole frame: the call equals m355_frame_export_rgb of the whole frame;
+ *   a sub-rectangle: it equals the R'G'B' export of a frame that holds only that rectangle — the resize clamps AND the chroma filter's clamps go to the
+ *   rectangle, whereas m355_frame_export_rgb of a rectangle reads the frame's samples outside it, so the two differ at the rectangle's rim;
+ *   a monochrome frame has u = v = 0; a constant frame gives a constant picture.
+ * M355_ERR_INVALID (nothing is enqueued, no destination byte written): whatever m355_frame_export_resized rejects for the frame handle, the rectangle,
+ * the output size and the ratio; whatever m355_frame_export_rgb rejects for layout, samples, matrix and full_range; a null dst for a plane the layout
+ * uses; a pitch below the OUTPUT row's bytes (out_width * 3 * element bytes packed, out_width * element bytes planar); for U16 a pointer or a pitch
+ * that is no multiple of 2; a null descriptor.
+ * Ordering, the gate and sharded contexts are those of m355_frame_export: asynchronous, a reader of the frame of the same kind — m355_frame_export_wait
+ * and m355_frame_export_order cover it, the next decode into the frame waits for it —, nothing is written behind a rejected decode, and destination
+ * bytes beyond an output row are never written. */
+typedef struct m355_resize_rgb_desc {
+  int32_t layout, samples, matrix, full_range;   /* M355_RGB_PACKED / _PLANAR, M355_RGB_U8 / _U16, M355_MATRIX_*, 0 / 1: as m355_rgb_desc */
+  int32_t x0, y0, width, height;    /* source luma rectangle, as m355_export_desc (width == 0: whole frame) */
+  int32_t out_width, out_height;    /* luma size of the result */
+  void*   dst[3];                   /* PACKED uses [0] only */
+  int64_t pitch[3];                 /* bytes per destination row, >= the OUTPUT row's bytes */
+} m355_resize_rgb_desc;             /* (LP64: 88 bytes) */
+M355_API int   m355_frame_export_resized_rgb(m355_ctx* ctx, int frame, const m355_resize_rgb_desc* desc);   /* asynchronous */
 M355_API int   m355_frame_export_wait(m355_ctx* ctx, int frame);
 M355_API int   m355_frame_export_order(m355_ctx* ctx, int frame, void* consumer_hipStream);
 /* Device memory for export destinations and blocking copies out of / into it, for applications (and the tests) that keep a second HIP

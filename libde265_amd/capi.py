@@ -72,6 +72,14 @@ class RgbDesc(ctypes.Structure):
                 ("dst", ctypes.c_void_p * 3), ("pitch", ctypes.c_int64 * 3)]
 
 
+class ResizeRgbDesc(ctypes.Structure):
+    """m355_resize_rgb_desc (include/de265_mi355x.h)"""
+    _fields_ = [("layout", ctypes.c_int32), ("samples", ctypes.c_int32), ("matrix", ctypes.c_int32), ("full_range", ctypes.c_int32),
+                ("x0", ctypes.c_int32), ("y0", ctypes.c_int32), ("width", ctypes.c_int32), ("height", ctypes.c_int32),
+                ("out_width", ctypes.c_int32), ("out_height", ctypes.c_int32),
+                ("dst", ctypes.c_void_p * 3), ("pitch", ctypes.c_int64 * 3)]
+
+
 class RgbCoeffs(ctypes.Structure):
     """m355_rgb_coeffs (include/de265_mi355x.h)"""
     _fields_ = [(n, ctypes.c_int32) for n in ("F", "y0", "c0", "cy", "crv", "cgu", "cgv", "cbu")]
@@ -145,6 +153,8 @@ class Library:
         if hasattr(L, "m355_frame_export_resized"):     # (absent from older builds loaded through M355_LIB for an A/B)
             L.m355_frame_export_resized.argtypes = [vp, i, ctypes.POINTER(ResizeDesc)]
             L.m355_resize_taps.argtypes = [i, i, i, i, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]
+        if hasattr(L, "m355_frame_export_resized_rgb"):  # (absent from older builds loaded through M355_LIB for an A/B)
+            L.m355_frame_export_resized_rgb.argtypes = [vp, i, ctypes.POINTER(ResizeRgbDesc)]
         L.m355_host_alloc.argtypes = [ctypes.c_size_t]
         L.m355_host_alloc.restype = vp
         L.m355_host_free.argtypes = [vp]
@@ -480,6 +490,37 @@ class Context:
                 bufs.append(p)
                 desc.dst[k] = p; desc.pitch[k] = pitch
             self.L.check(self.L.lib.m355_frame_export_rgb(self.h, f, ctypes.byref(desc)))
+        except Exception:
+            for p in bufs:
+                self.L.lib.m355_host_free(p) if host else self.device_free(p)
+            raise
+        return (f, shapes, bufs, [int(desc.pitch[k]) for k in range(len(shapes))], host)
+
+    def frame_export_resized_rgb(self, f, layout, samples, matrix, full_range, out_size, rect=None, host=False, pad=20):
+        """start m355_frame_export_resized_rgb of frame f to out_size = (out_width, out_height) luma samples (rect = the source rectangle (x0, y0,
+        width, height) in luma samples, None: the whole frame) into buffers of its own, made as frame_export_rgb makes them: every byte holds
+        DEVICE_FILL beforehand, the pitch is `pad` bytes larger than the row.  Packed: one plane of 3 * out_width elements per row; planar: R, G, B.
+        -> token for frame_export_finish"""
+        w, h = out_size
+        dt = np.dtype(np.uint16 if samples == RGB_U16 else np.uint8)
+        shapes = [(h, 3 * w, dt)] if layout == RGB_PACKED else [(h, w, dt)] * 3
+        desc = ResizeRgbDesc(layout=layout, samples=samples, matrix=matrix, full_range=full_range, out_width=w, out_height=h)
+        if rect is not None:
+            desc.x0, desc.y0, desc.width, desc.height = rect
+        bufs = []
+        try:
+            for k, (rows, n, _) in enumerate(shapes):
+                pitch = n * dt.itemsize + pad
+                if host:
+                    p = self.L.lib.m355_host_alloc(rows * pitch)
+                    if not p:
+                        raise M355Error(4, self.L.error())
+                    ctypes.memset(p, DEVICE_FILL, rows * pitch)
+                else:
+                    p = self.device_alloc(rows * pitch)
+                bufs.append(p)
+                desc.dst[k] = p; desc.pitch[k] = pitch
+            self.L.check(self.L.lib.m355_frame_export_resized_rgb(self.h, f, ctypes.byref(desc)))
         except Exception:
             for p in bufs:
                 self.L.lib.m355_host_free(p) if host else self.device_free(p)

@@ -333,6 +333,26 @@ struct ExportResizedArgs {
 /* src_bytes / dst_bytes: 1 or 2 per sample */
 void m355_launch_export_resized(const ExportResizedArgs& a, int src_bytes, int dst_bytes, bool semiplanar, hipStream_t st);
 
+/* one m355_frame_export_resized_rgb (k_export_resized_rgb.hip).  src[] = the rectangle's first sample of Y, Cb, Cr (the resize clamps to the rectangle),
+   pitches in BYTES (src_pitch[0] luma, [1] both chroma planes); dst[0] alone for the packed layout, else R, G, B.  Index 0 of sn / dn is the luma
+   grid, 1 the chroma grid (zeros for a monochrome frame): sn_x x sn_y source samples of the rectangle to dn_x x dn_y output samples; the horizontal
+   chroma axis of 4:2:0 / 4:2:2 is co-sited.  A workgroup owns a tile of tile_w <= M355_RESIZE_TILE_W luma output columns (even for 4:2:0 / 4:2:2)
+   x M355_RESIZE_TILE_H rows: tiles_x tiles per row of tiles, units tiles in all.  cf: chroma format 0..3; planar: 0 / 1; bdl / bdc: the bit depths;
+   k: the integers of m355_rgb_coefficients.  timeout / epoch: the gate (M355_GATE). */
+struct ExportResizedRgbArgs {
+  const uint8_t* src[3];
+  uint8_t* dst[3];
+  long long src_pitch[2], dst_pitch[3];
+  uint32_t sn_x[2], sn_y[2], dn_x[2], dn_y[2];
+  uint32_t tile_w, tiles_x, units;
+  int32_t cf, planar, bdl, bdc;
+  m355_rgb_coeffs k;
+  const uint32_t* timeout;
+  uint32_t epoch;
+};
+/* src_bytes / dst_bytes: 1 or 2 per sample / channel */
+void m355_launch_export_resized_rgb(const ExportResizedRgbArgs& a, int src_bytes, int dst_bytes, hipStream_t st);
+
 /* first statement of every kernel of a decode: a picture whose lists k_validate rejected is never acted upon */
 /* Element `c` (0..2, per lane) of a three-entry table of the kernel arguments (plane pointers, pitches, ...): all three entries are
  * read as scalars and the lane selects — indexing the argument segment with a per-lane value is a VECTOR memory load from it, i.e. one

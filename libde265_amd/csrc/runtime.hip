@@ -686,6 +686,72 @@ int m355_frame_export_resized(m355_ctx* c, int h, const m355_resize_desc* e)
   HIPCHK(hipGetLastError());
   return reader_end(c, f, RD_EXPORT, cs);
 }
+/* The width of k_export_resized_rgb's tiles: a pass of that kernel takes two luma rows, or two rows of Cb and of Cr, where their source vectors fit
+ * the workgroup's 256 lanes, and a workgroup's time follows its number of passes — so the widest width (even for 4:2:0 / 4:2:2: a tile's first column
+ * is a chroma column) not above resize_tile_w's at which they fit, but at least 64 columns, then the narrowest one with the same number of tiles. */
+static uint32_t resize_rgb_tile_w(int64_t sn, int64_t dn, int64_t csn, int64_t cdn, int sb, int sw)
+{
+  const int64_t S = 16 / sb;
+  const auto vectors = [&](int64_t w, int64_t s, int64_t d) { return ((w - 1) * s / d + 2 + m355_resize_max_taps(s, d) + S - 1) / S; };   /* (an upper bound) */
+  const auto fits = [&](int64_t w) { return 2 * vectors(w, sn, dn) <= 256 && (sw != 2 || 4 * vectors(w / 2 + 1, csn, cdn) <= 256); };
+  int64_t w = resize_tile_w(sn, dn, sb);
+  if (sw == 2) w = w > 2 ? w & ~(int64_t)1 : 2;
+  int64_t t = w;
+  while (t > 64 && !fits(t)) t -= sw;
+  if (fits(t)) w = t;
+  const int64_t tiles = (dn + w - 1) / w;
+  int64_t even = (dn + tiles - 1) / tiles;
+  if (sw == 2) even = (even + 1) & ~(int64_t)1;
+  return (uint32_t)(even < w ? even : w);
+}
+/* The same resize with the R'G'B' conversion of the resized picture behind it, in one launch (k_export_resized_rgb.hip): the frame handle and the
+ * rectangle are checked by export_plan — with destinations that cannot fail —, the output size and the ratio as for the resized export, the
+ * conversion and the destinations as for the R'G'B' export, with the OUTPUT width.  A reader of the kind RD_EXPORT, like the four above. */
+int m355_frame_export_resized_rgb(m355_ctx* c, int h, const m355_resize_rgb_desc* e)
+{
+  const char* who = "m355_frame_export_resized_rgb";
+  m355_export_desc yuv = {};
+  if (e) {
+    yuv.layout = M355_EXPORT_PLANAR; yuv.samples = M355_EXPORT_NATIVE;
+    yuv.x0 = e->x0; yuv.y0 = e->y0; yuv.width = e->width; yuv.height = e->height;
+    for (int p = 0; p < 3; p++) { yuv.dst[p] = (void*)e; yuv.pitch[p] = INT64_MAX; }
+  }
+  ExportPlan P;
+  int rc = export_plan(c, h, e ? &yuv : nullptr, 0, who, P);
+  if (rc) return rc;
+  Frame* f = P.f;
+  const int sw = (f->cf == 1 || f->cf == 2) ? 2 : 1, sh = f->cf == 1 ? 2 : 1;
+  if (e->out_width <= 0 || e->out_height <= 0 || e->out_width % sw || e->out_height % sh)
+    return fail(M355_ERR_INVALID, "%s: output size %dx%d is not positive or no multiple of %dx%d luma samples", who, e->out_width, e->out_height, sw, sh);
+  if (!m355_resize_ratio_ok(P.p[0].pw, e->out_width) || !m355_resize_ratio_ok(P.p[0].ph, e->out_height))
+    return fail(M355_ERR_INVALID, "%s: %dx%d to %dx%d is more than 8x down or up", who, P.p[0].pw, P.p[0].ph, e->out_width, e->out_height);
+  if (e->layout != M355_RGB_PACKED && e->layout != M355_RGB_PLANAR) return fail(M355_ERR_INVALID, "%s: unknown layout %d", who, e->layout);
+  ExportResizedRgbArgs a = {};
+  rc = m355_rgb_coefficients(e->matrix, e->full_range, f->bdl, f->bdc, e->samples, &a.k);
+  if (rc) return rc;
+  const bool planar = e->layout == M355_RGB_PLANAR;
+  const int db = e->samples == M355_RGB_U16 ? 2 : 1, sb = f->bpp[0];
+  const int64_t row_bytes = (int64_t)e->out_width * db * (planar ? 1 : 3);
+  for (int p = 0; p < (planar ? 3 : 1); p++) {
+    if (!e->dst[p]) return fail(M355_ERR_INVALID, "%s: no destination for plane %d", who, p);
+    if (e->pitch[p] < row_bytes) return fail(M355_ERR_INVALID, "%s: pitch %lld of plane %d is below its row of %lld bytes", who, (long long)e->pitch[p], p, (long long)row_bytes);
+    if (db == 2 && (((uintptr_t)e->dst[p] | (uint64_t)e->pitch[p]) & 1)) return fail(M355_ERR_INVALID, "%s: 16-bit plane %d at an odd address or pitch", who, p);
+    a.dst[p] = (uint8_t*)e->dst[p]; a.dst_pitch[p] = e->pitch[p];
+  }
+  for (int p = 0; p < P.np; p++) a.src[p] = P.p[p].src[0];
+  a.src_pitch[0] = P.p[0].src_pitch; a.src_pitch[1] = P.np > 1 ? P.p[1].src_pitch : 0;
+  a.sn_x[0] = (uint32_t)P.p[0].pw; a.sn_y[0] = (uint32_t)P.p[0].ph; a.dn_x[0] = (uint32_t)e->out_width; a.dn_y[0] = (uint32_t)e->out_height;
+  if (P.np > 1) { a.sn_x[1] = (uint32_t)P.p[1].pw; a.sn_y[1] = (uint32_t)P.p[1].ph; a.dn_x[1] = (uint32_t)(e->out_width / sw); a.dn_y[1] = (uint32_t)(e->out_height / sh); }
+  a.tile_w = resize_rgb_tile_w(P.p[0].pw, e->out_width, P.np > 1 ? P.p[1].pw : 0, e->out_width / sw, sb, sw);
+  a.tiles_x = ((uint32_t)e->out_width + a.tile_w - 1) / a.tile_w;
+  a.units = a.tiles_x * (((uint32_t)e->out_height + M355_RESIZE_TILE_H - 1) / M355_RESIZE_TILE_H);
+  a.cf = f->cf; a.planar = planar; a.bdl = f->bdl; a.bdc = f->bdc;
+  hipSetDevice(c->device);
+  const hipStream_t cs = reader_begin(c, f, RD_EXPORT, &a.timeout, &a.epoch);
+  m355_launch_export_resized_rgb(a, sb, db, cs);
+  HIPCHK(hipGetLastError());
+  return reader_end(c, f, RD_EXPORT, cs);
+}
 /* the host waits until this frame's last export has landed */
 int m355_frame_export_wait(m355_ctx* c, int h)
 {

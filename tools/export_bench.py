@@ -14,6 +14,10 @@
   (m), (n) m355_frame_export_resized to 1920x1080, NATIVE planar and U8 semi-planar: the output sizes of (h) and (j); the result line has (m) / (h)
       and (n) / (j), the cost of the triangle over the box at the same traffic
   (o), (p) m355_frame_export_resized NATIVE planar to 2560x1440 (ratio 3) and to 1280x720 (ratio 6)
+  (q), (r), (s) m355_frame_export_resized_rgb, BT.709 limited range: U8 packed and U16 planar to 1920x1080, U8 planar (CHW) to 1280x720
+  (t), (u), (v) m355_frame_export_rgb of a frame of the resized size — the second half of the chain that (q), (r), (s) replace: U8 packed and U16
+      planar of the 1920x1080 window of a 1920x1088 10-bit frame, U8 planar of a 1280x720 frame.  One launch must not lose to the two it fuses:
+      the bars are (q) <= (m) + (t), (r) <= (m) + (u), (s) <= (p) + (v), each + the spread of (b)
 
 and, beside them, m355_measure_copy_rate for the frame's byte count.  Every figure is the median of --iters launches; (b) is measured in
 --rounds separate rounds spread over the run, and the spread of their medians is the margin (c), (d), (g)-(j) and (m)-(p) are held against: a scaled or resized export reads exactly (b)'s source bytes and writes at most a
@@ -120,6 +124,24 @@ def main():
             d.dst[k] = rgb_dst[k]; d.pitch[k] = W * elem * (1 if layout == capi.RGB_PLANAR else 3)
         return lambda: lib.check(lib.lib.m355_frame_export_rgb(ctx.h, frame, ctypes.byref(d)))
 
+    def export_resized_rgb(layout, samples, out_size, elem):
+        d = capi.ResizeRgbDesc(layout=layout, samples=samples, matrix=capi.MATRIX_BT709, full_range=0, out_width=out_size[0], out_height=out_size[1])
+        for k in range(3):
+            d.dst[k] = rgb_dst[k]; d.pitch[k] = out_size[0] * elem * (1 if layout == capi.RGB_PLANAR else 3)
+        return lambda: lib.check(lib.lib.m355_frame_export_resized_rgb(ctx.h, frame, ctypes.byref(d)))
+
+    # frames of the resized sizes, for the R'G'B' export that the chain ends with (a frame's height is a multiple of 8: 1088 rows, of which 1080)
+    small = {(1920, 1080): ctx.frame_create(1920, 1088, 1, BD, BD), (1280, 720): ctx.frame_create(1280, 720, 1, BD, BD)}
+    for f in small.values():
+        ctx.frame_fill(f, 600, 500)
+
+    def export_rgb_small(layout, samples, size, elem):
+        d = capi.RgbDesc(layout=layout, samples=samples, matrix=capi.MATRIX_BT709, full_range=0)
+        d.x0, d.y0, d.width, d.height = 0, 0, size[0], size[1]
+        for k in range(3):
+            d.dst[k] = rgb_dst[k]; d.pitch[k] = size[0] * elem * (1 if layout == capi.RGB_PLANAR else 3)
+        return lambda: lib.check(lib.lib.m355_frame_export_rgb(ctx.h, small[size], ctypes.byref(d)))
+
     variants = {
         "a_memcpy2d_x3": copies,
         "b_native_planar": export(capi.EXPORT_PLANAR, capi.EXPORT_NATIVE, None, 2),
@@ -138,6 +160,12 @@ def main():
         "n_resized_u8_semiplanar_1080p": export_resized(capi.EXPORT_SEMIPLANAR, capi.EXPORT_U8, (1920, 1080), 1),
         "o_resized_native_planar_1440p": export_resized(capi.EXPORT_PLANAR, capi.EXPORT_NATIVE, (2560, 1440), 2),
         "p_resized_native_planar_720p": export_resized(capi.EXPORT_PLANAR, capi.EXPORT_NATIVE, (1280, 720), 2),
+        "q_resized_rgb_u8_packed_1080p": export_resized_rgb(capi.RGB_PACKED, capi.RGB_U8, (1920, 1080), 1),
+        "r_resized_rgb_u16_planar_1080p": export_resized_rgb(capi.RGB_PLANAR, capi.RGB_U16, (1920, 1080), 2),
+        "s_resized_rgb_u8_planar_720p": export_resized_rgb(capi.RGB_PLANAR, capi.RGB_U8, (1280, 720), 1),
+        "t_rgb_u8_packed_of_1080p": export_rgb_small(capi.RGB_PACKED, capi.RGB_U8, (1920, 1080), 1),
+        "u_rgb_u16_planar_of_1080p": export_rgb_small(capi.RGB_PLANAR, capi.RGB_U16, (1920, 1080), 2),
+        "v_rgb_u8_planar_of_720p": export_rgb_small(capi.RGB_PLANAR, capi.RGB_U8, (1280, 720), 1),
     }
     scaled = [n for n in variants if n[0] in "ghijmnop"]
     ms = {n: [] for n in variants}
@@ -158,11 +186,17 @@ def main():
                 "k_bytes_read_plus_written": frame_bytes + W * H * 3, "l_bytes_read_plus_written": frame_bytes + W * H * 6},
         "resized": {"m_over_h": res["m_resized_native_planar_1080p"] / res["h_native_planar_4x"],
                     "n_over_j": res["n_resized_u8_semiplanar_1080p"] / res["j_u8_semiplanar_4x"]},
+        "resized_rgb": {"q_over_m_plus_t": res["q_resized_rgb_u8_packed_1080p"] / (res["m_resized_native_planar_1080p"] + res["t_rgb_u8_packed_of_1080p"]),
+                        "r_over_m_plus_u": res["r_resized_rgb_u16_planar_1080p"] / (res["m_resized_native_planar_1080p"] + res["u_rgb_u16_planar_of_1080p"]),
+                        "s_over_p_plus_v": res["s_resized_rgb_u8_planar_720p"] / (res["p_resized_native_planar_720p"] + res["v_rgb_u8_planar_of_720p"])},
         "copy_rate_GBps_same_bytes": ctx.measure_copy_rate(frame_bytes, 9),
         "bars": {"b_le_a": res["b_native_planar"] <= res["a_memcpy2d_x3"],
                  "c_le_b_plus_spread": res["c_msb16_semiplanar_crop8"] <= res["b_native_planar"] + spread,
                  "d_le_b_plus_spread": res["d_u8_semiplanar"] <= res["b_native_planar"] + spread,
-                 **{n[0] + "_le_b_plus_spread": res[n] <= res["b_native_planar"] + spread for n in scaled}},
+                 **{n[0] + "_le_b_plus_spread": res[n] <= res["b_native_planar"] + spread for n in scaled},
+                 "q_le_m_plus_t_plus_spread": res["q_resized_rgb_u8_packed_1080p"] <= res["m_resized_native_planar_1080p"] + res["t_rgb_u8_packed_of_1080p"] + spread,
+                 "r_le_m_plus_u_plus_spread": res["r_resized_rgb_u16_planar_1080p"] <= res["m_resized_native_planar_1080p"] + res["u_rgb_u16_planar_of_1080p"] + spread,
+                 "s_le_p_plus_v_plus_spread": res["s_resized_rgb_u8_planar_720p"] <= res["p_resized_native_planar_720p"] + res["v_rgb_u8_planar_of_720p"] + spread},
     }
     line = json.dumps(out)
     print(line)
@@ -171,6 +205,8 @@ def main():
             f.write(line + "\n")
     for p in src + dst + rgb_dst:
         ctx.device_free(p)
+    for f in small.values():
+        ctx.frame_destroy(f)
     ctx.close()
 
 
