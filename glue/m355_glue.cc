@@ -86,7 +86,7 @@ namespace {
   X(m355_last_error) X(m355_device_count) X(m355_create) X(m355_destroy) X(m355_frame_create) X(m355_frame_destroy) \
   X(m355_frame_upload) X(m355_frame_download) X(m355_submit_picture) X(m355_wait) X(m355_set_pipeline_depth) \
   X(m355_host_alloc) X(m355_host_free) X(m355_frame_hash) X(m355_arena_begin) X(m355_last_serial) X(m355_decode_status) \
-  X(m355_frame_download_async) X(m355_frame_download_wait) X(m355_frame_export) X(m355_frame_export_scaled) X(m355_frame_export_rgb) X(m355_frame_export_resized) X(m355_frame_export_resized_rgb) X(m355_frame_export_order) \
+  X(m355_frame_download_async) X(m355_frame_download_wait) X(m355_frame_export) X(m355_frame_export_scaled) X(m355_frame_export_rgb) X(m355_frame_export_resized) X(m355_frame_export_resized_rgb) X(m355_frames_export_tensor) X(m355_frame_export_order) \
   X(m355_group_create) X(m355_group_destroy) X(m355_group_decode) X(m355_picture_upload) X(m355_picture_replace) X(m355_shard_owner_of_tile) \
   X(m355_picture_arena_begin) X(m355_frame_hash_async) X(m355_frame_hash_result) X(m355_frame_measure_async) X(m355_frame_measure_result)
 
@@ -1840,6 +1840,48 @@ LIBDE265_API int m355_glue_export_image_resized_rgb(const struct de265_image* im
   for (int c = 0; c < 3; c++) { d.dst[c] = dst[c]; d.pitch[c] = pitch[c]; }
   int rc = A->m355_frame_export_resized_rgb(g->mctx, frame, &d);
   if (rc == M355_OK) rc = A->m355_frame_export_order(g->mctx, frame, consumer_stream);
+  if (rc != M355_OK) g->error = A->m355_last_error();
+  return rc;
+}
+/* A BATCH of pictures of ONE decoder, each resized, converted to R'G'B', normalised and delivered as one float tensor in one launch
+ * (m355_frames_export_tensor: layout / dtype = M355_TENSOR_*, samples = M355_RGB_* of the integer stage; scale / bias per channel; dst and the strides in
+ * BYTES as in m355_tensor_desc), with the waiting behaviour of m355_glue_export_image: the only wait is for the worker to have enqueued every picture of
+ * the batch, and the consumer's stream is ordered behind the one launch.  The rectangle (NULL: the conformance window of imgs[0]), matrix == -1 and
+ * full_range == -1 are resolved from imgs[0] as in m355_glue_export_image_resized_rgb and hold for every picture; out_size as there. */
+LIBDE265_API int m355_glue_export_images_tensor(const struct de265_image* const* imgs, int n, int layout, int dtype, int samples, int matrix, int full_range,
+                                                const int rect[4], const int out_size[2], const float scale[3], const float bias[3], void* dst,
+                                                int64_t stride_n, int64_t stride_c, int64_t stride_h, void* consumer_stream)
+{
+  Api* A = api();
+  if (!A) return M355_ERR_NO_DEVICE;
+  if (!imgs || n < 1 || n > M355_TENSOR_MAX_FRAMES || !out_size || !scale || !bias) return M355_ERR_INVALID;
+  for (int i = 0; i < n; i++) if (!imgs[i] || !imgs[i]->decctx || imgs[i]->decctx != imgs[0]->decctx) return M355_ERR_INVALID;
+  Glue* g = glue_of(imgs[0]->decctx);
+  if (!g || g->n_ranks > 1) return M355_ERR_INVALID;
+  if (matrix == -1) {
+    const int mc = de265_get_image_matrix_coefficients(imgs[0]);
+    if (mc == 1 || mc == 2) matrix = M355_MATRIX_BT709;
+    else if (mc == 5 || mc == 6) matrix = M355_MATRIX_BT601;
+    else if (mc == 9) matrix = M355_MATRIX_BT2020;
+    else return M355_ERR_INVALID;
+  }
+  if (full_range == -1) full_range = de265_get_image_full_range_flag(imgs[0]) ? 1 : 0;
+  for (int i = 0; i < n; i++) wait_submitted(g, imgs[i]->get_ID());
+  std::lock_guard<std::mutex> api_lock(g->api_mu);
+  int r[4], frames[M355_TENSOR_MAX_FRAMES];
+  for (int i = n - 1; i >= 0; i--) {                             /* (last: imgs[0], whose rectangle is the batch's) */
+    frames[i] = frame_and_rect(g, imgs[i], rect, r);
+    if (frames[i] < 0) return M355_ERR_INVALID;
+  }
+  m355_tensor_desc d;
+  memset(&d, 0, sizeof(d));
+  d.layout = layout; d.dtype = dtype; d.samples = samples; d.matrix = matrix; d.full_range = full_range;
+  d.x0 = r[0]; d.y0 = r[1]; d.width = r[2]; d.height = r[3];
+  d.out_width = out_size[0]; d.out_height = out_size[1];
+  for (int c = 0; c < 3; c++) { d.scale[c] = scale[c]; d.bias[c] = bias[c]; }
+  d.dst = dst; d.stride_n = stride_n; d.stride_c = stride_c; d.stride_h = stride_h;
+  int rc = A->m355_frames_export_tensor(g->mctx, frames, n, &d);
+  if (rc == M355_OK) rc = A->m355_frame_export_order(g->mctx, frames[0], consumer_stream);
   if (rc != M355_OK) g->error = A->m355_last_error();
   return rc;
 }

@@ -541,8 +541,9 @@ M355_API int   m355_rgb_coefficients(int matrix, int full_range, int bit_depth_l
  * Ordering, the gate and sharded contexts are those of m355_frame_export: asynchronous, a reader of the frame of the same kind — m355_frame_export_wait
  * and m355_frame_export_order cover it, the next decode into the frame waits for it —, and nothing is written behind a rejected decode.
  * Not offered: filters with negative lobes (bicubic, Lanczos: signed sums and clipping), ratios beyond 8, another chroma siting, resizing into a
- * frame of the decoder; and of m355_frame_export_resized_rgb below: float / normalised output, another chroma siting, chroma resampled straight onto
- * the luma grid (it is resized on its own grid, then reconstructed), batches of frames per launch. */
+ * frame of the decoder; and of m355_frame_export_resized_rgb and m355_frames_export_tensor below: BGR order, another chroma siting, chroma resampled
+ * straight onto the luma grid (it is resized on its own grid, then reconstructed), per-frame rectangles or output sizes within a batch, writing into
+ * a tensor owned by a second HIP runtime without m355_frame_export_order. */
 #define M355_RESIZE_MAX_TAPS 16
 typedef struct m355_resize_desc {
   int32_t layout, samples;          /* M355_EXPORT_PLANAR / _SEMIPLANAR, M355_EXPORT_NATIVE / _MSB16 / _U8 */
@@ -584,6 +585,57 @@ typedef struct m355_resize_rgb_desc {
   int64_t pitch[3];                 /* bytes per destination row, >= the OUTPUT row's bytes */
 } m355_resize_rgb_desc;             /* (LP64: 88 bytes) */
 M355_API int   m355_frame_export_resized_rgb(m355_ctx* ctx, int frame, const m355_resize_rgb_desc* desc);   /* asynchronous */
+/* A BATCH of frames, each resized and converted to R'G'B' as above, NORMALISED and delivered as ONE float tensor in one launch (k_export_tensor.hip):
+ * the input of a model on the same GPU.  The definition is again a composition:
+ *   channel c (0 = R, 1 = G, 2 = B) of pixel (x, y) of slice i starts as the integer v that m355_frame_export_resized_rgb delivers for frames[i]
+ *   with this rectangle, this output size and the descriptor's samples (M355_RGB_U8: 0..255, M355_RGB_U16: 0..65535), matrix and full_range;
+ *   the element is m355_tensor_element(v, scale[c], bias[c], dtype), which is (libde265_amd/csrc/tensor_element.h: the one definition, compiled
+ *   into the kernel and into the host function):
+ *     p = (float)v                     exact
+ *     t = p * scale                    ONE binary32 multiplication, round to nearest even
+ *     r = t + bias                     ONE binary32 addition, round to nearest even — two roundings, NOT a fused multiply-add
+ *     M355_TENSOR_F32   r
+ *     M355_TENSOR_F16   r converted to IEEE binary16, round to nearest even; underflow is gradual (binary16 subnormals are produced), overflow
+ *                       gives infinity
+ *     M355_TENSOR_BF16  r converted to bfloat16, round to nearest even: (bits + 0x7FFF + ((bits >> 16) & 1)) >> 16 on r's binary32 bit pattern
+ *   *bits receives the element's bit pattern in the low 32 (F32) or 16 bits; the call returns M355_ERR_INVALID for an unknown dtype, a scale or bias
+ *   that is not finite, or a null `bits`, and is host only.
+ * A monochrome frame gives three equal channels before normalisation.  Cases in which t or r is a NONZERO binary32 SUBNORMAL are outside the
+ * contract (the device may flush them to zero); v = 0 and bias = 0 give an exact zero and are inside it.
+ * Where the elements go (eb = 4 for F32, else 2; strides in BYTES):
+ *   M355_TENSOR_NCHW   element (n, c, y, x) at dst + n * stride_n + c * stride_c + y * stride_h + x * eb
+ *   M355_TENSOR_NHWC   element (n, y, x, c) at dst + n * stride_n + y * stride_h + (3 * x + c) * eb       (stride_c is not used)
+ * Bytes that are no element of the tensor — row padding, gaps between planes and between slices — are never written.  The same frame may appear
+ * more than once in `frames`.
+ * M355_ERR_INVALID (nothing is enqueued, no destination byte written): n outside 1..M355_TENSOR_MAX_FRAMES, null `frames`, null descriptor, a bad
+ * handle; frames whose chroma format, bit depths or element size differ from frames[0]'s; a frame that does not contain the rectangle — with
+ * width == 0 (the whole frame) every frame must have frames[0]'s size —; whatever m355_frame_export_resized_rgb rejects for the rectangle, the output
+ * size, the ratio, samples, matrix and full_range; an unknown layout or dtype; a scale or bias that is not finite; a null dst; a dst or a USED
+ * stride (stride_h; stride_c for NCHW; stride_n for n > 1) that is no multiple of eb; stride_h below the row's bytes (row = out_width * eb for NCHW,
+ * 3 * out_width * eb for NHWC); strides that make planes or slices overlap — with E = (out_height - 1) * stride_h + row:
+ *   NCHW  stride_c >= E, and for n > 1  stride_n >= 2 * stride_c + E            NHWC  for n > 1  stride_n >= E.
+ * Ordering and the gate: asynchronous, and a reader of the kind of m355_frame_export of EVERY frame of the batch.  The launch is queued on the
+ * stream of frames[0]'s last writer, which first continues behind the last writer and the earlier export of every other frame of the batch; ONE
+ * mark behind the launch is kept by every frame, so m355_frame_export_wait / m355_frame_export_order on ANY frame of the batch cover the whole
+ * tensor, and the next decode into any of those frames waits for it.  Every frame carries its own gate: a slice whose frame sits behind a rejected
+ * decode is not written, the other slices are.  Tile-sharded contexts: as m355_frame_export_resized_rgb. */
+#define M355_TENSOR_MAX_FRAMES 32
+#define M355_TENSOR_NCHW 0
+#define M355_TENSOR_NHWC 1
+#define M355_TENSOR_F32  0
+#define M355_TENSOR_F16  1   /* IEEE binary16 */
+#define M355_TENSOR_BF16 2
+typedef struct m355_tensor_desc {
+  int32_t layout, dtype;                 /* M355_TENSOR_NCHW / _NHWC, M355_TENSOR_F32 / _F16 / _BF16 */
+  int32_t samples, matrix, full_range;   /* the INTEGER stage: M355_RGB_U8 / _U16, M355_MATRIX_*, 0 / 1, as m355_rgb_desc */
+  int32_t x0, y0, width, height;         /* source luma rectangle, the same in every frame (width == 0: the whole frame) */
+  int32_t out_width, out_height;         /* luma size of every slice */
+  float   scale[3], bias[3];             /* per channel R, G, B */
+  void*   dst;                           /* device memory, or m355_host_alloc memory */
+  int64_t stride_n, stride_c, stride_h;  /* BYTES */
+} m355_tensor_desc;                      /* (LP64: 104 bytes) */
+M355_API int   m355_frames_export_tensor(m355_ctx* ctx, const int* frames, int n, const m355_tensor_desc* desc);   /* asynchronous */
+M355_API int   m355_tensor_element(uint32_t v, float scale, float bias, int dtype, uint32_t* bits);                 /* host only */
 M355_API int   m355_frame_export_wait(m355_ctx* ctx, int frame);
 M355_API int   m355_frame_export_order(m355_ctx* ctx, int frame, void* consumer_hipStream);
 /* Device memory for export destinations and blocking copies out of / into it, for applications (and the tests) that keep a second HIP

@@ -80,6 +80,22 @@ class ResizeRgbDesc(ctypes.Structure):
                 ("dst", ctypes.c_void_p * 3), ("pitch", ctypes.c_int64 * 3)]
 
 
+TENSOR_MAX_FRAMES = 32
+TENSOR_NCHW, TENSOR_NHWC = 0, 1
+TENSOR_F32, TENSOR_F16, TENSOR_BF16 = 0, 1, 2
+
+
+class TensorDesc(ctypes.Structure):
+    """m355_tensor_desc (include/de265_mi355x.h)"""
+    _fields_ = [("layout", ctypes.c_int32), ("dtype", ctypes.c_int32),
+                ("samples", ctypes.c_int32), ("matrix", ctypes.c_int32), ("full_range", ctypes.c_int32),
+                ("x0", ctypes.c_int32), ("y0", ctypes.c_int32), ("width", ctypes.c_int32), ("height", ctypes.c_int32),
+                ("out_width", ctypes.c_int32), ("out_height", ctypes.c_int32),
+                ("scale", ctypes.c_float * 3), ("bias", ctypes.c_float * 3),
+                ("dst", ctypes.c_void_p),
+                ("stride_n", ctypes.c_int64), ("stride_c", ctypes.c_int64), ("stride_h", ctypes.c_int64)]
+
+
 class RgbCoeffs(ctypes.Structure):
     """m355_rgb_coeffs (include/de265_mi355x.h)"""
     _fields_ = [(n, ctypes.c_int32) for n in ("F", "y0", "c0", "cy", "crv", "cgu", "cgv", "cbu")]
@@ -155,6 +171,9 @@ class Library:
             L.m355_resize_taps.argtypes = [i, i, i, i, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]
         if hasattr(L, "m355_frame_export_resized_rgb"):  # (absent from older builds loaded through M355_LIB for an A/B)
             L.m355_frame_export_resized_rgb.argtypes = [vp, i, ctypes.POINTER(ResizeRgbDesc)]
+        if hasattr(L, "m355_frames_export_tensor"):     # (absent from older builds loaded through M355_LIB for an A/B)
+            L.m355_frames_export_tensor.argtypes = [vp, ctypes.POINTER(i), i, ctypes.POINTER(TensorDesc)]
+            L.m355_tensor_element.argtypes = [ctypes.c_uint32, ctypes.c_float, ctypes.c_float, i, ctypes.POINTER(ctypes.c_uint32)]
         L.m355_host_alloc.argtypes = [ctypes.c_size_t]
         L.m355_host_alloc.restype = vp
         L.m355_host_free.argtypes = [vp]
@@ -229,6 +248,12 @@ class Library:
         first, coeff = ctypes.c_int32(), (ctypes.c_int32 * RESIZE_MAX_TAPS)()
         n = self.lib.m355_resize_taps(src_n, dst_n, cosited, i, ctypes.byref(first), coeff)
         return None if n < 0 else (int(first.value), [int(coeff[k]) for k in range(n)])
+
+    def tensor_element(self, v, scale, bias, dtype):
+        """the float stage of m355_frames_export_tensor for one integer (m355_tensor_element; host only) -> the element's bit pattern"""
+        bits = ctypes.c_uint32(0)
+        self.check(self.lib.m355_tensor_element(v, scale, bias, dtype, ctypes.byref(bits)))
+        return int(bits.value)
 
     def pack_narrow(self, pic):
         """m355_pack_narrow on a picture's residual records and coefficient list (host only; worklist.pack_narrow is the numpy
@@ -526,6 +551,68 @@ class Context:
                 self.L.lib.m355_host_free(p) if host else self.device_free(p)
             raise
         return (f, shapes, bufs, [int(desc.pitch[k]) for k in range(len(shapes))], host)
+
+    def tensor_element(self, v, scale, bias, dtype):
+        """the float stage of m355_frames_export_tensor for one integer (m355_tensor_element) -> the element's bit pattern"""
+        return self.L.tensor_element(v, scale, bias, dtype)
+
+    def frames_export_tensor(self, frames, layout, dtype, samples, matrix, full_range, out_size, scale, bias, rect=None, host=False, pad=20):
+        """start m355_frames_export_tensor of the frames (handles; the same one may repeat) to out_size = (out_width, out_height) luma samples each
+        (rect = the source rectangle (x0, y0, width, height) in luma samples, the same in every frame; None: the whole frame) into ONE buffer of its
+        own, made as frame_export_resized_rgb makes its buffers: every byte holds DEVICE_FILL beforehand, and every stride is `pad` bytes (a multiple
+        of the element size) above the smallest one the call accepts — stride_h above the row, stride_c above a plane, stride_n above a slice.
+        scale, bias: three floats each (R, G, B).  -> token for tensor_export_finish"""
+        w, h = out_size
+        n, eb = len(frames), (4 if dtype == TENSOR_F32 else 2)
+        row = w * eb * (3 if layout == TENSOR_NHWC else 1)
+        stride_h = row + pad
+        extent = (h - 1) * stride_h + row
+        stride_c = extent + pad if layout == TENSOR_NCHW else 0
+        stride_n = (2 * stride_c + extent if layout == TENSOR_NCHW else extent) + pad
+        nbytes = (n - 1) * stride_n + (2 * stride_c + extent)
+        desc = TensorDesc(layout=layout, dtype=dtype, samples=samples, matrix=matrix, full_range=full_range, out_width=w, out_height=h,
+                          stride_n=stride_n, stride_c=stride_c, stride_h=stride_h)
+        desc.scale = (ctypes.c_float * 3)(*scale)
+        desc.bias = (ctypes.c_float * 3)(*bias)
+        if rect is not None:
+            desc.x0, desc.y0, desc.width, desc.height = rect
+        if host:
+            p = self.L.lib.m355_host_alloc(nbytes)
+            if not p:
+                raise M355Error(4, self.L.error())
+            ctypes.memset(p, DEVICE_FILL, nbytes)
+        else:
+            p = self.device_alloc(nbytes)
+        desc.dst = p
+        try:
+            self.L.check(self.L.lib.m355_frames_export_tensor(self.h, (ctypes.c_int * n)(*frames), n, ctypes.byref(desc)))
+        except Exception:
+            self.L.lib.m355_host_free(p) if host else self.device_free(p)
+            raise
+        return (list(frames), (n, h, w), layout, eb, p, nbytes, (stride_n, stride_c, stride_h), host)
+
+    def tensor_export_finish(self, token, wait_frame=None):
+        """the tensor of a frames_export_tensor, read back (device buffer: m355_device_read, which waits for the context's work; pinned host buffer:
+        behind m355_frame_export_wait of wait_frame, default the batch's last frame) and freed -> (elements, raw, outside): the elements' bit
+        patterns as a uint16 / uint32 array of shape (n, 3, h, w) or (n, h, w, 3), the whole buffer as bytes, and the bytes of it that are no
+        element of the tensor"""
+        frames, (n, h, w), layout, eb, p, nbytes, (stride_n, stride_c, stride_h), host = token
+        if host:
+            self.L.check(self.L.lib.m355_frame_export_wait(self.h, frames[-1] if wait_frame is None else wait_frame))
+            raw = np.ctypeslib.as_array(ctypes.cast(p, ctypes.POINTER(ctypes.c_uint8)), (nbytes,)).copy()
+            self.L.lib.m355_host_free(p)
+        else:
+            raw = self.device_read(p, nbytes)
+            self.device_free(p)
+        if layout == TENSOR_NCHW:
+            shape, strides = (n, 3, h, w, eb), (stride_n, stride_c, stride_h, eb, 1)
+        else:
+            shape, strides = (n, h, w, 3, eb), (stride_n, stride_h, 3 * eb, eb, 1)
+        view = np.lib.stride_tricks.as_strided(raw, shape, strides)
+        elements = np.ascontiguousarray(view).view(np.uint32 if eb == 4 else np.uint16).reshape(shape[:-1])
+        inside = np.zeros(nbytes, np.uint8)
+        np.lib.stride_tricks.as_strided(inside, shape, strides)[...] = 1
+        return elements, raw, raw[inside == 0]
 
     def frame_export_finish(self, token, raw=False):
         """the planes of a frame_export, read back (device buffers: m355_device_read, which waits for the context's work; pinned host buffers:

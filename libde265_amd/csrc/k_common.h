@@ -353,6 +353,30 @@ struct ExportResizedRgbArgs {
 /* src_bytes / dst_bytes: 1 or 2 per sample / channel */
 void m355_launch_export_resized_rgb(const ExportResizedRgbArgs& a, int src_bytes, int dst_bytes, hipStream_t st);
 
+/* one m355_frames_export_tensor (k_export_tensor.hip): the tile procedure of k_export_resized_rgb over n frames in one grid, unit = slice * units + the
+   tile inside the slice (units tiles per slice).  Per slice: src[] = the rectangle's first sample of Y, Cb, Cr in that frame, its two pitches (BYTES)
+   and the gate of the decode that wrote it.  Everything else is the batch's, with the meanings of ExportResizedRgbArgs: the grids, the tile width,
+   cf, bdl / bdc, k.  u16: the integer stage is M355_RGB_U16 (clip to 65535, else 255); nhwc / bf16: layout and, for 2-byte elements, the format;
+   dst and the strides (BYTES) as in m355_tensor_desc. */
+struct ExportTensorFrame {
+  const uint8_t* src[3];
+  long long src_pitch[2];
+  const uint32_t* timeout;
+  uint32_t epoch, pad;
+};
+struct ExportTensorArgs {
+  uint8_t* dst;
+  long long stride_n, stride_c, stride_h;
+  uint32_t sn_x[2], sn_y[2], dn_x[2], dn_y[2];
+  uint32_t tile_w, tiles_x, units, n;
+  int32_t cf, nhwc, bf16, u16, bdl, bdc;
+  float scale[3], bias[3];
+  m355_rgb_coeffs k;
+  ExportTensorFrame fr[M355_TENSOR_MAX_FRAMES];
+};
+/* src_bytes: 1 or 2 per sample; elem_bytes: 2 (F16 / BF16) or 4 (F32) */
+void m355_launch_export_tensor(const ExportTensorArgs& a, int src_bytes, int elem_bytes, hipStream_t st);
+
 /* first statement of every kernel of a decode: a picture whose lists k_validate rejected is never acted upon */
 /* Element `c` (0..2, per lane) of a three-entry table of the kernel arguments (plane pointers, pitches, ...): all three entries are
  * read as scalars and the lane selects — indexing the argument segment with a per-lane value is a VECTOR memory load from it, i.e. one

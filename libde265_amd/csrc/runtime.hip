@@ -11,6 +11,7 @@
  */
 #include "runtime_internal.h"
 #include "resize_taps.h"
+#include "tensor_element.h"
 
 thread_local std::string g_err;
 int fail(int code, const char* fmt, ...)
@@ -751,6 +752,101 @@ int m355_frame_export_resized_rgb(m355_ctx* c, int h, const m355_resize_rgb_desc
   m355_launch_export_resized_rgb(a, sb, db, cs);
   HIPCHK(hipGetLastError());
   return reader_end(c, f, RD_EXPORT, cs);
+}
+/* the float stage of m355_frames_export_tensor for one value (tensor_element.h: the function the kernel calls) */
+int m355_tensor_element(uint32_t v, float scale, float bias, int dtype, uint32_t* bits)
+{
+  const auto finite = [](float x) { return (m355_te_bits(x) & 0x7F800000u) != 0x7F800000u; };
+  if (!bits || (dtype != M355_TENSOR_F32 && dtype != M355_TENSOR_F16 && dtype != M355_TENSOR_BF16) || !finite(scale) || !finite(bias))
+    return fail(M355_ERR_INVALID, "m355_tensor_element: null result / unknown dtype %d / scale or bias not finite", dtype);
+  *bits = m355_te_element(v, scale, bias, dtype);
+  return M355_OK;
+}
+/* A batch of frames resized, converted, normalised and delivered as one float tensor in one launch (k_export_tensor.hip).  Every frame's handle and
+ * the rectangle in it are checked by export_plan — with destinations that cannot fail —, the output size, the ratio and the conversion as for
+ * m355_frame_export_resized_rgb, the tensor's layout here.  A reader of the kind RD_EXPORT of EVERY frame of the batch, as m355_frame_measure_async is
+ * of its two: the launch goes on the stream of frames[0]'s writer, which first continues behind the writer and the earlier export of each other
+ * frame; the one mark behind the launch is kept by all of them; each frame brings its own gate. */
+int m355_frames_export_tensor(m355_ctx* c, const int* frames, int n, const m355_tensor_desc* e)
+{
+  const char* who = "m355_frames_export_tensor";
+  if (!c || !frames || !e || n < 1 || n > M355_TENSOR_MAX_FRAMES) return fail(M355_ERR_INVALID, "%s: no context / frames / descriptor, or %d frames are not 1..%d", who, n, M355_TENSOR_MAX_FRAMES);
+  m355_export_desc yuv = {};
+  yuv.layout = M355_EXPORT_PLANAR; yuv.samples = M355_EXPORT_NATIVE;
+  yuv.x0 = e->x0; yuv.y0 = e->y0; yuv.width = e->width; yuv.height = e->height;
+  for (int p = 0; p < 3; p++) { yuv.dst[p] = (void*)e; yuv.pitch[p] = INT64_MAX; }
+  ExportPlan P[M355_TENSOR_MAX_FRAMES];
+  for (int i = 0; i < n; i++) {
+    int rc = export_plan(c, frames[i], &yuv, 0, who, P[i]);
+    if (rc) return rc;
+    const Frame *f = P[i].f, *f0 = P[0].f;
+    if (f->cf != f0->cf || f->bdl != f0->bdl || f->bdc != f0->bdc || f->bpp[0] != f0->bpp[0])
+      return fail(M355_ERR_INVALID, "%s: chroma format / bit depths of frame %d (entry %d) differ from those of frame %d", who, frames[i], i, frames[0]);
+    if (e->width == 0 && (f->w != f0->w || f->h != f0->h))
+      return fail(M355_ERR_INVALID, "%s: whole frames of different sizes (%dx%d, entry %d: %dx%d)", who, f0->w, f0->h, i, f->w, f->h);
+  }
+  Frame* f = P[0].f;
+  const ExportPlan& Q = P[0];
+  const int sw = (f->cf == 1 || f->cf == 2) ? 2 : 1, sh = f->cf == 1 ? 2 : 1;
+  if (e->out_width <= 0 || e->out_height <= 0 || e->out_width % sw || e->out_height % sh)
+    return fail(M355_ERR_INVALID, "%s: output size %dx%d is not positive or no multiple of %dx%d luma samples", who, e->out_width, e->out_height, sw, sh);
+  if (!m355_resize_ratio_ok(Q.p[0].pw, e->out_width) || !m355_resize_ratio_ok(Q.p[0].ph, e->out_height))
+    return fail(M355_ERR_INVALID, "%s: %dx%d to %dx%d is more than 8x down or up", who, Q.p[0].pw, Q.p[0].ph, e->out_width, e->out_height);
+  if (e->layout != M355_TENSOR_NCHW && e->layout != M355_TENSOR_NHWC) return fail(M355_ERR_INVALID, "%s: unknown layout %d", who, e->layout);
+  if (e->dtype != M355_TENSOR_F32 && e->dtype != M355_TENSOR_F16 && e->dtype != M355_TENSOR_BF16) return fail(M355_ERR_INVALID, "%s: unknown dtype %d", who, e->dtype);
+  ExportTensorArgs a = {};
+  int rc = m355_rgb_coefficients(e->matrix, e->full_range, f->bdl, f->bdc, e->samples, &a.k);
+  if (rc) return rc;
+  for (int k = 0; k < 3; k++) {
+    if ((m355_te_bits(e->scale[k]) & 0x7F800000u) == 0x7F800000u || (m355_te_bits(e->bias[k]) & 0x7F800000u) == 0x7F800000u)
+      return fail(M355_ERR_INVALID, "%s: scale / bias of channel %d is not finite", who, k);
+    a.scale[k] = e->scale[k]; a.bias[k] = e->bias[k];
+  }
+  const bool nhwc = e->layout == M355_TENSOR_NHWC;
+  const int eb = e->dtype == M355_TENSOR_F32 ? 4 : 2, sb = f->bpp[0];
+  const int64_t row = (int64_t)e->out_width * eb * (nhwc ? 3 : 1);
+  if (!e->dst) return fail(M355_ERR_INVALID, "%s: no destination", who);
+  if (((uintptr_t)e->dst | (uint64_t)e->stride_h | (nhwc ? 0u : (uint64_t)e->stride_c) | (n > 1 ? (uint64_t)e->stride_n : 0u)) & (uint64_t)(eb - 1))
+    return fail(M355_ERR_INVALID, "%s: the destination or a stride is no multiple of the %d-byte element", who, eb);
+  if (e->stride_h < row) return fail(M355_ERR_INVALID, "%s: stride_h %lld is below the row of %lld bytes", who, (long long)e->stride_h, (long long)row);
+  const __int128 E = (__int128)(e->out_height - 1) * e->stride_h + row;              /* first byte behind a plane's (NHWC: a slice's) last row */
+  if (!nhwc && (__int128)e->stride_c < E) return fail(M355_ERR_INVALID, "%s: stride_c %lld lets the planes overlap (%lld bytes each)", who, (long long)e->stride_c, (long long)E);
+  if (n > 1 && (__int128)e->stride_n < (nhwc ? E : 2 * (__int128)e->stride_c + E))
+    return fail(M355_ERR_INVALID, "%s: stride_n %lld lets the slices overlap", who, (long long)e->stride_n);
+  a.dst = (uint8_t*)e->dst; a.stride_n = n > 1 ? e->stride_n : 0; a.stride_c = nhwc ? 0 : e->stride_c; a.stride_h = e->stride_h;
+  a.sn_x[0] = (uint32_t)Q.p[0].pw; a.sn_y[0] = (uint32_t)Q.p[0].ph; a.dn_x[0] = (uint32_t)e->out_width; a.dn_y[0] = (uint32_t)e->out_height;
+  if (Q.np > 1) { a.sn_x[1] = (uint32_t)Q.p[1].pw; a.sn_y[1] = (uint32_t)Q.p[1].ph; a.dn_x[1] = (uint32_t)(e->out_width / sw); a.dn_y[1] = (uint32_t)(e->out_height / sh); }
+  a.tile_w = resize_rgb_tile_w(Q.p[0].pw, e->out_width, Q.np > 1 ? Q.p[1].pw : 0, e->out_width / sw, sb, sw);
+  a.tiles_x = ((uint32_t)e->out_width + a.tile_w - 1) / a.tile_w;
+  a.units = a.tiles_x * (((uint32_t)e->out_height + M355_RESIZE_TILE_H - 1) / M355_RESIZE_TILE_H);
+  a.n = (uint32_t)n;
+  a.cf = f->cf; a.nhwc = nhwc; a.bf16 = e->dtype == M355_TENSOR_BF16; a.u16 = e->samples == M355_RGB_U16; a.bdl = f->bdl; a.bdc = f->bdc;
+  for (int i = 0; i < n; i++) {
+    ExportTensorFrame& r = a.fr[i];
+    for (int p = 0; p < P[i].np; p++) r.src[p] = P[i].p[p].src[0];
+    r.src_pitch[0] = P[i].p[0].src_pitch; r.src_pitch[1] = P[i].np > 1 ? P[i].p[1].src_pitch : 0;
+  }
+  hipSetDevice(c->device);
+  const hipStream_t cs = reader_begin(c, f, RD_EXPORT, &a.fr[0].timeout, &a.fr[0].epoch);
+  for (int i = 1; i < n; i++) {
+    Frame* g = P[i].f;
+    int first = 0;
+    while (P[first].f != g) first++;
+    if (first < i) { a.fr[i].timeout = a.fr[first].timeout; a.fr[i].epoch = a.fr[first].epoch; continue; }   /* the same frame again */
+    ev_wait(c, cs, g->wr);                                  /* the frame's last writer (nothing to enqueue when that ran on `cs`) */
+    ev_wait(c, cs, g->reader[RD_EXPORT]);                   /* ... and its earlier export on another stream: the one mark kept stands for both */
+    if (g->wr_stream && g->wr_gate) { a.fr[i].timeout = g->wr_gate; a.fr[i].epoch = g->wr_epoch; }
+    else {                                                  /* no decode to be gated by: an epoch of its own, which no gate word holds (reader_begin) */
+      a.fr[i].timeout = lane(c).timeout; a.fr[i].epoch = ++c->epoch;
+      if (a.fr[i].epoch == 0) a.fr[i].epoch = ++c->epoch;
+    }
+  }
+  m355_launch_export_tensor(a, sb, eb, cs);
+  HIPCHK(hipGetLastError());
+  rc = reader_end(c, f, RD_EXPORT, cs);
+  if (rc) return rc;
+  for (int i = 1; i < n; i++) P[i].f->reader[RD_EXPORT] = f->reader[RD_EXPORT];
+  return M355_OK;
 }
 /* the host waits until this frame's last export has landed */
 int m355_frame_export_wait(m355_ctx* c, int h)

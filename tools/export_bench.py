@@ -18,6 +18,11 @@
   (t), (u), (v) m355_frame_export_rgb of a frame of the resized size — the second half of the chain that (q), (r), (s) replace: U8 packed and U16
       planar of the 1920x1080 window of a 1920x1088 10-bit frame, U8 planar of a 1280x720 frame.  One launch must not lose to the two it fuses:
       the bars are (q) <= (m) + (t), (r) <= (m) + (u), (s) <= (p) + (v), each + the spread of (b)
+  (w), (x) m355_frames_export_tensor of the one frame, F16 NHWC to 1920x1080, and m355_frame_export_resized_rgb U16 packed of the same geometry: the
+      same bytes written, only the epilogue differs; the bar is (w) <= (x) + the spread of (b).  (r) is the planar row beside (x)
+  (y8), (z8), (y32), (z32) a 224x224 export of the 1080x1080 window (420, 0) of N = 8 / 32 frames of 1920x1088: (y) N consecutive
+      m355_frame_export_resized_rgb U8 planar launches, one per frame; (z) ONE m355_frames_export_tensor batch of the same N frames, F16 NCHW.  A
+      slice is 14 workgroups, so a single launch leaves most of the chip empty; the bars are (z) <= (y) + the spread of (b)
 
 and, beside them, m355_measure_copy_rate for the frame's byte count.  Every figure is the median of --iters launches; (b) is measured in
 --rounds separate rounds spread over the run, and the spread of their medians is the margin (c), (d), (g)-(j) and (m)-(p) are held against: a scaled or resized export reads exactly (b)'s source bytes and writes at most a
@@ -142,6 +147,43 @@ def main():
             d.dst[k] = rgb_dst[k]; d.pitch[k] = size[0] * elem * (1 if layout == capi.RGB_PLANAR else 3)
         return lambda: lib.check(lib.lib.m355_frame_export_rgb(ctx.h, small[size], ctypes.byref(d)))
 
+    def export_tensor(frames, layout, dtype, samples, out_size, rect=None):
+        eb = 4 if dtype == capi.TENSOR_F32 else 2
+        ow, oh = out_size
+        row = ow * eb * (3 if layout == capi.TENSOR_NHWC else 1)
+        sc = oh * row if layout == capi.TENSOR_NCHW else 0
+        d = capi.TensorDesc(layout=layout, dtype=dtype, samples=samples, matrix=capi.MATRIX_BT709, full_range=0, out_width=ow, out_height=oh,
+                            stride_n=3 * ow * oh * eb, stride_c=sc, stride_h=row)
+        M = 65535.0 if samples == capi.RGB_U16 else 255.0
+        d.scale = (ctypes.c_float * 3)(*[1.0 / (M * x) for x in (0.229, 0.224, 0.225)])
+        d.bias = (ctypes.c_float * 3)(*[-m / x for m, x in zip((0.485, 0.456, 0.406), (0.229, 0.224, 0.225))])
+        if rect:
+            d.x0, d.y0, d.width, d.height = rect
+        assert len(frames) * 3 * ow * oh * eb <= W * 3 * H
+        d.dst = rgb_dst[0]
+        arr = (ctypes.c_int * len(frames))(*frames)
+        return lambda: lib.check(lib.lib.m355_frames_export_tensor(ctx.h, arr, len(frames), ctypes.byref(d)))
+
+    # the frames of the batch rows: 32 frames of 1920x1088, of which the centre square goes to a model's 224x224
+    batch = [ctx.frame_create(1920, 1088, 1, BD, BD) for _ in range(32)]
+    for k, f in enumerate(batch):
+        ctx.frame_fill(f, 300 + 20 * k, 400 + 10 * k)
+    SQUARE = (420, 0, 1080, 1080)
+
+    def singles(n):
+        descs = []
+        for k in range(n):
+            d = capi.ResizeRgbDesc(layout=capi.RGB_PLANAR, samples=capi.RGB_U8, matrix=capi.MATRIX_BT709, full_range=0, out_width=224, out_height=224)
+            d.x0, d.y0, d.width, d.height = SQUARE
+            for c in range(3):
+                d.dst[c] = rgb_dst[0] + (3 * k + c) * 224 * 224; d.pitch[c] = 224
+            descs.append(d)
+
+        def run():
+            for k in range(n):
+                lib.check(lib.lib.m355_frame_export_resized_rgb(ctx.h, batch[k], ctypes.byref(descs[k])))
+        return run
+
     variants = {
         "a_memcpy2d_x3": copies,
         "b_native_planar": export(capi.EXPORT_PLANAR, capi.EXPORT_NATIVE, None, 2),
@@ -166,6 +208,12 @@ def main():
         "t_rgb_u8_packed_of_1080p": export_rgb_small(capi.RGB_PACKED, capi.RGB_U8, (1920, 1080), 1),
         "u_rgb_u16_planar_of_1080p": export_rgb_small(capi.RGB_PLANAR, capi.RGB_U16, (1920, 1080), 2),
         "v_rgb_u8_planar_of_720p": export_rgb_small(capi.RGB_PLANAR, capi.RGB_U8, (1280, 720), 1),
+        "w_tensor_f16_nhwc_1080p": export_tensor([frame], capi.TENSOR_NHWC, capi.TENSOR_F16, capi.RGB_U16, (1920, 1080)),
+        "x_resized_rgb_u16_packed_1080p": export_resized_rgb(capi.RGB_PACKED, capi.RGB_U16, (1920, 1080), 2),
+        "y8_resized_rgb_u8_planar_224_x8": singles(8),
+        "z8_tensor_f16_nchw_224_batch8": export_tensor(batch[:8], capi.TENSOR_NCHW, capi.TENSOR_F16, capi.RGB_U8, (224, 224), SQUARE),
+        "y32_resized_rgb_u8_planar_224_x32": singles(32),
+        "z32_tensor_f16_nchw_224_batch32": export_tensor(batch, capi.TENSOR_NCHW, capi.TENSOR_F16, capi.RGB_U8, (224, 224), SQUARE),
     }
     scaled = [n for n in variants if n[0] in "ghijmnop"]
     ms = {n: [] for n in variants}
@@ -189,6 +237,11 @@ def main():
         "resized_rgb": {"q_over_m_plus_t": res["q_resized_rgb_u8_packed_1080p"] / (res["m_resized_native_planar_1080p"] + res["t_rgb_u8_packed_of_1080p"]),
                         "r_over_m_plus_u": res["r_resized_rgb_u16_planar_1080p"] / (res["m_resized_native_planar_1080p"] + res["u_rgb_u16_planar_of_1080p"]),
                         "s_over_p_plus_v": res["s_resized_rgb_u8_planar_720p"] / (res["p_resized_native_planar_720p"] + res["v_rgb_u8_planar_of_720p"])},
+        "tensor": {"w_over_x": res["w_tensor_f16_nhwc_1080p"] / res["x_resized_rgb_u16_packed_1080p"],
+                   "z8_over_y8": res["z8_tensor_f16_nchw_224_batch8"] / res["y8_resized_rgb_u8_planar_224_x8"],
+                   "z32_over_y32": res["z32_tensor_f16_nchw_224_batch32"] / res["y32_resized_rgb_u8_planar_224_x32"],
+                   "us_per_frame": {n: 1e3 * res[n] / k for n, k in (("y8_resized_rgb_u8_planar_224_x8", 8), ("z8_tensor_f16_nchw_224_batch8", 8),
+                                                                    ("y32_resized_rgb_u8_planar_224_x32", 32), ("z32_tensor_f16_nchw_224_batch32", 32))}},
         "copy_rate_GBps_same_bytes": ctx.measure_copy_rate(frame_bytes, 9),
         "bars": {"b_le_a": res["b_native_planar"] <= res["a_memcpy2d_x3"],
                  "c_le_b_plus_spread": res["c_msb16_semiplanar_crop8"] <= res["b_native_planar"] + spread,
@@ -196,7 +249,10 @@ def main():
                  **{n[0] + "_le_b_plus_spread": res[n] <= res["b_native_planar"] + spread for n in scaled},
                  "q_le_m_plus_t_plus_spread": res["q_resized_rgb_u8_packed_1080p"] <= res["m_resized_native_planar_1080p"] + res["t_rgb_u8_packed_of_1080p"] + spread,
                  "r_le_m_plus_u_plus_spread": res["r_resized_rgb_u16_planar_1080p"] <= res["m_resized_native_planar_1080p"] + res["u_rgb_u16_planar_of_1080p"] + spread,
-                 "s_le_p_plus_v_plus_spread": res["s_resized_rgb_u8_planar_720p"] <= res["p_resized_native_planar_720p"] + res["v_rgb_u8_planar_of_720p"] + spread},
+                 "s_le_p_plus_v_plus_spread": res["s_resized_rgb_u8_planar_720p"] <= res["p_resized_native_planar_720p"] + res["v_rgb_u8_planar_of_720p"] + spread,
+                 "w_le_x_plus_spread": res["w_tensor_f16_nhwc_1080p"] <= res["x_resized_rgb_u16_packed_1080p"] + spread,
+                 "z8_le_y8_plus_spread": res["z8_tensor_f16_nchw_224_batch8"] <= res["y8_resized_rgb_u8_planar_224_x8"] + spread,
+                 "z32_le_y32_plus_spread": res["z32_tensor_f16_nchw_224_batch32"] <= res["y32_resized_rgb_u8_planar_224_x32"] + spread},
     }
     line = json.dumps(out)
     print(line)
@@ -205,7 +261,7 @@ def main():
             f.write(line + "\n")
     for p in src + dst + rgb_dst:
         ctx.device_free(p)
-    for f in small.values():
+    for f in list(small.values()) + batch:
         ctx.frame_destroy(f)
     ctx.close()
 
