@@ -162,6 +162,12 @@ struct DevPic {
                                        Inter pictures: first the n_intra_ticket CTBs of dependency chains, longest remaining chain first (ticket
                                        order: a producer precedes its readers), then the CTBs without dependencies (by workgroup index) */
   int n_intra_work, n_intra_ticket;
+  /* inter pictures (k_intra_light.h): the work items [n_intra_heavy, n_intra_work) — CTBs without a cross-CTB dependency — are not run by a workgroup
+     each but as LIGHT items, one wave per (work item, colour component): x = the CTB's raster address | component << 30, y = the first of the component's
+     blocks in ibs[] / ib_aux[] (the CTB's sorted run), z = records from there to its last one, w = the work item's plan_base.  n_intra_heavy ==
+     n_intra_work, no items: intra pictures, sharded phases, 16-bit residuals */
+  int n_intra_heavy, n_intra_light;
+  const uint4* intra_light;
   int intra_grid;                   /* intra pictures: workgroups of k_intra's launch (persistent: each takes CTB after CTB); 0 = one per CTB */
   int intra_keeper;                 /* intra pictures: launch k_intra with its halo keeper wave (one picture at a time; k_intra.hip) */
   int test_halo_late;               /* test hook (M355_TEST_HALO_LATE=1, tests/test_intra_halo_late.py): k_intra's prologue takes no neighbour's

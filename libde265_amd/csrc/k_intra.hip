@@ -39,6 +39,9 @@
  *   - inside the workgroup the blocks run LEVEL BY LEVEL (host-derived levels, runtime_upload.hip intra_schedule: blocks of
  *     one level are independent); each colour component has 1, 2, 4 or 8 wavefronts that share a level's blocks, with
  *     a workgroup barrier between levels when there is more than one wave per component;
+ *   - inter pictures: the CTBs that take no part in a dependency chain — eight in ten at 8K — need none of this and do not get a workgroup: they run as
+ *     LIGHT items of the same launch, one wave per CTB and colour component that gathers each border straight from the picture (k_intra_light.h; the
+ *     block arithmetic of both paths is k_intra_block.h's);
  *   - the inverse transforms were done up front, in parallel, by k_residual.
  */
 #include <stdlib.h>
@@ -47,6 +50,8 @@
 #include "k_meta_tu.h"
 
 #include "k_intra_plan.h"
+#include "k_intra_block.h"
+#include "k_intra_light.h"
 typedef unsigned long long m355_granule;   /* (epoch << 32) | sample1 << 16 | sample0 */
 
 /* right-column granules of CTB column `col` of component c: index (row of the picture) >> 1 */
@@ -81,7 +86,7 @@ __device__ __forceinline__ uint32_t d_poll_halo(const m355_granule* top_row, con
 
 template <int CF> __global__ void __launch_bounds__(256) k_intra_plan(DevPic p, int work_n) { k_intra_plan_body<CF>(p, work_n, (int)blockIdx.x, (int)blockIdx.y, (int)gridDim.y); }
 template <int CF> __global__ void __launch_bounds__(256) k_intra_plan_batch(DevBatch b) { M355_BATCH_PIC(b); k_intra_plan_body<CF>(p, p.n_intra_work, (int)blockIdx.x, (int)blockIdx.y, (int)gridDim.y); }
-/* EXPERIMENT (M355_MERGE_TU_PLAN=1, emulator-verified only): the transform-edge scatter (k_meta_tu.h) and the border plans as ONE launch —
+/* the transform-edge scatter (k_meta_tu.h) and the border plans as ONE launch (m355_launch_tu_plan: what every picture's decode runs) —
    both only read what k_meta_planes wrote, and a launch costs about 2 us of pipeline time (profiles/r04_aj_*): blocks [0, nb_tu) walk the
    transform leaves, block nb_tu + item * n_parts + part plans part `part` of work item `item` */
 template <int CF> __global__ void __launch_bounds__(256) k_tu_plan(DevPic p, int nb_tu, int work_n, int n_parts)
@@ -148,6 +153,15 @@ __global__ void __launch_bounds__(64 * NW) M355_WAVES_PER_EU((DENSE || CF >= 2) 
      the component's plane pointers, pitches and granule offsets are scalar loads from the kernel arguments instead of vector
      loads, record fields live in SGPRs and the per-block branches are scalar */
   const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+
+  /* Inter pictures: the workgroups behind the CTB workgroups carry the LIGHT items (k_intra_light.h) — NW of them each, one per wave: the CTBs
+     without a cross-CTB dependency (runtime_upload.hip), which need none of what follows.  The waves share nothing and leave on their own. */
+  if constexpr (!DENSE && !BATCH && !W16) {
+    if ((int)blockIdx.x >= p0.n_intra_heavy) {
+      k_intra_light_item<PIX, CF>(p0, ((int)blockIdx.x - p0.n_intra_heavy) * NW + wv, s_raw[wv], s_f[wv]);
+      return;
+    }
+  }
 
   /* Work items.  Intra pictures (DENSE): the workgroup is PERSISTENT — it claims CTB after CTB through the ticket, in work-list
      order (CTBs that wait for no neighbour first, then the dependent ones in wavefront order), until the list is exhausted.  The
@@ -660,7 +674,7 @@ __global__ void __launch_bounds__(64 * NW) M355_WAVES_PER_EU((DENSE || CF >= 2) 
       /* ---- 4x4 / 8x8 (the chain of an intra picture): border entry e in lane e of ONE register, one sample per lane; every
          lane runs the arithmetic (a cross-lane read needs its source lane active), lanes beyond the block do not store ---- */
       auto small_block = [&](auto l2_) {
-        constexpr int LOG2 = decltype(l2_)::value, NT = 1 << LOG2, Z = 2 * NT, NENT = 4 * NT + 1;
+        constexpr int LOG2 = decltype(l2_)::value, NT = 1 << LOG2;
         const int x = lane & (NT - 1), y = lane >> LOG2;
         const bool inb = lane < NT * NT;
         uint32_t bv = bv0;
@@ -675,49 +689,7 @@ __global__ void __launch_bounds__(64 * NW) M355_WAVES_PER_EU((DENSE || CF >= 2) 
             bv = d_poll_halo(d_edge_row(p, cs, ctbY - 1, 0), d_edge_col(p, cs, ctbX - 1, 0), p.timeout, halo, (int)code0 - HALO_BASE, bv, pending, x0c, y0c, epoch);
         }
         PROF_T(1);
-        {   /* intra_prediction_sample_filtering (intrapred.h:185-258), [1 2 1] only (strong smoothing is 32x32) */
-          const uint32_t nb = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)bv, 0x138, 0xF, 0xF, false) + (uint32_t)__builtin_amdgcn_update_dpp(0, (int)bv, 0x130, 0xF, 0xF, false);
-          const uint32_t fbv = (nb + 2u * bv + 2u) >> 2;
-          if ((e0 & M355_IBX_FILT) && lane > 0 && lane < NENT - 1) bv = fbv;
-        }
-#define BRL(i) ((int)__builtin_amdgcn_readlane((int)bv, (i) + Z))                 /* border entry i, the same for every lane */
-#define BRP(i) ((int)__builtin_amdgcn_ds_bpermute(((i) + Z) << 2, (int)bv))       /* border entry i, per lane */
-        int v;
-        if (__builtin_expect(cls >= 3, 1)) {
-          /* angular (33 of the 35 modes; first in line, and one formula for both signs of the angle): ref[] of the reference is not
-             built — its entry i is border entry sgn*i for i >= 0 and, left of the corner (negative angles only), -sgn*((i*invAngle+128)>>8) */
-          const int a_ = vert ? y : x, b_ = vert ? x : y;
-          const int tt = __mul24(a_ + 1, angle), iIdx = tt >> 5, iFact = tt & 31;
-          const int x1 = b_ + iIdx + 1, x2 = x1 + 1;
-          const int p1 = (__mul24(x1, inv) + 128) >> 8, p2 = (__mul24(x2, inv) + 128) >> 8;     /* (invAngle is 0 for a positive angle, whose x1 is never negative) */
-          int i1 = x1 >= 0 ? x1 : -p1, i2 = x2 >= 0 ? x2 : -p2;
-          if (!vert) { i1 = -i1; i2 = -i2; }
-          const int r1 = BRP(i1), r2 = BRP(i2);
-          v = (32 * r1 + __mul24(iFact, r2 - r1) + 16) >> 5;   /* (= r1 when iFact is 0) */
-        } else if (cls == 0) {        /* planar (intrapred.h:261-285) */
-          const int l = BRP(-1 - y), t = BRP(1 + x), tr = BRL(1 + NT), bl = BRL(-1 - NT);
-          v = (__mul24(NT - 1 - x, l) + __mul24(x + 1, tr) + __mul24(NT - 1 - y, t) + __mul24(y + 1, bl) + NT) >> (LOG2 + 1);   /* (24-bit multiplies: full rate) */
-        } else if (cls == 1) {        /* DC (intrapred.h:288-310, 378-392) */
-          int s_ = (lane >= Z - NT && lane <= Z + NT && lane != Z) ? (int)bv : 0;
-          s_ += __builtin_amdgcn_update_dpp(0, s_, 0xB1, 0xF, 0xF, false);     /* quad_perm [1,0,3,2] */
-          s_ += __builtin_amdgcn_update_dpp(0, s_, 0x4E, 0xF, 0xF, false);     /* quad_perm [2,3,0,1] */
-          s_ += __builtin_amdgcn_update_dpp(0, s_, 0x141, 0xF, 0xF, false);    /* row_half_mirror */
-          s_ += __builtin_amdgcn_update_dpp(0, s_, 0x140, 0xF, 0xF, false);    /* row_mirror: every lane of a row of 16 holds the row's sum */
-          int sum = __builtin_amdgcn_readlane(s_, 0) + __builtin_amdgcn_readlane(s_, 16);
-          const int dc = (sum + NT) >> (LOG2 + 1);
-          v = dc;
-          if (bfilt) {
-            const int eb = BRP(y == 0 ? x + 1 : -y - 1), e2c = BRL(-1) + BRL(1);
-            if (x == 0 || y == 0) v = (eb + 3 * dc + 2) >> 2;
-            if (lane == 0) v = (e2c + 2 * dc + 2) >> 2;
-          }
-        } else {                      /* pure horizontal / vertical (intrapred.h:330-433 with intraPredAngle 0) */
-          const int l = BRP(-1 - y), t = BRP(1 + x), corner = BRL(0), first = vert ? BRL(1) : BRL(-1);
-          v = vert ? t : l;
-          if (bfilt && (vert ? x == 0 : y == 0)) v = d_clip3(0, pix_max, first + (((vert ? l : t) - corner) >> 1));
-        }
-#undef BRL
-#undef BRP
+        int v = d_intra_small_predict<LOG2>(bv, e0, cls, angle, inv, vert, bfilt, pix_max);      /* (k_intra_block.h) */
         v = d_clip3(0, pix_max, v + rs);   /* (a prediction is inside the sample range: no-op without a residual) */
         if (inb) body[d_baddr] = (uint16_t)v;
         /* ---- publish from the registers: a granule = two samples, the second one comes from the lane below / beside ---- */
@@ -745,7 +717,7 @@ __global__ void __launch_bounds__(64 * NW) M355_WAVES_PER_EU((DENSE || CF >= 2) 
       if (!(e0 & M355_IBX_PCM)) {
         /* ---- 16x16 / 32x32: the border lives in LDS (65 / 129 entries) ---- */
         if (it_lo < it_hi) {
-        const int nEnt = 4 * nT + 1, Z = 2 * nT;
+        const int nEnt = 4 * nT + 1;
         const uint16_t* pl = s_plan + ((e3 & 0xFFFFu) - plan_lo);
         /* (all plan entries, then all samples: two LDS round trips for the whole border, not two per 64-entry chunk) */
         uint32_t cd[3] = {0, 0, 0}, val[3] = {0, 0, 0};
@@ -779,37 +751,11 @@ __global__ void __launch_bounds__(64 * NW) M355_WAVES_PER_EU((DENSE || CF >= 2) 
         PROF_T(1);
         uint16_t* P = raw; /* border in use, entry index = i + 2nT */
         if (e0 & M355_IBX_FILT) {     /* intra_prediction_sample_filtering (intrapred.h:185-258) */
-          const bool bi = (e0 & M355_IBX_STRONG) && d_abs((int)raw[Z] + raw[Z + 64] - 2 * raw[Z + 32]) < thr_strong && d_abs((int)raw[Z] + raw[Z - 64] - 2 * raw[Z - 32]) < thr_strong;
-#pragma unroll
-          for (int q = 0; q < 3; q++) {
-            if (64 * q >= nEnt) continue;
-            const int e = lane + 64 * q;
-            if (e < nEnt) {
-              const int i = e - Z;
-              int v;
-              if (i == -Z || i == Z) v = raw[e];
-              else if (bi) {
-                if (i == 0) v = raw[Z];
-                else if (i < 0) v = raw[Z] + (((-i) * ((int)raw[Z - 64] - raw[Z]) + 32) >> 6);
-                else v = raw[Z] + ((i * ((int)raw[Z + 64] - raw[Z]) + 32) >> 6);
-              } else v = (raw[e + 1] + 2 * raw[e] + raw[e - 1] + 2) >> 2;
-              pf[e] = (uint16_t)v;
-            }
-          }
+          d_intra_big_filter(raw, pf, e0, nT, thr_strong);
           wave_sync();
           P = pf;
         }
-#define BRD(i) ((int)P[(i) + Z])
-        int dcVal = 0;
-        if (mode == 1) {
-          int s_ = 0;
-          if (lane < nT) s_ = BRD(lane + 1) + BRD(-lane - 1);
-          s_ += __builtin_amdgcn_update_dpp(0, s_, 0xB1, 0xF, 0xF, false);     /* sums over rows of 16 lanes, as in the 4x4 / 8x8 path */
-          s_ += __builtin_amdgcn_update_dpp(0, s_, 0x4E, 0xF, 0xF, false);
-          s_ += __builtin_amdgcn_update_dpp(0, s_, 0x141, 0xF, 0xF, false);
-          s_ += __builtin_amdgcn_update_dpp(0, s_, 0x140, 0xF, 0xF, false);
-          dcVal = (__builtin_amdgcn_readlane(s_, 0) + __builtin_amdgcn_readlane(s_, 16) + nT) >> (log2 + 1);
-        }
+        const int dcVal = mode == 1 ? d_intra_big_dc(P, nT, log2) : 0;
         {
           /* one loop per mode class, FOUR samples per lane in flight: their border taps and residuals are requested together (one
              LDS round trip per four samples, not two per sample), then the four are computed and stored */
@@ -818,52 +764,21 @@ __global__ void __launch_bounds__(64 * NW) M355_WAVES_PER_EU((DENSE || CF >= 2) 
           auto big_loop = [&](auto cls_) {
             constexpr int CLS = decltype(cls_)::value;
             const int x = xb;
-            /* what does not depend on the row */
-            const int t_x = (CLS == 0 || CLS == 2) ? BRD(1 + x) : 0;
-            const int u_tr = CLS == 0 ? BRD(1 + nT) : 0, u_bl = CLS == 0 ? BRD(-1 - nT) : 0;
-            const int u_c = CLS == 2 ? BRD(0) : 0, u_f = CLS == 2 ? (vert ? BRD(1) : BRD(-1)) : 0;
-            const int u_e2 = CLS == 1 ? BRD(-1) + BRD(1) : 0;
+            const IntraBigFixed fx = d_intra_big_fixed<CLS>(P, nT, x, vert);      /* what does not depend on the row */
             (void)nIt;
             for (int it0 = it_lo; it0 < it_hi; it0 += 4) {
               int ta[4], tb[4], fa[4], rs[4];
 #pragma unroll
               for (int u = 0; u < 4; u++) {
                 const int y = yb + min(it0 + u, it_hi - 1) * ystep;      /* (a share of 1 or 2 passes: the rest repeats the last one) */
-                fa[u] = 0; tb[u] = 0;
-                if (CLS == 0 || CLS == 2) ta[u] = BRD(-1 - y);
-                else if (CLS == 1) ta[u] = BRD(y == 0 ? x + 1 : -y - 1);
-                else {
-                  const int a_ = vert ? y : x, b_ = vert ? x : y;
-                  const int tt = __mul24(a_ + 1, angle), iIdx = tt >> 5;
-                  fa[u] = tt & 31;
-                  const int x1 = b_ + iIdx + 1, x2 = x1 + 1;
-                  int i1, i2;
-                  if (CLS == 3) { i1 = vert ? x1 : -x1; i2 = vert ? x2 : -x2; }
-                  else {
-                    const int p1 = (__mul24(x1, inv) + 128) >> 8, p2 = (__mul24(x2, inv) + 128) >> 8;
-                    i1 = x1 >= 0 ? x1 : -p1; i2 = x2 >= 0 ? x2 : -p2;
-                    if (!vert) { i1 = -i1; i2 = -i2; }
-                  }
-                  ta[u] = BRD(i1); tb[u] = BRD(fa[u] ? i2 : i1);   /* (no read beyond the border when the second tap has weight 0) */
-                }
+                d_intra_big_taps<CLS>(P, nT, x, y, vert, angle, inv, ta[u], tb[u], fa[u]);
                 rs[u] = (int)(int16_t)body[d_bofs + y * BODY_PITCH + x] & res_on;
                 if (res32) rs[u] = has_res ? res32buf[e1 + y * nT + x] : 0;
               }
 #pragma unroll
               for (int u = 0; u < 4; u++) {
                 const int y = yb + min(it0 + u, it_hi - 1) * ystep;
-                int v;
-                if (CLS == 0) v = (__mul24(nT - 1 - x, ta[u]) + __mul24(x + 1, u_tr) + __mul24(nT - 1 - y, t_x) + __mul24(y + 1, u_bl) + nT) >> (log2 + 1);
-                else if (CLS == 1) {
-                  v = dcVal;
-                  if (bfilt) {
-                    if (x == 0 || y == 0) v = (ta[u] + 3 * dcVal + 2) >> 2;
-                    if (x == 0 && y == 0) v = (u_e2 + 2 * dcVal + 2) >> 2;
-                  }
-                } else if (CLS == 2) {
-                  v = vert ? t_x : ta[u];
-                  if (bfilt && (vert ? x == 0 : y == 0)) v = d_clip3(0, pix_max, u_f + (((vert ? ta[u] : t_x) - u_c) >> 1));
-                } else v = (32 * ta[u] + __mul24(fa[u], tb[u] - ta[u]) + 16) >> 5;
+                int v = d_intra_big_value<CLS>(fx, nT, log2, x, y, vert, bfilt, dcVal, pix_max, ta[u], tb[u], fa[u]);
                 v = d_clip3(0, pix_max, v + rs[u]);          /* (a prediction is inside the sample range: no-op without a residual) */
                 body[d_bofs + y * BODY_PITCH + x] = (uint16_t)v;         /* for the next blocks' borders; the picture is written at the end */
               }
@@ -875,7 +790,6 @@ __global__ void __launch_bounds__(64 * NW) M355_WAVES_PER_EU((DENSE || CF >= 2) 
           else if (cls == 3) big_loop(std::integral_constant<int, 3>());
           else big_loop(std::integral_constant<int, 4>());
         }
-#undef BRD
         }   /* a share of the block */
       } else { /* raw block (slice.cc:4211-4255) */
         for (int o = lane; o < nT * nT; o += 64) {
@@ -949,7 +863,12 @@ static void launch_intra_cf(const DevPic& p, bool ticket_zero, hipStream_t st)
   const dim3 dense_grid(p.intra_grid > 0 && p.intra_grid < p.n_intra_work ? p.intra_grid : p.n_intra_work);
   if (p.intra_dense && p.intra_keeper) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_intra<PIX, CF, M355_INTRA_KEEPER_NW, true, false, W16>), dense_grid, dim3(64 * M355_INTRA_KEEPER_NW), 0, st, p, p.n_intra_work, (const DevPic*)nullptr, 1, (uint32_t*)nullptr);
   else if (p.intra_dense) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_intra<PIX, CF, M355_INTRA_DENSE_NW, true, false, W16>), dense_grid, dim3(64 * M355_INTRA_DENSE_NW), 0, st, p, p.n_intra_work, (const DevPic*)nullptr, 1, (uint32_t*)nullptr);
-  else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_intra<PIX, CF, M355_INTRA_SPARSE_NW, false, false, W16>), dim3(p.n_intra_work), dim3(64 * M355_INTRA_SPARSE_NW), 0, st, p, p.n_intra_work, (const DevPic*)nullptr, 1, (uint32_t*)nullptr);
+  else {
+    /* inter pictures: one workgroup per CTB of the items [0, n_intra_heavy) — the chain CTBs through the ticket, then the others by index —, and
+       behind them the light items, one per wave (k_intra_light.h; the W16 kernel has none: n_intra_heavy == n_intra_work there) */
+    const int n_wg = p.n_intra_heavy + (W16 ? 0 : (p.n_intra_light + M355_INTRA_SPARSE_NW - 1) / M355_INTRA_SPARSE_NW);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_intra<PIX, CF, M355_INTRA_SPARSE_NW, false, false, W16>), dim3(n_wg), dim3(64 * M355_INTRA_SPARSE_NW), 0, st, p, p.n_intra_heavy, (const DevPic*)nullptr, 1, (uint32_t*)nullptr);
+  }
 }
 
 void m355_launch_intra(const DevPic& p, bool hbd, hipStream_t st, bool ticket_zero)

@@ -160,6 +160,7 @@ int prepare(m355_ctx* c, Resident& r, DevPic& d_out, bool& want_sao_out, hipStre
   }
   d.epoch = ++c->epoch;
   if (d.epoch == 0) d.epoch = ++c->epoch;
+  c->dbg_intra[0] = r.n_intra_work; c->dbg_intra[1] = r.n_intra_ticket; c->dbg_intra[2] = r.n_intra_heavy; c->dbg_intra[3] = r.n_intra_light;   /* (m355_debug_intra_counts) */
   d_out = d; want_sao_out = want_sao;
   return M355_OK;
 }
@@ -470,6 +471,10 @@ int status_of(m355_ctx* c, m355_ctx::Status& s) {
 }
 
 unsigned long long m355_last_serial(m355_ctx* c) { return c->serial; }
+/* INTERNAL (tests, tools; not part of de265_mi355x.h): the intra work list of the decode prepared last on this context — out[0] work items (CTBs with
+   intra blocks), out[1] those of dependency chains (claimed through k_intra's ticket), out[2] those run by a workgroup each (the chains' and, by the schedule table,
+   more), out[3] light items (k_intra_light.h: one wave per CTB and component of the remaining work items) */
+M355_API void m355_debug_intra_counts(m355_ctx* c, int* out) { for (int i = 0; i < 4; i++) out[i] = c->dbg_intra[i]; }
 
 int m355_decode_status(m355_ctx* c, unsigned long long serial)
 {

@@ -66,6 +66,14 @@ constexpr int chain_split_min_depth = 3;
 constexpr int chain_residual_tiles_min_depth = 3;
 /* lanes 3.. decode INTRA pictures on a stream of the next priority class (own hardware queues): C2 0.340 ms per picture at depth 9 (profiles/r03_v_*) */
 constexpr int intra_class_first_lane = 3;
+/* inter pictures: the CTBs without a cross-CTB intra dependency run as LIGHT items of k_intra's launch — one wave per CTB and colour component, no CTB body
+   in LDS (k_intra_light.h) — instead of one workgroup each: C5 0.3210 / 0.3215 / 0.3224 -> 0.3148 / 0.3139 / 0.3119 ms three in flight (three alternating rounds
+   against the build before, medians of 5 regions; k_intra 39.3 -> 34.6 us one picture at a time, 90 -> 73 us three in flight, its wave-cycles 9.7e7 -> 5.4e7),
+   C3 0.0677 -> 0.0665, C4 0.0761 -> 0.0757 (profiles/r07_a_light_ab.txt, r07_a_*_kernel_stats.txt, r07_a_*_pmc_summary.txt).  This row: do the CTBs that hold a
+   32x32 intra block go there too?  One wave then predicts the block alone, where the CTB workgroup shares it among its component's waves: NO — on one box C5
+   0.3390 / 0.3378 / 0.3375 before, 0.3298 / 0.3305 / 0.3286 with them on the light path, 0.3280 / 0.3284 / 0.3277 with them kept as workgroups
+   (profiles/r07_a_light_32x32_ab.txt; M355_INTRA_LIGHT_32=0 / 1 overrides, tests/test_emu_intra_light.py and test_gpu_intra_light.py force the other setting) */
+constexpr bool intra_light_32x32 = false;
 }
 
 /* A MARK = "everything enqueued on `stream` up to here", one event of the context's ring (ev_mark / ev_wait / ev_sync below).  The
@@ -145,6 +153,7 @@ struct Resident {
   DevRef* refs_host = nullptr; /* pinned staging + last uploaded contents */
   bool refs_valid = false;
   int n_intra_work = 0;
+  int n_intra_ticket = 0, n_intra_heavy = 0, n_intra_light = 0;   /* (what m355_debug_intra_counts reports) */
   uint32_t n_iplan = 0;        /* border-plan entries of the picture's intra blocks (k_intra_plan -> k_intra) */
   /* tile sharding (m355_decode_phase) */
   bool sharded = false;
@@ -231,6 +240,7 @@ struct m355_ctx {
      their slot is reused, reported by the next m355_wait */
   unsigned long long lost_first = 0; int lost_count = 0;
   int stages = M355_STAGE_ALL;
+  int dbg_intra[4] = {0, 0, 0, 0};   /* the last prepared decode's intra work items, those of dependency chains (ticket), those run by a workgroup, light items: m355_debug_intra_counts */
   int shard_rank = 0, shard_n = 0;   /* shard_n == 0: sharding off */
   m355_comm comm = {nullptr, nullptr, nullptr};   /* exchanges of m355_decode_sharded */
   void* rccl = nullptr;              /* built-in RCCL communicator (m355_shard_rccl_init) */
@@ -292,7 +302,7 @@ struct Lay {
   Seg seg[32];
   int ns;
   size_t total;
-  int i_sl, i_ct, i_cu, i_tu, i_pb, i_wt, i_rb[4], i_ibin, i_ib, i_il, i_co, i_pc, i_sc, i_ts, i_rs, i_ti, i_iw, i_dp, i_ow;
+  int i_sl, i_ct, i_cu, i_tu, i_pb, i_wt, i_rb[4], i_ibin, i_ib, i_il, i_co, i_pc, i_sc, i_ts, i_rs, i_ti, i_iw, i_dp, i_ow, i_lt;
 };
 struct Id128 { char b[128]; };
 struct Rccl {

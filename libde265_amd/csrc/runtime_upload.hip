@@ -668,6 +668,7 @@ void make_layout(const m355_arena_caps& k, int nCtb, int halo_units, bool sharde
   L.i_iw = add(sizeof(DevIntraWork) * (size_t)nCtb);   /* intra_work */
   L.i_dp = add((size_t)nCtb);       /* ctb_dep */
   L.i_ow = add(sharded ? (size_t)nCtb : 0);                          /* ctb_owner */
+  L.i_lt = add(16 * 3 * (size_t)nCtb);                               /* intra_light: at most one item per CTB and component */
 }
 
 int upload(m355_ctx* c, Resident& r, const m355_picture* pic) {
@@ -706,7 +707,7 @@ int upload(m355_ctx* c, Resident& r, const m355_picture* pic) {
   const int ns = L.ns;
   const size_t total = L.total;
   const int i_sl = L.i_sl, i_ct = L.i_ct, i_cu = L.i_cu, i_tu = L.i_tu, i_pb = L.i_pb, i_wt = L.i_wt, i_ib = L.i_ib, i_il = L.i_il, i_co = L.i_co, i_pc = L.i_pc,
-            i_sc = L.i_sc, i_ts = L.i_ts, i_rs = L.i_rs, i_ti = L.i_ti, i_iw = L.i_iw, i_dp = L.i_dp, i_ow = L.i_ow;
+            i_sc = L.i_sc, i_ts = L.i_ts, i_rs = L.i_rs, i_ti = L.i_ti, i_iw = L.i_iw, i_dp = L.i_dp, i_ow = L.i_ow, i_lt = L.i_lt;
   /* used bytes (what travels to the device) and, when copying, where they come from */
   {
     size_t rb_o = 0;
@@ -804,7 +805,7 @@ int upload(m355_ctx* c, Resident& r, const m355_picture* pic) {
   intra_dependencies(ctbW, ctbH, tile_id, ctb_touch, ctb_need, (uint8_t*)(r.host + seg[i_dp].ofs));
   for (int i = 0; i < nCtb; i++) ((uint8_t*)(r.host + seg[i_dp].ofs))[i] |= (uint8_t)(log2_waves[i] << 5);
   const auto t_deps = now();
-  int nw = 0, n_free = 0, n_ticket = 0;
+  int nw = 0, n_free = 0, n_ticket = 0, n_heavy = 0, n_light = 0;
   uint32_t n_iplan = 0;                                     /* border-plan entries of the picture (k_intra_plan) */
   {
     const uint8_t* dep = (const uint8_t*)(r.host + seg[i_dp].ofs);
@@ -851,16 +852,38 @@ int upload(m355_ctx* c, Resident& r, const m355_picture* pic) {
           if ((dep[rs] >> n) & 1) { uint32_t& pr = rem[(size_t)(cy + dy[n]) * ctbW + (cx + dx[n])]; pr = std::max(pr, mine); }
       }
       /* (a producer's entry held its readers' maximum until its own turn came: every entry of a chain member is final now) */
-      bucket.assign((size_t)REM_CAP + 2 + (size_t)max_cnt + 2, 0);
-      size_t n_chain = 0;
-      auto slot_of = [&](size_t i) -> size_t {               /* chain members by falling rem, then the others by falling block count */
+      /* The CTBs without dependencies run as LIGHT items (k_intra_light.h: one wave per CTB and component, no CTB body in LDS) — those that hold a 32x32
+         intra block by sched::intra_light_32x32; bit 30 of a candidate's count marks the ones that stay workgroups.  They are everything k_intra's
+         cross-CTB machinery is not needed for: none of their blocks reads an intra sample of another CTB, nobody reads theirs.  Not for sharded phases
+         and not at 16 bits per sample (int32 residuals): those keep the one kernel they have. */
+      static const int light32_env = getenv("M355_INTRA_LIGHT_32") ? atoi(getenv("M355_INTRA_LIGHT_32")) : -1;
+      const bool light_on = !sharded && !m355_res32(pp);
+      const bool light_32 = light32_env >= 0 ? light32_env != 0 : sched::intra_light_32x32;
+      for (size_t i = 0; i < n_cand; i++) {
         const uint32_t rs = cand[2 * i];
-        return (dep[rs] & 31) ? (size_t)(REM_CAP - rem[rs]) : (size_t)REM_CAP + 1 + (size_t)(max_cnt - (cand[2 * i + 1] & 0x7FFFFFFFu));
+        bool heavy = !light_on;
+        if (light_on && !light_32 && !(dep[rs] & 31)) {
+          const m355_ctb& cb = pic->ctbs[rs];
+          for (uint32_t k = 0; k < cb.ib_count && !heavy; k++) heavy = pic->ibs[cb.ib_start + k].log2_size >= 5 && !(pic->ibs[cb.ib_start + k].flags & M355_IBF_PCM);
+        }
+        if (heavy) cand[2 * i + 1] |= 0x40000000u;
+      }
+      bucket.assign((size_t)REM_CAP + 2 + 2 * ((size_t)max_cnt + 2), 0);
+      size_t n_chain = 0, n_wg_free = 0;
+      auto slot_of = [&](size_t i) -> size_t {               /* chain members by falling rem, then the others by falling block count: first those that stay workgroups, then the light ones */
+        const uint32_t rs = cand[2 * i];
+        if (dep[rs] & 31) return (size_t)(REM_CAP - rem[rs]);
+        const size_t by_count = (size_t)(max_cnt - (cand[2 * i + 1] & 0x3FFFFFFFu));
+        return (size_t)REM_CAP + 1 + ((cand[2 * i + 1] & 0x40000000u) ? 0 : (size_t)max_cnt + 1) + by_count;
       };
-      for (size_t i = 0; i < n_cand; i++) { bucket[slot_of(i) + 1]++; if (dep[cand[2 * i]] & 31) n_chain++; }
+      for (size_t i = 0; i < n_cand; i++) {
+        bucket[slot_of(i) + 1]++;
+        if (dep[cand[2 * i]] & 31) n_chain++; else if (cand[2 * i + 1] & 0x40000000u) n_wg_free++;
+      }
       for (size_t i = 1; i < bucket.size(); i++) bucket[i] += bucket[i - 1];
       for (size_t i = 0; i < n_cand; i++) order[bucket[slot_of(i)]++] = cand[2 * i];
       n_ticket = (int)n_chain;
+      n_heavy = (int)(n_chain + n_wg_free);
     } else {
     n_free = (int)(n_cand - n_dep);
     n_ticket = (int)n_cand;                                  /* (an intra picture's persistent workgroups claim every item through the ticket) */
@@ -891,6 +914,26 @@ int upload(m355_ctx* c, Resident& r, const m355_picture* pic) {
     std::vector<uint32_t>& pbase = r.sched_u32b;
     pbase.resize((size_t)nw + 1);
     for (int k = 0; k < nw; k++) { pbase[(size_t)k] = n_iplan; n_iplan += (plan_count[order[(size_t)k]] + 7u) & ~7u; }
+    if (intra_dense) n_heavy = nw;
+    {
+      /* the light items: per work item behind n_heavy and component: the CTB, the span of the component's blocks in the CTB's sorted run, the item's plans */
+      uint4* const lt = (uint4*)(r.host + seg[i_lt].ofs);
+      const m355_ib* const sorted_ibs = (const m355_ib*)(r.host + seg[i_ib].ofs);
+      for (int k = n_heavy; k < nw; k++) {
+        const m355_ctb& cb = pic->ctbs[order[(size_t)k]];
+        uint32_t first[3] = {~0u, ~0u, ~0u}, last[3] = {0, 0, 0};
+        for (uint32_t j = 0; j < cb.ib_count; j++) {
+          const int q = sorted_ibs[cb.ib_start + j].cidx;
+          if (q > 2) continue;                               /* (rejected by validate()) */
+          if (first[q] == ~0u) first[q] = j;
+          last[q] = j;
+        }
+        for (int q = 0; q < 3; q++)
+          if (first[q] != ~0u) lt[n_light++] = make_uint4(order[(size_t)k] | ((uint32_t)q << 30), cb.ib_start + first[q], last[q] - first[q] + 1u, pbase[(size_t)k]);
+      }
+      static const bool level_stats = getenv("M355_INTRA_LEVEL_STATS") != nullptr;
+      if (level_stats) fprintf(stderr, "intra work list: n_intra_work %d, n_intra_ticket %d, workgroup items %d, light items %d (of %d CTBs)\n", nw, n_ticket, n_heavy, n_light, nw - n_heavy);
+    }
     /* a work item = the CTB's descriptor: block range, wave count code, and the 3x3 neighbourhood facts every availability
        test of intrapred.h:486-508 / :534-633 needs (picture, slice, tile, decode order across CTBs) */
     parallel_ranges((size_t)nw, 512, [&](size_t kb, size_t ke) {
@@ -915,7 +958,8 @@ int upload(m355_ctx* c, Resident& r, const m355_picture* pic) {
     });
   }
   seg[i_iw].bytes = sizeof(DevIntraWork) * (size_t)(nw ? nw : 1);
-  r.n_intra_work = nw; r.n_iplan = n_iplan;
+  seg[i_lt].bytes = sizeof(uint4) * (size_t)n_light;
+  r.n_intra_work = nw; r.n_iplan = n_iplan; r.n_intra_ticket = n_ticket; r.n_intra_heavy = n_heavy; r.n_intra_light = n_light;
   if (sharded) {
     uint8_t* ow = (uint8_t*)(r.host + seg[i_ow].ofs);
     const int n_tiles = pp.num_tile_cols * pp.num_tile_rows;
@@ -978,6 +1022,8 @@ int upload(m355_ctx* c, Resident& r, const m355_picture* pic) {
   d.tile_id = (const uint16_t*)(r.dev + seg[i_ti].ofs);
   d.intra_work = (const DevIntraWork*)(r.dev + seg[i_iw].ofs);
   d.n_intra_work = nw; d.n_intra_ticket = n_ticket;
+  d.n_intra_heavy = n_heavy; d.n_intra_light = n_light;
+  d.intra_light = (const uint4*)(r.dev + seg[i_lt].ofs);
   d.ctb_dep = (const uint8_t*)(r.dev + seg[i_dp].ofs);
   d.ctb_owner = sharded ? (const uint8_t*)(r.dev + seg[i_ow].ofs) : nullptr;
   d.halo_cu_base = pic->n_cus; d.halo_pb_base = pic->n_pbs;
