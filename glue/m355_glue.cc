@@ -86,7 +86,7 @@ namespace {
   X(m355_last_error) X(m355_device_count) X(m355_create) X(m355_destroy) X(m355_frame_create) X(m355_frame_destroy) \
   X(m355_frame_upload) X(m355_frame_download) X(m355_submit_picture) X(m355_wait) X(m355_set_pipeline_depth) \
   X(m355_host_alloc) X(m355_host_free) X(m355_frame_hash) X(m355_arena_begin) X(m355_last_serial) X(m355_decode_status) \
-  X(m355_frame_download_async) X(m355_frame_download_wait) X(m355_frame_export) X(m355_frame_export_scaled) X(m355_frame_export_rgb) X(m355_frame_export_resized) X(m355_frame_export_resized_rgb) X(m355_frames_export_tensor) X(m355_frame_export_order) \
+  X(m355_frame_download_async) X(m355_frame_download_wait) X(m355_frame_export) X(m355_frame_export_scaled) X(m355_frame_export_rgb) X(m355_frame_export_resized) X(m355_frame_export_resized_rgb) X(m355_frames_export_tensor) X(m355_frames_export_tensor_rois) X(m355_frame_export_order) \
   X(m355_group_create) X(m355_group_destroy) X(m355_group_decode) X(m355_picture_upload) X(m355_picture_replace) X(m355_shard_owner_of_tile) \
   X(m355_picture_arena_begin) X(m355_frame_hash_async) X(m355_frame_hash_result) X(m355_frame_measure_async) X(m355_frame_measure_result)
 
@@ -1881,6 +1881,51 @@ LIBDE265_API int m355_glue_export_images_tensor(const struct de265_image* const*
   for (int c = 0; c < 3; c++) { d.scale[c] = scale[c]; d.bias[c] = bias[c]; }
   d.dst = dst; d.stride_n = stride_n; d.stride_c = stride_c; d.stride_h = stride_h;
   int rc = A->m355_frames_export_tensor(g->mctx, frames, n, &d);
+  if (rc == M355_OK) rc = A->m355_frame_export_order(g->mctx, frames[0], consumer_stream);
+  if (rc != M355_OK) g->error = A->m355_last_error();
+  return rc;
+}
+/* A batch of REGIONS of pictures of ONE decoder, one rectangle per slice, as one float tensor in one launch (m355_frames_export_tensor_rois), with the
+ * waiting and ordering of m355_glue_export_images_tensor.  rois: n x {x0, y0, width, height, flags} in luma samples of the coded picture, flags = 0 or
+ * M355_ROI_MIRROR; an entry whose four rectangle fields are 0 means THAT picture's conformance window.  Every rectangle is resolved against ITS
+ * picture; the same picture may appear any number of times.  matrix == -1 and full_range == -1 are resolved from imgs[0]. */
+LIBDE265_API int m355_glue_export_images_tensor_rois(const struct de265_image* const* imgs, const int (*rois)[5], int n, int layout, int dtype, int samples,
+                                                     int matrix, int full_range, const int out_size[2], const float scale[3], const float bias[3], void* dst,
+                                                     int64_t stride_n, int64_t stride_c, int64_t stride_h, void* consumer_stream)
+{
+  Api* A = api();
+  if (!A) return M355_ERR_NO_DEVICE;
+  if (!imgs || !rois || n < 1 || n > M355_TENSOR_MAX_FRAMES || !out_size || !scale || !bias) return M355_ERR_INVALID;
+  for (int i = 0; i < n; i++) if (!imgs[i] || !imgs[i]->decctx || imgs[i]->decctx != imgs[0]->decctx) return M355_ERR_INVALID;
+  Glue* g = glue_of(imgs[0]->decctx);
+  if (!g || g->n_ranks > 1) return M355_ERR_INVALID;
+  if (matrix == -1) {
+    const int mc = de265_get_image_matrix_coefficients(imgs[0]);
+    if (mc == 1 || mc == 2) matrix = M355_MATRIX_BT709;
+    else if (mc == 5 || mc == 6) matrix = M355_MATRIX_BT601;
+    else if (mc == 9) matrix = M355_MATRIX_BT2020;
+    else return M355_ERR_INVALID;
+  }
+  if (full_range == -1) full_range = de265_get_image_full_range_flag(imgs[0]) ? 1 : 0;
+  for (int i = 0; i < n; i++) wait_submitted(g, imgs[i]->get_ID());
+  std::lock_guard<std::mutex> api_lock(g->api_mu);
+  int frames[M355_TENSOR_MAX_FRAMES];
+  m355_tensor_roi rr[M355_TENSOR_MAX_FRAMES];
+  for (int i = 0; i < n; i++) {
+    const int* q = rois[i];
+    const bool window = !q[0] && !q[1] && !q[2] && !q[3];
+    int r[4];
+    frames[i] = frame_and_rect(g, imgs[i], window ? nullptr : q, r);
+    if (frames[i] < 0) return M355_ERR_INVALID;
+    rr[i].x0 = r[0]; rr[i].y0 = r[1]; rr[i].width = r[2]; rr[i].height = r[3]; rr[i].flags = q[4];
+  }
+  m355_tensor_desc d;
+  memset(&d, 0, sizeof(d));
+  d.layout = layout; d.dtype = dtype; d.samples = samples; d.matrix = matrix; d.full_range = full_range;
+  d.out_width = out_size[0]; d.out_height = out_size[1];
+  for (int c = 0; c < 3; c++) { d.scale[c] = scale[c]; d.bias[c] = bias[c]; }
+  d.dst = dst; d.stride_n = stride_n; d.stride_c = stride_c; d.stride_h = stride_h;
+  int rc = A->m355_frames_export_tensor_rois(g->mctx, frames, rr, n, &d);
   if (rc == M355_OK) rc = A->m355_frame_export_order(g->mctx, frames[0], consumer_stream);
   if (rc != M355_OK) g->error = A->m355_last_error();
   return rc;

@@ -542,8 +542,9 @@ M355_API int   m355_rgb_coefficients(int matrix, int full_range, int bit_depth_l
  * and m355_frame_export_order cover it, the next decode into the frame waits for it —, and nothing is written behind a rejected decode.
  * Not offered: filters with negative lobes (bicubic, Lanczos: signed sums and clipping), ratios beyond 8, another chroma siting, resizing into a
  * frame of the decoder; and of m355_frame_export_resized_rgb and m355_frames_export_tensor below: BGR order, another chroma siting, chroma resampled
- * straight onto the luma grid (it is resized on its own grid, then reconstructed), per-frame rectangles or output sizes within a batch, writing into
- * a tensor owned by a second HIP runtime without m355_frame_export_order. */
+ * straight onto the luma grid (it is resized on its own grid, then reconstructed), per-frame output sizes within a batch (per-frame rectangles:
+ * m355_frames_export_tensor_rois, which rejects a region smaller than an eighth of the output and does not clamp it), writing into a tensor owned by
+ * a second HIP runtime without m355_frame_export_order. */
 #define M355_RESIZE_MAX_TAPS 16
 typedef struct m355_resize_desc {
   int32_t layout, samples;          /* M355_EXPORT_PLANAR / _SEMIPLANAR, M355_EXPORT_NATIVE / _MSB16 / _U8 */
@@ -636,6 +637,32 @@ typedef struct m355_tensor_desc {
 } m355_tensor_desc;                      /* (LP64: 104 bytes) */
 M355_API int   m355_frames_export_tensor(m355_ctx* ctx, const int* frames, int n, const m355_tensor_desc* desc);   /* asynchronous */
 M355_API int   m355_tensor_element(uint32_t v, float scale, float bias, int dtype, uint32_t* bits);                 /* host only */
+/* A batch of REGIONS as one float tensor in one launch: as m355_frames_export_tensor, but with ONE RECTANGLE PER SLICE — the boxes of a detector in
+ * one frame, each resized to a classifier's input; the random crops and flips of a training loader; whole frames of different sizes.  The definition
+ * is a composition and adds no arithmetic, constant or siting rule:
+ *   let T_i be what m355_frames_export_tensor delivers for n = 1, frames = {frames[i]}, this descriptor with its rectangle replaced by rois[i] and
+ *   dst replaced by dst + i * stride_n;
+ *   without M355_ROI_MIRROR in rois[i].flags, slice i is T_i, byte for byte;
+ *   with it, element (c, y, x) of slice i is element (c, y, out_width - 1 - x) of T_i: the pixels of a row are reversed, the three channels of an
+ *   NHWC pixel keep their order.
+ * rois[i].width == 0 means the whole of frames[i], by the rule of m355_export_desc, so frames of different SIZES may share a tensor (chroma format,
+ * bit depths and element size must still be frames[0]'s).  The same frame may appear any number of times.  Bytes that are no element of the tensor
+ * are never written.
+ * M355_ERR_INVALID (nothing is enqueued, no destination byte written; m355_last_error names the entry): whatever m355_frames_export_tensor rejects for
+ * n, the handles, chroma format, bit depths and element size against frames[0], the output size, samples, matrix, full_range, layout, dtype, scale,
+ * bias, dst and the strides; null `rois`; a descriptor whose x0, y0, width, height are not all 0 (the rectangles are the entries'); a flag bit other
+ * than M355_ROI_MIRROR; for ANY entry i: a rectangle that leaves frames[i], is off the chroma grid or has a negative size, or a ratio outside
+ * src <= 8 * out && out <= 8 * src on either axis for THAT entry — a region smaller than an eighth of the output is rejected, not clamped.
+ * Ordering, the gate, sharded contexts, m355_frame_export_wait and m355_frame_export_order: exactly those of m355_frames_export_tensor — one mark kept
+ * by every distinct frame, each slice behind its own frame's gate: the slices of a frame behind a rejected decode are skipped, the others written.
+ * Not offered: an output size per slice, ratios beyond 8, regions off the chroma grid, another siting. */
+#define M355_ROI_MIRROR 1                /* flags: the slice's columns in reverse order */
+typedef struct m355_tensor_roi {
+  int32_t x0, y0, width, height;         /* source luma rectangle in frames[i], as in m355_export_desc (width == 0: the whole frame) */
+  int32_t flags;                         /* 0 or M355_ROI_MIRROR */
+} m355_tensor_roi;                       /* (20 bytes) */
+M355_API int   m355_frames_export_tensor_rois(m355_ctx* ctx, const int* frames, const m355_tensor_roi* rois, int n,
+                                              const m355_tensor_desc* desc);   /* asynchronous */
 M355_API int   m355_frame_export_wait(m355_ctx* ctx, int frame);
 M355_API int   m355_frame_export_order(m355_ctx* ctx, int frame, void* consumer_hipStream);
 /* Device memory for export destinations and blocking copies out of / into it, for applications (and the tests) that keep a second HIP

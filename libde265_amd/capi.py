@@ -96,6 +96,14 @@ class TensorDesc(ctypes.Structure):
                 ("stride_n", ctypes.c_int64), ("stride_c", ctypes.c_int64), ("stride_h", ctypes.c_int64)]
 
 
+ROI_MIRROR = 1
+
+
+class TensorRoi(ctypes.Structure):
+    """m355_tensor_roi (include/de265_mi355x.h)"""
+    _fields_ = [("x0", ctypes.c_int32), ("y0", ctypes.c_int32), ("width", ctypes.c_int32), ("height", ctypes.c_int32), ("flags", ctypes.c_int32)]
+
+
 class RgbCoeffs(ctypes.Structure):
     """m355_rgb_coeffs (include/de265_mi355x.h)"""
     _fields_ = [(n, ctypes.c_int32) for n in ("F", "y0", "c0", "cy", "crv", "cgu", "cgv", "cbu")]
@@ -174,6 +182,8 @@ class Library:
         if hasattr(L, "m355_frames_export_tensor"):     # (absent from older builds loaded through M355_LIB for an A/B)
             L.m355_frames_export_tensor.argtypes = [vp, ctypes.POINTER(i), i, ctypes.POINTER(TensorDesc)]
             L.m355_tensor_element.argtypes = [ctypes.c_uint32, ctypes.c_float, ctypes.c_float, i, ctypes.POINTER(ctypes.c_uint32)]
+        if hasattr(L, "m355_frames_export_tensor_rois"):  # (absent from older builds loaded through M355_LIB for an A/B)
+            L.m355_frames_export_tensor_rois.argtypes = [vp, ctypes.POINTER(i), ctypes.POINTER(TensorRoi), i, ctypes.POINTER(TensorDesc)]
         L.m355_host_alloc.argtypes = [ctypes.c_size_t]
         L.m355_host_alloc.restype = vp
         L.m355_host_free.argtypes = [vp]
@@ -562,6 +572,16 @@ class Context:
         own, made as frame_export_resized_rgb makes its buffers: every byte holds DEVICE_FILL beforehand, and every stride is `pad` bytes (a multiple
         of the element size) above the smallest one the call accepts — stride_h above the row, stride_c above a plane, stride_n above a slice.
         scale, bias: three floats each (R, G, B).  -> token for tensor_export_finish"""
+        return self._frames_export_tensor(frames, None, layout, dtype, samples, matrix, full_range, out_size, scale, bias, rect, host, pad)
+
+    def frames_export_tensor_rois(self, frames, rois, layout, dtype, samples, matrix, full_range, out_size, scale, bias, host=False, pad=20):
+        """start m355_frames_export_tensor_rois: slice i is the rectangle rois[i] = (x0, y0, width, height, flags) of frames[i] (None or width 0: the
+        whole of that frame; flags: 0 or ROI_MIRROR), resized to out_size.  The buffer is made as frames_export_tensor makes it: DEVICE_FILL in every
+        byte, every stride `pad` bytes above the smallest one the call accepts.  -> token for tensor_export_finish"""
+        return self._frames_export_tensor(frames, [r if r is not None else (0, 0, 0, 0, 0) for r in rois], layout, dtype, samples, matrix, full_range,
+                                          out_size, scale, bias, None, host, pad)
+
+    def _frames_export_tensor(self, frames, rois, layout, dtype, samples, matrix, full_range, out_size, scale, bias, rect, host, pad):
         w, h = out_size
         n, eb = len(frames), (4 if dtype == TENSOR_F32 else 2)
         row = w * eb * (3 if layout == TENSOR_NHWC else 1)
@@ -585,7 +605,12 @@ class Context:
             p = self.device_alloc(nbytes)
         desc.dst = p
         try:
-            self.L.check(self.L.lib.m355_frames_export_tensor(self.h, (ctypes.c_int * n)(*frames), n, ctypes.byref(desc)))
+            if rois is None:
+                self.L.check(self.L.lib.m355_frames_export_tensor(self.h, (ctypes.c_int * n)(*frames), n, ctypes.byref(desc)))
+            else:
+                assert len(rois) == n
+                arr = (TensorRoi * n)(*[TensorRoi(*r) for r in rois])
+                self.L.check(self.L.lib.m355_frames_export_tensor_rois(self.h, (ctypes.c_int * n)(*frames), arr, n, ctypes.byref(desc)))
         except Exception:
             self.L.lib.m355_host_free(p) if host else self.device_free(p)
             raise

@@ -383,6 +383,34 @@ struct ExportTensorArgs {
 /* src_bytes: 1 or 2 per sample; elem_bytes: 2 (F16 / BF16) or 4 (F32) */
 void m355_launch_export_tensor(const ExportTensorArgs& a, int src_bytes, int elem_bytes, hipStream_t st);
 
+/* one m355_frames_export_tensor_rois (k_export_tensor.hip, ROI = true): the same tile procedure, with the GEOMETRY of the source per slice.  A slice's
+   record holds what ExportTensorFrame holds — src[] = the first sample of ITS rectangle in ITS frame, the pitches, the gate — and what is the batch's
+   there: the rectangle's size on the luma and the chroma grid (sn_x, sn_y; zeros for a monochrome frame), the tile width, the tiles per row of tiles
+   and the slice's units, each derived from the slice's own source size, and flags (M355_ROI_MIRROR: the epilogue stores the slice's columns in
+   reverse order).  The grid is two-dimensional: blockIdx.y = slice, blockIdx.x < max_units = the largest units of a slice; a workgroup beyond its
+   slice's units returns.  The output grids dn_*, cf, the bit depths, k, scale, bias, layout and dtype are the batch's.  The whole structure travels
+   as kernel arguments, whose segment holds 4 KiB. */
+struct ExportTensorRoi {
+  const uint8_t* src[3];
+  long long src_pitch[2];
+  const uint32_t* timeout;
+  uint32_t epoch, flags;
+  uint32_t sn_x[2], sn_y[2];
+  uint32_t tile_w, tiles_x, units, pad;
+};
+struct ExportTensorRoisArgs {
+  uint8_t* dst;
+  long long stride_n, stride_c, stride_h;
+  uint32_t dn_x[2], dn_y[2];
+  uint32_t max_units, n;
+  int32_t cf, nhwc, bf16, u16, bdl, bdc;
+  float scale[3], bias[3];
+  m355_rgb_coeffs k;
+  ExportTensorRoi fr[M355_TENSOR_MAX_FRAMES];
+};
+static_assert(sizeof(ExportTensorRoi) == 88 && sizeof(ExportTensorRoisArgs) <= 4096, "the records of a batch of regions must fit the kernel arguments");
+void m355_launch_export_tensor_rois(const ExportTensorRoisArgs& a, int src_bytes, int elem_bytes, hipStream_t st);
+
 /* first statement of every kernel of a decode: a picture whose lists k_validate rejected is never acted upon */
 /* Element `c` (0..2, per lane) of a three-entry table of the kernel arguments (plane pointers, pitches, ...): all three entries are
  * read as scalars and the lane selects — indexing the argument segment with a per-lane value is a VECTOR memory load from it, i.e. one

@@ -16,14 +16,27 @@
  * scalar registers): source sample bytes and element bytes are the template parameters, four instantiations.  The helpers are duplicated from
  * k_export_resized_rgb.hip, as that file duplicates k_export_resized.hip's: its instantiations stay byte for byte what they were.
  *
+ * ROI = true (m355_frames_export_tensor_rois, four more instantiations): a rectangle per slice.  The tile procedure is the same statements; what
+ * moves from the batch to the slice's record (ExportTensorRoi, read by scalar loads at the same wave-uniform index as the pointers) is the source
+ * size on both grids, the tile width, the tiles per row of tiles and the slice's unit count, each derived by the host from the slice's own source
+ * size, and the flags.  The filter rows still come from m355_resize_row in the prologue, now with the slice's source size.
+ *   Grid.  Slices have different unit counts, so the grid is two-dimensional: blockIdx.y = slice, blockIdx.x = the unit inside it, as wide as the
+ *   slice with the most units; a workgroup beyond its slice's count returns, behind the gate, before it touches anything.
+ *   Mirror.  M355_ROI_MIRROR touches the epilogue only: the lane of tile column t stages its pixel at position ncols - 1 - t of the staged row
+ *   (the channels of an NHWC pixel keep their order), and the tile's first destination column is out_width - c0 - ncols; loads, filter rows, LDS
+ *   tiles, the dword stores and the single trailing 2-byte element are unchanged.
+ * ROI = false reads the batch's fields as before; its four instantiations compile to the instructions, registers and LDS they had.
+ *
  * Reads stay inside the planes' allocations, by the argument of k_export_resized_rgb.hip applied to every frame of the batch: the host admits a
- * frame only if it contains the rectangle (export_plan per frame), so in every slice a filter row's source indices, clamped to the rectangle on
- * the plane's grid, name rows and samples of that frame's rectangle; every vector starts at a sample of the span, a lane reads at most 16 bytes
- * from there, and every frame's rows are padded to 128 bytes and its planes end with a 256-byte tail (runtime_internal.h frame_alloc).  The slice
- * index is below n <= M355_TENSOR_MAX_FRAMES, the size of the per-frame array, because blockIdx.x < n * units.  LDS indices are those of
- * k_export_resized_rgb.hip; the staged row is indexed below 256 * 3 * EB bytes (lane < 256, channel < 3).
- * Writes: element (slice, c, row, column) only, with row < out_height and column < out_width; the host has checked that the strides keep rows,
- * planes and slices apart.
+ * frame only if it contains the rectangle (export_plan per frame; ROI: entry i only if frames[i] contains rois[i], and the record's source size is
+ * that rectangle's), so in every slice a filter row's source indices, clamped to the slice's rectangle on the plane's grid, name rows and samples
+ * of that frame's rectangle; every vector starts at a sample of the span, a lane reads at most 16 bytes from there, and every frame's rows are
+ * padded to 128 bytes and its planes end with a 256-byte tail (runtime_internal.h frame_alloc).  The slice index is below
+ * n <= M355_TENSOR_MAX_FRAMES, the size of the per-frame array, because blockIdx.x < n * units (ROI: because blockIdx.y < n).  LDS indices are those
+ * of k_export_resized_rgb.hip — the host derives every slice's tile width by that kernel's rule from the slice's source size, so a tile's span fits
+ * s_t as there —; the staged row is indexed below 256 * 3 * EB bytes (position < ncols <= 256, channel < 3).
+ * Writes: element (slice, c, row, column) only, with row < out_height and column < out_width (mirrored: the tile's columns
+ * out_width - c0 - ncols .. out_width - c0 - 1); the host has checked that the strides keep rows, planes and slices apart.
  */
 #include "k_common.h"
 #include "resize_taps.h"
@@ -130,23 +143,34 @@ __device__ __forceinline__ unsigned d_te_horizontal(const unsigned* hq, const un
   return ((v >> 1) + (1u << (osh - 1))) >> osh;
 }
 
-template <int SB, int EB>
-__global__ void __launch_bounds__(256) k_export_tensor(ExportTensorArgs a)
+/* The kernel's arguments: ROI = false the batch's geometry (m355_frames_export_tensor), ROI = true a geometry per slice
+   (m355_frames_export_tensor_rois).  TE_GEOM(field) reads a field of the source's geometry from the slice's record or from the batch, at the place
+   where the kernel reads the batch's. */
+template <bool ROI> struct TeArgs { typedef ExportTensorArgs T; };
+template <> struct TeArgs<true> { typedef ExportTensorRoisArgs T; };
+#define TE_GEOM(field) ({ uint32_t g_; if constexpr (ROI) g_ = fr.field; else g_ = a.field; g_; })
+
+template <int SB, int EB, bool ROI>
+__global__ void __launch_bounds__(256) k_export_tensor(typename TeArgs<ROI>::T a)
 {
   constexpr int S = 16 / SB;
   constexpr uint32_t OB = TE_TW * 3 * EB;                       /* bytes of a staged output row: 256 pixels x 3 channels x EB bytes */
-  const uint32_t slice = blockIdx.x / a.units;                  /* (wave-uniform: the frame's record comes by scalar loads) */
+  uint32_t slice;                                               /* (wave-uniform: the frame's record comes by scalar loads) */
+  if constexpr (ROI) slice = blockIdx.y; else slice = blockIdx.x / a.units;
   if (slice >= a.n) return;
-  const ExportTensorFrame& fr = a.fr[slice];
+  const auto& fr = a.fr[slice];
   M355_GATE(fr);
+  if constexpr (ROI) { if (blockIdx.x >= fr.units) return; }    /* (the grid is as wide as the slice with the most units) */
   __shared__ unsigned s_t[2][TE_SPAN];                          /* [pass & 1]: the t rows of the pass's segments; in the prologue: the lanes' horizontal rows */
   __shared__ int32_t s_vy[2][TE_TH][2 + M355_RESIZE_MAX_TAPS];  /* [luma, chroma] per output row of the tile: first source row, number of rows, coefficients */
   __shared__ int32_t s_span[2][2];                              /* [luma, chroma] first and last source column of the tile */
   __shared__ unsigned short s_c[2][TE_TH][TE_CW];               /* the resized Cb and Cr samples the tile's pixels need */
   __shared__ __attribute__((aligned(16))) uint8_t s_o[2][2][OB];  /* [pass & 1][row of the pass]: the staged output rows */
-  const uint32_t tid = threadIdx.x, unit = blockIdx.x - slice * a.units;
-  const uint32_t run = unit / a.tiles_x, tile = unit - run * a.tiles_x;
-  const uint32_t tw = a.tile_w, c0 = tile * tw, j0 = run * TE_TH;
+  uint32_t unit;
+  if constexpr (ROI) unit = blockIdx.x; else unit = blockIdx.x - slice * a.units;
+  const uint32_t tid = threadIdx.x;
+  const uint32_t run = unit / TE_GEOM(tiles_x), tile = unit - run * TE_GEOM(tiles_x);
+  const uint32_t tw = TE_GEOM(tile_w), c0 = tile * tw, j0 = run * TE_TH;
   const uint32_t dnx = a.dn_x[0], dny = a.dn_y[0], cdx = a.dn_x[1], cdy = a.dn_y[1];
   const uint32_t ncols = dnx - c0 < tw ? dnx - c0 : tw, nrows = dny - j0 < (uint32_t)TE_TH ? dny - j0 : (uint32_t)TE_TH;
   const int cf = a.cf;
@@ -169,17 +193,17 @@ __global__ void __launch_bounds__(256) k_export_tensor(ExportTensorArgs a)
   int32_t* hrow = (int32_t*)&s_t[0][0];                        /* coefficient k of lane i at [k * TE_TW + i] */
   int32_t hfirst = 0, cfirst = 0;
   if (tid < ncc) {
-    const int hn = m355_resize_row(a.sn_x[1], cdx, (int)swl, cc0 + tid, &cfirst, hrow + tid, TE_TW);
+    const int hn = m355_resize_row(TE_GEOM(sn_x[1]), cdx, (int)swl, cc0 + tid, &cfirst, hrow + tid, TE_TW);
     if (tid == 0) s_span[1][0] = cfirst;
     if (tid == ncc - 1) s_span[1][1] = cfirst + hn - 1;
   }
   if (tid >= 256u - TE_TH && tid - (256u - TE_TH) < nrows) {
     const uint32_t jj = tid - (256u - TE_TH);
-    s_vy[0][jj][1] = m355_resize_row(a.sn_y[0], dny, 0, j0 + jj, &s_vy[0][jj][0], &s_vy[0][jj][2], 1);
+    s_vy[0][jj][1] = m355_resize_row(TE_GEOM(sn_y[0]), dny, 0, j0 + jj, &s_vy[0][jj][0], &s_vy[0][jj][2], 1);
   }
   if (tid >= 256u - 2 * TE_TH && tid - (256u - 2 * TE_TH) < ncr) {
     const uint32_t jj = tid - (256u - 2 * TE_TH);
-    s_vy[1][jj][1] = m355_resize_row(a.sn_y[1], cdy, 0, cj0 + jj, &s_vy[1][jj][0], &s_vy[1][jj][2], 1);
+    s_vy[1][jj][1] = m355_resize_row(TE_GEOM(sn_y[1]), cdy, 0, cj0 + jj, &s_vy[1][jj][0], &s_vy[1][jj][2], 1);
   }
   __syncthreads();
 
@@ -198,7 +222,7 @@ __global__ void __launch_bounds__(256) k_export_tensor(ExportTensorArgs a)
        vector would load it behind the first, not ahead), and two rows of each where four fit */
     const uint32_t cap = (nvec * S <= (uint32_t)(TE_SPAN / 4) && 4u * nvec <= 256u) ? 4u : ((nvec * S <= (uint32_t)(TE_SPAN / 2) && 2u * nvec <= 256u) ? 2u : 1u);
     const uint32_t npl = cap >= 2u ? 2u : 1u, rpp = cap / npl, nseg = cap, seglen = TE_SPAN / cap;
-    const int hmax = m355_resize_max_taps(a.sn_x[1], cdx);
+    const int hmax = m355_resize_max_taps(TE_GEOM(sn_x[1]), cdx);
     const int32_t hofs = cfirst - span0, lim = (int32_t)seglen;
     const uint32_t pitch = (uint32_t)fr.src_pitch[1];
     const int tsh = a.bdc - 4, osh = 31 - a.bdc;
@@ -231,7 +255,7 @@ __global__ void __launch_bounds__(256) k_export_tensor(ExportTensorArgs a)
   /* the horizontal rows of the tile's luma columns, derived here so that their registers are not held across the chroma phase */
   unsigned hq[M355_RESIZE_MAX_TAPS];
   if (tid < ncols) {
-    const int hn = m355_resize_row(a.sn_x[0], dnx, 0, c0 + tid, &hfirst, hrow + tid, TE_TW);
+    const int hn = m355_resize_row(TE_GEOM(sn_x[0]), dnx, 0, c0 + tid, &hfirst, hrow + tid, TE_TW);
     if (tid == 0) s_span[0][0] = hfirst;
     if (tid == ncols - 1) s_span[0][1] = hfirst + hn - 1;
   }
@@ -244,7 +268,7 @@ __global__ void __launch_bounds__(256) k_export_tensor(ExportTensorArgs a)
   uint32_t nvec = (uint32_t)(s_span[0][1] - span0 + S) / S;
   if (nvec > (uint32_t)(TE_SPAN / S)) nvec = TE_SPAN / S;
   const uint32_t rpp = (nvec * S <= (uint32_t)(TE_SPAN / 2) && 2u * nvec <= 256u) ? 2u : 1u, seglen = TE_SPAN / rpp;   /* two output rows per pass where two spans fit a row of s_t and the lanes */
-  const int hmax = m355_resize_max_taps(a.sn_x[0], dnx);
+  const int hmax = m355_resize_max_taps(TE_GEOM(sn_x[0]), dnx);
   const int32_t hofs = hfirst - span0;
   const uint32_t pitch = (uint32_t)fr.src_pitch[0];             /* (a frame's rows are far below 4 GiB) */
   const int tsh = a.bdl - 4, osh = 31 - a.bdl;
@@ -269,7 +293,12 @@ __global__ void __launch_bounds__(256) k_export_tensor(ExportTensorArgs a)
   /* where the staged row's bytes go: NHWC one segment of up to 192 * EB dwords, NCHW three of up to SEGW = 64 * EB (the planes of the slice) */
   constexpr uint32_t SEGW = TE_TW * EB / 4, SEGSH = EB == 4 ? 8 : 7;
   const uint32_t seg_bytes = ncols * (uint32_t)EB * (planar ? 1u : 3u);
-  M355_GLOBAL uint8_t* const dst0 = (M355_GLOBAL uint8_t*)a.dst + (size_t)slice * (size_t)a.stride_n + (size_t)c0 * (size_t)EB * (planar ? 1u : 3u);
+  /* a mirrored slice: the lane of tile column t stages its pixel at position ncols - 1 - t, and the tile's first destination column is
+     out_width - c0 - ncols; the stores themselves do not change */
+  bool mirror = false;
+  if constexpr (ROI) mirror = (fr.flags & M355_ROI_MIRROR) != 0;
+  const uint32_t pos = mirror ? ncols - 1u - tid : tid, col0 = mirror ? dnx - c0 - ncols : c0;
+  M355_GLOBAL uint8_t* const dst0 = (M355_GLOBAL uint8_t*)a.dst + (size_t)slice * (size_t)a.stride_n + (size_t)col0 * (size_t)EB * (planar ? 1u : 3u);
   const size_t stride_c = (size_t)a.stride_c, stride_h = (size_t)a.stride_h;
 
 #define TE_STORE_ROW(buf, row) \
@@ -331,7 +360,7 @@ __global__ void __launch_bounds__(256) k_export_tensor(ExportTensorArgs a)
         for (int c = 0; c < 3; c++) {
           const float f = m355_te_affine(e[c], sc[c], bi[c]);
           const uint32_t bits = EB == 4 ? m355_te_bits(f) : m355_te_half(f, bf16_mask);
-          const uint32_t at = planar ? (uint32_t)c * (SEGW * 4u) + tid * (uint32_t)EB : (3u * tid + (uint32_t)c) * (uint32_t)EB;
+          const uint32_t at = planar ? (uint32_t)c * (SEGW * 4u) + pos * (uint32_t)EB : (3u * pos + (uint32_t)c) * (uint32_t)EB;
           if (EB == 4) __builtin_memcpy(o + at, &bits, 4);
           else { const unsigned short h = (unsigned short)bits; __builtin_memcpy(o + at, &h, 2); }
         }
@@ -342,6 +371,7 @@ __global__ void __launch_bounds__(256) k_export_tensor(ExportTensorArgs a)
   for (uint32_t i = 0; i < staged; i++) { TE_STORE_ROW(s_o[par ^ 1u][i], j0 + staged_j + i) }
 #undef TE_STORE_ROW
 }
+#undef TE_GEOM
 #undef TE_LOAD_BATCH
 
 void m355_launch_export_tensor(const ExportTensorArgs& a, int src_bytes, int elem_bytes, hipStream_t st)
@@ -349,7 +379,18 @@ void m355_launch_export_tensor(const ExportTensorArgs& a, int src_bytes, int ele
   if (!a.units || !a.n) return;
   const dim3 grid(a.units * a.n), block(256);
 #define M355_EXPORT_TENSOR_CASE(SB, EB) \
-  if (src_bytes == SB && elem_bytes == EB) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_export_tensor<SB, EB>), grid, block, 0, st, a);
+  if (src_bytes == SB && elem_bytes == EB) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_export_tensor<SB, EB, false>), grid, block, 0, st, a);
+  M355_EXPORT_TENSOR_CASE(1, 2) M355_EXPORT_TENSOR_CASE(1, 4) M355_EXPORT_TENSOR_CASE(2, 2) M355_EXPORT_TENSOR_CASE(2, 4)
+#undef M355_EXPORT_TENSOR_CASE
+}
+
+/* the batch of regions: blockIdx.y = slice, blockIdx.x = the unit inside it, up to the largest unit count of a slice */
+void m355_launch_export_tensor_rois(const ExportTensorRoisArgs& a, int src_bytes, int elem_bytes, hipStream_t st)
+{
+  if (!a.max_units || !a.n) return;
+  const dim3 grid(a.max_units, a.n), block(256);
+#define M355_EXPORT_TENSOR_CASE(SB, EB) \
+  if (src_bytes == SB && elem_bytes == EB) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_export_tensor<SB, EB, true>), grid, block, 0, st, a);
   M355_EXPORT_TENSOR_CASE(1, 2) M355_EXPORT_TENSOR_CASE(1, 4) M355_EXPORT_TENSOR_CASE(2, 2) M355_EXPORT_TENSOR_CASE(2, 4)
 #undef M355_EXPORT_TENSOR_CASE
 }

@@ -848,6 +848,99 @@ int m355_frames_export_tensor(m355_ctx* c, const int* frames, int n, const m355_
   for (int i = 1; i < n; i++) P[i].f->reader[RD_EXPORT] = f->reader[RD_EXPORT];
   return M355_OK;
 }
+/* A batch of REGIONS, one rectangle per slice, as one float tensor in one launch (k_export_tensor.hip, ROI = true): slice i is what
+ * m355_frames_export_tensor delivers for frames[i] alone with rois[i] as the rectangle, its columns reversed under M355_ROI_MIRROR.  Every entry's
+ * handle and rectangle are checked by export_plan against ITS frame, the ratio per entry; tile width, tiles and units are resize_rgb_tile_w's for the
+ * entry's own source size.  Readers, streams, marks and gates are those of m355_frames_export_tensor. */
+int m355_frames_export_tensor_rois(m355_ctx* c, const int* frames, const m355_tensor_roi* rois, int n, const m355_tensor_desc* e)
+{
+  const char* who = "m355_frames_export_tensor_rois";
+  if (!c || !frames || !rois || !e || n < 1 || n > M355_TENSOR_MAX_FRAMES)
+    return fail(M355_ERR_INVALID, "%s: no context / frames / rois / descriptor, or %d entries are not 1..%d", who, n, M355_TENSOR_MAX_FRAMES);
+  if (e->x0 || e->y0 || e->width || e->height)
+    return fail(M355_ERR_INVALID, "%s: the descriptor's rectangle %d,%d %dx%d must be zero (the rectangles are the entries')", who, e->x0, e->y0, e->width, e->height);
+  ExportPlan P[M355_TENSOR_MAX_FRAMES];
+  for (int i = 0; i < n; i++) {
+    if (rois[i].flags & ~M355_ROI_MIRROR) return fail(M355_ERR_INVALID, "%s: unknown flags 0x%x of entry %d", who, (unsigned)rois[i].flags, i);
+    m355_export_desc yuv = {};
+    yuv.layout = M355_EXPORT_PLANAR; yuv.samples = M355_EXPORT_NATIVE;
+    yuv.x0 = rois[i].x0; yuv.y0 = rois[i].y0; yuv.width = rois[i].width; yuv.height = rois[i].height;
+    for (int p = 0; p < 3; p++) { yuv.dst[p] = (void*)e; yuv.pitch[p] = INT64_MAX; }
+    int rc = export_plan(c, frames[i], &yuv, 0, who, P[i]);
+    if (rc) return rc;
+    const Frame *f = P[i].f, *f0 = P[0].f;
+    if (f->cf != f0->cf || f->bdl != f0->bdl || f->bdc != f0->bdc || f->bpp[0] != f0->bpp[0])
+      return fail(M355_ERR_INVALID, "%s: chroma format / bit depths of frame %d (entry %d) differ from those of frame %d", who, frames[i], i, frames[0]);
+  }
+  Frame* f = P[0].f;
+  const int sw = (f->cf == 1 || f->cf == 2) ? 2 : 1, sh = f->cf == 1 ? 2 : 1;
+  if (e->out_width <= 0 || e->out_height <= 0 || e->out_width % sw || e->out_height % sh)
+    return fail(M355_ERR_INVALID, "%s: output size %dx%d is not positive or no multiple of %dx%d luma samples", who, e->out_width, e->out_height, sw, sh);
+  for (int i = 0; i < n; i++)
+    if (!m355_resize_ratio_ok(P[i].p[0].pw, e->out_width) || !m355_resize_ratio_ok(P[i].p[0].ph, e->out_height))
+      return fail(M355_ERR_INVALID, "%s: entry %d, %dx%d to %dx%d is more than 8x down or up", who, i, P[i].p[0].pw, P[i].p[0].ph, e->out_width, e->out_height);
+  if (e->layout != M355_TENSOR_NCHW && e->layout != M355_TENSOR_NHWC) return fail(M355_ERR_INVALID, "%s: unknown layout %d", who, e->layout);
+  if (e->dtype != M355_TENSOR_F32 && e->dtype != M355_TENSOR_F16 && e->dtype != M355_TENSOR_BF16) return fail(M355_ERR_INVALID, "%s: unknown dtype %d", who, e->dtype);
+  ExportTensorRoisArgs a = {};
+  int rc = m355_rgb_coefficients(e->matrix, e->full_range, f->bdl, f->bdc, e->samples, &a.k);
+  if (rc) return rc;
+  for (int k = 0; k < 3; k++) {
+    if ((m355_te_bits(e->scale[k]) & 0x7F800000u) == 0x7F800000u || (m355_te_bits(e->bias[k]) & 0x7F800000u) == 0x7F800000u)
+      return fail(M355_ERR_INVALID, "%s: scale / bias of channel %d is not finite", who, k);
+    a.scale[k] = e->scale[k]; a.bias[k] = e->bias[k];
+  }
+  const bool nhwc = e->layout == M355_TENSOR_NHWC;
+  const int eb = e->dtype == M355_TENSOR_F32 ? 4 : 2, sb = f->bpp[0];
+  const int64_t row = (int64_t)e->out_width * eb * (nhwc ? 3 : 1);
+  if (!e->dst) return fail(M355_ERR_INVALID, "%s: no destination", who);
+  if (((uintptr_t)e->dst | (uint64_t)e->stride_h | (nhwc ? 0u : (uint64_t)e->stride_c) | (n > 1 ? (uint64_t)e->stride_n : 0u)) & (uint64_t)(eb - 1))
+    return fail(M355_ERR_INVALID, "%s: the destination or a stride is no multiple of the %d-byte element", who, eb);
+  if (e->stride_h < row) return fail(M355_ERR_INVALID, "%s: stride_h %lld is below the row of %lld bytes", who, (long long)e->stride_h, (long long)row);
+  const __int128 E = (__int128)(e->out_height - 1) * e->stride_h + row;              /* first byte behind a plane's (NHWC: a slice's) last row */
+  if (!nhwc && (__int128)e->stride_c < E) return fail(M355_ERR_INVALID, "%s: stride_c %lld lets the planes overlap (%lld bytes each)", who, (long long)e->stride_c, (long long)E);
+  if (n > 1 && (__int128)e->stride_n < (nhwc ? E : 2 * (__int128)e->stride_c + E))
+    return fail(M355_ERR_INVALID, "%s: stride_n %lld lets the slices overlap", who, (long long)e->stride_n);
+  a.dst = (uint8_t*)e->dst; a.stride_n = n > 1 ? e->stride_n : 0; a.stride_c = nhwc ? 0 : e->stride_c; a.stride_h = e->stride_h;
+  a.dn_x[0] = (uint32_t)e->out_width; a.dn_y[0] = (uint32_t)e->out_height;
+  if (f->cf != 0) { a.dn_x[1] = (uint32_t)(e->out_width / sw); a.dn_y[1] = (uint32_t)(e->out_height / sh); }
+  a.n = (uint32_t)n;
+  a.cf = f->cf; a.nhwc = nhwc; a.bf16 = e->dtype == M355_TENSOR_BF16; a.u16 = e->samples == M355_RGB_U16; a.bdl = f->bdl; a.bdc = f->bdc;
+  const uint32_t runs = ((uint32_t)e->out_height + M355_RESIZE_TILE_H - 1) / M355_RESIZE_TILE_H;
+  for (int i = 0; i < n; i++) {
+    const ExportPlan& Q = P[i];
+    ExportTensorRoi& r = a.fr[i];
+    for (int p = 0; p < Q.np; p++) r.src[p] = Q.p[p].src[0];
+    r.src_pitch[0] = Q.p[0].src_pitch; r.src_pitch[1] = Q.np > 1 ? Q.p[1].src_pitch : 0;
+    r.flags = (uint32_t)rois[i].flags;
+    r.sn_x[0] = (uint32_t)Q.p[0].pw; r.sn_y[0] = (uint32_t)Q.p[0].ph;
+    if (Q.np > 1) { r.sn_x[1] = (uint32_t)Q.p[1].pw; r.sn_y[1] = (uint32_t)Q.p[1].ph; }
+    r.tile_w = resize_rgb_tile_w(Q.p[0].pw, e->out_width, Q.np > 1 ? Q.p[1].pw : 0, e->out_width / sw, sb, sw);
+    r.tiles_x = ((uint32_t)e->out_width + r.tile_w - 1) / r.tile_w;
+    r.units = r.tiles_x * runs;
+    if (r.units > a.max_units) a.max_units = r.units;
+  }
+  hipSetDevice(c->device);
+  const hipStream_t cs = reader_begin(c, f, RD_EXPORT, &a.fr[0].timeout, &a.fr[0].epoch);
+  for (int i = 1; i < n; i++) {
+    Frame* g = P[i].f;
+    int first = 0;
+    while (P[first].f != g) first++;
+    if (first < i) { a.fr[i].timeout = a.fr[first].timeout; a.fr[i].epoch = a.fr[first].epoch; continue; }   /* the same frame again */
+    ev_wait(c, cs, g->wr);                                  /* the frame's last writer (nothing to enqueue when that ran on `cs`) */
+    ev_wait(c, cs, g->reader[RD_EXPORT]);                   /* ... and its earlier export on another stream: the one mark kept stands for both */
+    if (g->wr_stream && g->wr_gate) { a.fr[i].timeout = g->wr_gate; a.fr[i].epoch = g->wr_epoch; }
+    else {                                                  /* no decode to be gated by: an epoch of its own, which no gate word holds (reader_begin) */
+      a.fr[i].timeout = lane(c).timeout; a.fr[i].epoch = ++c->epoch;
+      if (a.fr[i].epoch == 0) a.fr[i].epoch = ++c->epoch;
+    }
+  }
+  m355_launch_export_tensor_rois(a, sb, eb, cs);
+  HIPCHK(hipGetLastError());
+  rc = reader_end(c, f, RD_EXPORT, cs);
+  if (rc) return rc;
+  for (int i = 1; i < n; i++) P[i].f->reader[RD_EXPORT] = f->reader[RD_EXPORT];
+  return M355_OK;
+}
 /* the host waits until this frame's last export has landed */
 int m355_frame_export_wait(m355_ctx* c, int h)
 {

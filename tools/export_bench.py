@@ -23,6 +23,11 @@
   (y8), (z8), (y32), (z32) a 224x224 export of the 1080x1080 window (420, 0) of N = 8 / 32 frames of 1920x1088: (y) N consecutive
       m355_frame_export_resized_rgb U8 planar launches, one per frame; (z) ONE m355_frames_export_tensor batch of the same N frames, F16 NCHW.  A
       slice is 14 workgroups, so a single launch leaves most of the chip empty; the bars are (z) <= (y) + the spread of (b)
+  (R8), (R32) m355_frames_export_tensor_rois with 8 / 32 regions all equal to the window of (z8), (z32), of the same frames: the new call where the old
+      one can do the same; the bars are (R) <= (z) + the spread (max - min) of that (z) row's own rounds
+  (S32), (T32) 32 DIFFERENT regions of one 1920x1088 frame to 224x224, F16 NCHW — a seeded list (ROI_SEED) that holds both ratio limits (28x28: 8x up,
+      1792 columns: 8x down) and regions of two tiles across, printed in the result line: (S32) 32 m355_frames_export_tensor launches with n = 1,
+      one per region; (T32) ONE m355_frames_export_tensor_rois of the list, every fourth region mirrored.  The bar is (T32) <= (S32) + the spread of (b)
 
 and, beside them, m355_measure_copy_rate for the frame's byte count.  Every figure is the median of --iters launches; (b) is measured in
 --rounds separate rounds spread over the run, and the spread of their medians is the margin (c), (d), (g)-(j) and (m)-(p) are held against: a scaled or resized export reads exactly (b)'s source bytes and writes at most a
@@ -35,6 +40,7 @@ import argparse
 import ctypes
 import json
 import os
+import random
 import statistics
 import sys
 
@@ -44,6 +50,7 @@ from libde265_amd import capi  # noqa: E402
 
 W, H, BD = 7680, 4320, 10
 D2D = 3   # hipMemcpyDeviceToDevice
+ROI_SEED = 8500
 
 
 def hip_runtime():
@@ -164,6 +171,22 @@ def main():
         arr = (ctypes.c_int * len(frames))(*frames)
         return lambda: lib.check(lib.lib.m355_frames_export_tensor(ctx.h, arr, len(frames), ctypes.byref(d)))
 
+    def export_tensor_rois(frames, rois, layout, dtype, samples, out_size):
+        eb = 4 if dtype == capi.TENSOR_F32 else 2
+        ow, oh = out_size
+        row = ow * eb * (3 if layout == capi.TENSOR_NHWC else 1)
+        sc = oh * row if layout == capi.TENSOR_NCHW else 0
+        d = capi.TensorDesc(layout=layout, dtype=dtype, samples=samples, matrix=capi.MATRIX_BT709, full_range=0, out_width=ow, out_height=oh,
+                            stride_n=3 * ow * oh * eb, stride_c=sc, stride_h=row)
+        M = 65535.0 if samples == capi.RGB_U16 else 255.0
+        d.scale = (ctypes.c_float * 3)(*[1.0 / (M * x) for x in (0.229, 0.224, 0.225)])
+        d.bias = (ctypes.c_float * 3)(*[-m / x for m, x in zip((0.485, 0.456, 0.406), (0.229, 0.224, 0.225))])
+        assert len(frames) == len(rois) and len(frames) * 3 * ow * oh * eb <= W * 3 * H
+        d.dst = rgb_dst[0]
+        arr = (ctypes.c_int * len(frames))(*frames)
+        ra = (capi.TensorRoi * len(rois))(*[capi.TensorRoi(*r) for r in rois])
+        return lambda: lib.check(lib.lib.m355_frames_export_tensor_rois(ctx.h, arr, ra, len(frames), ctypes.byref(d)))
+
     # the frames of the batch rows: 32 frames of 1920x1088, of which the centre square goes to a model's 224x224
     batch = [ctx.frame_create(1920, 1088, 1, BD, BD) for _ in range(32)]
     for k, f in enumerate(batch):
@@ -182,6 +205,32 @@ def main():
         def run():
             for k in range(n):
                 lib.check(lib.lib.m355_frame_export_resized_rgb(ctx.h, batch[k], ctypes.byref(descs[k])))
+        return run
+
+    # 32 different regions of batch[0] that 224x224 accepts (28..1792 columns, 28..1088 rows, on the chroma grid): the two ratio limits first, then
+    # seeded ones, of which those of 510 columns and more have two tiles across
+    rng = random.Random(ROI_SEED)
+    roi_list = [(946, 530, 28, 28), (64, 0, 1792, 1088), (288, 4, 1344, 1080)]
+    while len(roi_list) < 32:
+        w, h = 2 * rng.randint(14, 896), 2 * rng.randint(14, 544)
+        r = (2 * rng.randint(0, (1920 - w) // 2), 2 * rng.randint(0, (1088 - h) // 2), w, h)
+        if r not in roi_list:
+            roi_list.append(r)
+
+    def single_rois():
+        calls = []
+        for k, r in enumerate(roi_list):
+            d = capi.TensorDesc(layout=capi.TENSOR_NCHW, dtype=capi.TENSOR_F16, samples=capi.RGB_U8, matrix=capi.MATRIX_BT709, full_range=0, out_width=224,
+                                out_height=224, stride_n=3 * 224 * 224 * 2, stride_c=224 * 224 * 2, stride_h=224 * 2)
+            d.scale = (ctypes.c_float * 3)(*[1.0 / (255.0 * x) for x in (0.229, 0.224, 0.225)])
+            d.bias = (ctypes.c_float * 3)(*[-m / x for m, x in zip((0.485, 0.456, 0.406), (0.229, 0.224, 0.225))])
+            d.x0, d.y0, d.width, d.height = r
+            d.dst = rgb_dst[0] + k * 3 * 224 * 224 * 2
+            calls.append((d, (ctypes.c_int * 1)(batch[0])))
+
+        def run():
+            for d, arr in calls:
+                lib.check(lib.lib.m355_frames_export_tensor(ctx.h, arr, 1, ctypes.byref(d)))
         return run
 
     variants = {
@@ -214,6 +263,11 @@ def main():
         "z8_tensor_f16_nchw_224_batch8": export_tensor(batch[:8], capi.TENSOR_NCHW, capi.TENSOR_F16, capi.RGB_U8, (224, 224), SQUARE),
         "y32_resized_rgb_u8_planar_224_x32": singles(32),
         "z32_tensor_f16_nchw_224_batch32": export_tensor(batch, capi.TENSOR_NCHW, capi.TENSOR_F16, capi.RGB_U8, (224, 224), SQUARE),
+        "R8_tensor_rois_f16_nchw_224_batch8": export_tensor_rois(batch[:8], [SQUARE + (0,)] * 8, capi.TENSOR_NCHW, capi.TENSOR_F16, capi.RGB_U8, (224, 224)),
+        "R32_tensor_rois_f16_nchw_224_batch32": export_tensor_rois(batch, [SQUARE + (0,)] * 32, capi.TENSOR_NCHW, capi.TENSOR_F16, capi.RGB_U8, (224, 224)),
+        "S32_tensor_f16_nchw_224_x32_regions": single_rois(),
+        "T32_tensor_rois_f16_nchw_224_32_regions": export_tensor_rois([batch[0]] * 32, [r + (capi.ROI_MIRROR if k % 4 == 3 else 0,) for k, r in enumerate(roi_list)],
+                                                                      capi.TENSOR_NCHW, capi.TENSOR_F16, capi.RGB_U8, (224, 224)),
     }
     scaled = [n for n in variants if n[0] in "ghijmnop"]
     ms = {n: [] for n in variants}
@@ -242,6 +296,13 @@ def main():
                    "z32_over_y32": res["z32_tensor_f16_nchw_224_batch32"] / res["y32_resized_rgb_u8_planar_224_x32"],
                    "us_per_frame": {n: 1e3 * res[n] / k for n, k in (("y8_resized_rgb_u8_planar_224_x8", 8), ("z8_tensor_f16_nchw_224_batch8", 8),
                                                                     ("y32_resized_rgb_u8_planar_224_x32", 32), ("z32_tensor_f16_nchw_224_batch32", 32))}},
+        "tensor_rois": {"roi_seed": ROI_SEED, "rois": roi_list,
+                        "z8_spread_ms": max(ms["z8_tensor_f16_nchw_224_batch8"]) - min(ms["z8_tensor_f16_nchw_224_batch8"]),
+                        "z32_spread_ms": max(ms["z32_tensor_f16_nchw_224_batch32"]) - min(ms["z32_tensor_f16_nchw_224_batch32"]),
+                        "R8_over_z8": res["R8_tensor_rois_f16_nchw_224_batch8"] / res["z8_tensor_f16_nchw_224_batch8"],
+                        "R32_over_z32": res["R32_tensor_rois_f16_nchw_224_batch32"] / res["z32_tensor_f16_nchw_224_batch32"],
+                        "T32_over_S32": res["T32_tensor_rois_f16_nchw_224_32_regions"] / res["S32_tensor_f16_nchw_224_x32_regions"],
+                        "us_per_region": {n: 1e3 * res[n] / 32 for n in ("S32_tensor_f16_nchw_224_x32_regions", "T32_tensor_rois_f16_nchw_224_32_regions")}},
         "copy_rate_GBps_same_bytes": ctx.measure_copy_rate(frame_bytes, 9),
         "bars": {"b_le_a": res["b_native_planar"] <= res["a_memcpy2d_x3"],
                  "c_le_b_plus_spread": res["c_msb16_semiplanar_crop8"] <= res["b_native_planar"] + spread,
@@ -252,7 +313,12 @@ def main():
                  "s_le_p_plus_v_plus_spread": res["s_resized_rgb_u8_planar_720p"] <= res["p_resized_native_planar_720p"] + res["v_rgb_u8_planar_of_720p"] + spread,
                  "w_le_x_plus_spread": res["w_tensor_f16_nhwc_1080p"] <= res["x_resized_rgb_u16_packed_1080p"] + spread,
                  "z8_le_y8_plus_spread": res["z8_tensor_f16_nchw_224_batch8"] <= res["y8_resized_rgb_u8_planar_224_x8"] + spread,
-                 "z32_le_y32_plus_spread": res["z32_tensor_f16_nchw_224_batch32"] <= res["y32_resized_rgb_u8_planar_224_x32"] + spread},
+                 "z32_le_y32_plus_spread": res["z32_tensor_f16_nchw_224_batch32"] <= res["y32_resized_rgb_u8_planar_224_x32"] + spread,
+                 "R8_le_z8_plus_z8_spread": res["R8_tensor_rois_f16_nchw_224_batch8"] <= res["z8_tensor_f16_nchw_224_batch8"]
+                 + max(ms["z8_tensor_f16_nchw_224_batch8"]) - min(ms["z8_tensor_f16_nchw_224_batch8"]),
+                 "R32_le_z32_plus_z32_spread": res["R32_tensor_rois_f16_nchw_224_batch32"] <= res["z32_tensor_f16_nchw_224_batch32"]
+                 + max(ms["z32_tensor_f16_nchw_224_batch32"]) - min(ms["z32_tensor_f16_nchw_224_batch32"]),
+                 "T32_le_S32_plus_spread": res["T32_tensor_rois_f16_nchw_224_32_regions"] <= res["S32_tensor_f16_nchw_224_x32_regions"] + spread},
     }
     line = json.dumps(out)
     print(line)
