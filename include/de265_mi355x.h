@@ -586,7 +586,7 @@ typedef struct m355_resize_rgb_desc {
   int64_t pitch[3];                 /* bytes per destination row, >= the OUTPUT row's bytes */
 } m355_resize_rgb_desc;             /* (LP64: 88 bytes) */
 M355_API int   m355_frame_export_resized_rgb(m355_ctx* ctx, int frame, const m355_resize_rgb_desc* desc);   /* asynchronous */
-/* A BATCH of frames, each resized and converted to R'G'B' as above, NORMALISED and delivered as ONE float tensor in one launch (k_export_tensor.hip):
+/* A BATCH of frames, each resized and converted to R'G'B' as above, NORMALISED and delivered as ONE float tensor in one launch (k_export_resized_rgb.hip):
  * the input of a model on the same GPU.  The definition is again a composition:
  *   channel c (0 = R, 1 = G, 2 = B) of pixel (x, y) of slice i starts as the integer v that m355_frame_export_resized_rgb delivers for frames[i]
  *   with this rectangle, this output size and the descriptor's samples (M355_RGB_U8: 0..255, M355_RGB_U16: 0..65535), matrix and full_range;

@@ -339,7 +339,7 @@ struct ExportResizedArgs {
 /* src_bytes / dst_bytes: 1 or 2 per sample */
 void m355_launch_export_resized(const ExportResizedArgs& a, int src_bytes, int dst_bytes, bool semiplanar, hipStream_t st);
 
-/* one m355_frame_export_resized_rgb (k_export_resized_rgb.hip).  src[] = the rectangle's first sample of Y, Cb, Cr (the resize clamps to the rectangle),
+/* one m355_frame_export_resized_rgb (k_export_resized_rgb.hip, RR_FRAME).  src[] = the rectangle's first sample of Y, Cb, Cr (the resize clamps to the rectangle),
    pitches in BYTES (src_pitch[0] luma, [1] both chroma planes); dst[0] alone for the packed layout, else R, G, B.  Index 0 of sn / dn is the luma
    grid, 1 the chroma grid (zeros for a monochrome frame): sn_x x sn_y source samples of the rectangle to dn_x x dn_y output samples; the horizontal
    chroma axis of 4:2:0 / 4:2:2 is co-sited.  A workgroup owns a tile of tile_w <= M355_RESIZE_TILE_W luma output columns (even for 4:2:0 / 4:2:2)
@@ -359,7 +359,7 @@ struct ExportResizedRgbArgs {
 /* src_bytes / dst_bytes: 1 or 2 per sample / channel */
 void m355_launch_export_resized_rgb(const ExportResizedRgbArgs& a, int src_bytes, int dst_bytes, hipStream_t st);
 
-/* one m355_frames_export_tensor (k_export_tensor.hip): the tile procedure of k_export_resized_rgb over n frames in one grid, unit = slice * units + the
+/* one m355_frames_export_tensor (k_export_resized_rgb.hip, RR_BATCH): the tile procedure over n frames in one grid, unit = slice * units + the
    tile inside the slice (units tiles per slice).  Per slice: src[] = the rectangle's first sample of Y, Cb, Cr in that frame, its two pitches (BYTES)
    and the gate of the decode that wrote it.  Everything else is the batch's, with the meanings of ExportResizedRgbArgs: the grids, the tile width,
    cf, bdl / bdc, k.  u16: the integer stage is M355_RGB_U16 (clip to 65535, else 255); nhwc / bf16: layout and, for 2-byte elements, the format;
@@ -383,7 +383,7 @@ struct ExportTensorArgs {
 /* src_bytes: 1 or 2 per sample; elem_bytes: 2 (F16 / BF16) or 4 (F32) */
 void m355_launch_export_tensor(const ExportTensorArgs& a, int src_bytes, int elem_bytes, hipStream_t st);
 
-/* one m355_frames_export_tensor_rois (k_export_tensor.hip, ROI = true): the same tile procedure, with the GEOMETRY of the source per slice.  A slice's
+/* one m355_frames_export_tensor_rois (k_export_resized_rgb.hip, RR_ROIS): the same tile procedure, with the GEOMETRY of the source per slice.  A slice's
    record holds what ExportTensorFrame holds — src[] = the first sample of ITS rectangle in ITS frame, the pitches, the gate — and what is the batch's
    there: the rectangle's size on the luma and the chroma grid (sn_x, sn_y; zeros for a monochrome frame), the tile width, the tiles per row of tiles
    and the slice's units, each derived from the slice's own source size, and flags (M355_ROI_MIRROR: the epilogue stores the slice's columns in

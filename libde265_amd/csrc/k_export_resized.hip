@@ -29,37 +29,11 @@
  */
 #include "k_common.h"
 #include "resize_taps.h"
+#include "k_resize_dev.h"
 
 #define RS_TW M355_RESIZE_TILE_W
 #define RS_TH M355_RESIZE_TILE_H
 #define RS_SPAN 2112                /* >= 255 * 8 + 1 + 16 + 15 = 2072, and 2 * RS_SPAN >= 16 * RS_TW for the prologue's coefficient rows */
-
-/* a 2-byte store at any address (k_asm.h has none) */
-#ifdef SIMT_EMU
-static inline void d_rs_stg2(void* p, unsigned v) { const unsigned short t = (unsigned short)v; memcpy(p, &t, 2); }
-#else
-__device__ __forceinline__ void d_rs_stg2(M355_GLOBAL void* p, unsigned v) { *(M355_GLOBAL m355_h1*)p = (unsigned short)v; }
-#endif
-
-/* c + a.lo * b.lo + a.hi * b.hi on packed unsigned 16-bit pairs (v_dot2_u32_u16: two rows of the vertical filter per issue), and c + a * b for
-   a, b < 2^24 (v_mad_u32_u24; a full 32-bit multiply is a quarter-rate instruction) — k_asm.h has the signed dot product only */
-#ifdef SIMT_EMU
-static inline unsigned d_rs_udot2(unsigned a, unsigned b, unsigned c) { return c + (a & 0xFFFFu) * (b & 0xFFFFu) + (a >> 16) * (b >> 16); }
-static inline unsigned d_rs_mad24(unsigned a, unsigned b, unsigned c) { return c + a * b; }
-#else
-__device__ __forceinline__ unsigned d_rs_udot2(unsigned a, unsigned b, unsigned c)
-{
-  return __builtin_amdgcn_udot2(__builtin_bit_cast(m355_ushort2, a), __builtin_bit_cast(m355_ushort2, b), c, false);
-}
-__device__ __forceinline__ unsigned d_rs_mad24(unsigned a, unsigned b, unsigned c) { return __umul24(a, b) + c; }
-#endif
-
-/* sample e of the 16-byte vectors of two rows as one 16-bit pair (row ra in the low half): what d_rs_udot2 takes beside the rows' coefficients */
-template <int SB> __device__ __forceinline__ unsigned d_rs_pair(const unsigned* ra, const unsigned* rb, int e)
-{
-  if (SB == 1) return d_perm(rb[e >> 2], ra[e >> 2], 0x0c000c00u | (unsigned)(e & 3) | ((unsigned)(4 + (e & 3)) << 16));
-  return (e & 1) ? d_pack_hi16(ra[e >> 1], rb[e >> 1]) : d_pack_lo16(ra[e >> 1], rb[e >> 1]);
-}
 
 /* (the selection idiom of k_export.hip: the three entries of an argument table as scalars, two scalar compares) */
 #define M355_EXPORT_SEL(arr) (p2 ? (arr)[2] : (p1 ? (arr)[1] : (arr)[0]))
@@ -147,7 +121,7 @@ __global__ void __launch_bounds__(256) k_export_resized(ExportResizedArgs a)
                  scalar registers across this loop spilled up to 12 of them in the 16-bit semi-planar instantiations; 2 spills are left there) */
               const unsigned q2 = (unsigned)(s_vy[jj][2 + b + r] | (s_vy[jj][3 + b + r] << 16));
 #pragma unroll
-              for (int e = 0; e < S; e++) u[e] = d_rs_udot2(d_rs_pair<SB>(raw[r], raw[r + 1], e), q2, u[e]);
+              for (int e = 0; e < S; e++) u[e] = d_udot2(d_pair<SB>(raw[r], raw[r + 1], e), q2, u[e]);
             }
           }
         }
@@ -172,18 +146,18 @@ __global__ void __launch_bounds__(256) k_export_resized(ExportResizedArgs a)
         for (int k = 0; k < M355_RESIZE_MAX_TAPS; k++) {
           if (k >= hmax) break;
           const int32_t x = hofs + k;
-          v = d_rs_mad24(hq[k], trow[c][x < RS_SPAN ? x : RS_SPAN - 1], v);     /* (behind the row's last coefficient: 0 times an entry of the array) */
+          v = d_umad24(hq[k], trow[c][x < RS_SPAN ? x : RS_SPAN - 1], v);     /* (behind the row's last coefficient: 0 times an entry of the array) */
         }
         unsigned w = ((v >> 1) + (1u << (osh - 1))) >> osh;
         if (DB == 1) w = w < 255u ? w : 255u;
         o[c] = w << lsh;
       }
       if (inter) {
-        if (DB == 1) d_rs_stg2(d, o[0] | (o[1] << 8));
+        if (DB == 1) d_stg2(d, o[0] | (o[1] << 8));
         else d_stg4(d, o[0] | (o[1] << 16));
       } else {
         if (DB == 1) d[0] = (uint8_t)o[0];
-        else d_rs_stg2(d, o[0]);
+        else d_stg2(d, o[0]);
       }
     }
     d += dpitch;

@@ -1,8 +1,12 @@
 /*
- * k_export_resized_rgb.hip — a decoded frame (or a rectangle of it) RESIZED and converted to R'G'B' in one launch (m355_frame_export_resized_rgb,
- * include/de265_mi355x.h): the composition of m355_frame_export_resized (planar, NATIVE) and m355_frame_export_rgb of the resized picture, byte for
- * byte, without a resized Y, Cb or Cr sample passing through global memory.  No new arithmetic: the filter rows are those of resize_taps.h, the
- * passes those of k_export_resized.hip, the chroma filter and the matrix those of k_export_rgb.hip.
+ * k_export_resized_rgb.hip — decoded frames (or a rectangle of each) RESIZED and converted to R'G'B' in one launch, in three modes:
+ *   RR_FRAME  one frame, integer R'G'B' of EB = 1 or 2 bytes per channel (m355_frame_export_resized_rgb, include/de265_mi355x.h): the composition
+ *             of m355_frame_export_resized (planar, NATIVE) and m355_frame_export_rgb of the resized picture, byte for byte, without a resized Y,
+ *             Cb or Cr sample passing through global memory;
+ *   RR_BATCH  n frames, one rectangle, as one float tensor of EB = 2 (F16 / BF16) or 4 (F32) bytes per element (m355_frames_export_tensor);
+ *   RR_ROIS   n frames, a rectangle per slice, as one float tensor (m355_frames_export_tensor_rois).
+ * No new arithmetic: the filter rows are those of resize_taps.h, the passes those of k_export_resized.hip, the chroma filter and the matrix those of
+ * k_export_rgb.hip, the float stage that of tensor_element.h.
  *
  * A workgroup of 256 lanes owns a tile of up to 256 luma output columns x 16 luma output rows (even width for 4:2:0 / 4:2:2, so that a tile's
  * first column is a chroma column).  Prologue: lane i derives the horizontal row of resized chroma column cc0 + i into registers (through LDS, as
@@ -21,53 +25,53 @@
  *   Luma phase: two output rows per pass where they fit, else one; the horizontal sum is rounded to a sample in a register; the lane's chroma comes
  *   from the LDS tile through the filter of k_export_rgb.hip (T = 3 C[j] + C[jn], even / odd column forms, c0 folded into the rounding constant),
  *   then the five v_mad_i32_i24 of the matrix, the shift and the clip.
- *   Stores: a lane holds one pixel of each row of the pass; the rows' channels are staged in LDS (packed: R,G,B per pixel; planar: three segments)
- *   and leave as dwords, a lane per dword of consecutive addresses; only the valid bytes at the end of the tile's row are stored, the last ones as
- *   single bytes.  The staged rows are stored behind the NEXT pass's barrier (two sets of staging rows alternate), so a pass costs one barrier.
- * Layout and chroma format are wave-uniform run-time switches (kernel arguments in scalar registers): source and destination sample bytes are
- * the template parameters, four instantiations.
+ *   Stores: a lane holds one pixel of each row of the pass; the rows' channels are staged in LDS as EB-byte elements (packed / NHWC: the three of a
+ *   pixel side by side; planar / NCHW: three segments) and leave as dwords, a lane per dword of consecutive addresses; only the valid bytes at the
+ *   end of the tile's row are stored.  The staged rows are stored behind the NEXT pass's barrier (two sets of staging rows alternate), so a pass
+ *   costs one barrier.
+ * What the modes differ in (`if constexpr`, at the place of the difference; a field that moves is read where it is used — RR_SRC, RR_PITCH, RR_GEOM —,
+ * never through a reference to the slice's record, which costs the tensor instantiations some 200 instructions and an unrolled loop):
+ *   Grid and gate.  RR_FRAME: blockIdx.x = the tile, one gate.  RR_BATCH: blockIdx.x runs over n * units, slice = blockIdx.x / units; RR_ROIS: slices
+ *   have different unit counts, so blockIdx.y = slice and blockIdx.x = the unit inside it, as wide as the slice with the most units (a workgroup
+ *   beyond its slice's count returns).  A slice picks its source pointers, two pitches, gate word and epoch from the per-slice array of the kernel
+ *   arguments (a wave-uniform index: scalar loads), and a slice whose frame sits behind a rejected decode returns before it touches anything.
+ *   RR_ROIS also reads the source size on both grids, the tile width and the tiles per row of tiles from the slice's record (the host derives
+ *   each from the slice's own source size); output size, bit depths, chroma format and coefficients are the launch's in every mode.
+ *   Epilogue.  RR_FRAME stages the clipped integers (clip by EB; a staged row is 1536 bytes, a planar segment 512, for both EB), stores the
+ *   trailing bytes of a row singly and finds segment s at dst[s] + row * dst_pitch[s].  The tensor modes clip by the u16 argument, pass the integers
+ *   through tensor_element.h (one multiplication, one addition, the conversion), stage rows of 768 * EB bytes, store a row's trailing half dword
+ *   (EB = 2, an odd number of elements) as one element and find segment s at dst + slice * stride_n + s * stride_c + row * stride_h.  Static LDS:
+ *   41 872 bytes, or 48 016 for EB = 4: three workgroups per CU in both (160 KiB of LDS).
+ *   Mirror (RR_ROIS, M355_ROI_MIRROR) touches the epilogue only: the lane of tile column t stages its pixel at position ncols - 1 - t of the
+ *   staged row (the channels of an NHWC pixel keep their order), and the tile's first destination column is out_width - c0 - ncols.
+ * Layout, chroma format, F16 against BF16 and U8 against U16 of the tensors' integer stage are wave-uniform run-time switches (kernel arguments in
+ * scalar registers): source sample bytes, element bytes and the mode are the template parameters, twelve instantiations.
  *
- * Reads stay inside the planes' allocations, by the argument of k_export_resized.hip for every plane: a filter row's source indices are clamped
- * to the rectangle on that plane's grid (resize_taps.h), so every row read — a luma row, or one of the chroma phase's rows, whose output indices
- * are clamped to the resized plane before their filter rows are derived — is a row of the rectangle; every vector starts at a sample of the span,
- * which runs from the first source column of the tile's first (chroma: cc0-th) column to the last source column of its last one, both samples of
- * the rectangle; a lane reads at most 16 bytes from there, i.e. less than 16 bytes beyond a sample inside a row of the plane, and rows are padded
- * to 128 bytes and a plane ends with a 256-byte tail (runtime_internal.h frame_alloc).  The t row holds RR_SPAN entries (256 columns advance by at
- * most 255 * 8 + 1 source samples, a row adds 16, the last vector 15); the vector count is clamped to the array all the same.  The chroma tile is
+ * Reads stay inside the planes' allocations, by the argument of k_export_resized.hip for every plane of every slice: the host admits a frame only
+ * if it contains the slice's rectangle (export_plan per frame), whose size is the source size the slice's rows are derived from.  A filter row's
+ * source indices are clamped to the rectangle on that plane's grid (resize_taps.h), so every row read — a luma row, or one of the chroma phase's
+ * rows, whose output indices are clamped to the resized plane before their filter rows are derived — is a row of the rectangle; every vector starts
+ * at a sample of the span, which runs from the first source column of the tile's first (chroma: cc0-th) column to the last source column of its
+ * last one, both samples of the rectangle; a lane reads at most 16 bytes from there, i.e. less than 16 bytes beyond a sample inside a row of the
+ * plane, and rows are padded to 128 bytes and a plane ends with a 256-byte tail (runtime_internal.h frame_alloc).  The slice index is below
+ * n <= M355_TENSOR_MAX_FRAMES, the size of the per-slice array (checked first).  The t row holds RR_SPAN entries (256 columns advance by at most
+ * 255 * 8 + 1 source samples, a row adds 16, the last vector 15); the vector count is clamped to the array all the same.  The chroma tile is
  * indexed by columns 0 .. cc1 - cc0 <= 256 and rows 0 .. cj1 - cj0 <= 15 only: the filter's neighbours are clamped to cc1 / cj0 / cj1, which the
- * clamp of the definition (the resized plane's last column and first / last row) never exceeds.
+ * clamp of the definition (the resized plane's last column and first / last row) never exceeds.  The staged row is indexed below its OB bytes
+ * (position < ncols <= 256, channel < 3).
+ * Writes: channel c of output pixel (row, column) of the slice only, with row < out_height and column < out_width (mirrored: the tile's columns
+ * out_width - c0 - ncols .. out_width - c0 - 1); the host has checked that pitches and strides keep rows, planes and slices apart.
  * Arithmetic: the resize in unsigned 32 bits as in k_export_resized.hip; the conversion in signed 32 bits as in k_export_rgb.hip.
  */
 #include "k_common.h"
 #include "resize_taps.h"
+#include "tensor_element.h"
+#include "k_resize_dev.h"
 
 #define RR_TW M355_RESIZE_TILE_W
 #define RR_TH M355_RESIZE_TILE_H
 #define RR_SPAN 2112                /* >= 255 * 8 + 1 + 16 + 15 = 2072, and 2 * RR_SPAN >= 16 * RR_TW for the prologue's coefficient rows */
 #define RR_CW 258                   /* entries of a row of the chroma tile: 4:4:4 256, 4:2:0 / 4:2:2 256 / 2 + 1 */
-#define RR_OB (RR_TW * 3 * 2)       /* bytes of a staged output row: 256 pixels x 3 channels x 2 bytes */
-
-/* the helpers of k_export_resized.hip and k_export_rgb.hip that this kernel needs too: c + a.lo * b.lo + a.hi * b.hi on packed unsigned 16-bit
-   pairs (v_dot2_u32_u16), c + a * b for a, b < 2^24 (v_mad_u32_u24), and the signed v_mad_i32_i24 */
-#ifdef SIMT_EMU
-static inline unsigned d_rr_udot2(unsigned a, unsigned b, unsigned c) { return c + (a & 0xFFFFu) * (b & 0xFFFFu) + (a >> 16) * (b >> 16); }
-static inline unsigned d_rr_umad24(unsigned a, unsigned b, unsigned c) { return c + a * b; }
-static inline int d_rr_mad24(int a, int b, int c) { return (int)((unsigned)a * (unsigned)b + (unsigned)c); }
-#else
-__device__ __forceinline__ unsigned d_rr_udot2(unsigned a, unsigned b, unsigned c)
-{
-  return __builtin_amdgcn_udot2(__builtin_bit_cast(m355_ushort2, a), __builtin_bit_cast(m355_ushort2, b), c, false);
-}
-__device__ __forceinline__ unsigned d_rr_umad24(unsigned a, unsigned b, unsigned c) { return __umul24(a, b) + c; }
-__device__ __forceinline__ int d_rr_mad24(int a, int b, int c) { return (int)((unsigned)__mul24(a, b) + (unsigned)c); }
-#endif
-
-/* sample e of the 16-byte vectors of two rows as one 16-bit pair (row ra in the low half) */
-template <int SB> __device__ __forceinline__ unsigned d_rr_pair(const unsigned* ra, const unsigned* rb, int e)
-{
-  if (SB == 1) return d_perm(rb[e >> 2], ra[e >> 2], 0x0c000c00u | (unsigned)(e & 3) | ((unsigned)(4 + (e & 3)) << 16));
-  return (e & 1) ? d_pack_hi16(ra[e >> 1], rb[e >> 1]) : d_pack_lo16(ra[e >> 1], rb[e >> 1]);
-}
 
 /* rows b .. b + 7 of a filter row of vn source rows, 16 bytes each from s (rows behind the vn-th: zeros) */
 #define RR_LOAD_BATCH(s, b, vn, pitch) \
@@ -118,7 +122,7 @@ __device__ __forceinline__ void d_rr_vertical(const M355_GLOBAL uint8_t* src0, c
           if (b + r < vn) {
             const unsigned q2 = (unsigned)(q[2 + b + r] | (q[3 + b + r] << 16));  /* (the same in every lane of a segment) */
 #pragma unroll
-            for (int e = 0; e < S; e++) u[e] = d_rr_udot2(d_rr_pair<SB>(raw[r], raw[r + 1], e), q2, u[e]);
+            for (int e = 0; e < S; e++) u[e] = d_udot2(d_pair<SB>(raw[r], raw[r + 1], e), q2, u[e]);
           }
         }
       }
@@ -138,29 +142,50 @@ __device__ __forceinline__ unsigned d_rr_horizontal(const unsigned* hq, const un
   for (int k = 0; k < M355_RESIZE_MAX_TAPS; k++) {
     if (k >= hmax) break;
     const int32_t x = hofs + k;
-    v = d_rr_umad24(hq[k], trow[x < lim ? x : lim - 1], v);     /* (behind the row's last coefficient: 0 times an entry of the row) */
+    v = d_umad24(hq[k], trow[x < lim ? x : lim - 1], v);        /* (behind the row's last coefficient: 0 times an entry of the row) */
   }
   return ((v >> 1) + (1u << (osh - 1))) >> osh;
 }
 
-template <int SB, int DB>
-__global__ void __launch_bounds__(256) k_export_resized_rgb(ExportResizedRgbArgs a)
+/* The modes and their kernel arguments.  RR_SRC(i) / RR_PITCH(i): plane i's first sample and pitch class i of the frame or of the slice's record;
+   RR_GEOM(field): a field of the source's geometry, the slice's in RR_ROIS, else the launch's — each read at the place of its use. */
+enum { RR_FRAME = 0, RR_BATCH = 1, RR_ROIS = 2 };
+template <int MODE> struct RrArgs { typedef ExportResizedRgbArgs T; };
+template <> struct RrArgs<RR_BATCH> { typedef ExportTensorArgs T; };
+template <> struct RrArgs<RR_ROIS> { typedef ExportTensorRoisArgs T; };
+#define RR_SRC(i) ({ const M355_GLOBAL uint8_t* g_; if constexpr (MODE == RR_FRAME) g_ = (const M355_GLOBAL uint8_t*)a.src[i]; else g_ = (const M355_GLOBAL uint8_t*)a.fr[slice].src[i]; g_; })
+#define RR_PITCH(i) ({ uint32_t g_; if constexpr (MODE == RR_FRAME) g_ = (uint32_t)a.src_pitch[i]; else g_ = (uint32_t)a.fr[slice].src_pitch[i]; g_; })
+#define RR_GEOM(field) ({ uint32_t g_; if constexpr (MODE == RR_ROIS) g_ = a.fr[slice].field; else g_ = a.field; g_; })
+
+template <int SB, int EB, int MODE>
+__global__ void __launch_bounds__(256) k_export_resized_rgb(typename RrArgs<MODE>::T a)
 {
-  M355_GATE(a);
-  constexpr int S = 16 / SB, M = DB == 1 ? 255 : 65535;
+  constexpr int S = 16 / SB;
+  constexpr uint32_t OB = RR_TW * 3 * (MODE == RR_FRAME ? 2 : EB);   /* bytes of a staged output row: 256 pixels x 3 channels x 2 (tensors: EB) bytes */
+  uint32_t slice = 0;                                           /* (wave-uniform: the slice's record comes by scalar loads) */
+  if constexpr (MODE == RR_FRAME) M355_GATE(a);
+  else {
+    if constexpr (MODE == RR_ROIS) slice = blockIdx.y; else slice = blockIdx.x / a.units;
+    if (slice >= a.n) return;
+    M355_GATE(a.fr[slice]);
+  }
+  if constexpr (MODE == RR_ROIS) { if (blockIdx.x >= a.fr[slice].units) return; }   /* (the grid is as wide as the slice with the most units) */
   __shared__ unsigned s_t[2][RR_SPAN];                          /* [pass & 1]: the t rows of the pass's segments; in the prologue: the lanes' horizontal rows */
   __shared__ int32_t s_vy[2][RR_TH][2 + M355_RESIZE_MAX_TAPS];  /* [luma, chroma] per output row of the tile: first source row, number of rows, coefficients */
   __shared__ int32_t s_span[2][2];                              /* [luma, chroma] first and last source column of the tile */
   __shared__ unsigned short s_c[2][RR_TH][RR_CW];               /* the resized Cb and Cr samples the tile's pixels need */
-  __shared__ __attribute__((aligned(16))) uint8_t s_o[2][2][RR_OB];  /* [pass & 1][row of the pass]: the staged output rows */
-  const uint32_t tid = threadIdx.x, unit = blockIdx.x;
-  if (unit >= a.units) return;
-  const uint32_t run = unit / a.tiles_x, tile = unit - run * a.tiles_x;
-  const uint32_t tw = a.tile_w, c0 = tile * tw, j0 = run * RR_TH;
+  __shared__ __attribute__((aligned(16))) uint8_t s_o[2][2][OB];  /* [pass & 1][row of the pass]: the staged output rows */
+  uint32_t unit = blockIdx.x;
+  if constexpr (MODE == RR_FRAME) { if (unit >= a.units) return; }   /* (here, not beside the gate: there the two exits become one branch and the code another) */
+  if constexpr (MODE == RR_BATCH) unit -= slice * a.units;
+  const uint32_t tid = threadIdx.x;
+  const uint32_t run = unit / RR_GEOM(tiles_x), tile = unit - run * RR_GEOM(tiles_x);
+  const uint32_t tw = RR_GEOM(tile_w), c0 = tile * tw, j0 = run * RR_TH;
   const uint32_t dnx = a.dn_x[0], dny = a.dn_y[0], cdx = a.dn_x[1], cdy = a.dn_y[1];
   const uint32_t ncols = dnx - c0 < tw ? dnx - c0 : tw, nrows = dny - j0 < (uint32_t)RR_TH ? dny - j0 : (uint32_t)RR_TH;
   const int cf = a.cf;
-  const bool planar = a.planar != 0;
+  bool planar;                                                  /* planar R'G'B' / NCHW: three staged segments */
+  if constexpr (MODE == RR_FRAME) planar = a.planar != 0; else planar = a.nhwc == 0;
   const uint32_t swl = (cf == 1 || cf == 2) ? 1u : 0u, shl = cf == 1 ? 1u : 0u;
   /* the chroma tile: columns cc0 .. cc1 and rows cj0 .. cj1 of the resized chroma planes */
   uint32_t cc0 = 0, ncc = 0, cj0 = 0, ncr = 0;
@@ -179,17 +204,17 @@ __global__ void __launch_bounds__(256) k_export_resized_rgb(ExportResizedRgbArgs
   int32_t* hrow = (int32_t*)&s_t[0][0];                        /* coefficient k of lane i at [k * RR_TW + i] */
   int32_t hfirst = 0, cfirst = 0;
   if (tid < ncc) {
-    const int hn = m355_resize_row(a.sn_x[1], cdx, (int)swl, cc0 + tid, &cfirst, hrow + tid, RR_TW);
+    const int hn = m355_resize_row(RR_GEOM(sn_x[1]), cdx, (int)swl, cc0 + tid, &cfirst, hrow + tid, RR_TW);
     if (tid == 0) s_span[1][0] = cfirst;
     if (tid == ncc - 1) s_span[1][1] = cfirst + hn - 1;
   }
   if (tid >= 256u - RR_TH && tid - (256u - RR_TH) < nrows) {
     const uint32_t jj = tid - (256u - RR_TH);
-    s_vy[0][jj][1] = m355_resize_row(a.sn_y[0], dny, 0, j0 + jj, &s_vy[0][jj][0], &s_vy[0][jj][2], 1);
+    s_vy[0][jj][1] = m355_resize_row(RR_GEOM(sn_y[0]), dny, 0, j0 + jj, &s_vy[0][jj][0], &s_vy[0][jj][2], 1);
   }
   if (tid >= 256u - 2 * RR_TH && tid - (256u - 2 * RR_TH) < ncr) {
     const uint32_t jj = tid - (256u - 2 * RR_TH);
-    s_vy[1][jj][1] = m355_resize_row(a.sn_y[1], cdy, 0, cj0 + jj, &s_vy[1][jj][0], &s_vy[1][jj][2], 1);
+    s_vy[1][jj][1] = m355_resize_row(RR_GEOM(sn_y[1]), cdy, 0, cj0 + jj, &s_vy[1][jj][0], &s_vy[1][jj][2], 1);
   }
   __syncthreads();
 
@@ -208,13 +233,13 @@ __global__ void __launch_bounds__(256) k_export_resized_rgb(ExportResizedRgbArgs
        vector would load it behind the first, not ahead), and two rows of each where four fit */
     const uint32_t cap = (nvec * S <= (uint32_t)(RR_SPAN / 4) && 4u * nvec <= 256u) ? 4u : ((nvec * S <= (uint32_t)(RR_SPAN / 2) && 2u * nvec <= 256u) ? 2u : 1u);
     const uint32_t npl = cap >= 2u ? 2u : 1u, rpp = cap / npl, nseg = cap, seglen = RR_SPAN / cap;
-    const int hmax = m355_resize_max_taps(a.sn_x[1], cdx);
+    const int hmax = m355_resize_max_taps(RR_GEOM(sn_x[1]), cdx);
     const int32_t hofs = cfirst - span0, lim = (int32_t)seglen;
-    const uint32_t pitch = (uint32_t)a.src_pitch[1];
+    const uint32_t pitch = RR_PITCH(1);
     const int tsh = a.bdc - 4, osh = 31 - a.bdc;
     for (uint32_t c = 0; c < 2; c += npl) {
-      const M355_GLOBAL uint8_t* const src0 = (const M355_GLOBAL uint8_t*)(c ? a.src[2] : a.src[1]);
-      const M355_GLOBAL uint8_t* const src1 = (const M355_GLOBAL uint8_t*)a.src[2];
+      const M355_GLOBAL uint8_t* const src0 = c ? RR_SRC(2) : RR_SRC(1);
+      const M355_GLOBAL uint8_t* const src1 = RR_SRC(2);
       const RrWhere me = d_rr_where<SB>(src0, src1, span0, nvec, npl, tid);
       const bool active = tid < nseg * nvec;
       if (active && me.row < ncr) {
@@ -241,7 +266,7 @@ __global__ void __launch_bounds__(256) k_export_resized_rgb(ExportResizedRgbArgs
   /* the horizontal rows of the tile's luma columns, derived here so that their registers are not held across the chroma phase */
   unsigned hq[M355_RESIZE_MAX_TAPS];
   if (tid < ncols) {
-    const int hn = m355_resize_row(a.sn_x[0], dnx, 0, c0 + tid, &hfirst, hrow + tid, RR_TW);
+    const int hn = m355_resize_row(RR_GEOM(sn_x[0]), dnx, 0, c0 + tid, &hfirst, hrow + tid, RR_TW);
     if (tid == 0) s_span[0][0] = hfirst;
     if (tid == ncols - 1) s_span[0][1] = hfirst + hn - 1;
   }
@@ -254,11 +279,11 @@ __global__ void __launch_bounds__(256) k_export_resized_rgb(ExportResizedRgbArgs
   uint32_t nvec = (uint32_t)(s_span[0][1] - span0 + S) / S;
   if (nvec > (uint32_t)(RR_SPAN / S)) nvec = RR_SPAN / S;
   const uint32_t rpp = (nvec * S <= (uint32_t)(RR_SPAN / 2) && 2u * nvec <= 256u) ? 2u : 1u, seglen = RR_SPAN / rpp;   /* two output rows per pass where two spans fit a row of s_t and the lanes */
-  const int hmax = m355_resize_max_taps(a.sn_x[0], dnx);
+  const int hmax = m355_resize_max_taps(RR_GEOM(sn_x[0]), dnx);
   const int32_t hofs = hfirst - span0;
-  const uint32_t pitch = (uint32_t)a.src_pitch[0];             /* (a frame's rows are far below 4 GiB) */
+  const uint32_t pitch = RR_PITCH(0);                           /* (a frame's rows are far below 4 GiB) */
   const int tsh = a.bdl - 4, osh = 31 - a.bdl;
-  const M355_GLOBAL uint8_t* const srcy = (const M355_GLOBAL uint8_t*)a.src[0];
+  const M355_GLOBAL uint8_t* const srcy = RR_SRC(0);
   const RrWhere me = d_rr_where<SB>(srcy, srcy, span0, nvec, 1u, tid);
   const bool active = tid < rpp * nvec;
   /* the constants of the launch (scalar): the rounding term and the luma offset in one, c0 folded into the chroma filter's rounding constants */
@@ -272,20 +297,45 @@ __global__ void __launch_bounds__(256) k_export_resized_rgb(ExportResizedRgbArgs
     ci = i - cc0; cin = swl ? in - cc0 : ci;
   }
   const bool odd = swl && (X & 1u);
-  /* where the staged row's bytes go: packed one segment of up to 384 dwords, planar three of up to 128 */
-  const uint32_t seg_bytes = ncols * (uint32_t)DB * (planar ? 1u : 3u);
-  const size_t col_bytes = (size_t)c0 * (size_t)DB * (planar ? 1u : 3u);
-
+  /* the epilogue of the launch (scalar): the clip of the integer stage; tensors: the element format, scale and bias per channel (RR_TE: 0 for a frame) */
+#define RR_TE(T, expr) ({ T g_ = 0; if constexpr (MODE != RR_FRAME) g_ = (expr); g_; })
+  const int M = MODE == RR_FRAME ? (EB == 1 ? 255 : 65535) : (RR_TE(int, a.u16) ? 65535 : 255);
+  const uint32_t bf16_mask = RR_TE(int, a.bf16) ? 0xFFFFFFFFu : 0u;
+  const float sc[3] = {RR_TE(float, a.scale[0]), RR_TE(float, a.scale[1]), RR_TE(float, a.scale[2])};
+  const float bi[3] = {RR_TE(float, a.bias[0]), RR_TE(float, a.bias[1]), RR_TE(float, a.bias[2])};
+  /* where the staged row's bytes go: packed / NHWC one segment of up to OB / 4 dwords, planar / NCHW three of up to SEGW (512 or 1024 bytes apart) */
+  constexpr uint32_t SEGW = OB / 12u, SEGSH = SEGW == 256u ? 8 : 7;
+  const uint32_t seg_bytes = ncols * (uint32_t)EB * (planar ? 1u : 3u);
+  /* a mirrored slice: the lane of tile column t stages its pixel at position ncols - 1 - t, and the tile's first destination column is
+     out_width - c0 - ncols; the stores themselves do not change */
+  bool mirror = false;
+  if constexpr (MODE == RR_ROIS) mirror = (a.fr[slice].flags & M355_ROI_MIRROR) != 0;
+  const uint32_t pos = mirror ? ncols - 1u - tid : tid, col0 = mirror ? dnx - c0 - ncols : c0;
+  /* the first byte of the tile's row of segment seg (RR_DST): in the frame's planes, or in the slice's place in the tensor */
+  size_t col_bytes = 0, stride_c = 0, stride_h = 0;
+  M355_GLOBAL uint8_t* dst0 = nullptr;
+  if constexpr (MODE == RR_FRAME) col_bytes = (size_t)col0 * (size_t)EB * (planar ? 1u : 3u);
+  else {
+    dst0 = (M355_GLOBAL uint8_t*)a.dst + (size_t)slice * (size_t)a.stride_n + (size_t)col0 * (size_t)EB * (planar ? 1u : 3u);
+    stride_c = (size_t)a.stride_c; stride_h = (size_t)a.stride_h;
+  }
+#define RR_DST(seg, row) ({ \
+    M355_GLOBAL uint8_t* d_; \
+    if constexpr (MODE == RR_FRAME) \
+      d_ = (M355_GLOBAL uint8_t*)(seg == 0 ? a.dst[0] : (seg == 1 ? a.dst[1] : a.dst[2])) + \
+           (size_t)(row) * (size_t)(seg == 0 ? a.dst_pitch[0] : (seg == 1 ? a.dst_pitch[1] : a.dst_pitch[2])) + col_bytes; \
+    else d_ = dst0 + (size_t)seg * stride_c + (size_t)(row) * stride_h; \
+    d_; })
 #define RR_STORE_ROW(buf, row) \
-  for (uint32_t q = tid; q < (uint32_t)(RR_OB / 4); q += 256u) { \
-    const uint32_t seg = planar ? q >> 7 : 0u, w = planar ? q & 127u : q; \
+  for (uint32_t q = tid; q < OB / 4u; q += 256u) { \
+    const uint32_t seg = planar ? q >> SEGSH : 0u, w = planar ? q & (SEGW - 1u) : q; \
     if (4u * w < seg_bytes) { \
-      M355_GLOBAL uint8_t* d = (M355_GLOBAL uint8_t*)(seg == 0 ? a.dst[0] : (seg == 1 ? a.dst[1] : a.dst[2])) + \
-                               (size_t)(row) * (size_t)(seg == 0 ? a.dst_pitch[0] : (seg == 1 ? a.dst_pitch[1] : a.dst_pitch[2])) + col_bytes + 4u * w; \
+      M355_GLOBAL uint8_t* d = RR_DST(seg, row) + 4u * w; \
       unsigned val; \
       __builtin_memcpy(&val, (buf) + 4u * q, 4); \
       if (4u * w + 4u <= seg_bytes) d_stg4(d, val); \
-      else for (uint32_t k = 0; k < 3; k++) if (4u * w + k < seg_bytes) d[k] = (uint8_t)(val >> (8 * k)); \
+      else if constexpr (MODE == RR_FRAME) { for (uint32_t k = 0; k < 3; k++) if (4u * w + k < seg_bytes) d[k] = (uint8_t)(val >> (8 * k)); } \
+      else d_stg2(d, val);                                     /* (EB = 2 only: the row's last element) */ \
     } \
   }
 
@@ -307,7 +357,7 @@ __global__ void __launch_bounds__(256) k_export_resized_rgb(ExportResizedRgbArgs
       const uint32_t jj = jp + ri;
       if (tid < ncols) {
         const int y = (int)d_rr_horizontal(hq, s_t[par] + ri * seglen, (int32_t)seglen, hofs, hmax, osh);
-        const int base = d_rr_mad24(cy, y, ky);
+        const int base = d_mad24(cy, y, ky);
         int r = base, g = base, b = base;
         if (cf != 0) {
           int uv[2];
@@ -326,17 +376,23 @@ __global__ void __launch_bounds__(256) k_export_resized_rgb(ExportResizedRgbArgs
               uv[c] = odd ? (t0 + t1 + 1 - 2 * kc0) >> 1 : t0 - kc0;
             }
           }
-          r = d_rr_mad24(crv, uv[1], base);
-          g = d_rr_mad24(ncgv, uv[1], d_rr_mad24(ncgu, uv[0], base));
-          b = d_rr_mad24(cbu, uv[0], base);
+          r = d_mad24(crv, uv[1], base);
+          g = d_mad24(ncgv, uv[1], d_mad24(ncgu, uv[0], base));
+          b = d_mad24(cbu, uv[0], base);
         }
         const unsigned e[3] = {(unsigned)d_clip3(0, M, r >> F), (unsigned)d_clip3(0, M, g >> F), (unsigned)d_clip3(0, M, b >> F)};
         uint8_t* o = s_o[par][ri];
 #pragma unroll
         for (int c = 0; c < 3; c++) {
-          const uint32_t at = planar ? (uint32_t)c * 512u + tid * (uint32_t)DB : (3u * tid + (uint32_t)c) * (uint32_t)DB;
-          if (DB == 1) o[at] = (uint8_t)e[c];
-          else { const unsigned short h = (unsigned short)e[c]; __builtin_memcpy(o + at, &h, 2); }
+          uint32_t bits = e[c];                                /* a frame: the clipped integer; a tensor: through the float stage */
+          if constexpr (MODE != RR_FRAME) {
+            const float f = m355_te_affine(e[c], sc[c], bi[c]);
+            bits = EB == 4 ? m355_te_bits(f) : m355_te_half(f, bf16_mask);
+          }
+          const uint32_t at = planar ? (uint32_t)c * (SEGW * 4u) + pos * (uint32_t)EB : (3u * pos + (uint32_t)c) * (uint32_t)EB;
+          if (EB == 4) __builtin_memcpy(o + at, &bits, 4);
+          else if (EB == 1) o[at] = (uint8_t)bits;
+          else { const unsigned short h = (unsigned short)bits; __builtin_memcpy(o + at, &h, 2); }
         }
       }
     }
@@ -344,15 +400,35 @@ __global__ void __launch_bounds__(256) k_export_resized_rgb(ExportResizedRgbArgs
   __syncthreads();
   for (uint32_t i = 0; i < staged; i++) { RR_STORE_ROW(s_o[par ^ 1u][i], j0 + staged_j + i) }
 #undef RR_STORE_ROW
+#undef RR_DST
+#undef RR_TE
 }
+#undef RR_GEOM
+#undef RR_PITCH
+#undef RR_SRC
 #undef RR_LOAD_BATCH
 
-void m355_launch_export_resized_rgb(const ExportResizedRgbArgs& a, int src_bytes, int dst_bytes, hipStream_t st)
+/* src_bytes: 1 or 2 per sample; elem_bytes: 1 or 2 per channel of a frame, 2 or 4 per element of a tensor */
+#define RR_LAUNCH(MODE, B0, B1, grid) \
+  const dim3 g_ grid, block(256); \
+  if (src_bytes == 1 && elem_bytes == B0) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_export_resized_rgb<1, B0, MODE>), g_, block, 0, st, a); \
+  if (src_bytes == 1 && elem_bytes == B1) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_export_resized_rgb<1, B1, MODE>), g_, block, 0, st, a); \
+  if (src_bytes == 2 && elem_bytes == B0) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_export_resized_rgb<2, B0, MODE>), g_, block, 0, st, a); \
+  if (src_bytes == 2 && elem_bytes == B1) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_export_resized_rgb<2, B1, MODE>), g_, block, 0, st, a);
+void m355_launch_export_resized_rgb(const ExportResizedRgbArgs& a, int src_bytes, int elem_bytes, hipStream_t st)
 {
   if (!a.units) return;
-  const dim3 grid(a.units), block(256);
-#define M355_EXPORT_RESIZED_RGB_CASE(SB, DB) \
-  if (src_bytes == SB && dst_bytes == DB) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_export_resized_rgb<SB, DB>), grid, block, 0, st, a);
-  M355_EXPORT_RESIZED_RGB_CASE(1, 1) M355_EXPORT_RESIZED_RGB_CASE(1, 2) M355_EXPORT_RESIZED_RGB_CASE(2, 1) M355_EXPORT_RESIZED_RGB_CASE(2, 2)
-#undef M355_EXPORT_RESIZED_RGB_CASE
+  RR_LAUNCH(RR_FRAME, 1, 2, (a.units))
 }
+void m355_launch_export_tensor(const ExportTensorArgs& a, int src_bytes, int elem_bytes, hipStream_t st)
+{
+  if (!a.units || !a.n) return;
+  RR_LAUNCH(RR_BATCH, 2, 4, (a.units * a.n))
+}
+/* the batch of regions: blockIdx.y = slice, blockIdx.x = the unit inside it, up to the largest unit count of a slice */
+void m355_launch_export_tensor_rois(const ExportTensorRoisArgs& a, int src_bytes, int elem_bytes, hipStream_t st)
+{
+  if (!a.max_units || !a.n) return;
+  RR_LAUNCH(RR_ROIS, 2, 4, (a.max_units, a.n))
+}
+#undef RR_LAUNCH

@@ -496,6 +496,41 @@ static int export_plan(m355_ctx* c, int h, const m355_export_desc* e, int k, con
   return M355_OK;
 }
 
+extern "C++" {             /* (templates over the descriptors and the kernel arguments) */
+/* export_plan for the calls that check their destinations themselves: r = what holds the rectangle (a descriptor or a region; null: no descriptor),
+ * planned as an export of `layout` / `samples` whose destinations — `dst` for every plane, with a pitch no row exceeds — cannot fail unless dst is null */
+template <class R>
+static int export_plan_rect(m355_ctx* c, int h, const R* r, const void* dst, const char* who, ExportPlan& P, int layout = M355_EXPORT_PLANAR, int samples = M355_EXPORT_NATIVE)
+{
+  m355_export_desc yuv = {};
+  if (r) {
+    yuv.layout = layout; yuv.samples = samples;
+    yuv.x0 = r->x0; yuv.y0 = r->y0; yuv.width = r->width; yuv.height = r->height;
+    for (int p = 0; p < 3; p++) { yuv.dst[p] = (void*)dst; yuv.pitch[p] = INT64_MAX; }
+  }
+  return export_plan(c, h, r ? &yuv : nullptr, 0, who, P);
+}
+/* The checks of the R'G'B' descriptors (m355_rgb_desc, m355_resize_rgb_desc) behind the plan: the layout, the conversion (into a.k) and the destinations
+ * of rows of `width` pixels (into a.dst / a.dst_pitch) */
+template <class D, class A>
+static int rgb_desc_check(const char* who, const D* e, const Frame* f, int64_t width, A& a, bool* planar_out, int* db_out)
+{
+  if (e->layout != M355_RGB_PACKED && e->layout != M355_RGB_PLANAR) return fail(M355_ERR_INVALID, "%s: unknown layout %d", who, e->layout);
+  int rc = m355_rgb_coefficients(e->matrix, e->full_range, f->bdl, f->bdc, e->samples, &a.k);
+  if (rc) return rc;
+  const bool planar = e->layout == M355_RGB_PLANAR;
+  const int db = e->samples == M355_RGB_U16 ? 2 : 1;
+  const int64_t row_bytes = width * db * (planar ? 1 : 3);
+  for (int p = 0; p < (planar ? 3 : 1); p++) {
+    if (!e->dst[p]) return fail(M355_ERR_INVALID, "%s: no destination for plane %d", who, p);
+    if (e->pitch[p] < row_bytes) return fail(M355_ERR_INVALID, "%s: pitch %lld of plane %d is below its row of %lld bytes", who, (long long)e->pitch[p], p, (long long)row_bytes);
+    if (db == 2 && (((uintptr_t)e->dst[p] | (uint64_t)e->pitch[p]) & 1)) return fail(M355_ERR_INVALID, "%s: 16-bit plane %d at an odd address or pitch", who, p);
+    a.dst[p] = (uint8_t*)e->dst[p]; a.dst_pitch[p] = e->pitch[p];
+  }
+  *planar_out = planar; *db_out = db;
+  return M355_OK;
+}
+}
 /* The frame, or a rectangle of it, converted into memory of the caller (k_export.hip): one launch for all planes.  The export is a READER of the
  * frame (reader_begin): the mark behind it is what the next decode into the frame waits for (dst_hazards), what m355_frame_export_wait blocks on
  * and what m355_frame_export_order makes a consumer's stream wait for. */
@@ -582,29 +617,18 @@ int m355_rgb_coefficients(int matrix, int full_range, int bdl, int bdc, int samp
  * export whose destinations cannot fail —, the destinations here.  A reader of the kind RD_EXPORT, like the two above. */
 int m355_frame_export_rgb(m355_ctx* c, int h, const m355_rgb_desc* e)
 {
-  m355_export_desc yuv = {};
-  if (e) {
-    yuv.layout = M355_EXPORT_PLANAR; yuv.samples = M355_EXPORT_NATIVE;
-    yuv.x0 = e->x0; yuv.y0 = e->y0; yuv.width = e->width; yuv.height = e->height;
-    for (int p = 0; p < 3; p++) { yuv.dst[p] = e->dst[0]; yuv.pitch[p] = INT64_MAX; }
-  }
+  const char* who = "m355_frame_export_rgb";
   ExportPlan P;
-  int rc = export_plan(c, h, e ? &yuv : nullptr, 0, "m355_frame_export_rgb", P);
+  int rc = export_plan_rect(c, h, e, e ? e->dst[0] : nullptr, who, P);
   if (rc) return rc;
   Frame* f = P.f;
-  if (e->layout != M355_RGB_PACKED && e->layout != M355_RGB_PLANAR) return fail(M355_ERR_INVALID, "m355_frame_export_rgb: unknown layout %d", e->layout);
   ExportRgbArgs a = {};
-  rc = m355_rgb_coefficients(e->matrix, e->full_range, f->bdl, f->bdc, e->samples, &a.k);
+  bool planar = false;
+  int db = 1;
+  const int sb = f->bpp[0];
+  const int64_t w = P.p[0].pw;
+  rc = rgb_desc_check(who, e, f, w, a, &planar, &db);
   if (rc) return rc;
-  const bool planar = e->layout == M355_RGB_PLANAR;
-  const int db = e->samples == M355_RGB_U16 ? 2 : 1, sb = f->bpp[0];
-  const int64_t w = P.p[0].pw, row_bytes = w * db * (planar ? 1 : 3);
-  for (int p = 0; p < (planar ? 3 : 1); p++) {
-    if (!e->dst[p]) return fail(M355_ERR_INVALID, "m355_frame_export_rgb: no destination for plane %d", p);
-    if (e->pitch[p] < row_bytes) return fail(M355_ERR_INVALID, "m355_frame_export_rgb: pitch %lld of plane %d is below its row of %lld bytes", (long long)e->pitch[p], p, (long long)row_bytes);
-    if (db == 2 && (((uintptr_t)e->dst[p] | (uint64_t)e->pitch[p]) & 1)) return fail(M355_ERR_INVALID, "m355_frame_export_rgb: 16-bit plane %d at an odd address or pitch", p);
-    a.dst[p] = (uint8_t*)e->dst[p]; a.dst_pitch[p] = e->pitch[p];
-  }
   for (int p = 0; p < 3; p++) a.src[p] = (const uint8_t*)f->plane[p];
   a.src_pitch[0] = (long long)f->stride[0] * sb; a.src_pitch[1] = (long long)f->stride[1] * sb;
   a.x0 = e->width ? (uint32_t)e->x0 : 0u; a.y0 = e->width ? (uint32_t)e->y0 : 0u;
@@ -636,27 +660,35 @@ static uint32_t resize_tile_w(int64_t sn, int64_t dn, int sb)
   if (k >= 1 && nv % 64 != 0 && nv % 64 <= 16) while (w > 1 && vectors(w) > 64 * k) w--;
   return (uint32_t)w;
 }
+/* What the resizing exports check behind their plans: the output size against the chroma grid, and the ratio of every plan (entries > 0: of every entry
+ * of a batch of regions, which the message then names) */
+static int resize_check(const char* who, const ExportPlan* P, int entries, int ow, int oh)
+{
+  const Frame* f = P[0].f;
+  const int sw = (f->cf == 1 || f->cf == 2) ? 2 : 1, sh = f->cf == 1 ? 2 : 1;
+  if (ow <= 0 || oh <= 0 || ow % sw || oh % sh)
+    return fail(M355_ERR_INVALID, "%s: output size %dx%d is not positive or no multiple of %dx%d luma samples", who, ow, oh, sw, sh);
+  for (int i = 0; i < (entries ? entries : 1); i++) {
+    const int pw = P[i].p[0].pw, ph = P[i].p[0].ph;
+    if (m355_resize_ratio_ok(pw, ow) && m355_resize_ratio_ok(ph, oh)) continue;
+    if (entries) return fail(M355_ERR_INVALID, "%s: entry %d, %dx%d to %dx%d is more than 8x down or up", who, i, pw, ph, ow, oh);
+    return fail(M355_ERR_INVALID, "%s: %dx%d to %dx%d is more than 8x down or up", who, pw, ph, ow, oh);
+  }
+  return M355_OK;
+}
 /* The frame, or a rectangle of it, resized to out_width x out_height luma samples (k_export_resized.hip): the frame handle, the rectangle, the layout and
  * the samples are checked by export_plan — with destinations that cannot fail, as for the R'G'B' export —, the output size, the ratio and the destinations
  * here.  A reader of the kind RD_EXPORT, like the three above. */
 int m355_frame_export_resized(m355_ctx* c, int h, const m355_resize_desc* e)
 {
   const char* who = "m355_frame_export_resized";
-  m355_export_desc yuv = {};
-  if (e) {
-    yuv.layout = e->layout; yuv.samples = e->samples;
-    yuv.x0 = e->x0; yuv.y0 = e->y0; yuv.width = e->width; yuv.height = e->height;
-    for (int p = 0; p < 3; p++) { yuv.dst[p] = (void*)e; yuv.pitch[p] = INT64_MAX; }
-  }
   ExportPlan P;
-  int rc = export_plan(c, h, e ? &yuv : nullptr, 0, who, P);
+  int rc = export_plan_rect(c, h, e, e, who, P, e ? e->layout : 0, e ? e->samples : 0);
   if (rc) return rc;
   Frame* f = P.f;
   const int sw = (f->cf == 1 || f->cf == 2) ? 2 : 1, sh = f->cf == 1 ? 2 : 1;
-  if (e->out_width <= 0 || e->out_height <= 0 || e->out_width % sw || e->out_height % sh)
-    return fail(M355_ERR_INVALID, "%s: output size %dx%d is not positive or no multiple of %dx%d luma samples", who, e->out_width, e->out_height, sw, sh);
-  if (!m355_resize_ratio_ok(P.p[0].pw, e->out_width) || !m355_resize_ratio_ok(P.p[0].ph, e->out_height))
-    return fail(M355_ERR_INVALID, "%s: %dx%d to %dx%d is more than 8x down or up", who, P.p[0].pw, P.p[0].ph, e->out_width, e->out_height);
+  rc = resize_check(who, &P, 0, e->out_width, e->out_height);
+  if (rc) return rc;
   ExportResizedArgs a = {};
   uint32_t units = 0;
   for (int p = 0; p < 3; p++) {
@@ -705,51 +737,49 @@ static uint32_t resize_rgb_tile_w(int64_t sn, int64_t dn, int64_t csn, int64_t c
   if (sw == 2) even = (even + 1) & ~(int64_t)1;
   return (uint32_t)(even < w ? even : w);
 }
-/* The same resize with the R'G'B' conversion of the resized picture behind it, in one launch (k_export_resized_rgb.hip): the frame handle and the
- * rectangle are checked by export_plan — with destinations that cannot fail —, the output size and the ratio as for the resized export, the
+extern "C++" {             /* (templates over the descriptors and the kernel arguments) */
+/* What the kernel arguments of k_export_resized_rgb.hip take from a plan.  plan_sources: the rectangle's first samples and the two pitches, into the
+ * launch's or the slice's record.  plan_geometry: the source size on both grids, the tile width, the tiles per row of tiles and the units into g (the
+ * launch's or the slice's record), the output size on both grids into d (the launch's). */
+template <class R> static void plan_sources(const ExportPlan& Q, R& r)
+{
+  for (int p = 0; p < Q.np; p++) r.src[p] = Q.p[p].src[0];
+  r.src_pitch[0] = Q.p[0].src_pitch; r.src_pitch[1] = Q.np > 1 ? Q.p[1].src_pitch : 0;
+}
+template <class G, class D> static void plan_geometry(const ExportPlan& Q, int ow, int oh, G& g, D& d)
+{
+  const Frame* f = Q.f;
+  const int sw = (f->cf == 1 || f->cf == 2) ? 2 : 1, sh = f->cf == 1 ? 2 : 1;
+  g.sn_x[0] = (uint32_t)Q.p[0].pw; g.sn_y[0] = (uint32_t)Q.p[0].ph; d.dn_x[0] = (uint32_t)ow; d.dn_y[0] = (uint32_t)oh;
+  if (Q.np > 1) { g.sn_x[1] = (uint32_t)Q.p[1].pw; g.sn_y[1] = (uint32_t)Q.p[1].ph; d.dn_x[1] = (uint32_t)(ow / sw); d.dn_y[1] = (uint32_t)(oh / sh); }
+  g.tile_w = resize_rgb_tile_w(Q.p[0].pw, ow, Q.np > 1 ? Q.p[1].pw : 0, ow / sw, f->bpp[0], sw);
+  g.tiles_x = ((uint32_t)ow + g.tile_w - 1) / g.tile_w;
+  g.units = g.tiles_x * (((uint32_t)oh + M355_RESIZE_TILE_H - 1) / M355_RESIZE_TILE_H);
+}
+}
+/* The same resize with the R'G'B' conversion of the resized picture behind it, in one launch (k_export_resized_rgb.hip, RR_FRAME): the frame handle and
+ * the rectangle are checked by export_plan — with destinations that cannot fail —, the output size and the ratio as for the resized export, the
  * conversion and the destinations as for the R'G'B' export, with the OUTPUT width.  A reader of the kind RD_EXPORT, like the four above. */
 int m355_frame_export_resized_rgb(m355_ctx* c, int h, const m355_resize_rgb_desc* e)
 {
   const char* who = "m355_frame_export_resized_rgb";
-  m355_export_desc yuv = {};
-  if (e) {
-    yuv.layout = M355_EXPORT_PLANAR; yuv.samples = M355_EXPORT_NATIVE;
-    yuv.x0 = e->x0; yuv.y0 = e->y0; yuv.width = e->width; yuv.height = e->height;
-    for (int p = 0; p < 3; p++) { yuv.dst[p] = (void*)e; yuv.pitch[p] = INT64_MAX; }
-  }
   ExportPlan P;
-  int rc = export_plan(c, h, e ? &yuv : nullptr, 0, who, P);
+  int rc = export_plan_rect(c, h, e, e, who, P);
   if (rc) return rc;
   Frame* f = P.f;
-  const int sw = (f->cf == 1 || f->cf == 2) ? 2 : 1, sh = f->cf == 1 ? 2 : 1;
-  if (e->out_width <= 0 || e->out_height <= 0 || e->out_width % sw || e->out_height % sh)
-    return fail(M355_ERR_INVALID, "%s: output size %dx%d is not positive or no multiple of %dx%d luma samples", who, e->out_width, e->out_height, sw, sh);
-  if (!m355_resize_ratio_ok(P.p[0].pw, e->out_width) || !m355_resize_ratio_ok(P.p[0].ph, e->out_height))
-    return fail(M355_ERR_INVALID, "%s: %dx%d to %dx%d is more than 8x down or up", who, P.p[0].pw, P.p[0].ph, e->out_width, e->out_height);
-  if (e->layout != M355_RGB_PACKED && e->layout != M355_RGB_PLANAR) return fail(M355_ERR_INVALID, "%s: unknown layout %d", who, e->layout);
-  ExportResizedRgbArgs a = {};
-  rc = m355_rgb_coefficients(e->matrix, e->full_range, f->bdl, f->bdc, e->samples, &a.k);
+  rc = resize_check(who, &P, 0, e->out_width, e->out_height);
   if (rc) return rc;
-  const bool planar = e->layout == M355_RGB_PLANAR;
-  const int db = e->samples == M355_RGB_U16 ? 2 : 1, sb = f->bpp[0];
-  const int64_t row_bytes = (int64_t)e->out_width * db * (planar ? 1 : 3);
-  for (int p = 0; p < (planar ? 3 : 1); p++) {
-    if (!e->dst[p]) return fail(M355_ERR_INVALID, "%s: no destination for plane %d", who, p);
-    if (e->pitch[p] < row_bytes) return fail(M355_ERR_INVALID, "%s: pitch %lld of plane %d is below its row of %lld bytes", who, (long long)e->pitch[p], p, (long long)row_bytes);
-    if (db == 2 && (((uintptr_t)e->dst[p] | (uint64_t)e->pitch[p]) & 1)) return fail(M355_ERR_INVALID, "%s: 16-bit plane %d at an odd address or pitch", who, p);
-    a.dst[p] = (uint8_t*)e->dst[p]; a.dst_pitch[p] = e->pitch[p];
-  }
-  for (int p = 0; p < P.np; p++) a.src[p] = P.p[p].src[0];
-  a.src_pitch[0] = P.p[0].src_pitch; a.src_pitch[1] = P.np > 1 ? P.p[1].src_pitch : 0;
-  a.sn_x[0] = (uint32_t)P.p[0].pw; a.sn_y[0] = (uint32_t)P.p[0].ph; a.dn_x[0] = (uint32_t)e->out_width; a.dn_y[0] = (uint32_t)e->out_height;
-  if (P.np > 1) { a.sn_x[1] = (uint32_t)P.p[1].pw; a.sn_y[1] = (uint32_t)P.p[1].ph; a.dn_x[1] = (uint32_t)(e->out_width / sw); a.dn_y[1] = (uint32_t)(e->out_height / sh); }
-  a.tile_w = resize_rgb_tile_w(P.p[0].pw, e->out_width, P.np > 1 ? P.p[1].pw : 0, e->out_width / sw, sb, sw);
-  a.tiles_x = ((uint32_t)e->out_width + a.tile_w - 1) / a.tile_w;
-  a.units = a.tiles_x * (((uint32_t)e->out_height + M355_RESIZE_TILE_H - 1) / M355_RESIZE_TILE_H);
+  ExportResizedRgbArgs a = {};
+  bool planar = false;
+  int db = 1;
+  rc = rgb_desc_check(who, e, f, e->out_width, a, &planar, &db);
+  if (rc) return rc;
+  plan_sources(P, a);
+  plan_geometry(P, e->out_width, e->out_height, a, a);
   a.cf = f->cf; a.planar = planar; a.bdl = f->bdl; a.bdc = f->bdc;
   hipSetDevice(c->device);
   const hipStream_t cs = reader_begin(c, f, RD_EXPORT, &a.timeout, &a.epoch);
-  m355_launch_export_resized_rgb(a, sb, db, cs);
+  m355_launch_export_resized_rgb(a, f->bpp[0], db, cs);
   HIPCHK(hipGetLastError());
   return reader_end(c, f, RD_EXPORT, cs);
 }
@@ -762,39 +792,25 @@ int m355_tensor_element(uint32_t v, float scale, float bias, int dtype, uint32_t
   *bits = m355_te_element(v, scale, bias, dtype);
   return M355_OK;
 }
-/* A batch of frames resized, converted, normalised and delivered as one float tensor in one launch (k_export_tensor.hip).  Every frame's handle and
- * the rectangle in it are checked by export_plan — with destinations that cannot fail —, the output size, the ratio and the conversion as for
- * m355_frame_export_resized_rgb, the tensor's layout here.  A reader of the kind RD_EXPORT of EVERY frame of the batch, as m355_frame_measure_async is
- * of its two: the launch goes on the stream of frames[0]'s writer, which first continues behind the writer and the earlier export of each other
- * frame; the one mark behind the launch is kept by all of them; each frame brings its own gate. */
-int m355_frames_export_tensor(m355_ctx* c, const int* frames, int n, const m355_tensor_desc* e)
+extern "C++" {             /* (templates over the descriptors and the kernel arguments) */
+/* What the two tensor exports share (k_export_resized_rgb.hip, RR_BATCH and RR_ROIS).  batch_frame_check: frame i of the batch against frame 0 —
+ * chroma format and bit depths, and the size where whole frames must agree. */
+static int batch_frame_check(const char* who, const int* frames, int i, const ExportPlan* P, bool same_size)
 {
-  const char* who = "m355_frames_export_tensor";
-  if (!c || !frames || !e || n < 1 || n > M355_TENSOR_MAX_FRAMES) return fail(M355_ERR_INVALID, "%s: no context / frames / descriptor, or %d frames are not 1..%d", who, n, M355_TENSOR_MAX_FRAMES);
-  m355_export_desc yuv = {};
-  yuv.layout = M355_EXPORT_PLANAR; yuv.samples = M355_EXPORT_NATIVE;
-  yuv.x0 = e->x0; yuv.y0 = e->y0; yuv.width = e->width; yuv.height = e->height;
-  for (int p = 0; p < 3; p++) { yuv.dst[p] = (void*)e; yuv.pitch[p] = INT64_MAX; }
-  ExportPlan P[M355_TENSOR_MAX_FRAMES];
-  for (int i = 0; i < n; i++) {
-    int rc = export_plan(c, frames[i], &yuv, 0, who, P[i]);
-    if (rc) return rc;
-    const Frame *f = P[i].f, *f0 = P[0].f;
-    if (f->cf != f0->cf || f->bdl != f0->bdl || f->bdc != f0->bdc || f->bpp[0] != f0->bpp[0])
-      return fail(M355_ERR_INVALID, "%s: chroma format / bit depths of frame %d (entry %d) differ from those of frame %d", who, frames[i], i, frames[0]);
-    if (e->width == 0 && (f->w != f0->w || f->h != f0->h))
-      return fail(M355_ERR_INVALID, "%s: whole frames of different sizes (%dx%d, entry %d: %dx%d)", who, f0->w, f0->h, i, f->w, f->h);
-  }
-  Frame* f = P[0].f;
-  const ExportPlan& Q = P[0];
-  const int sw = (f->cf == 1 || f->cf == 2) ? 2 : 1, sh = f->cf == 1 ? 2 : 1;
-  if (e->out_width <= 0 || e->out_height <= 0 || e->out_width % sw || e->out_height % sh)
-    return fail(M355_ERR_INVALID, "%s: output size %dx%d is not positive or no multiple of %dx%d luma samples", who, e->out_width, e->out_height, sw, sh);
-  if (!m355_resize_ratio_ok(Q.p[0].pw, e->out_width) || !m355_resize_ratio_ok(Q.p[0].ph, e->out_height))
-    return fail(M355_ERR_INVALID, "%s: %dx%d to %dx%d is more than 8x down or up", who, Q.p[0].pw, Q.p[0].ph, e->out_width, e->out_height);
+  const Frame *f = P[i].f, *f0 = P[0].f;
+  if (f->cf != f0->cf || f->bdl != f0->bdl || f->bdc != f0->bdc || f->bpp[0] != f0->bpp[0])
+    return fail(M355_ERR_INVALID, "%s: chroma format / bit depths of frame %d (entry %d) differ from those of frame %d", who, frames[i], i, frames[0]);
+  if (same_size && (f->w != f0->w || f->h != f0->h))
+    return fail(M355_ERR_INVALID, "%s: whole frames of different sizes (%dx%d, entry %d: %dx%d)", who, f0->w, f0->h, i, f->w, f->h);
+  return M355_OK;
+}
+/* the tensor's descriptor for n slices of frames like f: layout, dtype, conversion, scale and bias, the destination and the strides, which must keep
+ * rows, planes and slices apart; fills what the launch takes from them and *eb_out = the element's bytes */
+template <class A>
+static int tensor_desc_check(const char* who, const m355_tensor_desc* e, int n, const Frame* f, A& a, int* eb_out)
+{
   if (e->layout != M355_TENSOR_NCHW && e->layout != M355_TENSOR_NHWC) return fail(M355_ERR_INVALID, "%s: unknown layout %d", who, e->layout);
   if (e->dtype != M355_TENSOR_F32 && e->dtype != M355_TENSOR_F16 && e->dtype != M355_TENSOR_BF16) return fail(M355_ERR_INVALID, "%s: unknown dtype %d", who, e->dtype);
-  ExportTensorArgs a = {};
   int rc = m355_rgb_coefficients(e->matrix, e->full_range, f->bdl, f->bdc, e->samples, &a.k);
   if (rc) return rc;
   for (int k = 0; k < 3; k++) {
@@ -803,7 +819,7 @@ int m355_frames_export_tensor(m355_ctx* c, const int* frames, int n, const m355_
     a.scale[k] = e->scale[k]; a.bias[k] = e->bias[k];
   }
   const bool nhwc = e->layout == M355_TENSOR_NHWC;
-  const int eb = e->dtype == M355_TENSOR_F32 ? 4 : 2, sb = f->bpp[0];
+  const int eb = e->dtype == M355_TENSOR_F32 ? 4 : 2;
   const int64_t row = (int64_t)e->out_width * eb * (nhwc ? 3 : 1);
   if (!e->dst) return fail(M355_ERR_INVALID, "%s: no destination", who);
   if (((uintptr_t)e->dst | (uint64_t)e->stride_h | (nhwc ? 0u : (uint64_t)e->stride_c) | (n > 1 ? (uint64_t)e->stride_n : 0u)) & (uint64_t)(eb - 1))
@@ -814,44 +830,70 @@ int m355_frames_export_tensor(m355_ctx* c, const int* frames, int n, const m355_
   if (n > 1 && (__int128)e->stride_n < (nhwc ? E : 2 * (__int128)e->stride_c + E))
     return fail(M355_ERR_INVALID, "%s: stride_n %lld lets the slices overlap", who, (long long)e->stride_n);
   a.dst = (uint8_t*)e->dst; a.stride_n = n > 1 ? e->stride_n : 0; a.stride_c = nhwc ? 0 : e->stride_c; a.stride_h = e->stride_h;
-  a.sn_x[0] = (uint32_t)Q.p[0].pw; a.sn_y[0] = (uint32_t)Q.p[0].ph; a.dn_x[0] = (uint32_t)e->out_width; a.dn_y[0] = (uint32_t)e->out_height;
-  if (Q.np > 1) { a.sn_x[1] = (uint32_t)Q.p[1].pw; a.sn_y[1] = (uint32_t)Q.p[1].ph; a.dn_x[1] = (uint32_t)(e->out_width / sw); a.dn_y[1] = (uint32_t)(e->out_height / sh); }
-  a.tile_w = resize_rgb_tile_w(Q.p[0].pw, e->out_width, Q.np > 1 ? Q.p[1].pw : 0, e->out_width / sw, sb, sw);
-  a.tiles_x = ((uint32_t)e->out_width + a.tile_w - 1) / a.tile_w;
-  a.units = a.tiles_x * (((uint32_t)e->out_height + M355_RESIZE_TILE_H - 1) / M355_RESIZE_TILE_H);
   a.n = (uint32_t)n;
   a.cf = f->cf; a.nhwc = nhwc; a.bf16 = e->dtype == M355_TENSOR_BF16; a.u16 = e->samples == M355_RGB_U16; a.bdl = f->bdl; a.bdc = f->bdc;
-  for (int i = 0; i < n; i++) {
-    ExportTensorFrame& r = a.fr[i];
-    for (int p = 0; p < P[i].np; p++) r.src[p] = P[i].p[p].src[0];
-    r.src_pitch[0] = P[i].p[0].src_pitch; r.src_pitch[1] = P[i].np > 1 ? P[i].p[1].src_pitch : 0;
-  }
-  hipSetDevice(c->device);
-  const hipStream_t cs = reader_begin(c, f, RD_EXPORT, &a.fr[0].timeout, &a.fr[0].epoch);
+  *eb_out = eb;
+  return M355_OK;
+}
+/* The launch as a reader of the kind RD_EXPORT of EVERY frame of the batch, as m355_frame_measure_async is of its two: it goes on the stream of
+ * frames[0]'s writer, which first continues behind the writer and the earlier export of each other frame; the one mark behind the launch is kept by all
+ * of them (batch_reader_end); each slice's record fr[i] gets the gate of its frame. */
+template <class R>
+static hipStream_t batch_reader_begin(m355_ctx* c, const ExportPlan* P, int n, R* fr)
+{
+  const hipStream_t cs = reader_begin(c, P[0].f, RD_EXPORT, &fr[0].timeout, &fr[0].epoch);
   for (int i = 1; i < n; i++) {
     Frame* g = P[i].f;
     int first = 0;
     while (P[first].f != g) first++;
-    if (first < i) { a.fr[i].timeout = a.fr[first].timeout; a.fr[i].epoch = a.fr[first].epoch; continue; }   /* the same frame again */
+    if (first < i) { fr[i].timeout = fr[first].timeout; fr[i].epoch = fr[first].epoch; continue; }   /* the same frame again */
     ev_wait(c, cs, g->wr);                                  /* the frame's last writer (nothing to enqueue when that ran on `cs`) */
     ev_wait(c, cs, g->reader[RD_EXPORT]);                   /* ... and its earlier export on another stream: the one mark kept stands for both */
-    if (g->wr_stream && g->wr_gate) { a.fr[i].timeout = g->wr_gate; a.fr[i].epoch = g->wr_epoch; }
+    if (g->wr_stream && g->wr_gate) { fr[i].timeout = g->wr_gate; fr[i].epoch = g->wr_epoch; }
     else {                                                  /* no decode to be gated by: an epoch of its own, which no gate word holds (reader_begin) */
-      a.fr[i].timeout = lane(c).timeout; a.fr[i].epoch = ++c->epoch;
-      if (a.fr[i].epoch == 0) a.fr[i].epoch = ++c->epoch;
+      fr[i].timeout = lane(c).timeout; fr[i].epoch = ++c->epoch;
+      if (fr[i].epoch == 0) fr[i].epoch = ++c->epoch;
     }
   }
-  m355_launch_export_tensor(a, sb, eb, cs);
-  HIPCHK(hipGetLastError());
-  rc = reader_end(c, f, RD_EXPORT, cs);
+  return cs;
+}
+static int batch_reader_end(m355_ctx* c, const ExportPlan* P, int n, hipStream_t cs)
+{
+  Frame* f = P[0].f;
+  int rc = reader_end(c, f, RD_EXPORT, cs);
   if (rc) return rc;
   for (int i = 1; i < n; i++) P[i].f->reader[RD_EXPORT] = f->reader[RD_EXPORT];
   return M355_OK;
 }
-/* A batch of REGIONS, one rectangle per slice, as one float tensor in one launch (k_export_tensor.hip, ROI = true): slice i is what
+}
+/* A batch of frames resized, converted, normalised and delivered as one float tensor in one launch (k_export_resized_rgb.hip, RR_BATCH).  Every frame's
+ * handle and the rectangle in it are checked by export_plan — with destinations that cannot fail —, the output size, the ratio and the conversion as for
+ * m355_frame_export_resized_rgb, the tensor's layout by tensor_desc_check. */
+int m355_frames_export_tensor(m355_ctx* c, const int* frames, int n, const m355_tensor_desc* e)
+{
+  const char* who = "m355_frames_export_tensor";
+  if (!c || !frames || !e || n < 1 || n > M355_TENSOR_MAX_FRAMES) return fail(M355_ERR_INVALID, "%s: no context / frames / descriptor, or %d frames are not 1..%d", who, n, M355_TENSOR_MAX_FRAMES);
+  ExportPlan P[M355_TENSOR_MAX_FRAMES];
+  int rc, eb = 0;
+  for (int i = 0; i < n; i++) {
+    if ((rc = export_plan_rect(c, frames[i], e, e, who, P[i])) != 0) return rc;
+    if ((rc = batch_frame_check(who, frames, i, P, e->width == 0)) != 0) return rc;
+  }
+  if ((rc = resize_check(who, P, 0, e->out_width, e->out_height)) != 0) return rc;
+  ExportTensorArgs a = {};
+  if ((rc = tensor_desc_check(who, e, n, P[0].f, a, &eb)) != 0) return rc;
+  plan_geometry(P[0], e->out_width, e->out_height, a, a);
+  for (int i = 0; i < n; i++) plan_sources(P[i], a.fr[i]);
+  hipSetDevice(c->device);
+  const hipStream_t cs = batch_reader_begin(c, P, n, a.fr);
+  m355_launch_export_tensor(a, P[0].f->bpp[0], eb, cs);
+  HIPCHK(hipGetLastError());
+  return batch_reader_end(c, P, n, cs);
+}
+/* A batch of REGIONS, one rectangle per slice, as one float tensor in one launch (k_export_resized_rgb.hip, RR_ROIS): slice i is what
  * m355_frames_export_tensor delivers for frames[i] alone with rois[i] as the rectangle, its columns reversed under M355_ROI_MIRROR.  Every entry's
  * handle and rectangle are checked by export_plan against ITS frame, the ratio per entry; tile width, tiles and units are resize_rgb_tile_w's for the
- * entry's own source size.  Readers, streams, marks and gates are those of m355_frames_export_tensor. */
+ * entry's own source size. */
 int m355_frames_export_tensor_rois(m355_ctx* c, const int* frames, const m355_tensor_roi* rois, int n, const m355_tensor_desc* e)
 {
   const char* who = "m355_frames_export_tensor_rois";
@@ -860,86 +902,27 @@ int m355_frames_export_tensor_rois(m355_ctx* c, const int* frames, const m355_te
   if (e->x0 || e->y0 || e->width || e->height)
     return fail(M355_ERR_INVALID, "%s: the descriptor's rectangle %d,%d %dx%d must be zero (the rectangles are the entries')", who, e->x0, e->y0, e->width, e->height);
   ExportPlan P[M355_TENSOR_MAX_FRAMES];
+  int rc, eb = 0;
   for (int i = 0; i < n; i++) {
     if (rois[i].flags & ~M355_ROI_MIRROR) return fail(M355_ERR_INVALID, "%s: unknown flags 0x%x of entry %d", who, (unsigned)rois[i].flags, i);
-    m355_export_desc yuv = {};
-    yuv.layout = M355_EXPORT_PLANAR; yuv.samples = M355_EXPORT_NATIVE;
-    yuv.x0 = rois[i].x0; yuv.y0 = rois[i].y0; yuv.width = rois[i].width; yuv.height = rois[i].height;
-    for (int p = 0; p < 3; p++) { yuv.dst[p] = (void*)e; yuv.pitch[p] = INT64_MAX; }
-    int rc = export_plan(c, frames[i], &yuv, 0, who, P[i]);
-    if (rc) return rc;
-    const Frame *f = P[i].f, *f0 = P[0].f;
-    if (f->cf != f0->cf || f->bdl != f0->bdl || f->bdc != f0->bdc || f->bpp[0] != f0->bpp[0])
-      return fail(M355_ERR_INVALID, "%s: chroma format / bit depths of frame %d (entry %d) differ from those of frame %d", who, frames[i], i, frames[0]);
+    if ((rc = export_plan_rect(c, frames[i], &rois[i], e, who, P[i])) != 0) return rc;
+    if ((rc = batch_frame_check(who, frames, i, P, false)) != 0) return rc;
   }
-  Frame* f = P[0].f;
-  const int sw = (f->cf == 1 || f->cf == 2) ? 2 : 1, sh = f->cf == 1 ? 2 : 1;
-  if (e->out_width <= 0 || e->out_height <= 0 || e->out_width % sw || e->out_height % sh)
-    return fail(M355_ERR_INVALID, "%s: output size %dx%d is not positive or no multiple of %dx%d luma samples", who, e->out_width, e->out_height, sw, sh);
-  for (int i = 0; i < n; i++)
-    if (!m355_resize_ratio_ok(P[i].p[0].pw, e->out_width) || !m355_resize_ratio_ok(P[i].p[0].ph, e->out_height))
-      return fail(M355_ERR_INVALID, "%s: entry %d, %dx%d to %dx%d is more than 8x down or up", who, i, P[i].p[0].pw, P[i].p[0].ph, e->out_width, e->out_height);
-  if (e->layout != M355_TENSOR_NCHW && e->layout != M355_TENSOR_NHWC) return fail(M355_ERR_INVALID, "%s: unknown layout %d", who, e->layout);
-  if (e->dtype != M355_TENSOR_F32 && e->dtype != M355_TENSOR_F16 && e->dtype != M355_TENSOR_BF16) return fail(M355_ERR_INVALID, "%s: unknown dtype %d", who, e->dtype);
+  if ((rc = resize_check(who, P, n, e->out_width, e->out_height)) != 0) return rc;
   ExportTensorRoisArgs a = {};
-  int rc = m355_rgb_coefficients(e->matrix, e->full_range, f->bdl, f->bdc, e->samples, &a.k);
-  if (rc) return rc;
-  for (int k = 0; k < 3; k++) {
-    if ((m355_te_bits(e->scale[k]) & 0x7F800000u) == 0x7F800000u || (m355_te_bits(e->bias[k]) & 0x7F800000u) == 0x7F800000u)
-      return fail(M355_ERR_INVALID, "%s: scale / bias of channel %d is not finite", who, k);
-    a.scale[k] = e->scale[k]; a.bias[k] = e->bias[k];
-  }
-  const bool nhwc = e->layout == M355_TENSOR_NHWC;
-  const int eb = e->dtype == M355_TENSOR_F32 ? 4 : 2, sb = f->bpp[0];
-  const int64_t row = (int64_t)e->out_width * eb * (nhwc ? 3 : 1);
-  if (!e->dst) return fail(M355_ERR_INVALID, "%s: no destination", who);
-  if (((uintptr_t)e->dst | (uint64_t)e->stride_h | (nhwc ? 0u : (uint64_t)e->stride_c) | (n > 1 ? (uint64_t)e->stride_n : 0u)) & (uint64_t)(eb - 1))
-    return fail(M355_ERR_INVALID, "%s: the destination or a stride is no multiple of the %d-byte element", who, eb);
-  if (e->stride_h < row) return fail(M355_ERR_INVALID, "%s: stride_h %lld is below the row of %lld bytes", who, (long long)e->stride_h, (long long)row);
-  const __int128 E = (__int128)(e->out_height - 1) * e->stride_h + row;              /* first byte behind a plane's (NHWC: a slice's) last row */
-  if (!nhwc && (__int128)e->stride_c < E) return fail(M355_ERR_INVALID, "%s: stride_c %lld lets the planes overlap (%lld bytes each)", who, (long long)e->stride_c, (long long)E);
-  if (n > 1 && (__int128)e->stride_n < (nhwc ? E : 2 * (__int128)e->stride_c + E))
-    return fail(M355_ERR_INVALID, "%s: stride_n %lld lets the slices overlap", who, (long long)e->stride_n);
-  a.dst = (uint8_t*)e->dst; a.stride_n = n > 1 ? e->stride_n : 0; a.stride_c = nhwc ? 0 : e->stride_c; a.stride_h = e->stride_h;
-  a.dn_x[0] = (uint32_t)e->out_width; a.dn_y[0] = (uint32_t)e->out_height;
-  if (f->cf != 0) { a.dn_x[1] = (uint32_t)(e->out_width / sw); a.dn_y[1] = (uint32_t)(e->out_height / sh); }
-  a.n = (uint32_t)n;
-  a.cf = f->cf; a.nhwc = nhwc; a.bf16 = e->dtype == M355_TENSOR_BF16; a.u16 = e->samples == M355_RGB_U16; a.bdl = f->bdl; a.bdc = f->bdc;
-  const uint32_t runs = ((uint32_t)e->out_height + M355_RESIZE_TILE_H - 1) / M355_RESIZE_TILE_H;
+  if ((rc = tensor_desc_check(who, e, n, P[0].f, a, &eb)) != 0) return rc;
   for (int i = 0; i < n; i++) {
-    const ExportPlan& Q = P[i];
     ExportTensorRoi& r = a.fr[i];
-    for (int p = 0; p < Q.np; p++) r.src[p] = Q.p[p].src[0];
-    r.src_pitch[0] = Q.p[0].src_pitch; r.src_pitch[1] = Q.np > 1 ? Q.p[1].src_pitch : 0;
+    plan_sources(P[i], r);
+    plan_geometry(P[i], e->out_width, e->out_height, r, a);
     r.flags = (uint32_t)rois[i].flags;
-    r.sn_x[0] = (uint32_t)Q.p[0].pw; r.sn_y[0] = (uint32_t)Q.p[0].ph;
-    if (Q.np > 1) { r.sn_x[1] = (uint32_t)Q.p[1].pw; r.sn_y[1] = (uint32_t)Q.p[1].ph; }
-    r.tile_w = resize_rgb_tile_w(Q.p[0].pw, e->out_width, Q.np > 1 ? Q.p[1].pw : 0, e->out_width / sw, sb, sw);
-    r.tiles_x = ((uint32_t)e->out_width + r.tile_w - 1) / r.tile_w;
-    r.units = r.tiles_x * runs;
     if (r.units > a.max_units) a.max_units = r.units;
   }
   hipSetDevice(c->device);
-  const hipStream_t cs = reader_begin(c, f, RD_EXPORT, &a.fr[0].timeout, &a.fr[0].epoch);
-  for (int i = 1; i < n; i++) {
-    Frame* g = P[i].f;
-    int first = 0;
-    while (P[first].f != g) first++;
-    if (first < i) { a.fr[i].timeout = a.fr[first].timeout; a.fr[i].epoch = a.fr[first].epoch; continue; }   /* the same frame again */
-    ev_wait(c, cs, g->wr);                                  /* the frame's last writer (nothing to enqueue when that ran on `cs`) */
-    ev_wait(c, cs, g->reader[RD_EXPORT]);                   /* ... and its earlier export on another stream: the one mark kept stands for both */
-    if (g->wr_stream && g->wr_gate) { a.fr[i].timeout = g->wr_gate; a.fr[i].epoch = g->wr_epoch; }
-    else {                                                  /* no decode to be gated by: an epoch of its own, which no gate word holds (reader_begin) */
-      a.fr[i].timeout = lane(c).timeout; a.fr[i].epoch = ++c->epoch;
-      if (a.fr[i].epoch == 0) a.fr[i].epoch = ++c->epoch;
-    }
-  }
-  m355_launch_export_tensor_rois(a, sb, eb, cs);
+  const hipStream_t cs = batch_reader_begin(c, P, n, a.fr);
+  m355_launch_export_tensor_rois(a, P[0].f->bpp[0], eb, cs);
   HIPCHK(hipGetLastError());
-  rc = reader_end(c, f, RD_EXPORT, cs);
-  if (rc) return rc;
-  for (int i = 1; i < n; i++) P[i].f->reader[RD_EXPORT] = f->reader[RD_EXPORT];
-  return M355_OK;
+  return batch_reader_end(c, P, n, cs);
 }
 /* the host waits until this frame's last export has landed */
 int m355_frame_export_wait(m355_ctx* c, int h)

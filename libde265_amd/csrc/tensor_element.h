@@ -2,7 +2,7 @@
  * tensor_element.h — the ONE definition of the float stage of m355_frames_export_tensor (include/de265_mi355x.h): an integer channel value v of
  * the R'G'B' stage becomes  r = (float)v * scale + bias  — one binary32 multiplication and one binary32 addition, each rounded to nearest even,
  * NOT a fused multiply-add — delivered as binary32, as binary16 or as bfloat16, both rounded to nearest even from r.  Compiled three times, as
- * resize_taps.h is: into k_export_tensor.hip (device), into the SIMT-interpreter build of that kernel (SIMT_EMU, plain C++) and into
+ * resize_taps.h is: into k_export_resized_rgb.hip (device), into the SIMT-interpreter build of that kernel (SIMT_EMU, plain C++) and into
  * m355_tensor_element (runtime.hip, host), which the tests run over every v.
  *   binary16  gradual underflow (subnormals are produced), overflow gives infinity.  Device: v_cvt_f16_f32 (round to nearest even, binary16
  *             denormals on, as HIP code objects have them); host and interpreter: the integer statement below.

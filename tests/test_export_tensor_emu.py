@@ -5,7 +5,7 @@ m355_frame_download returns through export_tensor_util.py (the integer restateme
 then the float stage in numpy); every comparison is bit-exact, and every byte of the destination outside the tensor's elements must be untouched —
 every export here has padded stride_h, stride_c and stride_n (capi.Context.frames_export_tensor), apart from the boundary cases of the argument test.
 
-The build holds four instantiations, k_export_tensor<source bytes, element bytes>; layout, F16 / BF16, chroma format and U8 / U16 of the integer stage
+The build holds four instantiations, k_export_resized_rgb<source bytes, element bytes, RR_BATCH>; layout, F16 / BF16, chroma format and U8 / U16 of the integer stage
 are run-time switches.  Which test reaches which (every test of the matrix runs NCHW and NHWC, U8 and U16, with F32, F16 and BF16):
   <1, 2>, <1, 4>  test_tensor_format_matrix[bd8_8_cf1], [bd8_8_cf4] (monochrome), test_tensor_minimum_sizes[8], test_tensor_gate_is_per_slice
   <2, 2>, <2, 4>  test_tensor_format_matrix[bd10_10_cf1], [bd12_12_cf2] (4:2:2), [bd10_10_cf3] (4:4:4), [bd10_9_cf1], test_tensor_minimum_sizes[10],

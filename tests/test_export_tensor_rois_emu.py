@@ -4,15 +4,15 @@ argument checks, the gate per slice, the reader bookkeeping and a pinned-host de
 (export_tensor_rois_util.py): the restatement of the planes m355_frame_download returns, and m355_frames_export_tensor with n = 1 for the same frame
 and rectangle; every comparison is bit-exact, and every byte of the destination outside the tensor's elements must be untouched.
 
-The build holds four more instantiations of the tensor kernel, k_export_tensor<source bytes, element bytes, ROI = true>; layout, F16 / BF16, chroma
+The build holds four instantiations for this call, k_export_resized_rgb<source bytes, element bytes, RR_ROIS>; layout, F16 / BF16, chroma
 format, U8 / U16 and the mirror are run-time switches.  Which test reaches which:
-  <1, 2, true>, <1, 4, true>  test_regions_of_an_8bit_frame (4:2:0, two tiles across in every slice), test_mirror_at_odd_output_widths (monochrome,
-                              <1, 2, true>), test_rois_gate_is_per_slice
-  <2, 2, true>, <2, 4, true>  test_regions_of_one_frame, test_slices_of_different_unit_counts, test_whole_frames_of_different_sizes,
+  <1, 2, RR_ROIS>, <1, 4, RR_ROIS>  test_regions_of_an_8bit_frame (4:2:0, two tiles across in every slice), test_mirror_at_odd_output_widths (monochrome,
+                              <1, 2, RR_ROIS>), test_rois_gate_is_per_slice
+  <2, 2, RR_ROIS>, <2, 4, RR_ROIS>  test_regions_of_one_frame, test_slices_of_different_unit_counts, test_whole_frames_of_different_sizes,
                               test_mirrored_regions_of_one_frame, test_mirror_across_the_seam_of_two_tiles, test_mirror_at_odd_output_widths (4:4:4,
-                              <2, 2, true>), test_full_record_array, test_rois_export_behind_recycled_frames (<2, 2, true>),
+                              <2, 2, RR_ROIS>), test_full_record_array, test_rois_export_behind_recycled_frames (<2, 2, RR_ROIS>),
                               test_rois_export_into_pinned_host_memory
-The single calls they are held against run the ROI = false instantiations."""
+The single calls they are held against run the RR_BATCH instantiations."""
 import ctypes
 
 import numpy as np

@@ -4,7 +4,7 @@ and the frame hazard (a decode into a frame waits for the export of the frame's 
 1920x1088 10-bit picture whose 1920x1080 window is exported down to two sizes and up to one.  Expected values: the planes m355_frame_download returns
 through the two restatements composed (export_resized_rgb_util.py); all exact.
 
-The build holds four instantiations, k_export_resized_rgb<source bytes, destination bytes>; layout and chroma format are run-time switches.
+The build holds four instantiations, k_export_resized_rgb<source bytes, destination bytes, RR_FRAME>; layout and chroma format are run-time switches.
 Which test reaches which (every test below runs packed AND planar unless it says otherwise):
   <1, 1>  test_resized_rgb_format_matrix[bd8_8_cf1], [bd8_8_cf4] (monochrome), test_resized_rgb_values_and_clips[8], test_resized_rgb_minimum_sizes[8],
           test_whole_frame_at_its_own_size_is_the_rgb_export[8-*], test_resized_rgb_export_behind_a_rejected_decode_writes_nothing (packed)

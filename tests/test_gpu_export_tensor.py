@@ -1,11 +1,11 @@
-"""m355_frames_export_tensor on the GPU: the drivers of tests/test_export_tensor_emu.py through the real k_export_tensor instantiations — the format
+"""m355_frames_export_tensor on the GPU: the drivers of tests/test_export_tensor_emu.py through the real k_export_resized_rgb<., ., RR_BATCH> instantiations — the format
 matrix at 64x32, the composition through the public calls, batches of distinct frames of different pitches with one and with several workgroups per
 slice, the same frame twice, the smallest outputs, the gate per slice, a pinned-host destination read behind m355_frame_export_wait of one frame of the
 batch —, the frame hazard (a decode into a frame of a batch waits for the batch) with one and three pictures in flight, and one realistic case: a
 1920x1088 10-bit picture, its reference frame and a second picture as a batch of 3 distinct frames, centre square to 224x224 with the ImageNet normalisation.  Expected values: the
 planes m355_frame_download returns through export_tensor_util.py; all bit-exact, the bytes outside the tensor's elements included.
 
-The build holds four instantiations, k_export_tensor<source bytes, element bytes>; layout, F16 / BF16, chroma format and U8 / U16 of the integer stage
+The build holds four instantiations, k_export_resized_rgb<source bytes, element bytes, RR_BATCH>; layout, F16 / BF16, chroma format and U8 / U16 of the integer stage
 are run-time switches.  Which test reaches which (the matrix runs NCHW and NHWC, U8 and U16, with F32, F16 and BF16):
   <1, 2>, <1, 4>  test_tensor_format_matrix[bd8_8_cf1], [bd8_8_cf4] (monochrome), test_tensor_minimum_sizes[8], test_tensor_gate_is_per_slice
   <2, 2>, <2, 4>  test_tensor_format_matrix[bd10_10_cf1], [bd12_12_cf2] (4:2:2), [bd10_10_cf3] (4:4:4), [bd10_9_cf1], test_tensor_minimum_sizes[10],

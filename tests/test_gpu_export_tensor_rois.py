@@ -1,4 +1,4 @@
-"""m355_frames_export_tensor_rois on the GPU: the drivers of tests/test_export_tensor_rois_emu.py through the real k_export_tensor<., ., ROI = true>
+"""m355_frames_export_tensor_rois on the GPU: the drivers of tests/test_export_tensor_rois_emu.py through the real k_export_resized_rgb<., ., RR_ROIS>
 instantiations — regions of one frame at both ratio limits, slices of different unit counts in one two-dimensional grid, whole frames of different
 sizes, mirrored slices (the seam between two tiles, output rows that end in half a dword), the full record array, the gate per slice, a pinned-host
 destination read behind m355_frame_export_wait of one frame of the batch —, the frame hazard with one and three pictures in flight, and one realistic
@@ -7,12 +7,12 @@ expectations (export_tensor_rois_util.py): the restatement of the planes m355_fr
 the same frame and rectangle, which runs another instantiation of the kernel; all bit-exact, the bytes outside the tensor's elements included.
 
 Which test reaches which instantiation (layout, F16 / BF16, chroma format, U8 / U16 and the mirror are run-time switches):
-  <1, 2, true>, <1, 4, true>  test_regions_of_an_8bit_frame (4:2:0, two tiles across in every slice), test_mirror_at_odd_output_widths (monochrome,
-                              <1, 2, true>), test_rois_gate_is_per_slice
-  <2, 2, true>, <2, 4, true>  test_regions_of_one_frame, test_slices_of_different_unit_counts, test_whole_frames_of_different_sizes,
+  <1, 2, RR_ROIS>, <1, 4, RR_ROIS>  test_regions_of_an_8bit_frame (4:2:0, two tiles across in every slice), test_mirror_at_odd_output_widths (monochrome,
+                              <1, 2, RR_ROIS>), test_rois_gate_is_per_slice
+  <2, 2, RR_ROIS>, <2, 4, RR_ROIS>  test_regions_of_one_frame, test_slices_of_different_unit_counts, test_whole_frames_of_different_sizes,
                               test_mirrored_regions_of_one_frame, test_mirror_across_the_seam_of_two_tiles, test_mirror_at_odd_output_widths (4:4:4,
-                              <2, 2, true>), test_full_record_array, test_rois_export_is_waited_for_by_the_next_decode (<2, 2, true>),
-                              test_rois_export_into_pinned_host_memory, test_rois_1080p_regions_to_224 (<2, 2, true>: F16 NCHW and BF16 NHWC)"""
+                              <2, 2, RR_ROIS>), test_full_record_array, test_rois_export_is_waited_for_by_the_next_decode (<2, 2, RR_ROIS>),
+                              test_rois_export_into_pinned_host_memory, test_rois_1080p_regions_to_224 (<2, 2, RR_ROIS>: F16 NCHW and BF16 NHWC)"""
 import numpy as np
 import pytest
 
