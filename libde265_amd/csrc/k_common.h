@@ -93,6 +93,7 @@ static inline DevPicParams dev_pic_params(const m355_pic_params& q)
   return d;
 }
 
+#define M355_JOB_RANGES 2             /* ranges of the inter job list: MAIN, EDGE (k_meta_pb, k_inter_jobs) */
 struct DevPic {
   DevPicParams pp;
   int sw, sh;                       /* SubWidthC, SubHeightC */
@@ -138,9 +139,10 @@ struct DevPic {
   int res_front;                    /* 1: this launch of k_residual stores tiles instead of adding */
   uint16_t* sao_nb;                 /* [component][CTB]: bit (dy+1)*3+(dx+1) set = SAO edge neighbours in that CTB are not usable; bit 15 = the CTB's slice has SAO on for the component (k_meta_sao) */
   uint32_t* jobs;                   /* inter jobs: pb index | strip << 25 | row block << 29 (k_meta_pb) */
-  uint32_t* job_base;               /* [256-PB chunk][4]: the chunk's jobs per range (uni, bi, weighted, edge): k_job_count leaves the counts here, every
+  uint32_t* job_base;               /* [256-PB chunk][M355_JOB_RANGES]: the chunk's jobs per range (MAIN, EDGE): k_job_count leaves the counts here, every
                                        workgroup of k_meta_pb sums the ones in front of its chunk (lane scratch) */
-  uint32_t* job_tot;                /* range ENDS: [0] one-list jobs, [1] + bi-predicted, [2] + explicitly weighted = where the EDGE range starts, [3] all jobs (k_meta_pb's workgroup 0; clamped to jobs_cap) */
+  uint32_t* job_tot;                /* range ENDS: [0] MAIN jobs (the PBs whose windows stay inside the picture: one list, two lists and explicit weights together,
+                                       in PB order) = where the EDGE range starts, [1] all jobs (k_meta_pb's workgroup 0; clamped to jobs_cap) */
   uint32_t jobs_cap;                /* entries of jobs[]: >= what any list of disjoint prediction blocks produces (runtime.hip prepare) */
   int fill_pb_of_in_meta;           /* 1: k_meta_pb fills pb_of (inter stage off); 0: k_inter_jobs does, two units per job */
   /* intra wavefront state */

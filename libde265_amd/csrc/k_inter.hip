@@ -577,10 +577,31 @@ __device__ __forceinline__ void d_mc_chroma_lean(const M355_GLOBAL PIX* rp, int 
 }
 
 /* One job of the lean kernels (bit depths <= 12).  MODE 0: windows inside the picture, no explicit weights: the lists are the workgroup's
- * (bi: wave-uniform) and the write-back is packed 16-bit arithmetic; 1: explicit weights — one or two lists per lane, the 32-bit
- * write-back; 2: EDGE — windows that leave the picture (clamped rows), weights per lane. */
+ * (bi: wave-uniform) and the write-back is packed 16-bit arithmetic; 1: a wave that mixes kinds, or explicit weights — one or two lists and
+ * weights or none per lane, the 32-bit write-back; 2: EDGE — windows that leave the picture (clamped rows), lists and weights per lane. */
 template <class PIX, int MODE>
 __device__ __forceinline__ void d_inter_job_lean(const DevPic& p, uint32_t job, bool bi_u, const unsigned* s_ql, const unsigned* s_qv, const unsigned* s_cl, const unsigned* s_cv, unsigned* ext, const DevRef* s_refs);
+
+/* kind of a MAIN job, numbered in the order a workgroup runs its jobs — the longest waves start first: 0 two lists, 1 one list, 2 explicit weights */
+__host__ __device__ static inline int d_job_class(unsigned pb_flags)
+{
+  if (pb_flags & M355_PBF_WEIGHTED) return 2;
+  return ((pb_flags & M355_PBF_MC_L0) && (pb_flags & M355_PBF_MC_L1)) ? 0 : 1;
+}
+/* stable partition of a workgroup's jobs by kind: where the job goes that is the rank-th of kind `key` within wave `wave`, given every wave's count per
+   kind (cnt[wave][kind]); n[] receives the workgroup's totals per kind.  Plain integer code, shared with the host (tests, tools) */
+__host__ __device__ static inline int d_job_part_dest(const int (*cnt)[3], int n_waves, int wave, int key, int rank, int n[3])
+{
+  int before = 0;
+  n[0] = n[1] = n[2] = 0;
+  for (int w = 0; w < n_waves; w++)
+    for (int k = 0; k < 3; k++) {
+      const int c = cnt[w][k];
+      n[k] += c;
+      if (w < wave && k == key) before += c;
+    }
+  return (key > 0 ? n[0] : 0) + (key > 1 ? n[1] : 0) + before + rank;
+}
 
 /* one launch for the main and the edge job range: blocks [0, nblk_edge8) take edge jobs */
 template <class PIX>
@@ -588,32 +609,24 @@ __global__ void __launch_bounds__(M355_INTER_BLOCK, M355_INTER_WAVES) k_inter_jo
 {
   M355_GATE(p);
   /* the job counts live on the device (k_job_count / k_meta_pb); the grid is an upper bound: surplus workgroups leave here.
-     Ranges: [0, tot0) one list, [tot0, tot1) two lists, [tot1, tot2) explicit weights, [tot2, tot3) EDGE (windows that leave the picture) */
-  const int t0 = (int)p.job_tot[0], t1 = (int)p.job_tot[1], t2 = (int)p.job_tot[2], t3 = (int)p.job_tot[3];
+     Ranges: [0, tot0) MAIN (one list, two lists, explicit weights: in PB order), [tot0, tot1) EDGE (windows that leave the picture) */
+  const int tm = (int)p.job_tot[0], te = (int)p.job_tot[1];
   auto blocks8 = [](int jobs) { return (((jobs + M355_INTER_BLOCK - 1) / M355_INTER_BLOCK + 7) / 8) * 8; };
-  const int nblk_uni8 = blocks8(t0), nblk_bi8 = blocks8(t1 - t0), nblk_w8 = blocks8(t2 - t1), nblk_edge8 = blocks8(t3 - t2);
-  if ((int)blockIdx.x >= nblk_edge8 + nblk_bi8 + nblk_uni8 + nblk_w8) return;
+  const int nblk_main8 = blocks8(tm), nblk_edge8 = blocks8(te - tm);
+  if ((int)blockIdx.x >= nblk_edge8 + nblk_main8) return;
   /* Dispatch order = expected cost, longest first: edge blocks (clamped loads make them latency-bound; started early they overlap with
-     everything else; spread round-robin over the XCDs), then the other classes in an XCD-aware order: block b runs on XCD b % 8, and
-     every XCD gets one contiguous eighth of each range (= compact regions of the picture) so reference-window overlap hits that XCD's
-     own L2.  Within an XCD the classes are interleaved in proportion (all lists are in PB order, so block i/per_a of one and block
-     i/per_b of another cover the same part of the picture): they then read the same reference region while it is still in that
-     XCD's L2 — run one class after the other and every region is fetched twice, far apart in time. */
+     everything else; spread round-robin over the XCDs), then the MAIN range in an XCD-aware order: block b runs on XCD b % 8, and
+     every XCD gets one contiguous eighth of the range (= a compact region of the picture) so reference-window overlap hits that XCD's
+     own L2.  A workgroup takes 256 consecutive MAIN jobs whatever their kinds — a compact region too: the window lines that neighbouring
+     PBs share hit in its CU's L1.  (Sorted by kind picture-wide, a workgroup's jobs were a checkerboard with the PBs of the other kinds
+     in the holes, on other CUs: every shared line missed in two L1s, and L1 misses are what this kernel waits for — DESIGN.md §4 Round 8.) */
   const int b = blockIdx.x;
-  int cls, ji, jend;
-  if (b < nblk_edge8) { cls = 3; ji = t2 + b * M355_INTER_BLOCK; jend = t3; }
+  const bool edge = b < nblk_edge8;
+  int ji, jend;
+  if (edge) { ji = tm + b * M355_INTER_BLOCK; jend = te; }
   else {
     const int bm = b - nblk_edge8, xcd = bm & 7, slot = bm >> 3;
-    const int per_bi = nblk_bi8 >> 3, per_uni = nblk_uni8 >> 3, per_w = nblk_w8 >> 3;
-    const int per = per_bi + per_uni + per_w;
-    const int bi_before = (int)(((long long)slot * per_bi) / per), bi_after = (int)(((long long)(slot + 1) * per_bi) / per);
-    if (bi_after != bi_before) { cls = 1; ji = t0 + (xcd * per_bi + bi_before) * M355_INTER_BLOCK; jend = t1; }
-    else {
-      const int s2 = slot - bi_before, per2 = per_uni + per_w;
-      const int w_before = (int)(((long long)s2 * per_w) / per2), w_after = (int)(((long long)(s2 + 1) * per_w) / per2);
-      if (w_after != w_before) { cls = 2; ji = t1 + (xcd * per_w + w_before) * M355_INTER_BLOCK; jend = t2; }
-      else { cls = 0; ji = (xcd * per_uni + s2 - w_before) * M355_INTER_BLOCK; jend = t0; }
-    }
+    ji = (xcd * (nblk_main8 >> 3) + slot) * M355_INTER_BLOCK; jend = tm;
   }
   if (ji >= jend) return;          /* (workgroup-uniform: the padding blocks of a range) */
   ji += threadIdx.x;
@@ -631,14 +644,44 @@ __global__ void __launch_bounds__(M355_INTER_BLOCK, M355_INTER_WAVES) k_inter_jo
   if (threadIdx.x < LT_WORDS / 4) ((uint4*)s_tab)[threadIdx.x] = ((const uint4*)p.inter_tabs)[threadIdx.x];
   uint32_t job = 0;
   if (ji < jend) job = p.jobs[ji];          /* (requested beside the tables) */
-  __syncthreads();
-  if (ji >= jend) return;
-  /* EDGE jobs extend their window rows in LDS: 20 words per lane (d_mc_luma_lean) */
+  /* EDGE jobs extend their window rows in LDS: 20 words per lane (d_mc_luma_lean); a MAIN workgroup sorts its job words through the first 256 */
   __shared__ __attribute__((aligned(16))) unsigned s_ext[M355_INTER_BLOCK * 20];
   unsigned* ext = s_ext + threadIdx.x * 20;
-  if (cls == 3) d_inter_job_lean<PIX, 2>(p, job, false, s_tab + LT_QL, s_tab + LT_QV, s_tab + LT_CL, s_tab + LT_CV, ext, s_refs);
-  else if (cls == 2) d_inter_job_lean<PIX, 1>(p, job, false, s_tab + LT_QL, s_tab + LT_QV, s_tab + LT_CL, s_tab + LT_CV, ext, s_refs);
-  else d_inter_job_lean<PIX, 0>(p, job, cls == 1, s_tab + LT_QL, s_tab + LT_QV, s_tab + LT_CL, s_tab + LT_CV, ext, s_refs);
+  if (edge) {
+    __syncthreads();
+    if (ji < jend) d_inter_job_lean<PIX, 2>(p, job, false, s_tab + LT_QL, s_tab + LT_QV, s_tab + LT_CL, s_tab + LT_CV, ext, s_refs);
+    return;
+  }
+  /* MAIN: the workgroup partitions its jobs stably by kind (two lists, one list, explicit weights: d_job_class), lane t goes on with the job
+     of rank t: most waves then hold one kind and take its wave-uniform path, and the two-list jobs — two passes — start first.  Ranks
+     within a wave by ballot, the waves' counts through LDS (behind the barrier the tables need anyway), the job words through LDS */
+  constexpr int NW = M355_INTER_BLOCK / 64;
+  __shared__ int s_cnt[NW][3];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int key = 3, rank = 0;
+  if (ji < jend) key = d_job_class(p.pbs[job & 0x1FFFFFFu].flags);
+#pragma unroll
+  for (int k = 0; k < 3; k++) {
+    const unsigned long long m = __ballot(key == k);
+    if (key == k) rank = __popcll(m & ((1ull << lane) - 1ull));
+    if (lane == 0) s_cnt[wave][k] = __popcll(m);
+  }
+  __syncthreads();
+  int n[3];
+  const int dest = d_job_part_dest(s_cnt, NW, wave, key, rank, n);
+  if (key < 3) s_ext[dest] = job;
+  __syncthreads();
+  const int n_bi = __builtin_amdgcn_readfirstlane(n[0]), n_one = __builtin_amdgcn_readfirstlane(n[1]);
+  const int total = n_bi + n_one + __builtin_amdgcn_readfirstlane(n[2]);
+  if ((int)threadIdx.x >= total) return;
+  job = s_ext[threadIdx.x];
+  /* a wave whose jobs are all of two lists, or all of one: MODE 0 with the wave's bi; anything else: lists and weights per lane (MODE 1; its one-list
+     lanes idle through the second pass).  MODE 0 with the lane's own bi for the waves that mix one and two lists measured no better in the library
+      */
+  const int lo = __builtin_amdgcn_readfirstlane(wave) * 64, hi = min(lo + 64, total);
+  const bool all_bi = hi <= n_bi, all_one = lo >= n_bi && hi <= n_bi + n_one;
+  if (all_bi || all_one) d_inter_job_lean<PIX, 0>(p, job, all_bi, s_tab + LT_QL, s_tab + LT_QV, s_tab + LT_CL, s_tab + LT_CV, ext, s_refs);
+  else d_inter_job_lean<PIX, 1>(p, job, false, s_tab + LT_QL, s_tab + LT_QV, s_tab + LT_CL, s_tab + LT_CV, ext, s_refs);
 }
 
 template <class PIX, int MODE>
@@ -666,7 +709,7 @@ __device__ __forceinline__ void d_inter_job_lean(const DevPic& p, uint32_t job, 
   /* weights of component c as the one formula of d_wpred (WEIGHTED jobs only; see d_inter_job) */
   auto make_ws = [&](int c, int bd) {
     WtSel ws;
-    const bool weighted = !EDGE || (pb.flags & M355_PBF_WEIGHTED) != 0;      /* (an edge job carries explicit weights or not, per lane) */
+    const bool weighted = (pb.flags & M355_PBF_WEIGHTED) != 0;      /* (a job of these modes carries explicit weights or not, per lane) */
     m355_wt wa, wb;
     if (weighted) { wa = p.wts[wtA]; wb = p.wts[wtB]; }
     const int shift3 = max(2, 14 - bd), shift2 = max(3, 15 - bd);
@@ -822,7 +865,7 @@ static void launch_jobs(const DevPic& p, hipStream_t st)
 {
   /* each range's blocks are padded to a multiple of 8 for the XCD-contiguous block order; the counts are on the device, so the
      grid covers the most jobs the list can hold */
-  const unsigned grid = (unsigned)((p.jobs_cap + M355_INTER_BLOCK - 1) / M355_INTER_BLOCK) + 4 * 8;
+  const unsigned grid = (unsigned)((p.jobs_cap + M355_INTER_BLOCK - 1) / M355_INTER_BLOCK) + M355_JOB_RANGES * 8;
   hipLaunchKernelGGL(HIP_KERNEL_NAME(k_inter_jobs<PIX>), dim3(grid), dim3(M355_INTER_BLOCK), 0, st, p);
 }
 

@@ -72,10 +72,10 @@ __device__ __forceinline__ void k_meta_cu_body(const DevPic& p, const int blk)
 }
 
 /* ---- job counts on the device (the host no longer reads the PB list of a picture recorded in place) ----
- * k_job_count: one workgroup per 256-PB chunk (= one k_meta_pb workgroup): the chunk's jobs per range -> job_base[chunk][3].
- * k_meta_pb  : every workgroup sums the counts of the chunks in front of its own (and all of them, for the range starts: one list, two
- *              lists, picture edge — one after the other) itself: 3 x n_chunks words out of the L2 per workgroup instead of a
- *              one-workgroup scan launch on the picture's critical path; workgroup 0 leaves the range ends in job_tot[0..2].  A malformed record counts nothing here (k_validate
+ * k_job_count: one workgroup per 256-PB chunk (= one k_meta_pb workgroup): the chunk's jobs per range -> job_base[chunk][M355_JOB_RANGES].
+ * k_meta_pb  : every workgroup sums the counts of the chunks in front of its own (and all of them, for the range starts: MAIN, then
+ *              EDGE) itself: 2 x n_chunks words out of the L2 per workgroup instead of a
+ *              one-workgroup scan launch on the picture's critical path; workgroup 0 leaves the range ends in job_tot[0..1].  A malformed record counts nothing here (k_validate
  *              rejects the picture); lists whose blocks overlap can exceed jobs[]: the ends are clamped and k_meta_pb drops what
  *              does not fit (memory-safe, the picture is garbage either way). */
 __device__ __forceinline__ int d_pb_jobs(const m355_pb& pb)
@@ -83,13 +83,12 @@ __device__ __forceinline__ int d_pb_jobs(const m355_pb& pb)
   if (pb.w < 4 || pb.h < 4 || pb.w > 64 || pb.h > 64 || (pb.w & 3) || (pb.h & 3)) return 0;
   return (pb.w >> 2) * ((pb.h + 7) >> 3);
 }
-/* job class of a PB (= the range of the job list its jobs go to, k_inter_jobs): 0 one list, 1 two lists, 2 explicit weights,
-   3 EDGE = a reference window leaves the picture (coordinate-clamped loads) */
-__device__ __forceinline__ int d_pb_class(const DevPic& p, const m355_pb& pb)
+/* range of the job list a PB's jobs go to: 0 MAIN, 1 EDGE = a reference window leaves the picture (coordinate-clamped loads).  MAIN holds
+   the PBs of one list, of two lists and with explicit weights together, in PB order: 256 consecutive jobs are a compact region of the
+   picture whatever their kinds; k_inter_jobs sorts a workgroup's jobs by kind itself (d_job_class, k_inter.hip) */
+__device__ __forceinline__ int d_pb_range(const DevPic& p, const m355_pb& pb)
 {
-  if (m355_pb_is_edge(pb, p.pp.width, p.pp.height, p.pp.chroma_format_idc)) return 3;
-  if (pb.flags & M355_PBF_WEIGHTED) return 2;
-  return ((pb.flags & M355_PBF_MC_L0) && (pb.flags & M355_PBF_MC_L1)) ? 1 : 0;
+  return m355_pb_is_edge(pb, p.pp.width, p.pp.height, p.pp.chroma_format_idc) ? 1 : 0;
 }
 /* 16-byte units of edge_tu | edge_pb | cb_cu (prepare() in runtime_decode.hip: cb_cu starts at the next multiple of 64, 64 spare bytes behind) */
 __host__ __device__ static inline size_t d_meta_fill16(const DevPic& p) { return ((((size_t)2 * p.w4 * p.h4 + 63) & ~(size_t)63) + (size_t)p.wcb * p.hcb * 4 + 15) / 16; }
@@ -106,32 +105,34 @@ __global__ void __launch_bounds__(256) k_job_count(DevPic p, int clear_planes)
     for (size_t k = (size_t)blockIdx.x * 256 + threadIdx.x; k < n16; k += (size_t)gridDim.x * 256) q[k] = make_uint4(0, 0, 0, 0);
   }
   const int i = blockIdx.x * 256 + threadIdx.x;
-  int cnt[4] = {0, 0, 0, 0};
+  constexpr int NR = M355_JOB_RANGES;
+  int cnt[NR] = {0, 0};
   if (i < p.n_pbs) {
     const m355_pb pb = p.pbs[i];
-    const int cls = d_pb_class(p, pb);
+    const int rng = d_pb_range(p, pb);
     const int n = d_pb_jobs(pb);
 #pragma unroll
-    for (int k = 0; k < 4; k++) cnt[k] = cls == k ? n : 0;
+    for (int k = 0; k < NR; k++) cnt[k] = rng == k ? n : 0;
   }
-  __shared__ int s_w[4][4];
+  __shared__ int s_w[4][NR];
 #pragma unroll
-  for (int k = 0; k < 4; k++) {
+  for (int k = 0; k < NR; k++) {
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) cnt[k] += __shfl_xor(cnt[k], d, 64);
   }
   if ((threadIdx.x & 63) == 0) {
 #pragma unroll
-    for (int k = 0; k < 4; k++) s_w[threadIdx.x >> 6][k] = cnt[k];
+    for (int k = 0; k < NR; k++) s_w[threadIdx.x >> 6][k] = cnt[k];
   }
   __syncthreads();
-  if (threadIdx.x < 4) p.job_base[blockIdx.x * 4 + threadIdx.x] = (uint32_t)(s_w[0][threadIdx.x] + s_w[1][threadIdx.x] + s_w[2][threadIdx.x] + s_w[3][threadIdx.x]);
+  if (threadIdx.x < NR) p.job_base[blockIdx.x * NR + threadIdx.x] = (uint32_t)(s_w[0][threadIdx.x] + s_w[1][threadIdx.x] + s_w[2][threadIdx.x] + s_w[3][threadIdx.x]);
 }
 /* one thread per prediction block: PB index plane (pb_info, image.cc set_mv_info) and the job list of
  * k_inter_jobs: (w/4) x ceil(h/8) jobs per PB, row block major so consecutive jobs are horizontally
- * adjacent; three ranges (one-list, bi-predicted, picture-edge jobs), each in PB order. */
+ * adjacent; two ranges (MAIN, EDGE: d_pb_range), each in PB order. */
 __device__ __forceinline__ void k_meta_pb_body(const DevPic& p, const int chunk, const int n_chunks)
 {
+  constexpr int NR = M355_JOB_RANGES;
   const int i = chunk * 256 + (int)threadIdx.x;
   const int lane = threadIdx.x & 63;
   const bool active = i < p.n_pbs;
@@ -139,65 +140,64 @@ __device__ __forceinline__ void k_meta_pb_body(const DevPic& p, const int chunk,
   if (active) pb = p.pbs[i]; else { pb.x = pb.y = 0; pb.w = pb.h = 0; pb.flags = 0; }
   const int ns = pb.w >> 2;
   const int njobs = active ? d_pb_jobs(pb) : 0;              /* (as k_job_count counted it) */
-  /* four ranges: one-list jobs, bi-predicted jobs (so a wave never idles through a second pass it does not need), explicitly weighted
-     jobs, edge jobs; wave-level exclusive scans */
-  const int cls = !active ? 4 : d_pb_class(p, pb);
-  int incl[4];
+  /* wave-level exclusive scans, one per range */
+  const int rng = !active ? NR : d_pb_range(p, pb);
+  int incl[NR];
 #pragma unroll
-  for (int k = 0; k < 4; k++) incl[k] = cls == k ? njobs : 0;
+  for (int k = 0; k < NR; k++) incl[k] = rng == k ? njobs : 0;
 #pragma unroll
   for (int d = 1; d < 64; d <<= 1) {
 #pragma unroll
-    for (int k = 0; k < 4; k++) { const int t = __shfl_up(incl[k], (unsigned)d, 64); if (lane >= d) incl[k] += t; }
+    for (int k = 0; k < NR; k++) { const int t = __shfl_up(incl[k], (unsigned)d, 64); if (lane >= d) incl[k] += t; }
   }
   /* first job of this wave per range = the chunk's base + the totals of the workgroup's earlier waves (no atomics: the job list is
      in PB order, deterministic and spatially coherent) */
-  __shared__ int s_wtot[4][4];
+  __shared__ int s_wtot[4][NR];
   const int wave = threadIdx.x >> 6;
   if (lane == 63) {
 #pragma unroll
-    for (int k = 0; k < 4; k++) s_wtot[wave][k] = incl[k];
+    for (int k = 0; k < NR; k++) s_wtot[wave][k] = incl[k];
   }
   __syncthreads();
   /* the chunk's first job per range: sum of the counts (k_job_count) of the chunks before it + where the range starts */
-  __shared__ uint32_t s_red[4][8];
+  __shared__ uint32_t s_red[4][2 * NR];
   {
-    uint32_t acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};              /* [0..3] all chunks, [4..7] the chunks in front of this one */
+    uint32_t acc[2 * NR] = {0, 0, 0, 0};                      /* [0..NR) all chunks, [NR..2 NR) the chunks in front of this one */
     for (int ch = (int)threadIdx.x; ch < n_chunks; ch += 256) {
 #pragma unroll
-      for (int k = 0; k < 4; k++) {
-        const uint32_t n = p.job_base[ch * 4 + k];
+      for (int k = 0; k < NR; k++) {
+        const uint32_t n = p.job_base[ch * NR + k];
         acc[k] += n;
-        acc[4 + k] += ch < chunk ? n : 0u;
+        acc[NR + k] += ch < chunk ? n : 0u;
       }
     }
 #pragma unroll
-    for (int k = 0; k < 8; k++) {
+    for (int k = 0; k < 2 * NR; k++) {
 #pragma unroll
       for (int d = 32; d >= 1; d >>= 1) acc[k] += (uint32_t)__shfl_xor((int)acc[k], d, 64);
     }
     if (lane == 0) {
 #pragma unroll
-      for (int k = 0; k < 8; k++) s_red[wave][k] = acc[k];
+      for (int k = 0; k < 2 * NR; k++) s_red[wave][k] = acc[k];
     }
   }
   __syncthreads();
-  uint32_t base[4];
+  uint32_t base[NR];
   {
-    uint32_t tot[8];
+    uint32_t tot[2 * NR];
 #pragma unroll
-    for (int k = 0; k < 8; k++) tot[k] = s_red[0][k] + s_red[1][k] + s_red[2][k] + s_red[3][k];
+    for (int k = 0; k < 2 * NR; k++) tot[k] = s_red[0][k] + s_red[1][k] + s_red[2][k] + s_red[3][k];
     uint32_t start = 0;
 #pragma unroll
-    for (int k = 0; k < 4; k++) { base[k] = start + tot[4 + k]; start += tot[k]; }
+    for (int k = 0; k < NR; k++) { base[k] = start + tot[NR + k]; start += tot[k]; }
     if (chunk == 0 && threadIdx.x == 0) {
       const uint32_t cap = p.jobs_cap;
       uint32_t end = 0;
 #pragma unroll
-      for (int k = 0; k < 4; k++) { end += tot[k]; p.job_tot[k] = min(end, cap); }
+      for (int k = 0; k < NR; k++) { end += tot[k]; p.job_tot[k] = min(end, cap); }
     }
 #pragma unroll
-    for (int k = 0; k < 4; k++)
+    for (int k = 0; k < NR; k++)
       for (int w = 0; w < wave; w++) base[k] += (uint32_t)s_wtot[w][k];
   }
   /* emit the wave's jobs cooperatively: slot t of the wave's total belongs to the PB found by a binary
@@ -210,7 +210,7 @@ __device__ __forceinline__ void k_meta_pb_body(const DevPic& p, const int chunk,
   const int excl_all = incl_all - njobs;
   uint32_t dst0 = 0;
 #pragma unroll
-  for (int k = 0; k < 4; k++) dst0 = cls == k ? base[k] + (uint32_t)(incl[k] - njobs) : dst0;
+  for (int k = 0; k < NR; k++) dst0 = rng == k ? base[k] + (uint32_t)(incl[k] - njobs) : dst0;
   for (int t0 = 0; t0 < total; t0 += 64) {
     const int t = t0 + lane;
     int k = 0;

@@ -105,8 +105,8 @@ int prepare(m355_ctx* c, Resident& r, DevPic& d_out, bool& want_sao_out, hipStre
     const size_t cap = pic.n_pbs > 0 ? std::min(area / 16, area / 32 + 8 * (size_t)pic.n_pbs) + 256 : 1;
     const size_t n_chunks = ((size_t)(pic.n_pbs > 0 ? pic.n_pbs : 0) + 255) / 256;
     if ((rc = grow(&L.jobs, &L.cap_jobs, cap, st, false))) return rc;
-    if ((rc = grow(&L.job_base, &L.cap_jobbase, n_chunks * 4 + 8, st, true))) return rc;
-    d.jobs_cap = (uint32_t)cap; d.job_base = L.job_base; d.job_tot = L.job_base + n_chunks * 4;
+    if ((rc = grow(&L.job_base, &L.cap_jobbase, n_chunks * M355_JOB_RANGES + 8, st, true))) return rc;
+    d.jobs_cap = (uint32_t)cap; d.job_base = L.job_base; d.job_tot = L.job_base + n_chunks * M355_JOB_RANGES;
   }
   if ((rc = grow(&L.iplan, &L.cap_iplan, (size_t)r.n_iplan + 8, st, false))) return rc;
 

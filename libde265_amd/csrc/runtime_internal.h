@@ -205,7 +205,7 @@ struct Lane {
   uint32_t* jobs = nullptr;
   uint16_t* sao_nb = nullptr;
   uint16_t* iplan = nullptr;   /* border plans of the picture's intra blocks */
-  uint32_t* job_base = nullptr; /* per 256-PB chunk the first job of each range + the three range ends (k_job_count / k_meta_pb) */
+  uint32_t* job_base = nullptr; /* per 256-PB chunk its jobs per range (MAIN, EDGE), behind them the two range ends = DevPic::job_tot (k_job_count / k_meta_pb) */
   size_t cap_cb = 0, cap_u4 = 0, cap_edge = 0, cap_cuf = 0, cap_res = 0, cap_jobs = 0, cap_sao = 0, cap_iplan = 0, cap_jobbase = 0;
 };
 

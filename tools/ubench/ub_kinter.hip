@@ -1,12 +1,15 @@
 // k_inter_jobs<u16> outside the library: the PRODUCT kernel (this file includes libde265_amd/csrc/k_inter.hip) on a synthetic picture whose block mix, vectors and
 // list use this harness controls, beside cut-down outer kernels around the same job function (d_inter_job_lean) — where does the time go that the traffic model
 // (ub_tile.hip: the same loads and stores, a checksum instead of the filters) does not need?
-//   V0  the product kernel as launched by the library (gate word, range ends from device memory, reference table + tap tables to LDS, all three job modes)
-//   V1  no gate word, range ends as kernel arguments (two dependent round trips less in front of the job word)
+//   V0  the product kernel as launched by the library (gate word, range ends from device memory, reference table + tap tables to LDS, all three job modes):
+//       256 consecutive jobs of the MAIN range per workgroup, sorted by kind inside it
+//   V1  the job list sorted by kind picture-wide (one-list jobs, then two-list jobs) and a workgroup per 256 jobs of one kind, the kinds interleaved in
+//       proportion — the kernel's order before the compact workgroups —; no gate word, range ends as kernel arguments
 //   V2  V1 with the main job mode only in the kernel (no explicit-weight / EDGE code: 120 registers instead of 158), still 3 waves per SIMD
 //   V3  V2 at 4 waves per SIMD
 // Every variant's destination planes are compared with V0's.
-// usage: ub_kinter [bipred_pct (default 100)]
+// usage: ub_kinter [bipred_pct (default 100)] [clustered (default 0; 1: one list / two lists drawn per CTB instead of per PB: the workgroups of V1-V3 become
+//        compact at CTB granularity and nothing else changes)]
 #include "../../libde265_amd/csrc/k_inter.hip"
 #include <stdio.h>
 #include <vector>
@@ -78,14 +81,16 @@ __global__ void __launch_bounds__(256) k_stream_read_nt(const v4u* src, size_t n
 static unsigned rnd_state = 12345;
 static unsigned rnd() { rnd_state ^= rnd_state << 13; rnd_state ^= rnd_state >> 17; rnd_state ^= rnd_state << 5; return rnd_state; }
 static int bipred_pct = 100;
+static int clustered = 0;      /* 1: one list / two lists drawn per CTB instead of per PB, at the same share (every other draw as in the scattered arm) */
 
-static void gen_pbs(std::vector<m355_pb>& pbs, int x, int y, int size, int S)
+static void gen_pbs(std::vector<m355_pb>& pbs, int x, int y, int size, int S, bool ctb_bi)
 {
-  if (size > S) { const int h = size / 2; for (int i = 0; i < 4; i++) gen_pbs(pbs, x + (i & 1) * h, y + (i >> 1) * h, h, S); return; }
+  if (size > S) { const int h = size / 2; for (int i = 0; i < 4; i++) gen_pbs(pbs, x + (i & 1) * h, y + (i >> 1) * h, h, S, ctb_bi); return; }
   if (x >= PW || y >= PH) return;
   m355_pb pb; memset(&pb, 0, sizeof pb);
   pb.x = (uint16_t)x; pb.y = (uint16_t)y; pb.w = (uint8_t)S; pb.h = (uint8_t)std::min(S, PH - y);
-  const bool bi = (int)(rnd() % 100) < bipred_pct;
+  const bool bi_pb = (int)(rnd() % 100) < bipred_pct;
+  const bool bi = clustered ? ctb_bi : bi_pb;
   const int only = rnd() & 1;
   pb.ref_slot[0] = pb.ref_slot[1] = -1;
   for (int l = 0; l < 2; l++) {
@@ -103,6 +108,7 @@ static void gen_pbs(std::vector<m355_pb>& pbs, int x, int y, int size, int S)
 int main(int argc, char** argv)
 {
   if (argc > 1) bipred_pct = atoi(argv[1]);
+  if (argc > 2) clustered = atoi(argv[2]);
   // reference frames (two, three planes each) and the destination
   DevRef href[M355_MAX_REF_FRAMES]; memset(href, 0, sizeof href);
   std::vector<uint16_t> h((size_t)PW * PH);
@@ -132,27 +138,35 @@ int main(int argc, char** argv)
 
   const int mixes[][4] = {{8, 16, 32, 64}, {64, 64, 64, 64}, {16, 16, 16, 16}, {8, 8, 8, 8}};
   const char* mixname[] = {"mix 8/16/32/64 per CTB", "64x64 only", "16x16 only", "8x8 only"};
-  printf("bipred_pct %d\n", bipred_pct);
+  printf("bipred_pct %d, one list / two lists drawn per %s\n", bipred_pct, clustered ? "CTB (clustered)" : "PB (scattered)");
   for (int m = 0; m < 4; m++) {
     std::vector<m355_pb> pbs;
     rnd_state = 12345;
-    for (int cy = 0; cy < PH; cy += 64) for (int cx = 0; cx < PW; cx += 64) gen_pbs(pbs, cx, cy, 64, mixes[m][rnd() & 3]);
-    // job list as k_meta_pb leaves it: one-list jobs, then two-list jobs, each in PB order, strips left to right, row blocks top to bottom
-    std::vector<uint32_t> jobs[2];
+    for (int cy = 0; cy < PH; cy += 64) for (int cx = 0; cx < PW; cx += 64) {
+      const unsigned hsh = ((unsigned)(cy / 64) * 131u + (unsigned)(cx / 64)) * 2654435761u;      /* (a draw of its own: the PB stream stays that of the scattered arm) */
+      gen_pbs(pbs, cx, cy, 64, mixes[m][rnd() & 3], (int)((hsh >> 8) % 100) < bipred_pct);
+    }
+    // V0: the job list as k_meta_pb leaves it (the MAIN range: every PB's jobs in PB order, strips left to right, row blocks top to bottom).
+    // V1-V3: the list sorted by kind picture-wide, as it was before the compact workgroups: one-list jobs, then two-list jobs, each in PB order
+    std::vector<uint32_t> jobs[2], main_list;
     for (size_t i = 0; i < pbs.size(); i++) {
       const m355_pb& pb = pbs[i];
       const int bi = (pb.flags & M355_PBF_MC_L0) && (pb.flags & M355_PBF_MC_L1);
-      for (int rb = 0; rb < (pb.h + 7) / 8; rb++) for (int st = 0; st < pb.w / 4; st++) jobs[bi].push_back((uint32_t)i | ((uint32_t)st << 25) | ((uint32_t)rb << 29));
+      for (int rb = 0; rb < (pb.h + 7) / 8; rb++) for (int st = 0; st < pb.w / 4; st++) { const uint32_t j = (uint32_t)i | ((uint32_t)st << 25) | ((uint32_t)rb << 29); jobs[bi].push_back(j); main_list.push_back(j); }
     }
     const int t0 = (int)jobs[0].size(), t1 = t0 + (int)jobs[1].size();
     std::vector<uint32_t> all(jobs[0]); all.insert(all.end(), jobs[1].begin(), jobs[1].end());
     { m355_pb* d; CHK(hipMalloc(&d, pbs.size() * sizeof(m355_pb))); CHK(hipMemcpy(d, pbs.data(), pbs.size() * sizeof(m355_pb), hipMemcpyHostToDevice)); p.pbs = d; p.n_pbs = (int)pbs.size(); }
-    { uint32_t* d; CHK(hipMalloc(&d, all.size() * 4 + 64)); CHK(hipMemcpy(d, all.data(), all.size() * 4, hipMemcpyHostToDevice)); p.jobs = d; p.jobs_cap = (uint32_t)all.size(); }
-    { uint32_t tot[4] = {(uint32_t)t0, (uint32_t)t1, (uint32_t)t1, (uint32_t)t1}; uint32_t* d; CHK(hipMalloc(&d, 16)); CHK(hipMemcpy(d, tot, 16, hipMemcpyHostToDevice)); p.job_tot = d; }
+    uint32_t *d_sorted, *d_main;
+    CHK(hipMalloc(&d_sorted, all.size() * 4 + 64)); CHK(hipMemcpy(d_sorted, all.data(), all.size() * 4, hipMemcpyHostToDevice));
+    CHK(hipMalloc(&d_main, main_list.size() * 4 + 64)); CHK(hipMemcpy(d_main, main_list.data(), main_list.size() * 4, hipMemcpyHostToDevice));
+    p.jobs = d_main; p.jobs_cap = (uint32_t)all.size();
+    { uint32_t tot[M355_JOB_RANGES] = {(uint32_t)t1, (uint32_t)t1}; uint32_t* d; CHK(hipMalloc(&d, sizeof tot)); CHK(hipMemcpy(d, tot, sizeof tot, hipMemcpyHostToDevice)); p.job_tot = d; }
     printf("%-26s %7zu PBs, %8d jobs (%d from one list)\n", mixname[m], pbs.size(), t1, t0);
     const unsigned grid = (unsigned)((p.jobs_cap + 255) / 256) + 4 * 8;
     std::vector<uint16_t> ref0, got;
     for (int v = 0; v < 4; v++) {
+      p.jobs = v ? d_sorted : d_main;
       for (int c = 0; c < 3; c++) { p.plane[c] = dst[v ? 1 : 0][c]; CHK(hipMemset(p.plane[c], 0, (size_t)p.pw[c] * p.ph[c] * 2)); }
       std::vector<float> t;
       for (int r = 0; r < 8; r++) {
@@ -170,12 +184,13 @@ int main(int argc, char** argv)
       bool same = true;
       if (v == 0) { ref0.resize((size_t)PW * PH * 3 / 2); size_t o = 0; for (int c = 0; c < 3; c++) { CHK(hipMemcpy(ref0.data() + o, dst[0][c], (size_t)p.pw[c] * p.ph[c] * 2, hipMemcpyDeviceToHost)); o += (size_t)p.pw[c] * p.ph[c]; } }
       else { got.resize(ref0.size()); size_t o = 0; for (int c = 0; c < 3; c++) { CHK(hipMemcpy(got.data() + o, dst[1][c], (size_t)p.pw[c] * p.ph[c] * 2, hipMemcpyDeviceToHost)); o += (size_t)p.pw[c] * p.ph[c]; } same = memcmp(got.data(), ref0.data(), ref0.size() * 2) == 0; }
-      const char* what[] = {"V0 product kernel", "V1 no gate, ends in arguments", "V2 main mode only, 3 waves", "V3 main mode only, 4 waves"};
-      printf("    %-32s %.4f ms (min %.4f)%s\n", what[v], t[t.size() / 2], t[0], v ? (same ? "  = V0" : "  DIFFERS from V0") : "");
+      const char* what[] = {"V0 product kernel (compact workgroups)", "V1 sorted by kind; no gate, ends in arguments", "V2 sorted by kind; main mode only, 3 waves", "V3 sorted by kind; main mode only, 4 waves"};
+      printf("    %-48s %.4f ms (min %.4f)%s\n", what[v], t[t.size() / 2], t[0], v ? (same ? "  = V0" : "  DIFFERS from V0") : "");
     }
     /* the product kernel by the state of the caches: as above (launch after launch: the two reference frames, 199 MB, largely stay in the 256 MB Infinity Cache),
        behind a 1 GiB streaming write (cold), and behind that write + a streaming read of both reference frames (prefetched) */
     for (int c = 0; c < 3; c++) p.plane[c] = dst[0][c];
+    p.jobs = d_main;
     for (int mode = 0; mode < 7; mode++) {
       std::vector<float> t, tp;
       for (int r = 0; r < 6; r++) {
@@ -201,7 +216,7 @@ int main(int argc, char** argv)
       printf("    V0 %-48s %.4f ms\n", st[mode], t[t.size() / 2]);
       if (mode == 2) printf("       (the streaming read of the 199 MB itself: %.4f ms)\n", tp[tp.size() / 2]);
     }
-    CHK(hipFree((void*)p.pbs)); CHK(hipFree(p.jobs)); CHK(hipFree(p.job_tot));
+    CHK(hipFree((void*)p.pbs)); CHK(hipFree(d_sorted)); CHK(hipFree(d_main)); CHK(hipFree(p.job_tot));
   }
   return 0;
 }
