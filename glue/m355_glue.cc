@@ -86,7 +86,7 @@ namespace {
   X(m355_last_error) X(m355_device_count) X(m355_create) X(m355_destroy) X(m355_frame_create) X(m355_frame_destroy) \
   X(m355_frame_upload) X(m355_frame_download) X(m355_submit_picture) X(m355_wait) X(m355_set_pipeline_depth) \
   X(m355_host_alloc) X(m355_host_free) X(m355_frame_hash) X(m355_arena_begin) X(m355_last_serial) X(m355_decode_status) \
-  X(m355_frame_download_async) X(m355_frame_download_wait) X(m355_frame_export) X(m355_frame_export_scaled) X(m355_frame_export_rgb) X(m355_frame_export_resized) X(m355_frame_export_resized_rgb) X(m355_frames_export_tensor) X(m355_frames_export_tensor_rois) X(m355_frame_export_order) \
+  X(m355_frame_download_async) X(m355_frame_download_wait) X(m355_frame_export) X(m355_frame_export_scaled) X(m355_frame_export_rgb) X(m355_frame_export_resized_filtered) X(m355_frame_export_resized_rgb_filtered) X(m355_frames_export_tensor_filtered) X(m355_frames_export_tensor_rois_filtered) X(m355_frame_export_order) \
   X(m355_group_create) X(m355_group_destroy) X(m355_group_decode) X(m355_picture_upload) X(m355_picture_replace) X(m355_shard_owner_of_tile) \
   X(m355_picture_arena_begin) X(m355_frame_hash_async) X(m355_frame_hash_result) X(m355_frame_measure_async) X(m355_frame_measure_result)
 
@@ -1782,9 +1782,11 @@ LIBDE265_API int m355_glue_export_image_rgb(const struct de265_image* img, int l
 }
 /* The picture RESIZED on the device to out_size = {out_width, out_height} luma samples (m355_frame_export_resized: one separable triangle filter,
  * antialiased when downscaling, integer-exact; layout / samples = M355_EXPORT_*), with the waiting behaviour of m355_glue_export_image: the only wait
- * is for the worker to have enqueued the picture.  rect = the SOURCE rectangle, NULL: the image's conformance window. */
-LIBDE265_API int m355_glue_export_image_resized(const struct de265_image* img, int layout, int samples, const int rect[4], const int out_size[2],
-                                                void* const dst[3], const int64_t pitch[3], void* consumer_stream)
+ * is for the worker to have enqueued the picture.  rect = the SOURCE rectangle, NULL: the image's conformance window.  The _filtered form takes the
+ * filter, M355_FILTER_TRIANGLE or M355_FILTER_CUBIC (Catmull-Rom, at most 4x down), as do the _filtered forms of the three calls below; each plain form
+ * is its _filtered form with M355_FILTER_TRIANGLE. */
+LIBDE265_API int m355_glue_export_image_resized_filtered(const struct de265_image* img, int layout, int samples, const int rect[4], const int out_size[2],
+                                                         void* const dst[3], const int64_t pitch[3], int filter, void* consumer_stream)
 {
   Api* A = api();
   if (!A) return M355_ERR_NO_DEVICE;
@@ -1802,17 +1804,22 @@ LIBDE265_API int m355_glue_export_image_resized(const struct de265_image* img, i
   d.x0 = r[0]; d.y0 = r[1]; d.width = r[2]; d.height = r[3];
   d.out_width = out_size[0]; d.out_height = out_size[1];
   for (int c = 0; c < 3; c++) { d.dst[c] = dst[c]; d.pitch[c] = pitch[c]; }
-  int rc = A->m355_frame_export_resized(g->mctx, frame, &d);
+  int rc = A->m355_frame_export_resized_filtered(g->mctx, frame, &d, filter);
   if (rc == M355_OK) rc = A->m355_frame_export_order(g->mctx, frame, consumer_stream);
   if (rc != M355_OK) g->error = A->m355_last_error();
   return rc;
+}
+LIBDE265_API int m355_glue_export_image_resized(const struct de265_image* img, int layout, int samples, const int rect[4], const int out_size[2],
+                                                void* const dst[3], const int64_t pitch[3], void* consumer_stream)
+{
+  return m355_glue_export_image_resized_filtered(img, layout, samples, rect, out_size, dst, pitch, M355_FILTER_TRIANGLE, consumer_stream);
 }
 /* The picture RESIZED to out_size = {out_width, out_height} luma samples and converted to R'G'B' in one launch (m355_frame_export_resized_rgb: the
  * resized export and the R'G'B' export of the resized picture composed, integer-exact), with the waiting behaviour of m355_glue_export_image.  The frame,
  * the rectangle (NULL: the image's conformance window), matrix == -1 and full_range == -1 are resolved as in m355_glue_export_image_rgb, out_size as in
  * m355_glue_export_image_resized.  PACKED uses dst[0] and pitch[0] only. */
-LIBDE265_API int m355_glue_export_image_resized_rgb(const struct de265_image* img, int layout, int samples, int matrix, int full_range, const int rect[4],
-                                                    const int out_size[2], void* const dst[3], const int64_t pitch[3], void* consumer_stream)
+LIBDE265_API int m355_glue_export_image_resized_rgb_filtered(const struct de265_image* img, int layout, int samples, int matrix, int full_range, const int rect[4],
+                                                             const int out_size[2], void* const dst[3], const int64_t pitch[3], int filter, void* consumer_stream)
 {
   Api* A = api();
   if (!A) return M355_ERR_NO_DEVICE;
@@ -1838,19 +1845,24 @@ LIBDE265_API int m355_glue_export_image_resized_rgb(const struct de265_image* im
   d.x0 = r[0]; d.y0 = r[1]; d.width = r[2]; d.height = r[3];
   d.out_width = out_size[0]; d.out_height = out_size[1];
   for (int c = 0; c < 3; c++) { d.dst[c] = dst[c]; d.pitch[c] = pitch[c]; }
-  int rc = A->m355_frame_export_resized_rgb(g->mctx, frame, &d);
+  int rc = A->m355_frame_export_resized_rgb_filtered(g->mctx, frame, &d, filter);
   if (rc == M355_OK) rc = A->m355_frame_export_order(g->mctx, frame, consumer_stream);
   if (rc != M355_OK) g->error = A->m355_last_error();
   return rc;
+}
+LIBDE265_API int m355_glue_export_image_resized_rgb(const struct de265_image* img, int layout, int samples, int matrix, int full_range, const int rect[4],
+                                                    const int out_size[2], void* const dst[3], const int64_t pitch[3], void* consumer_stream)
+{
+  return m355_glue_export_image_resized_rgb_filtered(img, layout, samples, matrix, full_range, rect, out_size, dst, pitch, M355_FILTER_TRIANGLE, consumer_stream);
 }
 /* A BATCH of pictures of ONE decoder, each resized, converted to R'G'B', normalised and delivered as one float tensor in one launch
  * (m355_frames_export_tensor: layout / dtype = M355_TENSOR_*, samples = M355_RGB_* of the integer stage; scale / bias per channel; dst and the strides in
  * BYTES as in m355_tensor_desc), with the waiting behaviour of m355_glue_export_image: the only wait is for the worker to have enqueued every picture of
  * the batch, and the consumer's stream is ordered behind the one launch.  The rectangle (NULL: the conformance window of imgs[0]), matrix == -1 and
  * full_range == -1 are resolved from imgs[0] as in m355_glue_export_image_resized_rgb and hold for every picture; out_size as there. */
-LIBDE265_API int m355_glue_export_images_tensor(const struct de265_image* const* imgs, int n, int layout, int dtype, int samples, int matrix, int full_range,
-                                                const int rect[4], const int out_size[2], const float scale[3], const float bias[3], void* dst,
-                                                int64_t stride_n, int64_t stride_c, int64_t stride_h, void* consumer_stream)
+LIBDE265_API int m355_glue_export_images_tensor_filtered(const struct de265_image* const* imgs, int n, int layout, int dtype, int samples, int matrix, int full_range,
+                                                         const int rect[4], const int out_size[2], const float scale[3], const float bias[3], void* dst,
+                                                         int64_t stride_n, int64_t stride_c, int64_t stride_h, int filter, void* consumer_stream)
 {
   Api* A = api();
   if (!A) return M355_ERR_NO_DEVICE;
@@ -1880,18 +1892,25 @@ LIBDE265_API int m355_glue_export_images_tensor(const struct de265_image* const*
   d.out_width = out_size[0]; d.out_height = out_size[1];
   for (int c = 0; c < 3; c++) { d.scale[c] = scale[c]; d.bias[c] = bias[c]; }
   d.dst = dst; d.stride_n = stride_n; d.stride_c = stride_c; d.stride_h = stride_h;
-  int rc = A->m355_frames_export_tensor(g->mctx, frames, n, &d);
+  int rc = A->m355_frames_export_tensor_filtered(g->mctx, frames, n, &d, filter);
   if (rc == M355_OK) rc = A->m355_frame_export_order(g->mctx, frames[0], consumer_stream);
   if (rc != M355_OK) g->error = A->m355_last_error();
   return rc;
+}
+LIBDE265_API int m355_glue_export_images_tensor(const struct de265_image* const* imgs, int n, int layout, int dtype, int samples, int matrix, int full_range,
+                                                const int rect[4], const int out_size[2], const float scale[3], const float bias[3], void* dst,
+                                                int64_t stride_n, int64_t stride_c, int64_t stride_h, void* consumer_stream)
+{
+  return m355_glue_export_images_tensor_filtered(imgs, n, layout, dtype, samples, matrix, full_range, rect, out_size, scale, bias, dst, stride_n, stride_c, stride_h,
+                                                 M355_FILTER_TRIANGLE, consumer_stream);
 }
 /* A batch of REGIONS of pictures of ONE decoder, one rectangle per slice, as one float tensor in one launch (m355_frames_export_tensor_rois), with the
  * waiting and ordering of m355_glue_export_images_tensor.  rois: n x {x0, y0, width, height, flags} in luma samples of the coded picture, flags = 0 or
  * M355_ROI_MIRROR; an entry whose four rectangle fields are 0 means THAT picture's conformance window.  Every rectangle is resolved against ITS
  * picture; the same picture may appear any number of times.  matrix == -1 and full_range == -1 are resolved from imgs[0]. */
-LIBDE265_API int m355_glue_export_images_tensor_rois(const struct de265_image* const* imgs, const int (*rois)[5], int n, int layout, int dtype, int samples,
-                                                     int matrix, int full_range, const int out_size[2], const float scale[3], const float bias[3], void* dst,
-                                                     int64_t stride_n, int64_t stride_c, int64_t stride_h, void* consumer_stream)
+LIBDE265_API int m355_glue_export_images_tensor_rois_filtered(const struct de265_image* const* imgs, const int (*rois)[5], int n, int layout, int dtype, int samples,
+                                                              int matrix, int full_range, const int out_size[2], const float scale[3], const float bias[3], void* dst,
+                                                              int64_t stride_n, int64_t stride_c, int64_t stride_h, int filter, void* consumer_stream)
 {
   Api* A = api();
   if (!A) return M355_ERR_NO_DEVICE;
@@ -1925,10 +1944,17 @@ LIBDE265_API int m355_glue_export_images_tensor_rois(const struct de265_image* c
   d.out_width = out_size[0]; d.out_height = out_size[1];
   for (int c = 0; c < 3; c++) { d.scale[c] = scale[c]; d.bias[c] = bias[c]; }
   d.dst = dst; d.stride_n = stride_n; d.stride_c = stride_c; d.stride_h = stride_h;
-  int rc = A->m355_frames_export_tensor_rois(g->mctx, frames, rr, n, &d);
+  int rc = A->m355_frames_export_tensor_rois_filtered(g->mctx, frames, rr, n, &d, filter);
   if (rc == M355_OK) rc = A->m355_frame_export_order(g->mctx, frames[0], consumer_stream);
   if (rc != M355_OK) g->error = A->m355_last_error();
   return rc;
+}
+LIBDE265_API int m355_glue_export_images_tensor_rois(const struct de265_image* const* imgs, const int (*rois)[5], int n, int layout, int dtype, int samples,
+                                                     int matrix, int full_range, const int out_size[2], const float scale[3], const float bias[3], void* dst,
+                                                     int64_t stride_n, int64_t stride_c, int64_t stride_h, void* consumer_stream)
+{
+  return m355_glue_export_images_tensor_rois_filtered(imgs, rois, n, layout, dtype, samples, matrix, full_range, out_size, scale, bias, dst, stride_n, stride_c, stride_h,
+                                                      M355_FILTER_TRIANGLE, consumer_stream);
 }
 /* The picture COMPARED with another one on the device — what dec265 -m YUV does with MSE() of quality.cc on downloaded planes (dec265.cc:388-419); this call is
  * what a -m implementation on this backend calls.  ref / pitch: the reference picture's planes for the rectangle (rect = {x0, y0, width, height} in luma

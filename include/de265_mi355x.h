@@ -511,8 +511,9 @@ M355_API int   m355_frame_export_rgb(m355_ctx* ctx, int frame, const m355_rgb_de
 typedef struct m355_rgb_coeffs { int32_t F, y0, c0, cy, crv, cgu, cgv, cbu; } m355_rgb_coeffs;
 M355_API int   m355_rgb_coefficients(int matrix, int full_range, int bit_depth_luma, int bit_depth_chroma, int samples, m355_rgb_coeffs* out);
 /* The frame's rectangle RESIZED to out_width x out_height luma samples (k_export_resized.hip): every plane is resampled on its own grid — chroma to
- * out_width / SubWidthC x out_height / SubHeightC — and goes to the caller's memory in the layouts and sample formats of m355_frame_export.  ONE
- * filter: a separable triangle, widened by the downscale ratio — an antialiased bilinear filter when downscaling, plain bilinear when upscaling.
+ * out_width / SubWidthC x out_height / SubHeightC — and goes to the caller's memory in the layouts and sample formats of m355_frame_export.  The
+ * filter of this call (M355_FILTER_TRIANGLE; the cubic one follows below): a separable triangle, widened by the downscale ratio — an antialiased
+ * bilinear filter when downscaling, plain bilinear when upscaling.
  * Integer arithmetic only: what lands is a closed-form function of the samples m355_frame_download returns, the same on every build.
  * One axis of one plane maps sn source samples (the rectangle's, on that plane's grid) to dn output samples.  With 64-bit integers and
  * rdiv(a, b) = (2a + b) / (2b), for output index i:
@@ -540,12 +541,39 @@ M355_API int   m355_rgb_coefficients(int matrix, int full_range, int bit_depth_l
  * for a plane that exists; a pitch below the OUTPUT row's bytes.  A monochrome frame exports luma only; bytes beyond an output row are never written.
  * Ordering, the gate and sharded contexts are those of m355_frame_export: asynchronous, a reader of the frame of the same kind — m355_frame_export_wait
  * and m355_frame_export_order cover it, the next decode into the frame waits for it —, and nothing is written behind a rejected decode.
- * Not offered: filters with negative lobes (bicubic, Lanczos: signed sums and clipping), ratios beyond 8, another chroma siting, resizing into a
+ * A SECOND FILTER, M355_FILTER_CUBIC (the _filtered entry points below; M355_FILTER_TRIANGLE = 0 is the filter above, and with it every _filtered
+ * entry point IS the plain one): Catmull-Rom — Keys' cubic with a = -1/2, the kernel of an antialiased "bicubic" resize —, widened by the downscale
+ * ratio like the triangle, defined in integers in the same notation.  With D = 2 dn, M and C as above, for every integer k with d = |D k - C| < 2 M:
+ *   n_k = 3 d^3 - 5 M d^2 + 2 M^3                    for d <= M
+ *   n_k = -d^3 + 5 M d^2 - 8 M^2 d + 4 M^3           for M < d < 2 M           (2 M^3 w(d / M) with the Catmull-Rom w; negative in this lobe)
+ * N = sum n_k > 0, and P_k, q_k and rdiv — floor((2a + b) / (2b)) on SIGNED values — as above: the q_k sum to exactly 1 << 14 but may be negative; the
+ * clamp of k to the rectangle and the folding are the triangle's.  N has up to 48 bits; m355_resize_taps_filtered returns the exact row all the same.
+ * Limits: 16 coefficients per row need sn <= 4 dn, so the cubic filter takes at most 4x DOWN and, as the triangle, at most 8x up on either axis, and
+ * sn and dn at most M355_RESIZE_CUBIC_MAX_N = 16384 on every axis resized with it; outside: M355_ERR_INVALID, nothing enqueued.
+ * Passes, per plane, everything in SIGNED 32 bits, >> arithmetic; the intermediate keeps 16 bits of fraction so that the horizontal sum with its
+ * overshoot fits (a row's sum of |q_k| is at most 20 788, reached at 13 -> 12 co-sited; 4 * 23000^2 + 2^21 < 2^31):
+ *   u = sum_k qy[k] S[k][x]                            |u| < 2^31
+ *   t = (u + (1 << (bd - 3))) >> (bd - 2)              not clipped: about -0.27 * 2^16 .. 1.27 * 2^16
+ *   v = sum_k qx[k] t[k]                               |v| + 2^21 < 2^31
+ *   NATIVE  a = clip(0, 2^bd - 1, (v + (1 << (29 - bd))) >> (30 - bd))
+ *   MSB16   (uint16)(a << (16 - bd))
+ *   U8      clip(0, 255, (v + (1 << 21)) >> 22)        — ONE rounding from v, not a rounding of a
+ * A constant plane stays constant; out == rectangle gives the rows {0, 1 << 14, 0} and delivers what m355_frame_export delivers, byte for byte; a
+ * rectangle's resize equals the resize of a frame that holds only the rectangle.  The three composed exports below keep their definitions word for
+ * word, "the resized export" meaning the resized export with this filter: chroma is resized on its own grid with the SAME filter, rounded and clipped
+ * to a sample (a above), reconstructed by the bilinear filter of m355_frame_export_rgb, then the matrix, then m355_tensor_element.
+ * An unknown filter is M355_ERR_INVALID (m355_resize_taps_filtered: < 0); m355_frames_export_tensor_rois_filtered checks the filter's ratio and size
+ * limit per entry.
+ * Not offered: Lanczos, a selectable a, the cubic filter beyond 4x down (32 coefficients per row), sizes above 16384 per axis with it, a filter per
+ * slice, ratios beyond 8, another chroma siting, resizing into a
  * frame of the decoder; and of m355_frame_export_resized_rgb and m355_frames_export_tensor below: BGR order, another chroma siting, chroma resampled
  * straight onto the luma grid (it is resized on its own grid, then reconstructed), per-frame output sizes within a batch (per-frame rectangles:
  * m355_frames_export_tensor_rois, which rejects a region smaller than an eighth of the output and does not clamp it), writing into a tensor owned by
  * a second HIP runtime without m355_frame_export_order. */
 #define M355_RESIZE_MAX_TAPS 16
+#define M355_FILTER_TRIANGLE 0          /* the separable triangle: antialiased bilinear */
+#define M355_FILTER_CUBIC    1          /* Catmull-Rom: antialiased bicubic, at most 4x down */
+#define M355_RESIZE_CUBIC_MAX_N 16384   /* samples of an axis, source or output, under M355_FILTER_CUBIC */
 typedef struct m355_resize_desc {
   int32_t layout, samples;          /* M355_EXPORT_PLANAR / _SEMIPLANAR, M355_EXPORT_NATIVE / _MSB16 / _U8 */
   int32_t x0, y0, width, height;    /* source luma rectangle, exactly as in m355_export_desc (width == 0: whole frame) */
@@ -554,9 +582,12 @@ typedef struct m355_resize_desc {
   int64_t pitch[3];                 /* bytes per destination row, >= the OUTPUT row's bytes */
 } m355_resize_desc;
 M355_API int   m355_frame_export_resized(m355_ctx* ctx, int frame, const m355_resize_desc* desc);   /* asynchronous */
+M355_API int   m355_frame_export_resized_filtered(m355_ctx* ctx, int frame, const m355_resize_desc* desc, int filter);   /* M355_FILTER_*; asynchronous */
 /* row i of one axis' filter: returns the number of coefficients (1..16), *first = source index of coeff[0]; < 0 on bad arguments (a size below 1,
  * a ratio outside the limit, i outside [0, dst_n), cosited not 0 or 1, a null pointer) */
 M355_API int   m355_resize_taps(int src_n, int dst_n, int cosited, int i, int32_t* first, int32_t coeff[M355_RESIZE_MAX_TAPS]);
+/* the same for M355_FILTER_*: also < 0 for an unknown filter and, under M355_FILTER_CUBIC, beyond 4x down or a size above M355_RESIZE_CUBIC_MAX_N */
+M355_API int   m355_resize_taps_filtered(int filter, int src_n, int dst_n, int cosited, int i, int32_t* first, int32_t coeff[M355_RESIZE_MAX_TAPS]);
 /* The frame's rectangle RESIZED to out_width x out_height luma samples AND converted to R'G'B', in one launch (k_export_resized_rgb.hip): what a model
  * (its input size) or a compositor (its window's size) on the same GPU takes.  The definition is a COMPOSITION and adds no arithmetic, constant or
  * siting rule of its own:
@@ -586,6 +617,7 @@ typedef struct m355_resize_rgb_desc {
   int64_t pitch[3];                 /* bytes per destination row, >= the OUTPUT row's bytes */
 } m355_resize_rgb_desc;             /* (LP64: 88 bytes) */
 M355_API int   m355_frame_export_resized_rgb(m355_ctx* ctx, int frame, const m355_resize_rgb_desc* desc);   /* asynchronous */
+M355_API int   m355_frame_export_resized_rgb_filtered(m355_ctx* ctx, int frame, const m355_resize_rgb_desc* desc, int filter);   /* M355_FILTER_* */
 /* A BATCH of frames, each resized and converted to R'G'B' as above, NORMALISED and delivered as ONE float tensor in one launch (k_export_resized_rgb.hip):
  * the input of a model on the same GPU.  The definition is again a composition:
  *   channel c (0 = R, 1 = G, 2 = B) of pixel (x, y) of slice i starts as the integer v that m355_frame_export_resized_rgb delivers for frames[i]
@@ -636,6 +668,7 @@ typedef struct m355_tensor_desc {
   int64_t stride_n, stride_c, stride_h;  /* BYTES */
 } m355_tensor_desc;                      /* (LP64: 104 bytes) */
 M355_API int   m355_frames_export_tensor(m355_ctx* ctx, const int* frames, int n, const m355_tensor_desc* desc);   /* asynchronous */
+M355_API int   m355_frames_export_tensor_filtered(m355_ctx* ctx, const int* frames, int n, const m355_tensor_desc* desc, int filter);   /* M355_FILTER_* */
 M355_API int   m355_tensor_element(uint32_t v, float scale, float bias, int dtype, uint32_t* bits);                 /* host only */
 /* A batch of REGIONS as one float tensor in one launch: as m355_frames_export_tensor, but with ONE RECTANGLE PER SLICE — the boxes of a detector in
  * one frame, each resized to a classifier's input; the random crops and flips of a training loader; whole frames of different sizes.  The definition
@@ -655,7 +688,8 @@ M355_API int   m355_tensor_element(uint32_t v, float scale, float bias, int dtyp
  * src <= 8 * out && out <= 8 * src on either axis for THAT entry — a region smaller than an eighth of the output is rejected, not clamped.
  * Ordering, the gate, sharded contexts, m355_frame_export_wait and m355_frame_export_order: exactly those of m355_frames_export_tensor — one mark kept
  * by every distinct frame, each slice behind its own frame's gate: the slices of a frame behind a rejected decode are skipped, the others written.
- * Not offered: an output size per slice, ratios beyond 8, regions off the chroma grid, another siting. */
+ * Not offered: an output size per slice, a filter per slice, ratios beyond 8 (M355_FILTER_CUBIC: beyond 4 down), regions off the chroma grid,
+ * another siting. */
 #define M355_ROI_MIRROR 1                /* flags: the slice's columns in reverse order */
 typedef struct m355_tensor_roi {
   int32_t x0, y0, width, height;         /* source luma rectangle in frames[i], as in m355_export_desc (width == 0: the whole frame) */
@@ -663,6 +697,8 @@ typedef struct m355_tensor_roi {
 } m355_tensor_roi;                       /* (20 bytes) */
 M355_API int   m355_frames_export_tensor_rois(m355_ctx* ctx, const int* frames, const m355_tensor_roi* rois, int n,
                                               const m355_tensor_desc* desc);   /* asynchronous */
+M355_API int   m355_frames_export_tensor_rois_filtered(m355_ctx* ctx, const int* frames, const m355_tensor_roi* rois, int n,
+                                                       const m355_tensor_desc* desc, int filter);   /* M355_FILTER_*; its limits per entry */
 M355_API int   m355_frame_export_wait(m355_ctx* ctx, int frame);
 M355_API int   m355_frame_export_order(m355_ctx* ctx, int frame, void* consumer_hipStream);
 /* Device memory for export destinations and blocking copies out of / into it, for applications (and the tests) that keep a second HIP

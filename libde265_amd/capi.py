@@ -97,6 +97,8 @@ class TensorDesc(ctypes.Structure):
 
 
 ROI_MIRROR = 1
+FILTER_TRIANGLE, FILTER_CUBIC = 0, 1      # M355_FILTER_*
+RESIZE_CUBIC_MAX_N = 16384
 
 
 class TensorRoi(ctypes.Structure):
@@ -184,6 +186,12 @@ class Library:
             L.m355_tensor_element.argtypes = [ctypes.c_uint32, ctypes.c_float, ctypes.c_float, i, ctypes.POINTER(ctypes.c_uint32)]
         if hasattr(L, "m355_frames_export_tensor_rois"):  # (absent from older builds loaded through M355_LIB for an A/B)
             L.m355_frames_export_tensor_rois.argtypes = [vp, ctypes.POINTER(i), ctypes.POINTER(TensorRoi), i, ctypes.POINTER(TensorDesc)]
+        if hasattr(L, "m355_frame_export_resized_filtered"):  # (absent from older builds loaded through M355_LIB for an A/B)
+            L.m355_frame_export_resized_filtered.argtypes = [vp, i, ctypes.POINTER(ResizeDesc), i]
+            L.m355_frame_export_resized_rgb_filtered.argtypes = [vp, i, ctypes.POINTER(ResizeRgbDesc), i]
+            L.m355_frames_export_tensor_filtered.argtypes = [vp, ctypes.POINTER(i), i, ctypes.POINTER(TensorDesc), i]
+            L.m355_frames_export_tensor_rois_filtered.argtypes = [vp, ctypes.POINTER(i), ctypes.POINTER(TensorRoi), i, ctypes.POINTER(TensorDesc), i]
+            L.m355_resize_taps_filtered.argtypes = [i, i, i, i, i, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]
         L.m355_host_alloc.argtypes = [ctypes.c_size_t]
         L.m355_host_alloc.restype = vp
         L.m355_host_free.argtypes = [vp]
@@ -253,10 +261,14 @@ class Library:
         self.check(self.lib.m355_rgb_coefficients(matrix, full_range, bit_depth_luma, bit_depth_chroma, samples, ctypes.byref(k)))
         return {n: int(getattr(k, n)) for n, _ in RgbCoeffs._fields_}
 
-    def resize_taps(self, src_n, dst_n, cosited, i):
-        """row i of one axis of the resize filter (m355_resize_taps; host only) -> (first source index, [coefficients]), or None for arguments it rejects"""
+    def resize_taps(self, src_n, dst_n, cosited, i, filter=0, filtered_entry=False):
+        """row i of one axis of the resize filter (m355_resize_taps, or m355_resize_taps_filtered for filter != 0 or on request; host only) ->
+        (first source index, [coefficients]), or None for arguments it rejects"""
         first, coeff = ctypes.c_int32(), (ctypes.c_int32 * RESIZE_MAX_TAPS)()
-        n = self.lib.m355_resize_taps(src_n, dst_n, cosited, i, ctypes.byref(first), coeff)
+        if filter != 0 or filtered_entry:
+            n = self.lib.m355_resize_taps_filtered(filter, src_n, dst_n, cosited, i, ctypes.byref(first), coeff)
+        else:
+            n = self.lib.m355_resize_taps(src_n, dst_n, cosited, i, ctypes.byref(first), coeff)
         return None if n < 0 else (int(first.value), [int(coeff[k]) for k in range(n)])
 
     def tensor_element(self, v, scale, bias, dtype):
@@ -463,14 +475,15 @@ class Context:
             raise
         return (f, shapes, bufs, [int(desc.pitch[k]) for k in range(len(shapes))], host)
 
-    def resize_taps(self, src_n, dst_n, cosited, i):
+    def resize_taps(self, src_n, dst_n, cosited, i, filter=0, filtered_entry=False):
         """row i of one axis of the resize filter (m355_resize_taps) -> (first source index, [coefficients]), or None for arguments it rejects"""
-        return self.L.resize_taps(src_n, dst_n, cosited, i)
+        return self.L.resize_taps(src_n, dst_n, cosited, i, filter, filtered_entry)
 
-    def frame_export_resized(self, f, layout, samples, out_size, rect=None, host=False, pad=20):
+    def frame_export_resized(self, f, layout, samples, out_size, rect=None, host=False, pad=20, filter=0, filtered_entry=False):
         """start m355_frame_export_resized of frame f to out_size = (out_width, out_height) luma samples (rect = the source rectangle (x0, y0, width,
         height) in luma samples, None: the whole frame) into buffers of its own, made as frame_export makes them: every byte holds DEVICE_FILL
-        beforehand, the pitch is `pad` bytes larger than the row.  -> token for frame_export_finish"""
+        beforehand, the pitch is `pad` bytes larger than the row.  filter = FILTER_*: a filter other than 0, or filtered_entry, goes
+        through m355_frame_export_resized_filtered (so do the three helpers below through theirs).  -> token for frame_export_finish"""
         shapes = self.export_shapes(f, layout, samples, (0, 0, out_size[0], out_size[1]))
         desc = ResizeDesc(layout=layout, samples=samples, out_width=out_size[0], out_height=out_size[1])
         if rect is not None:
@@ -488,7 +501,10 @@ class Context:
                     p = self.device_alloc(rows * pitch)
                 bufs.append(p)
                 desc.dst[k] = p; desc.pitch[k] = pitch
-            self.L.check(self.L.lib.m355_frame_export_resized(self.h, f, ctypes.byref(desc)))
+            if filter != 0 or filtered_entry:
+                self.L.check(self.L.lib.m355_frame_export_resized_filtered(self.h, f, ctypes.byref(desc), filter))
+            else:
+                self.L.check(self.L.lib.m355_frame_export_resized(self.h, f, ctypes.byref(desc)))
         except Exception:
             for p in bufs:
                 self.L.lib.m355_host_free(p) if host else self.device_free(p)
@@ -531,7 +547,7 @@ class Context:
             raise
         return (f, shapes, bufs, [int(desc.pitch[k]) for k in range(len(shapes))], host)
 
-    def frame_export_resized_rgb(self, f, layout, samples, matrix, full_range, out_size, rect=None, host=False, pad=20):
+    def frame_export_resized_rgb(self, f, layout, samples, matrix, full_range, out_size, rect=None, host=False, pad=20, filter=0, filtered_entry=False):
         """start m355_frame_export_resized_rgb of frame f to out_size = (out_width, out_height) luma samples (rect = the source rectangle (x0, y0,
         width, height) in luma samples, None: the whole frame) into buffers of its own, made as frame_export_rgb makes them: every byte holds
         DEVICE_FILL beforehand, the pitch is `pad` bytes larger than the row.  Packed: one plane of 3 * out_width elements per row; planar: R, G, B.
@@ -555,7 +571,10 @@ class Context:
                     p = self.device_alloc(rows * pitch)
                 bufs.append(p)
                 desc.dst[k] = p; desc.pitch[k] = pitch
-            self.L.check(self.L.lib.m355_frame_export_resized_rgb(self.h, f, ctypes.byref(desc)))
+            if filter != 0 or filtered_entry:
+                self.L.check(self.L.lib.m355_frame_export_resized_rgb_filtered(self.h, f, ctypes.byref(desc), filter))
+            else:
+                self.L.check(self.L.lib.m355_frame_export_resized_rgb(self.h, f, ctypes.byref(desc)))
         except Exception:
             for p in bufs:
                 self.L.lib.m355_host_free(p) if host else self.device_free(p)
@@ -566,22 +585,25 @@ class Context:
         """the float stage of m355_frames_export_tensor for one integer (m355_tensor_element) -> the element's bit pattern"""
         return self.L.tensor_element(v, scale, bias, dtype)
 
-    def frames_export_tensor(self, frames, layout, dtype, samples, matrix, full_range, out_size, scale, bias, rect=None, host=False, pad=20):
+    def frames_export_tensor(self, frames, layout, dtype, samples, matrix, full_range, out_size, scale, bias, rect=None, host=False, pad=20, filter=0,
+                             filtered_entry=False):
         """start m355_frames_export_tensor of the frames (handles; the same one may repeat) to out_size = (out_width, out_height) luma samples each
         (rect = the source rectangle (x0, y0, width, height) in luma samples, the same in every frame; None: the whole frame) into ONE buffer of its
         own, made as frame_export_resized_rgb makes its buffers: every byte holds DEVICE_FILL beforehand, and every stride is `pad` bytes (a multiple
         of the element size) above the smallest one the call accepts — stride_h above the row, stride_c above a plane, stride_n above a slice.
         scale, bias: three floats each (R, G, B).  -> token for tensor_export_finish"""
-        return self._frames_export_tensor(frames, None, layout, dtype, samples, matrix, full_range, out_size, scale, bias, rect, host, pad)
+        return self._frames_export_tensor(frames, None, layout, dtype, samples, matrix, full_range, out_size, scale, bias, rect, host, pad,
+                                          filter if filter != 0 or filtered_entry else None)
 
-    def frames_export_tensor_rois(self, frames, rois, layout, dtype, samples, matrix, full_range, out_size, scale, bias, host=False, pad=20):
+    def frames_export_tensor_rois(self, frames, rois, layout, dtype, samples, matrix, full_range, out_size, scale, bias, host=False, pad=20, filter=0,
+                                  filtered_entry=False):
         """start m355_frames_export_tensor_rois: slice i is the rectangle rois[i] = (x0, y0, width, height, flags) of frames[i] (None or width 0: the
         whole of that frame; flags: 0 or ROI_MIRROR), resized to out_size.  The buffer is made as frames_export_tensor makes it: DEVICE_FILL in every
         byte, every stride `pad` bytes above the smallest one the call accepts.  -> token for tensor_export_finish"""
         return self._frames_export_tensor(frames, [r if r is not None else (0, 0, 0, 0, 0) for r in rois], layout, dtype, samples, matrix, full_range,
-                                          out_size, scale, bias, None, host, pad)
+                                          out_size, scale, bias, None, host, pad, filter if filter != 0 or filtered_entry else None)
 
-    def _frames_export_tensor(self, frames, rois, layout, dtype, samples, matrix, full_range, out_size, scale, bias, rect, host, pad):
+    def _frames_export_tensor(self, frames, rois, layout, dtype, samples, matrix, full_range, out_size, scale, bias, rect, host, pad, filter=None):
         w, h = out_size
         n, eb = len(frames), (4 if dtype == TENSOR_F32 else 2)
         row = w * eb * (3 if layout == TENSOR_NHWC else 1)
@@ -606,11 +628,17 @@ class Context:
         desc.dst = p
         try:
             if rois is None:
-                self.L.check(self.L.lib.m355_frames_export_tensor(self.h, (ctypes.c_int * n)(*frames), n, ctypes.byref(desc)))
+                if filter is not None:
+                    self.L.check(self.L.lib.m355_frames_export_tensor_filtered(self.h, (ctypes.c_int * n)(*frames), n, ctypes.byref(desc), filter))
+                else:
+                    self.L.check(self.L.lib.m355_frames_export_tensor(self.h, (ctypes.c_int * n)(*frames), n, ctypes.byref(desc)))
             else:
                 assert len(rois) == n
                 arr = (TensorRoi * n)(*[TensorRoi(*r) for r in rois])
-                self.L.check(self.L.lib.m355_frames_export_tensor_rois(self.h, (ctypes.c_int * n)(*frames), arr, n, ctypes.byref(desc)))
+                if filter is not None:
+                    self.L.check(self.L.lib.m355_frames_export_tensor_rois_filtered(self.h, (ctypes.c_int * n)(*frames), arr, n, ctypes.byref(desc), filter))
+                else:
+                    self.L.check(self.L.lib.m355_frames_export_tensor_rois(self.h, (ctypes.c_int * n)(*frames), arr, n, ctypes.byref(desc)))
         except Exception:
             self.L.lib.m355_host_free(p) if host else self.device_free(p)
             raise

@@ -339,7 +339,7 @@ struct ExportResizedArgs {
   uint32_t epoch;
 };
 /* src_bytes / dst_bytes: 1 or 2 per sample */
-void m355_launch_export_resized(const ExportResizedArgs& a, int src_bytes, int dst_bytes, bool semiplanar, hipStream_t st);
+void m355_launch_export_resized(const ExportResizedArgs& a, int src_bytes, int dst_bytes, bool semiplanar, int filter, hipStream_t st);
 
 /* one m355_frame_export_resized_rgb (k_export_resized_rgb.hip, RR_FRAME).  src[] = the rectangle's first sample of Y, Cb, Cr (the resize clamps to the rectangle),
    pitches in BYTES (src_pitch[0] luma, [1] both chroma planes); dst[0] alone for the packed layout, else R, G, B.  Index 0 of sn / dn is the luma
@@ -359,7 +359,7 @@ struct ExportResizedRgbArgs {
   uint32_t epoch;
 };
 /* src_bytes / dst_bytes: 1 or 2 per sample / channel */
-void m355_launch_export_resized_rgb(const ExportResizedRgbArgs& a, int src_bytes, int dst_bytes, hipStream_t st);
+void m355_launch_export_resized_rgb(const ExportResizedRgbArgs& a, int src_bytes, int dst_bytes, int filter, hipStream_t st);
 
 /* one m355_frames_export_tensor (k_export_resized_rgb.hip, RR_BATCH): the tile procedure over n frames in one grid, unit = slice * units + the
    tile inside the slice (units tiles per slice).  Per slice: src[] = the rectangle's first sample of Y, Cb, Cr in that frame, its two pitches (BYTES)
@@ -383,7 +383,7 @@ struct ExportTensorArgs {
   ExportTensorFrame fr[M355_TENSOR_MAX_FRAMES];
 };
 /* src_bytes: 1 or 2 per sample; elem_bytes: 2 (F16 / BF16) or 4 (F32) */
-void m355_launch_export_tensor(const ExportTensorArgs& a, int src_bytes, int elem_bytes, hipStream_t st);
+void m355_launch_export_tensor(const ExportTensorArgs& a, int src_bytes, int elem_bytes, int filter, hipStream_t st);
 
 /* one m355_frames_export_tensor_rois (k_export_resized_rgb.hip, RR_ROIS): the same tile procedure, with the GEOMETRY of the source per slice.  A slice's
    record holds what ExportTensorFrame holds — src[] = the first sample of ITS rectangle in ITS frame, the pitches, the gate — and what is the batch's
@@ -411,7 +411,7 @@ struct ExportTensorRoisArgs {
   ExportTensorRoi fr[M355_TENSOR_MAX_FRAMES];
 };
 static_assert(sizeof(ExportTensorRoi) == 88 && sizeof(ExportTensorRoisArgs) <= 4096, "the records of a batch of regions must fit the kernel arguments");
-void m355_launch_export_tensor_rois(const ExportTensorRoisArgs& a, int src_bytes, int elem_bytes, hipStream_t st);
+void m355_launch_export_tensor_rois(const ExportTensorRoisArgs& a, int src_bytes, int elem_bytes, int filter, hipStream_t st);
 
 /* first statement of every kernel of a decode: a picture whose lists k_validate rejected is never acted upon */
 /* Element `c` (0..2, per lane) of a three-entry table of the kernel arguments (plane pointers, pitches, ...): all three entries are

@@ -2,7 +2,8 @@
  * k_export_resized.hip — a decoded frame (or a rectangle of it) into memory of the caller, every plane RESIZED on its own grid to the size the
  * consumer asks for (m355_frame_export_resized, include/de265_mi355x.h holds the definition): a separable triangle filter widened by the downscale
  * ratio, coefficients of 14 bits from resize_taps.h — the function m355_resize_taps is —, vertical pass, ONE rounding to an 18-bit intermediate t,
- * horizontal pass, the sample formats of k_export.hip applied to the horizontal sum (one rounding).  Integer-exact.
+ * horizontal pass, the sample formats of k_export.hip applied to the horizontal sum (one rounding).  Integer-exact.  The filter is a template parameter:
+ * M355_FILTER_CUBIC (Catmull-Rom, m355_frame_export_resized_filtered) runs the same procedure in signed arithmetic, as the comment at the template says.
  *
  * ONE launch covers every plane.  A workgroup of 256 lanes owns a tile of up to 256 output columns x 16 output rows of one plane (of Cb AND Cr for an
  * interleaved plane).  Prologue: lane i derives the horizontal row of output column i into registers (through LDS: the row function indexes its
@@ -20,7 +21,8 @@
  * of the rectangle and every vector starts at a sample of the span, which ends at a sample of the rectangle; a lane reads at most 16 bytes from
  * there, i.e. less than 16 bytes beyond a sample inside a row of the plane, and rows are padded to 128 bytes and a plane ends with a 256-byte tail
  * (runtime_internal.h frame_alloc) — the argument of k_export_scaled.hip.  The t row holds RS_SPAN entries: 256 columns advance by at most
- * 255 * 8 + 1 source samples, a row adds at most 16 and the last vector at most 15 more; the vector count is clamped to the array all the same.
+ * 255 * 8 + 1 source samples, a row adds at most 16 and the last vector at most 15 more (the cubic filter: at most 255 * 4 + 1, and 16, and 15); the
+ * vector count is clamped to the array all the same.
  * Arithmetic in unsigned 32 bits: u < 2^(bd + 14) <= 2^30, t < 2^18, v < 2^32 (the coefficients of a row sum to 1 << 14), and
  * ((v >> 1) + (1 << (30 - b))) >> (31 - b) is (v + (1 << (31 - b))) >> (32 - b) without the 33rd bit (b: the bit depth, 8 for U8).
  * Traffic: every source row is read by the two output rows it contributes to when downscaling (the second read is served by the caches) and once
@@ -38,11 +40,16 @@
 /* (the selection idiom of k_export.hip: the three entries of an argument table as scalars, two scalar compares) */
 #define M355_EXPORT_SEL(arr) (p2 ? (arr)[2] : (p1 ? (arr)[1] : (arr)[0]))
 
-template <int SB, int DB, int SEMI>
+/* FILTER = M355_FILTER_CUBIC: the same procedure in signed 32 bits — rows of resize_taps.h's cubic filter (coefficients of 16 bits, some negative), the
+   vertical pass with the signed dot product, the rounding to a t of 16 bits of fraction (a.tshift = bd - 2), v_mad_i32_i24 in the horizontal pass
+   (|t| < 2^18, |q| < 2^15), an arithmetic shift (a.oshift = 30 - bd, 22 for U8) and the clip to the sample range.  Samples of 16 bits are no signed
+   16-bit operands: they are taken less 2^15 (one XOR per packed pair) and 2^15 * 2^14 is added to the sum, which is exact since a row sums to 1 << 14. */
+template <int SB, int DB, int SEMI, int FILTER>
 __global__ void __launch_bounds__(256) k_export_resized(ExportResizedArgs a)
 {
   M355_GATE(a);
   constexpr int S = 16 / SB;
+  constexpr bool CUBIC = FILTER == M355_FILTER_CUBIC;
   __shared__ unsigned s_t[2][2][RS_SPAN];         /* [output row & 1][plane]: the t row of the plane (of Cb and Cr); in the prologue: the lanes' horizontal rows */
   __shared__ int32_t s_vy[RS_TH][2 + M355_RESIZE_MAX_TAPS];   /* per output row of the tile: first source row, number of rows, coefficients */
   __shared__ int32_t s_span[2];                   /* first and last source column of the tile */
@@ -62,13 +69,16 @@ __global__ void __launch_bounds__(256) k_export_resized(ExportResizedArgs a)
   int32_t hfirst = 0;
   unsigned hq[M355_RESIZE_MAX_TAPS];
   if (tid < ncols) {
-    const int hn = m355_resize_row(snx, dnx, (int)M355_EXPORT_SEL(a.cosited), c0 + tid, &hfirst, hrow + tid, RS_TW);
+    int hn;
+    if constexpr (CUBIC) hn = m355_resize_row_cubic(snx, dnx, (int)M355_EXPORT_SEL(a.cosited), c0 + tid, &hfirst, hrow + tid, RS_TW);
+    else hn = m355_resize_row(snx, dnx, (int)M355_EXPORT_SEL(a.cosited), c0 + tid, &hfirst, hrow + tid, RS_TW);
     if (tid == 0) s_span[0] = hfirst;
     if (tid == ncols - 1) s_span[1] = hfirst + hn - 1;
   }
   if (tid >= 256u - RS_TH && tid - (256u - RS_TH) < nrows) {
     const uint32_t jj = tid - (256u - RS_TH);
-    s_vy[jj][1] = m355_resize_row(sny, dny, 0, j0 + jj, &s_vy[jj][0], &s_vy[jj][2], 1);
+    if constexpr (CUBIC) s_vy[jj][1] = m355_resize_row_cubic(sny, dny, 0, j0 + jj, &s_vy[jj][0], &s_vy[jj][2], 1);
+    else s_vy[jj][1] = m355_resize_row(sny, dny, 0, j0 + jj, &s_vy[jj][0], &s_vy[jj][2], 1);
   }
 #pragma unroll
   for (int k = 0; k < M355_RESIZE_MAX_TAPS; k++) hq[k] = tid < ncols ? (unsigned)hrow[k * RS_TW + tid] : 0u;
@@ -77,7 +87,7 @@ __global__ void __launch_bounds__(256) k_export_resized(ExportResizedArgs a)
   const int32_t span0 = s_span[0];
   uint32_t nvec = (uint32_t)(s_span[1] - span0 + S) / S;
   if (nvec > (uint32_t)(RS_SPAN / S)) nvec = RS_SPAN / S;
-  const int hmax = m355_resize_max_taps(snx, dnx);
+  const int hmax = m355_resize_max_taps_filtered(FILTER, snx, dnx);
   const int32_t hofs = hfirst - span0;
   const uint32_t pitch = (uint32_t)M355_EXPORT_SEL(a.src_pitch);    /* (a frame's rows are far below 4 GiB) */
   const long long dpitch = M355_EXPORT_SEL(a.dst_pitch);
@@ -86,6 +96,9 @@ __global__ void __launch_bounds__(256) k_export_resized(ExportResizedArgs a)
   /* this lane's sample of the tile's first row */
   M355_GLOBAL uint8_t* d = (M355_GLOBAL uint8_t*)M355_EXPORT_SEL(a.dst) + (size_t)j0 * (size_t)dpitch + (size_t)(c0 + tid) * (inter ? 2 * DB : DB);
   const int tsh = M355_EXPORT_SEL(a.tshift), osh = M355_EXPORT_SEL(a.oshift), lsh = M355_EXPORT_SEL(a.lshift);
+  /* cubic: the bias of 16-bit samples (tsh = bd - 2) and the largest sample (one destination byte: 8 bits, NATIVE or U8) */
+  const unsigned sbias = CUBIC && SB == 2 && tsh == 14 ? 0x80008000u : 0u;
+  const int top = DB == 1 ? 255 : (1 << (tsh + 2)) - 1;
 
   /* the first batch of rows of this lane's first vector, loaded one output row ahead: the loads of row jj + 1 are issued before the horizontal pass
      of row jj, which hides their latency */
@@ -119,15 +132,24 @@ __global__ void __launch_bounds__(256) k_export_resized(ExportResizedArgs a)
             if (b + r < vn) {
               /* the coefficients of rows b + r and b + r + 1 as a 16-bit pair: a broadcast read, the same in every lane (a row's eight pairs held in
                  scalar registers across this loop spilled up to 12 of them in the 16-bit semi-planar instantiations; 2 spills are left there) */
-              const unsigned q2 = (unsigned)(s_vy[jj][2 + b + r] | (s_vy[jj][3 + b + r] << 16));
+              if constexpr (CUBIC) {
+                const unsigned q2 = (unsigned)(s_vy[jj][2 + b + r] & 0xFFFF) | ((unsigned)s_vy[jj][3 + b + r] << 16);
 #pragma unroll
-              for (int e = 0; e < S; e++) u[e] = d_udot2(d_pair<SB>(raw[r], raw[r + 1], e), q2, u[e]);
+                for (int e = 0; e < S; e++) u[e] = (unsigned)d_dot2(SB == 2 ? d_pair<SB>(raw[r], raw[r + 1], e) ^ sbias : d_pair<SB>(raw[r], raw[r + 1], e), q2, (int)u[e]);
+              } else {
+                const unsigned q2 = (unsigned)(s_vy[jj][2 + b + r] | (s_vy[jj][3 + b + r] << 16));
+#pragma unroll
+                for (int e = 0; e < S; e++) u[e] = d_udot2(d_pair<SB>(raw[r], raw[r + 1], e), q2, u[e]);
+              }
             }
           }
         }
         /* 2. the rounding to t */
 #pragma unroll
-        for (int e = 0; e < S; e++) trow[c][v * S + e] = (u[e] + (1u << (tsh - 1))) >> tsh;
+        for (int e = 0; e < S; e++) {
+          if constexpr (CUBIC) trow[c][v * S + e] = (unsigned)(((int)u[e] + (sbias ? 1 << 29 : 0) + (1 << (tsh - 1))) >> tsh);
+          else trow[c][v * S + e] = (u[e] + (1u << (tsh - 1))) >> tsh;
+        }
       }
     }
     if (jj + 1 < nrows && tid < nvec) {
@@ -146,10 +168,15 @@ __global__ void __launch_bounds__(256) k_export_resized(ExportResizedArgs a)
         for (int k = 0; k < M355_RESIZE_MAX_TAPS; k++) {
           if (k >= hmax) break;
           const int32_t x = hofs + k;
-          v = d_umad24(hq[k], trow[c][x < RS_SPAN ? x : RS_SPAN - 1], v);     /* (behind the row's last coefficient: 0 times an entry of the array) */
+          if constexpr (CUBIC) v = (unsigned)d_mad24((int)hq[k], (int)trow[c][x < RS_SPAN ? x : RS_SPAN - 1], (int)v);
+          else v = d_umad24(hq[k], trow[c][x < RS_SPAN ? x : RS_SPAN - 1], v);     /* (behind the row's last coefficient: 0 times an entry of the array) */
         }
-        unsigned w = ((v >> 1) + (1u << (osh - 1))) >> osh;
-        if (DB == 1) w = w < 255u ? w : 255u;
+        unsigned w;
+        if constexpr (CUBIC) w = (unsigned)d_clip3(0, top, ((int)v + (1 << (osh - 1))) >> osh);
+        else {
+          w = ((v >> 1) + (1u << (osh - 1))) >> osh;
+          if (DB == 1) w = w < 255u ? w : 255u;
+        }
         o[c] = w << lsh;
       }
       if (inter) {
@@ -166,15 +193,18 @@ __global__ void __launch_bounds__(256) k_export_resized(ExportResizedArgs a)
 #undef RS_LOAD_BATCH
 }
 
-void m355_launch_export_resized(const ExportResizedArgs& a, int src_bytes, int dst_bytes, bool semiplanar, hipStream_t st)
+void m355_launch_export_resized(const ExportResizedArgs& a, int src_bytes, int dst_bytes, bool semiplanar, int filter, hipStream_t st)
 {
   const uint32_t units = a.unit_end[2];
   if (!units) return;
   const dim3 grid(units), block(256);
 #define M355_EXPORT_RESIZED_CASE(SB, DB) \
   if (src_bytes == SB && dst_bytes == DB) { \
-    if (semiplanar) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_export_resized<SB, DB, 1>), grid, block, 0, st, a); \
-    else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_export_resized<SB, DB, 0>), grid, block, 0, st, a); \
+    if (filter == M355_FILTER_CUBIC) { \
+      if (semiplanar) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_export_resized<SB, DB, 1, M355_FILTER_CUBIC>), grid, block, 0, st, a); \
+      else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_export_resized<SB, DB, 0, M355_FILTER_CUBIC>), grid, block, 0, st, a); \
+    } else if (semiplanar) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_export_resized<SB, DB, 1, M355_FILTER_TRIANGLE>), grid, block, 0, st, a); \
+    else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_export_resized<SB, DB, 0, M355_FILTER_TRIANGLE>), grid, block, 0, st, a); \
   }
   M355_EXPORT_RESIZED_CASE(1, 1) M355_EXPORT_RESIZED_CASE(1, 2) M355_EXPORT_RESIZED_CASE(2, 1) M355_EXPORT_RESIZED_CASE(2, 2)
 #undef M355_EXPORT_RESIZED_CASE

@@ -6,7 +6,9 @@
  *   RR_BATCH  n frames, one rectangle, as one float tensor of EB = 2 (F16 / BF16) or 4 (F32) bytes per element (m355_frames_export_tensor);
  *   RR_ROIS   n frames, a rectangle per slice, as one float tensor (m355_frames_export_tensor_rois).
  * No new arithmetic: the filter rows are those of resize_taps.h, the passes those of k_export_resized.hip, the chroma filter and the matrix those of
- * k_export_rgb.hip, the float stage that of tensor_element.h.
+ * k_export_rgb.hip, the float stage that of tensor_element.h.  The filter (M355_FILTER_TRIANGLE, or M355_FILTER_CUBIC of the _filtered entry points) is a
+ * template parameter of the tile procedure — d_rr_row, d_rr_vertical, d_rr_horizontal — and so of every mode; the cubic passes are those of the cubic
+ * k_export_resized: signed, 16 bits of fraction in t, luma and chroma clipped to a sample behind the horizontal pass.
  *
  * A workgroup of 256 lanes owns a tile of up to 256 luma output columns x 16 luma output rows (even width for 4:2:0 / 4:2:2, so that a tile's
  * first column is a chroma column).  Prologue: lane i derives the horizontal row of resized chroma column cc0 + i into registers (through LDS, as
@@ -45,7 +47,7 @@
  *   Mirror (RR_ROIS, M355_ROI_MIRROR) touches the epilogue only: the lane of tile column t stages its pixel at position ncols - 1 - t of the
  *   staged row (the channels of an NHWC pixel keep their order), and the tile's first destination column is out_width - c0 - ncols.
  * Layout, chroma format, F16 against BF16 and U8 against U16 of the tensors' integer stage are wave-uniform run-time switches (kernel arguments in
- * scalar registers): source sample bytes, element bytes and the mode are the template parameters, twelve instantiations.
+ * scalar registers): source sample bytes, element bytes, the mode and the filter are the template parameters, twelve instantiations per filter.
  *
  * Reads stay inside the planes' allocations, by the argument of k_export_resized.hip for every plane of every slice: the host admits a frame only
  * if it contains the slice's rectangle (export_plan per frame), whose size is the source size the slice's rows are derived from.  A filter row's
@@ -61,7 +63,7 @@
  * (position < ncols <= 256, channel < 3).
  * Writes: channel c of output pixel (row, column) of the slice only, with row < out_height and column < out_width (mirrored: the tile's columns
  * out_width - c0 - ncols .. out_width - c0 - 1); the host has checked that pitches and strides keep rows, planes and slices apart.
- * Arithmetic: the resize in unsigned 32 bits as in k_export_resized.hip; the conversion in signed 32 bits as in k_export_rgb.hip.
+ * Arithmetic: the resize in unsigned 32 bits (cubic: signed) as in k_export_resized.hip; the conversion in signed 32 bits as in k_export_rgb.hip.
  */
 #include "k_common.h"
 #include "resize_taps.h"
@@ -98,12 +100,14 @@ __device__ __forceinline__ RrWhere d_rr_where(const M355_GLOBAL uint8_t* src0, c
 /* The vertical pass of the segments of one pass and its rounding to t (steps 1 and 2 of k_export_resized.hip): a lane owns one 16-byte vector of
    the span of each source row of its segment's filter row vy[row] = {first source row, number of rows, coefficients} (LDS); rows_left: the rows
    from vy[0] to the tile's end.  The first batch of rows of this lane's first vector is in raw already (loaded a pass ahead). */
-template <int SB>
+template <int SB, int FILTER>
 __device__ __forceinline__ void d_rr_vertical(const M355_GLOBAL uint8_t* src0, const M355_GLOBAL uint8_t* src1, uint32_t pitch, int32_t span0, uint32_t nvec,
                                               uint32_t nplanes, uint32_t nseg, uint32_t seglen, const int32_t (*vy)[2 + M355_RESIZE_MAX_TAPS], uint32_t rows_left,
                                               int tsh, unsigned* trow, uint32_t tid, unsigned (&raw)[8][4])
 {
   constexpr int S = 16 / SB;
+  constexpr bool CUBIC = FILTER == M355_FILTER_CUBIC;
+  const unsigned sbias = CUBIC && SB == 2 && tsh == 14 ? 0x80008000u : 0u;     /* cubic (tsh = bd - 2): 16-bit samples are taken less 2^15 */
   for (uint32_t vv = tid; vv < nseg * nvec; vv += 256u) {
     const RrWhere w = d_rr_where<SB>(src0, src1, span0, nvec, nplanes, vv);
     if (w.row >= rows_left) continue;
@@ -120,31 +124,50 @@ __device__ __forceinline__ void d_rr_vertical(const M355_GLOBAL uint8_t* src0, c
 #pragma unroll
         for (int r = 0; r < 8; r += 2) {
           if (b + r < vn) {
-            const unsigned q2 = (unsigned)(q[2 + b + r] | (q[3 + b + r] << 16));  /* (the same in every lane of a segment) */
+            if constexpr (CUBIC) {
+              const unsigned q2 = (unsigned)(q[2 + b + r] & 0xFFFF) | ((unsigned)q[3 + b + r] << 16);
 #pragma unroll
-            for (int e = 0; e < S; e++) u[e] = d_udot2(d_pair<SB>(raw[r], raw[r + 1], e), q2, u[e]);
+              for (int e = 0; e < S; e++) u[e] = (unsigned)d_dot2(SB == 2 ? d_pair<SB>(raw[r], raw[r + 1], e) ^ sbias : d_pair<SB>(raw[r], raw[r + 1], e), q2, (int)u[e]);
+            } else {
+              const unsigned q2 = (unsigned)(q[2 + b + r] | (q[3 + b + r] << 16));  /* (the same in every lane of a segment) */
+#pragma unroll
+              for (int e = 0; e < S; e++) u[e] = d_udot2(d_pair<SB>(raw[r], raw[r + 1], e), q2, u[e]);
+            }
           }
         }
       }
     }
     unsigned* const t = trow + w.seg * seglen + w.v * S;
 #pragma unroll
-    for (int e = 0; e < S; e++) t[e] = (u[e] + (1u << (tsh - 1))) >> tsh;
+    for (int e = 0; e < S; e++) {
+      if constexpr (CUBIC) t[e] = (unsigned)(((int)u[e] + (sbias ? 1 << 29 : 0) + (1 << (tsh - 1))) >> tsh);   /* (2^15 * 2^14 back: a row sums to 1 << 14) */
+      else t[e] = (u[e] + (1u << (tsh - 1))) >> tsh;
+    }
   }
 }
 
 /* The horizontal pass of one output sample (step 3) and its rounding to a sample of bd bits (osh = 31 - bd): hq = the lane's coefficients, hofs =
-   where its first one lies in the t row of lim entries */
-__device__ __forceinline__ unsigned d_rr_horizontal(const unsigned* hq, const unsigned* trow, int32_t lim, int32_t hofs, int hmax, int osh)
+   where its first one lies in the t row of lim entries.  Cubic: signed (v_mad_i32_i24: |t| < 2^18, |q| < 2^15), osh = 30 - bd, clipped to 0 .. top */
+template <int FILTER>
+__device__ __forceinline__ unsigned d_rr_horizontal(const unsigned* hq, const unsigned* trow, int32_t lim, int32_t hofs, int hmax, int osh, int top)
 {
   unsigned v = 0;
 #pragma unroll
   for (int k = 0; k < M355_RESIZE_MAX_TAPS; k++) {
     if (k >= hmax) break;
     const int32_t x = hofs + k;
-    v = d_umad24(hq[k], trow[x < lim ? x : lim - 1], v);        /* (behind the row's last coefficient: 0 times an entry of the row) */
+    if constexpr (FILTER == M355_FILTER_CUBIC) v = (unsigned)d_mad24((int)hq[k], (int)trow[x < lim ? x : lim - 1], (int)v);
+    else v = d_umad24(hq[k], trow[x < lim ? x : lim - 1], v);        /* (behind the row's last coefficient: 0 times an entry of the row) */
   }
-  return ((v >> 1) + (1u << (osh - 1))) >> osh;
+  if constexpr (FILTER == M355_FILTER_CUBIC) return (unsigned)d_clip3(0, top, ((int)v + (1 << (osh - 1))) >> osh);
+  else return ((v >> 1) + (1u << (osh - 1))) >> osh;
+}
+/* a row of resize_taps.h under the kernel's filter */
+template <int FILTER>
+__device__ __forceinline__ int d_rr_row(int64_t sn, int64_t dn, int cosited, int64_t i, int32_t* first, int32_t* coeff, int stride)
+{
+  if constexpr (FILTER == M355_FILTER_CUBIC) return m355_resize_row_cubic(sn, dn, cosited, i, first, coeff, stride);
+  else return m355_resize_row(sn, dn, cosited, i, first, coeff, stride);
 }
 
 /* The modes and their kernel arguments.  RR_SRC(i) / RR_PITCH(i): plane i's first sample and pitch class i of the frame or of the slice's record;
@@ -157,9 +180,10 @@ template <> struct RrArgs<RR_ROIS> { typedef ExportTensorRoisArgs T; };
 #define RR_PITCH(i) ({ uint32_t g_; if constexpr (MODE == RR_FRAME) g_ = (uint32_t)a.src_pitch[i]; else g_ = (uint32_t)a.fr[slice].src_pitch[i]; g_; })
 #define RR_GEOM(field) ({ uint32_t g_; if constexpr (MODE == RR_ROIS) g_ = a.fr[slice].field; else g_ = a.field; g_; })
 
-template <int SB, int EB, int MODE>
+template <int SB, int EB, int MODE, int FILTER>
 __global__ void __launch_bounds__(256) k_export_resized_rgb(typename RrArgs<MODE>::T a)
 {
+  constexpr bool CUBIC = FILTER == M355_FILTER_CUBIC;
   constexpr int S = 16 / SB;
   constexpr uint32_t OB = RR_TW * 3 * (MODE == RR_FRAME ? 2 : EB);   /* bytes of a staged output row: 256 pixels x 3 channels x 2 (tensors: EB) bytes */
   uint32_t slice = 0;                                           /* (wave-uniform: the slice's record comes by scalar loads) */
@@ -204,17 +228,17 @@ __global__ void __launch_bounds__(256) k_export_resized_rgb(typename RrArgs<MODE
   int32_t* hrow = (int32_t*)&s_t[0][0];                        /* coefficient k of lane i at [k * RR_TW + i] */
   int32_t hfirst = 0, cfirst = 0;
   if (tid < ncc) {
-    const int hn = m355_resize_row(RR_GEOM(sn_x[1]), cdx, (int)swl, cc0 + tid, &cfirst, hrow + tid, RR_TW);
+    const int hn = d_rr_row<FILTER>(RR_GEOM(sn_x[1]), cdx, (int)swl, cc0 + tid, &cfirst, hrow + tid, RR_TW);
     if (tid == 0) s_span[1][0] = cfirst;
     if (tid == ncc - 1) s_span[1][1] = cfirst + hn - 1;
   }
   if (tid >= 256u - RR_TH && tid - (256u - RR_TH) < nrows) {
     const uint32_t jj = tid - (256u - RR_TH);
-    s_vy[0][jj][1] = m355_resize_row(RR_GEOM(sn_y[0]), dny, 0, j0 + jj, &s_vy[0][jj][0], &s_vy[0][jj][2], 1);
+    s_vy[0][jj][1] = d_rr_row<FILTER>(RR_GEOM(sn_y[0]), dny, 0, j0 + jj, &s_vy[0][jj][0], &s_vy[0][jj][2], 1);
   }
   if (tid >= 256u - 2 * RR_TH && tid - (256u - 2 * RR_TH) < ncr) {
     const uint32_t jj = tid - (256u - 2 * RR_TH);
-    s_vy[1][jj][1] = m355_resize_row(RR_GEOM(sn_y[1]), cdy, 0, cj0 + jj, &s_vy[1][jj][0], &s_vy[1][jj][2], 1);
+    s_vy[1][jj][1] = d_rr_row<FILTER>(RR_GEOM(sn_y[1]), cdy, 0, cj0 + jj, &s_vy[1][jj][0], &s_vy[1][jj][2], 1);
   }
   __syncthreads();
 
@@ -233,10 +257,10 @@ __global__ void __launch_bounds__(256) k_export_resized_rgb(typename RrArgs<MODE
        vector would load it behind the first, not ahead), and two rows of each where four fit */
     const uint32_t cap = (nvec * S <= (uint32_t)(RR_SPAN / 4) && 4u * nvec <= 256u) ? 4u : ((nvec * S <= (uint32_t)(RR_SPAN / 2) && 2u * nvec <= 256u) ? 2u : 1u);
     const uint32_t npl = cap >= 2u ? 2u : 1u, rpp = cap / npl, nseg = cap, seglen = RR_SPAN / cap;
-    const int hmax = m355_resize_max_taps(RR_GEOM(sn_x[1]), cdx);
+    const int hmax = m355_resize_max_taps_filtered(FILTER, RR_GEOM(sn_x[1]), cdx);
     const int32_t hofs = cfirst - span0, lim = (int32_t)seglen;
     const uint32_t pitch = RR_PITCH(1);
-    const int tsh = a.bdc - 4, osh = 31 - a.bdc;
+    const int tsh = a.bdc - (CUBIC ? 2 : 4), osh = (CUBIC ? 30 : 31) - a.bdc, top = (1 << a.bdc) - 1;
     for (uint32_t c = 0; c < 2; c += npl) {
       const M355_GLOBAL uint8_t* const src0 = c ? RR_SRC(2) : RR_SRC(1);
       const M355_GLOBAL uint8_t* const src1 = RR_SRC(2);
@@ -247,7 +271,7 @@ __global__ void __launch_bounds__(256) k_export_resized_rgb(typename RrArgs<MODE
         RR_LOAD_BATCH(me.p + (size_t)vfirst * (size_t)pitch, 0, vn, pitch)
       }
       for (uint32_t r = 0; r < ncr; r += rpp, par ^= 1u) {
-        d_rr_vertical<SB>(src0, src1, pitch, span0, nvec, npl, nseg, seglen, &s_vy[1][r], ncr - r, tsh, s_t[par], tid, raw);
+        d_rr_vertical<SB, FILTER>(src0, src1, pitch, span0, nvec, npl, nseg, seglen, &s_vy[1][r], ncr - r, tsh, s_t[par], tid, raw);
         if (active && r + rpp + me.row < ncr) {                /* the next pass's first batch, in flight across the horizontal pass */
           const int nfirst = s_vy[1][r + rpp + me.row][0], nn = s_vy[1][r + rpp + me.row][1];
           RR_LOAD_BATCH(me.p + (size_t)nfirst * (size_t)pitch, 0, nn, pitch)
@@ -256,7 +280,7 @@ __global__ void __launch_bounds__(256) k_export_resized_rgb(typename RrArgs<MODE
         if (tid < ncc) {
           for (uint32_t i = 0; i < rpp && r + i < ncr; i++)
             for (uint32_t pl = 0; pl < npl; pl++)
-              s_c[c + pl][r + i][tid] = (unsigned short)d_rr_horizontal(cq, s_t[par] + (i * npl + pl) * seglen, lim, hofs, hmax, osh);
+              s_c[c + pl][r + i][tid] = (unsigned short)d_rr_horizontal<FILTER>(cq, s_t[par] + (i * npl + pl) * seglen, lim, hofs, hmax, osh, top);
         }
         /* (no second barrier: the next pass's t goes to the other half of s_t, and the pass after it is written behind the next barrier) */
       }
@@ -266,7 +290,7 @@ __global__ void __launch_bounds__(256) k_export_resized_rgb(typename RrArgs<MODE
   /* the horizontal rows of the tile's luma columns, derived here so that their registers are not held across the chroma phase */
   unsigned hq[M355_RESIZE_MAX_TAPS];
   if (tid < ncols) {
-    const int hn = m355_resize_row(RR_GEOM(sn_x[0]), dnx, 0, c0 + tid, &hfirst, hrow + tid, RR_TW);
+    const int hn = d_rr_row<FILTER>(RR_GEOM(sn_x[0]), dnx, 0, c0 + tid, &hfirst, hrow + tid, RR_TW);
     if (tid == 0) s_span[0][0] = hfirst;
     if (tid == ncols - 1) s_span[0][1] = hfirst + hn - 1;
   }
@@ -279,10 +303,10 @@ __global__ void __launch_bounds__(256) k_export_resized_rgb(typename RrArgs<MODE
   uint32_t nvec = (uint32_t)(s_span[0][1] - span0 + S) / S;
   if (nvec > (uint32_t)(RR_SPAN / S)) nvec = RR_SPAN / S;
   const uint32_t rpp = (nvec * S <= (uint32_t)(RR_SPAN / 2) && 2u * nvec <= 256u) ? 2u : 1u, seglen = RR_SPAN / rpp;   /* two output rows per pass where two spans fit a row of s_t and the lanes */
-  const int hmax = m355_resize_max_taps(RR_GEOM(sn_x[0]), dnx);
+  const int hmax = m355_resize_max_taps_filtered(FILTER, RR_GEOM(sn_x[0]), dnx);
   const int32_t hofs = hfirst - span0;
   const uint32_t pitch = RR_PITCH(0);                           /* (a frame's rows are far below 4 GiB) */
-  const int tsh = a.bdl - 4, osh = 31 - a.bdl;
+  const int tsh = a.bdl - (CUBIC ? 2 : 4), osh = (CUBIC ? 30 : 31) - a.bdl, top = (1 << a.bdl) - 1;
   const M355_GLOBAL uint8_t* const srcy = RR_SRC(0);
   const RrWhere me = d_rr_where<SB>(srcy, srcy, span0, nvec, 1u, tid);
   const bool active = tid < rpp * nvec;
@@ -345,7 +369,7 @@ __global__ void __launch_bounds__(256) k_export_resized_rgb(typename RrArgs<MODE
   }
   uint32_t staged = 0, staged_j = 0;                           /* the rows staged by the pass before, and the first of them */
   for (uint32_t jp = 0; jp < nrows; jp += rpp, par ^= 1u) {
-    d_rr_vertical<SB>(srcy, srcy, pitch, span0, nvec, 1u, rpp, seglen, &s_vy[0][jp], nrows - jp, tsh, s_t[par], tid, raw);
+    d_rr_vertical<SB, FILTER>(srcy, srcy, pitch, span0, nvec, 1u, rpp, seglen, &s_vy[0][jp], nrows - jp, tsh, s_t[par], tid, raw);
     if (active && jp + rpp + me.row < nrows) {                 /* the next pass's first batch, in flight across the horizontal pass */
       const int nfirst = s_vy[0][jp + rpp + me.row][0], nn = s_vy[0][jp + rpp + me.row][1];
       RR_LOAD_BATCH(me.p + (size_t)nfirst * (size_t)pitch, 0, nn, pitch)
@@ -356,7 +380,7 @@ __global__ void __launch_bounds__(256) k_export_resized_rgb(typename RrArgs<MODE
     for (uint32_t ri = 0; ri < staged; ri++) {
       const uint32_t jj = jp + ri;
       if (tid < ncols) {
-        const int y = (int)d_rr_horizontal(hq, s_t[par] + ri * seglen, (int32_t)seglen, hofs, hmax, osh);
+        const int y = (int)d_rr_horizontal<FILTER>(hq, s_t[par] + ri * seglen, (int32_t)seglen, hofs, hmax, osh, top);
         const int base = d_mad24(cy, y, ky);
         int r = base, g = base, b = base;
         if (cf != 0) {
@@ -409,26 +433,30 @@ __global__ void __launch_bounds__(256) k_export_resized_rgb(typename RrArgs<MODE
 #undef RR_LOAD_BATCH
 
 /* src_bytes: 1 or 2 per sample; elem_bytes: 1 or 2 per channel of a frame, 2 or 4 per element of a tensor */
+#define RR_LAUNCH_F(MODE, B0, B1, F) \
+  if (src_bytes == 1 && elem_bytes == B0) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_export_resized_rgb<1, B0, MODE, F>), g_, block, 0, st, a); \
+  if (src_bytes == 1 && elem_bytes == B1) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_export_resized_rgb<1, B1, MODE, F>), g_, block, 0, st, a); \
+  if (src_bytes == 2 && elem_bytes == B0) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_export_resized_rgb<2, B0, MODE, F>), g_, block, 0, st, a); \
+  if (src_bytes == 2 && elem_bytes == B1) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_export_resized_rgb<2, B1, MODE, F>), g_, block, 0, st, a);
 #define RR_LAUNCH(MODE, B0, B1, grid) \
   const dim3 g_ grid, block(256); \
-  if (src_bytes == 1 && elem_bytes == B0) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_export_resized_rgb<1, B0, MODE>), g_, block, 0, st, a); \
-  if (src_bytes == 1 && elem_bytes == B1) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_export_resized_rgb<1, B1, MODE>), g_, block, 0, st, a); \
-  if (src_bytes == 2 && elem_bytes == B0) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_export_resized_rgb<2, B0, MODE>), g_, block, 0, st, a); \
-  if (src_bytes == 2 && elem_bytes == B1) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_export_resized_rgb<2, B1, MODE>), g_, block, 0, st, a);
-void m355_launch_export_resized_rgb(const ExportResizedRgbArgs& a, int src_bytes, int elem_bytes, hipStream_t st)
+  if (filter == M355_FILTER_CUBIC) { RR_LAUNCH_F(MODE, B0, B1, M355_FILTER_CUBIC) } \
+  else { RR_LAUNCH_F(MODE, B0, B1, M355_FILTER_TRIANGLE) }
+void m355_launch_export_resized_rgb(const ExportResizedRgbArgs& a, int src_bytes, int elem_bytes, int filter, hipStream_t st)
 {
   if (!a.units) return;
   RR_LAUNCH(RR_FRAME, 1, 2, (a.units))
 }
-void m355_launch_export_tensor(const ExportTensorArgs& a, int src_bytes, int elem_bytes, hipStream_t st)
+void m355_launch_export_tensor(const ExportTensorArgs& a, int src_bytes, int elem_bytes, int filter, hipStream_t st)
 {
   if (!a.units || !a.n) return;
   RR_LAUNCH(RR_BATCH, 2, 4, (a.units * a.n))
 }
 /* the batch of regions: blockIdx.y = slice, blockIdx.x = the unit inside it, up to the largest unit count of a slice */
-void m355_launch_export_tensor_rois(const ExportTensorRoisArgs& a, int src_bytes, int elem_bytes, hipStream_t st)
+void m355_launch_export_tensor_rois(const ExportTensorRoisArgs& a, int src_bytes, int elem_bytes, int filter, hipStream_t st)
 {
   if (!a.max_units || !a.n) return;
   RR_LAUNCH(RR_ROIS, 2, 4, (a.max_units, a.n))
 }
 #undef RR_LAUNCH
+#undef RR_LAUNCH_F

@@ -1,6 +1,6 @@
 /*
  * k_resize_dev.h — the primitives the resize kernels share (k_export_resized.hip, k_export_resized_rgb.hip) and k_asm.h does not have (it has the
- * signed dot product only), each with its twin for the SIMT interpreter.  Include behind k_common.h.
+ * signed dot product only, d_dot2, which the cubic filter's vertical pass uses), each with its twin for the SIMT interpreter.  Include behind k_common.h.
  */
 #pragma once
 

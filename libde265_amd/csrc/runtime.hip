@@ -644,33 +644,43 @@ int m355_frame_export_rgb(m355_ctx* c, int h, const m355_rgb_desc* e)
   return reader_end(c, f, RD_EXPORT, cs);
 }
 /* row i of one axis of the resize filter (resize_taps.h: the function k_export_resized.hip derives its rows with) */
+int m355_resize_taps_filtered(int filter, int src_n, int dst_n, int cosited, int i, int32_t* first, int32_t coeff[M355_RESIZE_MAX_TAPS])
+{
+  if (!first || !coeff || (cosited != 0 && cosited != 1) || !m355_resize_ratio_ok_filtered(filter, src_n, dst_n) || i < 0 || i >= dst_n) return -1;
+  return m355_resize_row_filtered(filter, src_n, dst_n, cosited, i, first, coeff, 1);
+}
 int m355_resize_taps(int src_n, int dst_n, int cosited, int i, int32_t* first, int32_t coeff[M355_RESIZE_MAX_TAPS])
 {
-  if (!first || !coeff || (cosited != 0 && cosited != 1) || !m355_resize_ratio_ok(src_n, dst_n) || i < 0 || i >= dst_n) return -1;
-  return m355_resize_row(src_n, dst_n, cosited, i, first, coeff, 1);
+  return m355_resize_taps_filtered(M355_FILTER_TRIANGLE, src_n, dst_n, cosited, i, first, coeff);
 }
 /* The width of k_export_resized's tiles on one plane: 256 output columns, or a few less where that saves a wavefront — the lanes of the vertical pass
  * own the 16-byte vectors of the tile's source span, and a span of 64 k + a few vectors (256 columns at ratio 4: 129) would run a wavefront for them. */
-static uint32_t resize_tile_w(int64_t sn, int64_t dn, int sb)
+static uint32_t resize_tile_w(int filter, int64_t sn, int64_t dn, int sb)
 {
-  const int64_t S = 16 / sb, T = m355_resize_max_taps(sn, dn);
+  const int64_t S = 16 / sb, T = m355_resize_max_taps_filtered(filter, sn, dn);
   const auto vectors = [&](int64_t w) { return ((w - 1) * sn / dn + 2 + T + S - 1) / S; };   /* (an upper bound of the span of w columns) */
   int64_t w = M355_RESIZE_TILE_W;
   const int64_t nv = vectors(w), k = nv / 64;
   if (k >= 1 && nv % 64 != 0 && nv % 64 <= 16) while (w > 1 && vectors(w) > 64 * k) w--;
   return (uint32_t)w;
 }
-/* What the resizing exports check behind their plans: the output size against the chroma grid, and the ratio of every plan (entries > 0: of every entry
- * of a batch of regions, which the message then names) */
-static int resize_check(const char* who, const ExportPlan* P, int entries, int ow, int oh)
+/* What the resizing exports check behind their plans: the filter, the output size against the chroma grid, and the filter's limits — the ratio, and for
+ * the cubic filter the sizes — of every plan (entries > 0: of every entry of a batch of regions, which the message then names).  The chroma planes'
+ * ratios are the luma plane's and their sizes smaller. */
+static int resize_check(const char* who, const ExportPlan* P, int entries, int ow, int oh, int filter)
 {
+  if (filter != M355_FILTER_TRIANGLE && filter != M355_FILTER_CUBIC) return fail(M355_ERR_INVALID, "%s: unknown filter %d", who, filter);
   const Frame* f = P[0].f;
   const int sw = (f->cf == 1 || f->cf == 2) ? 2 : 1, sh = f->cf == 1 ? 2 : 1;
   if (ow <= 0 || oh <= 0 || ow % sw || oh % sh)
     return fail(M355_ERR_INVALID, "%s: output size %dx%d is not positive or no multiple of %dx%d luma samples", who, ow, oh, sw, sh);
   for (int i = 0; i < (entries ? entries : 1); i++) {
     const int pw = P[i].p[0].pw, ph = P[i].p[0].ph;
-    if (m355_resize_ratio_ok(pw, ow) && m355_resize_ratio_ok(ph, oh)) continue;
+    if (m355_resize_ratio_ok_filtered(filter, pw, ow) && m355_resize_ratio_ok_filtered(filter, ph, oh)) continue;
+    if (filter == M355_FILTER_CUBIC && entries)
+      return fail(M355_ERR_INVALID, "%s: entry %d, %dx%d to %dx%d is more than 4x down or 8x up, or a size above %d (cubic filter)", who, i, pw, ph, ow, oh, M355_RESIZE_CUBIC_MAX_N);
+    if (filter == M355_FILTER_CUBIC)
+      return fail(M355_ERR_INVALID, "%s: %dx%d to %dx%d is more than 4x down or 8x up, or a size above %d (cubic filter)", who, pw, ph, ow, oh, M355_RESIZE_CUBIC_MAX_N);
     if (entries) return fail(M355_ERR_INVALID, "%s: entry %d, %dx%d to %dx%d is more than 8x down or up", who, i, pw, ph, ow, oh);
     return fail(M355_ERR_INVALID, "%s: %dx%d to %dx%d is more than 8x down or up", who, pw, ph, ow, oh);
   }
@@ -679,7 +689,7 @@ static int resize_check(const char* who, const ExportPlan* P, int entries, int o
 /* The frame, or a rectangle of it, resized to out_width x out_height luma samples (k_export_resized.hip): the frame handle, the rectangle, the layout and
  * the samples are checked by export_plan — with destinations that cannot fail, as for the R'G'B' export —, the output size, the ratio and the destinations
  * here.  A reader of the kind RD_EXPORT, like the three above. */
-int m355_frame_export_resized(m355_ctx* c, int h, const m355_resize_desc* e)
+int m355_frame_export_resized_filtered(m355_ctx* c, int h, const m355_resize_desc* e, int filter)
 {
   const char* who = "m355_frame_export_resized";
   ExportPlan P;
@@ -687,8 +697,9 @@ int m355_frame_export_resized(m355_ctx* c, int h, const m355_resize_desc* e)
   if (rc) return rc;
   Frame* f = P.f;
   const int sw = (f->cf == 1 || f->cf == 2) ? 2 : 1, sh = f->cf == 1 ? 2 : 1;
-  rc = resize_check(who, &P, 0, e->out_width, e->out_height);
+  rc = resize_check(who, &P, 0, e->out_width, e->out_height, filter);
   if (rc) return rc;
+  const bool cubic = filter == M355_FILTER_CUBIC;               /* (its intermediate keeps 16 bits of fraction and its sums their sign: shifts 2 and 1 less) */
   ExportResizedArgs a = {};
   uint32_t units = 0;
   for (int p = 0; p < 3; p++) {
@@ -704,10 +715,10 @@ int m355_frame_export_resized(m355_ctx* c, int h, const m355_resize_desc* e)
       a.src_pitch[p] = q.src_pitch;
       a.sn_x[p] = (uint32_t)q.pw; a.sn_y[p] = (uint32_t)q.ph; a.dn_x[p] = (uint32_t)ow; a.dn_y[p] = (uint32_t)oh;
       a.cosited[p] = p && sw == 2;
-      a.tile_w[p] = resize_tile_w(q.pw, ow, q.sb);
+      a.tile_w[p] = resize_tile_w(filter, q.pw, ow, q.sb);
       a.tiles_x[p] = ((uint32_t)ow + a.tile_w[p] - 1) / a.tile_w[p];
-      a.tshift[p] = q.bd - 4;
-      a.oshift[p] = e->samples == M355_EXPORT_U8 ? 23 : 31 - q.bd;
+      a.tshift[p] = q.bd - (cubic ? 2 : 4);
+      a.oshift[p] = (e->samples == M355_EXPORT_U8 ? 23 : 31 - q.bd) - (cubic ? 1 : 0);
       a.lshift[p] = e->samples == M355_EXPORT_MSB16 ? 16 - q.bd : 0;
       units += a.tiles_x[p] * (((uint32_t)oh + M355_RESIZE_TILE_H - 1) / M355_RESIZE_TILE_H);
     }
@@ -715,19 +726,20 @@ int m355_frame_export_resized(m355_ctx* c, int h, const m355_resize_desc* e)
   }
   hipSetDevice(c->device);
   const hipStream_t cs = reader_begin(c, f, RD_EXPORT, &a.timeout, &a.epoch);
-  m355_launch_export_resized(a, f->bpp[0], P.p[0].db, P.semi, cs);
+  m355_launch_export_resized(a, f->bpp[0], P.p[0].db, P.semi, filter, cs);
   HIPCHK(hipGetLastError());
   return reader_end(c, f, RD_EXPORT, cs);
 }
+int m355_frame_export_resized(m355_ctx* c, int h, const m355_resize_desc* e) { return m355_frame_export_resized_filtered(c, h, e, M355_FILTER_TRIANGLE); }
 /* The width of k_export_resized_rgb's tiles: a pass of that kernel takes two luma rows, or two rows of Cb and of Cr, where their source vectors fit
  * the workgroup's 256 lanes, and a workgroup's time follows its number of passes — so the widest width (even for 4:2:0 / 4:2:2: a tile's first column
  * is a chroma column) not above resize_tile_w's at which they fit, but at least 64 columns, then the narrowest one with the same number of tiles. */
-static uint32_t resize_rgb_tile_w(int64_t sn, int64_t dn, int64_t csn, int64_t cdn, int sb, int sw)
+static uint32_t resize_rgb_tile_w(int filter, int64_t sn, int64_t dn, int64_t csn, int64_t cdn, int sb, int sw)
 {
   const int64_t S = 16 / sb;
-  const auto vectors = [&](int64_t w, int64_t s, int64_t d) { return ((w - 1) * s / d + 2 + m355_resize_max_taps(s, d) + S - 1) / S; };   /* (an upper bound) */
+  const auto vectors = [&](int64_t w, int64_t s, int64_t d) { return ((w - 1) * s / d + 2 + m355_resize_max_taps_filtered(filter, s, d) + S - 1) / S; };   /* (an upper bound) */
   const auto fits = [&](int64_t w) { return 2 * vectors(w, sn, dn) <= 256 && (sw != 2 || 4 * vectors(w / 2 + 1, csn, cdn) <= 256); };
-  int64_t w = resize_tile_w(sn, dn, sb);
+  int64_t w = resize_tile_w(filter, sn, dn, sb);
   if (sw == 2) w = w > 2 ? w & ~(int64_t)1 : 2;
   int64_t t = w;
   while (t > 64 && !fits(t)) t -= sw;
@@ -746,13 +758,13 @@ template <class R> static void plan_sources(const ExportPlan& Q, R& r)
   for (int p = 0; p < Q.np; p++) r.src[p] = Q.p[p].src[0];
   r.src_pitch[0] = Q.p[0].src_pitch; r.src_pitch[1] = Q.np > 1 ? Q.p[1].src_pitch : 0;
 }
-template <class G, class D> static void plan_geometry(const ExportPlan& Q, int ow, int oh, G& g, D& d)
+template <class G, class D> static void plan_geometry(const ExportPlan& Q, int ow, int oh, int filter, G& g, D& d)
 {
   const Frame* f = Q.f;
   const int sw = (f->cf == 1 || f->cf == 2) ? 2 : 1, sh = f->cf == 1 ? 2 : 1;
   g.sn_x[0] = (uint32_t)Q.p[0].pw; g.sn_y[0] = (uint32_t)Q.p[0].ph; d.dn_x[0] = (uint32_t)ow; d.dn_y[0] = (uint32_t)oh;
   if (Q.np > 1) { g.sn_x[1] = (uint32_t)Q.p[1].pw; g.sn_y[1] = (uint32_t)Q.p[1].ph; d.dn_x[1] = (uint32_t)(ow / sw); d.dn_y[1] = (uint32_t)(oh / sh); }
-  g.tile_w = resize_rgb_tile_w(Q.p[0].pw, ow, Q.np > 1 ? Q.p[1].pw : 0, ow / sw, f->bpp[0], sw);
+  g.tile_w = resize_rgb_tile_w(filter, Q.p[0].pw, ow, Q.np > 1 ? Q.p[1].pw : 0, ow / sw, f->bpp[0], sw);
   g.tiles_x = ((uint32_t)ow + g.tile_w - 1) / g.tile_w;
   g.units = g.tiles_x * (((uint32_t)oh + M355_RESIZE_TILE_H - 1) / M355_RESIZE_TILE_H);
 }
@@ -760,14 +772,14 @@ template <class G, class D> static void plan_geometry(const ExportPlan& Q, int o
 /* The same resize with the R'G'B' conversion of the resized picture behind it, in one launch (k_export_resized_rgb.hip, RR_FRAME): the frame handle and
  * the rectangle are checked by export_plan — with destinations that cannot fail —, the output size and the ratio as for the resized export, the
  * conversion and the destinations as for the R'G'B' export, with the OUTPUT width.  A reader of the kind RD_EXPORT, like the four above. */
-int m355_frame_export_resized_rgb(m355_ctx* c, int h, const m355_resize_rgb_desc* e)
+int m355_frame_export_resized_rgb_filtered(m355_ctx* c, int h, const m355_resize_rgb_desc* e, int filter)
 {
   const char* who = "m355_frame_export_resized_rgb";
   ExportPlan P;
   int rc = export_plan_rect(c, h, e, e, who, P);
   if (rc) return rc;
   Frame* f = P.f;
-  rc = resize_check(who, &P, 0, e->out_width, e->out_height);
+  rc = resize_check(who, &P, 0, e->out_width, e->out_height, filter);
   if (rc) return rc;
   ExportResizedRgbArgs a = {};
   bool planar = false;
@@ -775,14 +787,15 @@ int m355_frame_export_resized_rgb(m355_ctx* c, int h, const m355_resize_rgb_desc
   rc = rgb_desc_check(who, e, f, e->out_width, a, &planar, &db);
   if (rc) return rc;
   plan_sources(P, a);
-  plan_geometry(P, e->out_width, e->out_height, a, a);
+  plan_geometry(P, e->out_width, e->out_height, filter, a, a);
   a.cf = f->cf; a.planar = planar; a.bdl = f->bdl; a.bdc = f->bdc;
   hipSetDevice(c->device);
   const hipStream_t cs = reader_begin(c, f, RD_EXPORT, &a.timeout, &a.epoch);
-  m355_launch_export_resized_rgb(a, f->bpp[0], db, cs);
+  m355_launch_export_resized_rgb(a, f->bpp[0], db, filter, cs);
   HIPCHK(hipGetLastError());
   return reader_end(c, f, RD_EXPORT, cs);
 }
+int m355_frame_export_resized_rgb(m355_ctx* c, int h, const m355_resize_rgb_desc* e) { return m355_frame_export_resized_rgb_filtered(c, h, e, M355_FILTER_TRIANGLE); }
 /* the float stage of m355_frames_export_tensor for one value (tensor_element.h: the function the kernel calls) */
 int m355_tensor_element(uint32_t v, float scale, float bias, int dtype, uint32_t* bits)
 {
@@ -869,7 +882,7 @@ static int batch_reader_end(m355_ctx* c, const ExportPlan* P, int n, hipStream_t
 /* A batch of frames resized, converted, normalised and delivered as one float tensor in one launch (k_export_resized_rgb.hip, RR_BATCH).  Every frame's
  * handle and the rectangle in it are checked by export_plan — with destinations that cannot fail —, the output size, the ratio and the conversion as for
  * m355_frame_export_resized_rgb, the tensor's layout by tensor_desc_check. */
-int m355_frames_export_tensor(m355_ctx* c, const int* frames, int n, const m355_tensor_desc* e)
+int m355_frames_export_tensor_filtered(m355_ctx* c, const int* frames, int n, const m355_tensor_desc* e, int filter)
 {
   const char* who = "m355_frames_export_tensor";
   if (!c || !frames || !e || n < 1 || n > M355_TENSOR_MAX_FRAMES) return fail(M355_ERR_INVALID, "%s: no context / frames / descriptor, or %d frames are not 1..%d", who, n, M355_TENSOR_MAX_FRAMES);
@@ -879,22 +892,23 @@ int m355_frames_export_tensor(m355_ctx* c, const int* frames, int n, const m355_
     if ((rc = export_plan_rect(c, frames[i], e, e, who, P[i])) != 0) return rc;
     if ((rc = batch_frame_check(who, frames, i, P, e->width == 0)) != 0) return rc;
   }
-  if ((rc = resize_check(who, P, 0, e->out_width, e->out_height)) != 0) return rc;
+  if ((rc = resize_check(who, P, 0, e->out_width, e->out_height, filter)) != 0) return rc;
   ExportTensorArgs a = {};
   if ((rc = tensor_desc_check(who, e, n, P[0].f, a, &eb)) != 0) return rc;
-  plan_geometry(P[0], e->out_width, e->out_height, a, a);
+  plan_geometry(P[0], e->out_width, e->out_height, filter, a, a);
   for (int i = 0; i < n; i++) plan_sources(P[i], a.fr[i]);
   hipSetDevice(c->device);
   const hipStream_t cs = batch_reader_begin(c, P, n, a.fr);
-  m355_launch_export_tensor(a, P[0].f->bpp[0], eb, cs);
+  m355_launch_export_tensor(a, P[0].f->bpp[0], eb, filter, cs);
   HIPCHK(hipGetLastError());
   return batch_reader_end(c, P, n, cs);
 }
+int m355_frames_export_tensor(m355_ctx* c, const int* frames, int n, const m355_tensor_desc* e) { return m355_frames_export_tensor_filtered(c, frames, n, e, M355_FILTER_TRIANGLE); }
 /* A batch of REGIONS, one rectangle per slice, as one float tensor in one launch (k_export_resized_rgb.hip, RR_ROIS): slice i is what
  * m355_frames_export_tensor delivers for frames[i] alone with rois[i] as the rectangle, its columns reversed under M355_ROI_MIRROR.  Every entry's
  * handle and rectangle are checked by export_plan against ITS frame, the ratio per entry; tile width, tiles and units are resize_rgb_tile_w's for the
  * entry's own source size. */
-int m355_frames_export_tensor_rois(m355_ctx* c, const int* frames, const m355_tensor_roi* rois, int n, const m355_tensor_desc* e)
+int m355_frames_export_tensor_rois_filtered(m355_ctx* c, const int* frames, const m355_tensor_roi* rois, int n, const m355_tensor_desc* e, int filter)
 {
   const char* who = "m355_frames_export_tensor_rois";
   if (!c || !frames || !rois || !e || n < 1 || n > M355_TENSOR_MAX_FRAMES)
@@ -908,21 +922,25 @@ int m355_frames_export_tensor_rois(m355_ctx* c, const int* frames, const m355_te
     if ((rc = export_plan_rect(c, frames[i], &rois[i], e, who, P[i])) != 0) return rc;
     if ((rc = batch_frame_check(who, frames, i, P, false)) != 0) return rc;
   }
-  if ((rc = resize_check(who, P, n, e->out_width, e->out_height)) != 0) return rc;
+  if ((rc = resize_check(who, P, n, e->out_width, e->out_height, filter)) != 0) return rc;
   ExportTensorRoisArgs a = {};
   if ((rc = tensor_desc_check(who, e, n, P[0].f, a, &eb)) != 0) return rc;
   for (int i = 0; i < n; i++) {
     ExportTensorRoi& r = a.fr[i];
     plan_sources(P[i], r);
-    plan_geometry(P[i], e->out_width, e->out_height, r, a);
+    plan_geometry(P[i], e->out_width, e->out_height, filter, r, a);
     r.flags = (uint32_t)rois[i].flags;
     if (r.units > a.max_units) a.max_units = r.units;
   }
   hipSetDevice(c->device);
   const hipStream_t cs = batch_reader_begin(c, P, n, a.fr);
-  m355_launch_export_tensor_rois(a, P[0].f->bpp[0], eb, cs);
+  m355_launch_export_tensor_rois(a, P[0].f->bpp[0], eb, filter, cs);
   HIPCHK(hipGetLastError());
   return batch_reader_end(c, P, n, cs);
+}
+int m355_frames_export_tensor_rois(m355_ctx* c, const int* frames, const m355_tensor_roi* rois, int n, const m355_tensor_desc* e)
+{
+  return m355_frames_export_tensor_rois_filtered(c, frames, rois, n, e, M355_FILTER_TRIANGLE);
 }
 /* the host waits until this frame's last export has landed */
 int m355_frame_export_wait(m355_ctx* c, int h)

@@ -28,6 +28,10 @@
   (S32), (T32) 32 DIFFERENT regions of one 1920x1088 frame to 224x224, F16 NCHW — a seeded list (ROI_SEED) that holds both ratio limits (28x28: 8x up,
       1792 columns: 8x down) and regions of two tiles across, printed in the result line: (S32) 32 m355_frames_export_tensor launches with n = 1,
       one per region; (T32) ONE m355_frames_export_tensor_rois of the list, every fourth region mirrored.  The bar is (T32) <= (S32) + the spread of (b)
+  (Q8), (Q32) m355_frames_export_tensor_rois with 8 / 32 regions of 896x896 at (512, 96) of the frames of (z8), (z32) to 224x224, F16 NCHW: ratio
+      exactly 4, the most M355_FILTER_CUBIC takes
+  --filter cubic adds, beside (m), (n), (q), (w), (Q8), (Q32), the same calls through the _filtered entry points with M355_FILTER_CUBIC as (Cm), (Cn),
+      (Cq), (Cw), (CQ8), (CQ32) — 8K to 1080p is ratio exactly 4 — and their ratios to the triangle's rows in the result line; no bar is set for them
 
 and, beside them, m355_measure_copy_rate for the frame's byte count.  Every figure is the median of --iters launches; (b) is measured in
 --rounds separate rounds spread over the run, and the spread of their medians is the margin (c), (d), (g)-(j) and (m)-(p) are held against: a scaled or resized export reads exactly (b)'s source bytes and writes at most a
@@ -67,6 +71,7 @@ def main():
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--out", default=None, help="append the result lines to this file")
+    ap.add_argument("--filter", choices=("triangle", "cubic"), default="triangle", help="cubic: also measure the cubic filter's rows beside the triangle's")
     args = ap.parse_args()
 
     lib = capi.Library()
@@ -120,12 +125,14 @@ def main():
             return lambda: lib.check(lib.lib.m355_frame_export_scaled(ctx.h, frame, ctypes.byref(d), log2_scale))
         return lambda: lib.check(lib.lib.m355_frame_export(ctx.h, frame, ctypes.byref(d)))
 
-    def export_resized(layout, samples, out_size, elem):
+    def export_resized(layout, samples, out_size, elem, filter=0):
         d = capi.ResizeDesc(layout=layout, samples=samples, out_width=out_size[0], out_height=out_size[1])
         w = out_size[0]
         rows = [w * elem, w * elem if layout else w // 2 * elem, w // 2 * elem]
         for k in range(3):
             d.dst[k] = dst[k]; d.pitch[k] = rows[k]
+        if filter:
+            return lambda: lib.check(lib.lib.m355_frame_export_resized_filtered(ctx.h, frame, ctypes.byref(d), filter))
         return lambda: lib.check(lib.lib.m355_frame_export_resized(ctx.h, frame, ctypes.byref(d)))
 
     rgb_dst = [ctx.device_alloc(n, fill=None) for n in (W * 3 * H, W * 2 * H, W * 2 * H)]
@@ -136,10 +143,12 @@ def main():
             d.dst[k] = rgb_dst[k]; d.pitch[k] = W * elem * (1 if layout == capi.RGB_PLANAR else 3)
         return lambda: lib.check(lib.lib.m355_frame_export_rgb(ctx.h, frame, ctypes.byref(d)))
 
-    def export_resized_rgb(layout, samples, out_size, elem):
+    def export_resized_rgb(layout, samples, out_size, elem, filter=0):
         d = capi.ResizeRgbDesc(layout=layout, samples=samples, matrix=capi.MATRIX_BT709, full_range=0, out_width=out_size[0], out_height=out_size[1])
         for k in range(3):
             d.dst[k] = rgb_dst[k]; d.pitch[k] = out_size[0] * elem * (1 if layout == capi.RGB_PLANAR else 3)
+        if filter:
+            return lambda: lib.check(lib.lib.m355_frame_export_resized_rgb_filtered(ctx.h, frame, ctypes.byref(d), filter))
         return lambda: lib.check(lib.lib.m355_frame_export_resized_rgb(ctx.h, frame, ctypes.byref(d)))
 
     # frames of the resized sizes, for the R'G'B' export that the chain ends with (a frame's height is a multiple of 8: 1088 rows, of which 1080)
@@ -154,7 +163,7 @@ def main():
             d.dst[k] = rgb_dst[k]; d.pitch[k] = size[0] * elem * (1 if layout == capi.RGB_PLANAR else 3)
         return lambda: lib.check(lib.lib.m355_frame_export_rgb(ctx.h, small[size], ctypes.byref(d)))
 
-    def export_tensor(frames, layout, dtype, samples, out_size, rect=None):
+    def export_tensor(frames, layout, dtype, samples, out_size, rect=None, filter=0):
         eb = 4 if dtype == capi.TENSOR_F32 else 2
         ow, oh = out_size
         row = ow * eb * (3 if layout == capi.TENSOR_NHWC else 1)
@@ -169,9 +178,11 @@ def main():
         assert len(frames) * 3 * ow * oh * eb <= W * 3 * H
         d.dst = rgb_dst[0]
         arr = (ctypes.c_int * len(frames))(*frames)
+        if filter:
+            return lambda: lib.check(lib.lib.m355_frames_export_tensor_filtered(ctx.h, arr, len(frames), ctypes.byref(d), filter))
         return lambda: lib.check(lib.lib.m355_frames_export_tensor(ctx.h, arr, len(frames), ctypes.byref(d)))
 
-    def export_tensor_rois(frames, rois, layout, dtype, samples, out_size):
+    def export_tensor_rois(frames, rois, layout, dtype, samples, out_size, filter=0):
         eb = 4 if dtype == capi.TENSOR_F32 else 2
         ow, oh = out_size
         row = ow * eb * (3 if layout == capi.TENSOR_NHWC else 1)
@@ -185,6 +196,8 @@ def main():
         d.dst = rgb_dst[0]
         arr = (ctypes.c_int * len(frames))(*frames)
         ra = (capi.TensorRoi * len(rois))(*[capi.TensorRoi(*r) for r in rois])
+        if filter:
+            return lambda: lib.check(lib.lib.m355_frames_export_tensor_rois_filtered(ctx.h, arr, ra, len(frames), ctypes.byref(d), filter))
         return lambda: lib.check(lib.lib.m355_frames_export_tensor_rois(ctx.h, arr, ra, len(frames), ctypes.byref(d)))
 
     # the frames of the batch rows: 32 frames of 1920x1088, of which the centre square goes to a model's 224x224
@@ -192,6 +205,7 @@ def main():
     for k, f in enumerate(batch):
         ctx.frame_fill(f, 300 + 20 * k, 400 + 10 * k)
     SQUARE = (420, 0, 1080, 1080)
+    SQUARE4 = (512, 96, 896, 896)      # to 224x224: ratio exactly 4
 
     def singles(n):
         descs = []
@@ -269,6 +283,25 @@ def main():
         "T32_tensor_rois_f16_nchw_224_32_regions": export_tensor_rois([batch[0]] * 32, [r + (capi.ROI_MIRROR if k % 4 == 3 else 0,) for k, r in enumerate(roi_list)],
                                                                       capi.TENSOR_NCHW, capi.TENSOR_F16, capi.RGB_U8, (224, 224)),
     }
+    def region_rows(prefix, filter):
+        return {"%sQ%d_tensor_rois_f16_nchw_224_of_896_batch%d" % (prefix, n, n):
+                export_tensor_rois(batch[:n], [SQUARE4 + (0,)] * n, capi.TENSOR_NCHW, capi.TENSOR_F16, capi.RGB_U8, (224, 224), filter) for n in (8, 32)}
+
+    variants.update(region_rows("", 0))
+    cubic_of = {}                      # a cubic row -> the triangle's row of the same call
+    if args.filter == "cubic":
+        C = capi.FILTER_CUBIC
+        variants.update({
+            "Cm_cubic_resized_native_planar_1080p": export_resized(capi.EXPORT_PLANAR, capi.EXPORT_NATIVE, (1920, 1080), 2, C),
+            "Cn_cubic_resized_u8_semiplanar_1080p": export_resized(capi.EXPORT_SEMIPLANAR, capi.EXPORT_U8, (1920, 1080), 1, C),
+            "Cq_cubic_resized_rgb_u8_packed_1080p": export_resized_rgb(capi.RGB_PACKED, capi.RGB_U8, (1920, 1080), 1, C),
+            "Cw_cubic_tensor_f16_nhwc_1080p": export_tensor([frame], capi.TENSOR_NHWC, capi.TENSOR_F16, capi.RGB_U16, (1920, 1080), None, C),
+        })
+        variants.update(region_rows("C", C))
+        for n in variants:
+            if n[0] == "C":
+                key = n[1:].split("_")[0] + "_"
+                cubic_of[n] = [t for t in variants if t.startswith(key)][0]
     scaled = [n for n in variants if n[0] in "ghijmnop"]
     ms = {n: [] for n in variants}
     for _ in range(args.rounds):
@@ -303,6 +336,7 @@ def main():
                         "R32_over_z32": res["R32_tensor_rois_f16_nchw_224_batch32"] / res["z32_tensor_f16_nchw_224_batch32"],
                         "T32_over_S32": res["T32_tensor_rois_f16_nchw_224_32_regions"] / res["S32_tensor_f16_nchw_224_x32_regions"],
                         "us_per_region": {n: 1e3 * res[n] / 32 for n in ("S32_tensor_f16_nchw_224_x32_regions", "T32_tensor_rois_f16_nchw_224_32_regions")}},
+        "cubic_over_triangle": {n: res[n] / res[t] for n, t in cubic_of.items()},
         "copy_rate_GBps_same_bytes": ctx.measure_copy_rate(frame_bytes, 9),
         "bars": {"b_le_a": res["b_native_planar"] <= res["a_memcpy2d_x3"],
                  "c_le_b_plus_spread": res["c_msb16_semiplanar_crop8"] <= res["b_native_planar"] + spread,
