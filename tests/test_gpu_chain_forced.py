@@ -135,10 +135,12 @@ elif what == "suites":
     from test_deblock_smooth import CHAIN_CASES as SMOOTH_CASES   # smoothed references: the luma deblocking filters at work (10 / 12 / 15 / 16 bits)
     from deblock_content import make_smooth_case
     cases += [("smooth %%d" %% i, c) for i, c in enumerate(SMOOTH_CASES)]
+    from test_residual_inrange import CHAIN_CASES as INRANGE_CASES, make_inrange_case   # attenuated levels: residuals that reach the picture unclipped (8 / 10 4:4:4 / 12 bits)
+    cases += [("inrange %%d" %% i, c) for i, c in enumerate(INRANGE_CASES)]
     n = 0
     for name, case in cases:
         try:
-            pic, refs = (make_smooth_case if name.startswith("smooth") else make_case)(**case)
+            pic, refs = (make_smooth_case if name.startswith("smooth") else make_inrange_case if name.startswith("inrange") else make_case)(**case)
         except RuntimeError:
             continue
         want = oracle_decode(Oracle(o), pic, refs)
