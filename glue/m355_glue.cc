@@ -86,7 +86,7 @@ namespace {
   X(m355_last_error) X(m355_device_count) X(m355_create) X(m355_destroy) X(m355_frame_create) X(m355_frame_destroy) \
   X(m355_frame_upload) X(m355_frame_download) X(m355_submit_picture) X(m355_wait) X(m355_set_pipeline_depth) \
   X(m355_host_alloc) X(m355_host_free) X(m355_frame_hash) X(m355_arena_begin) X(m355_last_serial) X(m355_decode_status) \
-  X(m355_frame_download_async) X(m355_frame_download_wait) X(m355_frame_export) X(m355_frame_export_scaled) X(m355_frame_export_rgb) X(m355_frame_export_resized_filtered) X(m355_frame_export_resized_rgb_filtered) X(m355_frames_export_tensor_filtered) X(m355_frames_export_tensor_rois_filtered) X(m355_frame_export_order) \
+  X(m355_frame_download_async) X(m355_frame_download_wait) X(m355_frame_export) X(m355_frame_export_scaled) X(m355_frame_export_rgb_opts) X(m355_frame_export_resized_opts) X(m355_frame_export_resized_rgb_opts) X(m355_frames_export_tensor_opts) X(m355_frames_export_tensor_rois_opts) X(m355_frame_export_order) \
   X(m355_group_create) X(m355_group_destroy) X(m355_group_decode) X(m355_picture_upload) X(m355_picture_replace) X(m355_shard_owner_of_tile) \
   X(m355_picture_arena_begin) X(m355_frame_hash_async) X(m355_frame_hash_result) X(m355_frame_measure_async) X(m355_frame_measure_result)
 
@@ -1744,13 +1744,37 @@ LIBDE265_API int m355_glue_export_image_scaled(const struct de265_image* img, in
   if (log2_scale < 0 || log2_scale > 3) return M355_ERR_INVALID;
   return export_image(img, layout, samples, rect, log2_scale, dst, pitch, consumer_stream);
 }
+/* The chroma sample location type the picture's stream signals: its SPS' vui.chroma_sample_loc_type_top_field (0..5), or 0 where the SPS has no VUI,
+ * the VUI no chroma_loc_info, or the picture is not 4:2:0 (the standard defines the field for 4:2:0 alone). */
+LIBDE265_API int m355_glue_image_chroma_loc(const struct de265_image* img)
+{
+  if (!img || !img->has_sps()) return 0;
+  const seq_parameter_set& sps = img->get_sps();
+  if (sps.chroma_format_idc != 1 || !sps.vui_parameters_present_flag || !sps.vui.chroma_loc_info_present_flag) return 0;
+  return sps.vui.chroma_sample_loc_type_top_field;
+}
+/* the options of a _sited call: chroma_loc = -1 is what the stream signals (of imgs[0] for a batch, like matrix = -1), where the bottom-sited types 4
+ * and 5 are M355_ERR_INVALID like an unmapped matrix; every other value is the backend's to judge */
+static int sited_opts(const de265_image* img, int filter, int chroma_loc, m355_export_opts* o)
+{
+  memset(o, 0, sizeof(*o));
+  if (chroma_loc == -1) {
+    chroma_loc = m355_glue_image_chroma_loc(img);
+    if (chroma_loc > 3) return M355_ERR_INVALID;
+  }
+  o->filter = filter; o->chroma_loc = chroma_loc;
+  return M355_OK;
+}
 /* The picture as R'G'B' (m355_frame_export_rgb: layout / samples = M355_RGB_*, one chroma reconstruction filter, integer-exact), with the waiting
  * behaviour of m355_glue_export_image: the only wait is for the worker to have enqueued the picture.  matrix = M355_MATRIX_*, or -1: what the stream
  * signals (de265_get_image_matrix_coefficients: 1 -> BT.709; 5, 6 -> BT.601; 9 -> BT.2020 non-constant luminance; 2, unspecified -> BT.709; anything
  * else is M355_ERR_INVALID: there is no integer matrix for it here).  full_range = 0 / 1, or -1: de265_get_image_full_range_flag.  PACKED uses dst[0]
- * and pitch[0] only. */
-LIBDE265_API int m355_glue_export_image_rgb(const struct de265_image* img, int layout, int samples, int matrix, int full_range, const int rect[4],
-                                            void* const dst[3], const int64_t pitch[3], void* consumer_stream)
+ * and pitch[0] only.
+ * The _sited form — of this call and of the four below — takes `filter` (M355_FILTER_*; 0 here, where nothing is resized) and `chroma_loc`, the chroma
+ * sample location type 0..3 of m355_export_opts, or -1: what the stream signals (m355_glue_image_chroma_loc; of imgs[0] for a batch; a signalled 4 or 5 is
+ * M355_ERR_INVALID).  The plain and the _filtered forms keep type 0. */
+LIBDE265_API int m355_glue_export_image_rgb_sited(const struct de265_image* img, int layout, int samples, int matrix, int full_range, const int rect[4],
+                                                  void* const dst[3], const int64_t pitch[3], int filter, int chroma_loc, void* consumer_stream)
 {
   Api* A = api();
   if (!A) return M355_ERR_NO_DEVICE;
@@ -1765,6 +1789,8 @@ LIBDE265_API int m355_glue_export_image_rgb(const struct de265_image* img, int l
     else return M355_ERR_INVALID;
   }
   if (full_range == -1) full_range = de265_get_image_full_range_flag(img) ? 1 : 0;
+  m355_export_opts o;
+  if (sited_opts(img, filter, chroma_loc, &o) != M355_OK) return M355_ERR_INVALID;
   wait_submitted(g, img->get_ID());
   std::lock_guard<std::mutex> api_lock(g->api_mu);
   int r[4];
@@ -1775,24 +1801,31 @@ LIBDE265_API int m355_glue_export_image_rgb(const struct de265_image* img, int l
   d.layout = layout; d.samples = samples; d.matrix = matrix; d.full_range = full_range;
   d.x0 = r[0]; d.y0 = r[1]; d.width = r[2]; d.height = r[3];
   for (int c = 0; c < 3; c++) { d.dst[c] = dst[c]; d.pitch[c] = pitch[c]; }
-  int rc = A->m355_frame_export_rgb(g->mctx, frame, &d);
+  int rc = A->m355_frame_export_rgb_opts(g->mctx, frame, &d, &o);
   if (rc == M355_OK) rc = A->m355_frame_export_order(g->mctx, frame, consumer_stream);
   if (rc != M355_OK) g->error = A->m355_last_error();
   return rc;
+}
+LIBDE265_API int m355_glue_export_image_rgb(const struct de265_image* img, int layout, int samples, int matrix, int full_range, const int rect[4],
+                                            void* const dst[3], const int64_t pitch[3], void* consumer_stream)
+{
+  return m355_glue_export_image_rgb_sited(img, layout, samples, matrix, full_range, rect, dst, pitch, M355_FILTER_TRIANGLE, 0, consumer_stream);
 }
 /* The picture RESIZED on the device to out_size = {out_width, out_height} luma samples (m355_frame_export_resized: one separable triangle filter,
  * antialiased when downscaling, integer-exact; layout / samples = M355_EXPORT_*), with the waiting behaviour of m355_glue_export_image: the only wait
  * is for the worker to have enqueued the picture.  rect = the SOURCE rectangle, NULL: the image's conformance window.  The _filtered form takes the
  * filter, M355_FILTER_TRIANGLE or M355_FILTER_CUBIC (Catmull-Rom, at most 4x down), as do the _filtered forms of the three calls below; each plain form
  * is its _filtered form with M355_FILTER_TRIANGLE. */
-LIBDE265_API int m355_glue_export_image_resized_filtered(const struct de265_image* img, int layout, int samples, const int rect[4], const int out_size[2],
-                                                         void* const dst[3], const int64_t pitch[3], int filter, void* consumer_stream)
+LIBDE265_API int m355_glue_export_image_resized_sited(const struct de265_image* img, int layout, int samples, const int rect[4], const int out_size[2],
+                                                      void* const dst[3], const int64_t pitch[3], int filter, int chroma_loc, void* consumer_stream)
 {
   Api* A = api();
   if (!A) return M355_ERR_NO_DEVICE;
   if (!img || !img->decctx || !out_size || !dst || !pitch) return M355_ERR_INVALID;
   Glue* g = glue_of(img->decctx);
   if (!g || g->n_ranks > 1) return M355_ERR_INVALID;
+  m355_export_opts o;
+  if (sited_opts(img, filter, chroma_loc, &o) != M355_OK) return M355_ERR_INVALID;
   wait_submitted(g, img->get_ID());
   std::lock_guard<std::mutex> api_lock(g->api_mu);
   int r[4];
@@ -1804,10 +1837,15 @@ LIBDE265_API int m355_glue_export_image_resized_filtered(const struct de265_imag
   d.x0 = r[0]; d.y0 = r[1]; d.width = r[2]; d.height = r[3];
   d.out_width = out_size[0]; d.out_height = out_size[1];
   for (int c = 0; c < 3; c++) { d.dst[c] = dst[c]; d.pitch[c] = pitch[c]; }
-  int rc = A->m355_frame_export_resized_filtered(g->mctx, frame, &d, filter);
+  int rc = A->m355_frame_export_resized_opts(g->mctx, frame, &d, &o);
   if (rc == M355_OK) rc = A->m355_frame_export_order(g->mctx, frame, consumer_stream);
   if (rc != M355_OK) g->error = A->m355_last_error();
   return rc;
+}
+LIBDE265_API int m355_glue_export_image_resized_filtered(const struct de265_image* img, int layout, int samples, const int rect[4], const int out_size[2],
+                                                         void* const dst[3], const int64_t pitch[3], int filter, void* consumer_stream)
+{
+  return m355_glue_export_image_resized_sited(img, layout, samples, rect, out_size, dst, pitch, filter, 0, consumer_stream);
 }
 LIBDE265_API int m355_glue_export_image_resized(const struct de265_image* img, int layout, int samples, const int rect[4], const int out_size[2],
                                                 void* const dst[3], const int64_t pitch[3], void* consumer_stream)
@@ -1818,8 +1856,9 @@ LIBDE265_API int m355_glue_export_image_resized(const struct de265_image* img, i
  * resized export and the R'G'B' export of the resized picture composed, integer-exact), with the waiting behaviour of m355_glue_export_image.  The frame,
  * the rectangle (NULL: the image's conformance window), matrix == -1 and full_range == -1 are resolved as in m355_glue_export_image_rgb, out_size as in
  * m355_glue_export_image_resized.  PACKED uses dst[0] and pitch[0] only. */
-LIBDE265_API int m355_glue_export_image_resized_rgb_filtered(const struct de265_image* img, int layout, int samples, int matrix, int full_range, const int rect[4],
-                                                             const int out_size[2], void* const dst[3], const int64_t pitch[3], int filter, void* consumer_stream)
+LIBDE265_API int m355_glue_export_image_resized_rgb_sited(const struct de265_image* img, int layout, int samples, int matrix, int full_range, const int rect[4],
+                                                          const int out_size[2], void* const dst[3], const int64_t pitch[3], int filter, int chroma_loc,
+                                                          void* consumer_stream)
 {
   Api* A = api();
   if (!A) return M355_ERR_NO_DEVICE;
@@ -1834,6 +1873,8 @@ LIBDE265_API int m355_glue_export_image_resized_rgb_filtered(const struct de265_
     else return M355_ERR_INVALID;
   }
   if (full_range == -1) full_range = de265_get_image_full_range_flag(img) ? 1 : 0;
+  m355_export_opts o;
+  if (sited_opts(img, filter, chroma_loc, &o) != M355_OK) return M355_ERR_INVALID;
   wait_submitted(g, img->get_ID());
   std::lock_guard<std::mutex> api_lock(g->api_mu);
   int r[4];
@@ -1845,10 +1886,15 @@ LIBDE265_API int m355_glue_export_image_resized_rgb_filtered(const struct de265_
   d.x0 = r[0]; d.y0 = r[1]; d.width = r[2]; d.height = r[3];
   d.out_width = out_size[0]; d.out_height = out_size[1];
   for (int c = 0; c < 3; c++) { d.dst[c] = dst[c]; d.pitch[c] = pitch[c]; }
-  int rc = A->m355_frame_export_resized_rgb_filtered(g->mctx, frame, &d, filter);
+  int rc = A->m355_frame_export_resized_rgb_opts(g->mctx, frame, &d, &o);
   if (rc == M355_OK) rc = A->m355_frame_export_order(g->mctx, frame, consumer_stream);
   if (rc != M355_OK) g->error = A->m355_last_error();
   return rc;
+}
+LIBDE265_API int m355_glue_export_image_resized_rgb_filtered(const struct de265_image* img, int layout, int samples, int matrix, int full_range, const int rect[4],
+                                                             const int out_size[2], void* const dst[3], const int64_t pitch[3], int filter, void* consumer_stream)
+{
+  return m355_glue_export_image_resized_rgb_sited(img, layout, samples, matrix, full_range, rect, out_size, dst, pitch, filter, 0, consumer_stream);
 }
 LIBDE265_API int m355_glue_export_image_resized_rgb(const struct de265_image* img, int layout, int samples, int matrix, int full_range, const int rect[4],
                                                     const int out_size[2], void* const dst[3], const int64_t pitch[3], void* consumer_stream)
@@ -1860,9 +1906,9 @@ LIBDE265_API int m355_glue_export_image_resized_rgb(const struct de265_image* im
  * BYTES as in m355_tensor_desc), with the waiting behaviour of m355_glue_export_image: the only wait is for the worker to have enqueued every picture of
  * the batch, and the consumer's stream is ordered behind the one launch.  The rectangle (NULL: the conformance window of imgs[0]), matrix == -1 and
  * full_range == -1 are resolved from imgs[0] as in m355_glue_export_image_resized_rgb and hold for every picture; out_size as there. */
-LIBDE265_API int m355_glue_export_images_tensor_filtered(const struct de265_image* const* imgs, int n, int layout, int dtype, int samples, int matrix, int full_range,
-                                                         const int rect[4], const int out_size[2], const float scale[3], const float bias[3], void* dst,
-                                                         int64_t stride_n, int64_t stride_c, int64_t stride_h, int filter, void* consumer_stream)
+LIBDE265_API int m355_glue_export_images_tensor_sited(const struct de265_image* const* imgs, int n, int layout, int dtype, int samples, int matrix, int full_range,
+                                                      const int rect[4], const int out_size[2], const float scale[3], const float bias[3], void* dst,
+                                                      int64_t stride_n, int64_t stride_c, int64_t stride_h, int filter, int chroma_loc, void* consumer_stream)
 {
   Api* A = api();
   if (!A) return M355_ERR_NO_DEVICE;
@@ -1878,6 +1924,8 @@ LIBDE265_API int m355_glue_export_images_tensor_filtered(const struct de265_imag
     else return M355_ERR_INVALID;
   }
   if (full_range == -1) full_range = de265_get_image_full_range_flag(imgs[0]) ? 1 : 0;
+  m355_export_opts o;
+  if (sited_opts(imgs[0], filter, chroma_loc, &o) != M355_OK) return M355_ERR_INVALID;
   for (int i = 0; i < n; i++) wait_submitted(g, imgs[i]->get_ID());
   std::lock_guard<std::mutex> api_lock(g->api_mu);
   int r[4], frames[M355_TENSOR_MAX_FRAMES];
@@ -1892,10 +1940,17 @@ LIBDE265_API int m355_glue_export_images_tensor_filtered(const struct de265_imag
   d.out_width = out_size[0]; d.out_height = out_size[1];
   for (int c = 0; c < 3; c++) { d.scale[c] = scale[c]; d.bias[c] = bias[c]; }
   d.dst = dst; d.stride_n = stride_n; d.stride_c = stride_c; d.stride_h = stride_h;
-  int rc = A->m355_frames_export_tensor_filtered(g->mctx, frames, n, &d, filter);
+  int rc = A->m355_frames_export_tensor_opts(g->mctx, frames, n, &d, &o);
   if (rc == M355_OK) rc = A->m355_frame_export_order(g->mctx, frames[0], consumer_stream);
   if (rc != M355_OK) g->error = A->m355_last_error();
   return rc;
+}
+LIBDE265_API int m355_glue_export_images_tensor_filtered(const struct de265_image* const* imgs, int n, int layout, int dtype, int samples, int matrix, int full_range,
+                                                         const int rect[4], const int out_size[2], const float scale[3], const float bias[3], void* dst,
+                                                         int64_t stride_n, int64_t stride_c, int64_t stride_h, int filter, void* consumer_stream)
+{
+  return m355_glue_export_images_tensor_sited(imgs, n, layout, dtype, samples, matrix, full_range, rect, out_size, scale, bias, dst, stride_n, stride_c, stride_h,
+                                              filter, 0, consumer_stream);
 }
 LIBDE265_API int m355_glue_export_images_tensor(const struct de265_image* const* imgs, int n, int layout, int dtype, int samples, int matrix, int full_range,
                                                 const int rect[4], const int out_size[2], const float scale[3], const float bias[3], void* dst,
@@ -1908,9 +1963,9 @@ LIBDE265_API int m355_glue_export_images_tensor(const struct de265_image* const*
  * waiting and ordering of m355_glue_export_images_tensor.  rois: n x {x0, y0, width, height, flags} in luma samples of the coded picture, flags = 0 or
  * M355_ROI_MIRROR; an entry whose four rectangle fields are 0 means THAT picture's conformance window.  Every rectangle is resolved against ITS
  * picture; the same picture may appear any number of times.  matrix == -1 and full_range == -1 are resolved from imgs[0]. */
-LIBDE265_API int m355_glue_export_images_tensor_rois_filtered(const struct de265_image* const* imgs, const int (*rois)[5], int n, int layout, int dtype, int samples,
-                                                              int matrix, int full_range, const int out_size[2], const float scale[3], const float bias[3], void* dst,
-                                                              int64_t stride_n, int64_t stride_c, int64_t stride_h, int filter, void* consumer_stream)
+LIBDE265_API int m355_glue_export_images_tensor_rois_sited(const struct de265_image* const* imgs, const int (*rois)[5], int n, int layout, int dtype, int samples,
+                                                           int matrix, int full_range, const int out_size[2], const float scale[3], const float bias[3], void* dst,
+                                                           int64_t stride_n, int64_t stride_c, int64_t stride_h, int filter, int chroma_loc, void* consumer_stream)
 {
   Api* A = api();
   if (!A) return M355_ERR_NO_DEVICE;
@@ -1926,6 +1981,8 @@ LIBDE265_API int m355_glue_export_images_tensor_rois_filtered(const struct de265
     else return M355_ERR_INVALID;
   }
   if (full_range == -1) full_range = de265_get_image_full_range_flag(imgs[0]) ? 1 : 0;
+  m355_export_opts o;
+  if (sited_opts(imgs[0], filter, chroma_loc, &o) != M355_OK) return M355_ERR_INVALID;
   for (int i = 0; i < n; i++) wait_submitted(g, imgs[i]->get_ID());
   std::lock_guard<std::mutex> api_lock(g->api_mu);
   int frames[M355_TENSOR_MAX_FRAMES];
@@ -1944,10 +2001,17 @@ LIBDE265_API int m355_glue_export_images_tensor_rois_filtered(const struct de265
   d.out_width = out_size[0]; d.out_height = out_size[1];
   for (int c = 0; c < 3; c++) { d.scale[c] = scale[c]; d.bias[c] = bias[c]; }
   d.dst = dst; d.stride_n = stride_n; d.stride_c = stride_c; d.stride_h = stride_h;
-  int rc = A->m355_frames_export_tensor_rois_filtered(g->mctx, frames, rr, n, &d, filter);
+  int rc = A->m355_frames_export_tensor_rois_opts(g->mctx, frames, rr, n, &d, &o);
   if (rc == M355_OK) rc = A->m355_frame_export_order(g->mctx, frames[0], consumer_stream);
   if (rc != M355_OK) g->error = A->m355_last_error();
   return rc;
+}
+LIBDE265_API int m355_glue_export_images_tensor_rois_filtered(const struct de265_image* const* imgs, const int (*rois)[5], int n, int layout, int dtype, int samples,
+                                                              int matrix, int full_range, const int out_size[2], const float scale[3], const float bias[3], void* dst,
+                                                              int64_t stride_n, int64_t stride_c, int64_t stride_h, int filter, void* consumer_stream)
+{
+  return m355_glue_export_images_tensor_rois_sited(imgs, rois, n, layout, dtype, samples, matrix, full_range, out_size, scale, bias, dst, stride_n, stride_c, stride_h,
+                                                   filter, 0, consumer_stream);
 }
 LIBDE265_API int m355_glue_export_images_tensor_rois(const struct de265_image* const* imgs, const int (*rois)[5], int n, int layout, int dtype, int samples,
                                                      int matrix, int full_range, const int out_size[2], const float scale[3], const float bias[3], void* dst,

@@ -480,7 +480,7 @@ M355_API int   m355_frame_export_scaled(m355_ctx* ctx, int frame, const m355_exp
  * (within 0.5 + 0.5 (|y| + |u| + |v|) / 2^F output LSB of the real-valued conversion: below 1 LSB for 8..12-bit sources, up to 3.2 at 16 -> U16).
  * A monochrome frame has u = v = 0.  M355_RGB_U16 is full scale 0..65535, not the frame's bit depth MSB-aligned.
  * Cb', Cr' are the chroma samples AT THE LUMA POSITION.  There is ONE reconstruction filter, the bilinear one for chroma sample location type 0
- * (horizontally co-sited, vertically midway); no other siting is offered.  It works on the FRAME's chroma plane C of CW x CH samples with indices
+ * (horizontally co-sited, vertically midway); types 1..3 are chosen through m355_export_opts (the _opts entry points below).  It works on the FRAME's chroma plane C of CW x CH samples with indices
  * clamped to that plane — samples outside the rectangle but inside the frame are read as they are, so an exported rectangle equals the same
  * rectangle cut from a whole-frame export — and its result is a sample of the chroma bit depth, rounded BEFORE the matrix.  For luma (X, Y):
  *   4:4:4  C[Y][X]
@@ -524,7 +524,7 @@ M355_API int   m355_rgb_coefficients(int matrix, int full_range, int bit_depth_l
  * equals the resize of a frame that holds only that rectangle — and coefficients that land on the same index are added.  m355_resize_taps returns this
  * folded row, which is contiguous (libde265_amd/csrc/resize_taps.h: the one definition, which the kernel calls too).
  * Grids: luma and every vertical axis are centre-aligned; the horizontal chroma axis of 4:2:0 and 4:2:2 is co-sited (chroma sample location type 0,
- * the siting m355_frame_export_rgb assumes), so resized chroma stays where type 0 puts it.  No other siting is offered.
+ * the siting m355_frame_export_rgb assumes), so resized chroma stays where type 0 puts it.  Types 1..3: m355_export_opts below.
  * Per plane, bd its bit depth, S the rectangle's samples, qy_j / qx_i the rows of the vertical / horizontal axis: the VERTICAL pass first, ONE
  * rounding to an 18-bit intermediate, then the horizontal pass, everything unsigned:
  *   u(x, j) = sum_k qy_j[k] S[k][x]                      < 2^(bd + 14)
@@ -565,8 +565,8 @@ M355_API int   m355_rgb_coefficients(int matrix, int full_range, int bit_depth_l
  * An unknown filter is M355_ERR_INVALID (m355_resize_taps_filtered: < 0); m355_frames_export_tensor_rois_filtered checks the filter's ratio and size
  * limit per entry.
  * Not offered: Lanczos, a selectable a, the cubic filter beyond 4x down (32 coefficients per row), sizes above 16384 per axis with it, a filter per
- * slice, ratios beyond 8, another chroma siting, resizing into a
- * frame of the decoder; and of m355_frame_export_resized_rgb and m355_frames_export_tensor below: BGR order, another chroma siting, chroma resampled
+ * slice, ratios beyond 8, the bottom-sited chroma sample location types 4 and 5, a siting per slice, siting for 4:2:2, resizing into a
+ * frame of the decoder; and of m355_frame_export_resized_rgb and m355_frames_export_tensor below: BGR order, chroma resampled
  * straight onto the luma grid (it is resized on its own grid, then reconstructed), per-frame output sizes within a batch (per-frame rectangles:
  * m355_frames_export_tensor_rois, which rejects a region smaller than an eighth of the output and does not clamp it), writing into a tensor owned by
  * a second HIP runtime without m355_frame_export_order. */
@@ -689,7 +689,7 @@ M355_API int   m355_tensor_element(uint32_t v, float scale, float bias, int dtyp
  * Ordering, the gate, sharded contexts, m355_frame_export_wait and m355_frame_export_order: exactly those of m355_frames_export_tensor — one mark kept
  * by every distinct frame, each slice behind its own frame's gate: the slices of a frame behind a rejected decode are skipped, the others written.
  * Not offered: an output size per slice, a filter per slice, ratios beyond 8 (M355_FILTER_CUBIC: beyond 4 down), regions off the chroma grid,
- * another siting. */
+ * a siting per slice. */
 #define M355_ROI_MIRROR 1                /* flags: the slice's columns in reverse order */
 typedef struct m355_tensor_roi {
   int32_t x0, y0, width, height;         /* source luma rectangle in frames[i], as in m355_export_desc (width == 0: the whole frame) */
@@ -699,6 +699,44 @@ M355_API int   m355_frames_export_tensor_rois(m355_ctx* ctx, const int* frames, 
                                               const m355_tensor_desc* desc);   /* asynchronous */
 M355_API int   m355_frames_export_tensor_rois_filtered(m355_ctx* ctx, const int* frames, const m355_tensor_roi* rois, int n,
                                                        const m355_tensor_desc* desc, int filter);   /* M355_FILTER_*; its limits per entry */
+/* OPTIONS of the five exports that bring chroma to the luma grid or resize it: the filter of the _filtered entry points and the CHROMA SAMPLE
+ * LOCATION TYPE of the 4:2:0 source (H.265 Figure E.1, chroma_sample_loc_type; HDR / BT.2020 streams signal type 2).  One structure, so that the
+ * chain of suffixes ends here: every plain and every _filtered call IS its _opts call with chroma_loc = 0 (and the triangle filter), and a NULL
+ * `opts` means {M355_FILTER_TRIANGLE, 0}.  chroma_loc = 0..3 is two independent positions:
+ *                 horizontal hx = chroma_loc & 1                          vertical vy = chroma_loc >> 1
+ *   0   LEFT:   chroma column i sits on luma column 2i                    MID: chroma row j sits midway between luma rows 2j and 2j + 1
+ *   1   CENTRE: chroma column i sits midway between columns 2i, 2i + 1    TOP: chroma row j sits on luma row 2j
+ * so type 0 = (LEFT, MID), 1 = (CENTRE, MID), 2 = (LEFT, TOP), 3 = (CENTRE, TOP).
+ * The RECONSTRUCTION FILTER for luma (X, Y) is bilinear with weights in quarters per axis and ONE rounding.  i = X >> 1, j = Y >> 1, indices
+ * clamped to the plane the filter reads (the FRAME's in m355_frame_export_rgb, the RESIZED plane in the composed exports), {index: weight}:
+ *   LEFT    X even {i: 4}             X odd {i: 2, i + 1: 2}          MID   Y even {j: 3, j - 1: 1}     Y odd {j: 3, j + 1: 1}
+ *   CENTRE  X even {i: 3, i - 1: 1}   X odd {i: 3, i + 1: 1}          TOP   Y even {j: 4}               Y odd {j: 2, j + 1: 2}
+ *   C' = (sum over rows and columns of wv * wh * C[row][col] + 8) >> 4        a sample of the chroma bit depth, rounded BEFORE the matrix; the
+ *                                                                             sum stays below 2^20
+ * For type 0 this is the filter stated at m355_frame_export_rgb bit for bit: (4 T + 8) >> 4 = (T + 2) >> 2 and (2 T + 2 T' + 8) >> 4 =
+ * (T + T' + 4) >> 3 with T = 3 C[j] + C[jn].
+ * RESIZE GRIDS keep the siting: planes are still resized each on its own grid; the horizontal chroma axis is co-sited iff LEFT (CENTRE: centre-
+ * aligned), the vertical chroma axis is co-sited iff TOP (MID: centre-aligned); a co-sited axis has C = 2 i sn, the rows m355_resize_taps returns for
+ * cosited = 1.  Luma, both filters, every rounding, the clamp to the rectangle and all limits are unchanged, and the composed exports remain
+ * compositions: resize every plane on these grids, reconstruct on the resized chroma with the filter above, then the matrix / m355_tensor_element.
+ * For a batch chroma_loc is the batch's, like the filter.
+ * M355_ERR_INVALID (nothing is enqueued, no destination byte written) beyond what the plain call rejects: a non-zero `reserved` entry; an unknown
+ * filter, and for m355_frame_export_rgb_opts, which resizes nothing, any filter but 0; chroma_loc outside 0..3 (4 and 5, bottom-sited, included);
+ * a non-zero chroma_loc for a frame that is not 4:2:0 (the standard defines the field for 4:2:0 alone).
+ * m355_frame_export, m355_frame_export_scaled (a box average without siting correction), the hashes, the measurements and the downloads deliver
+ * samples on their own grids and know no siting.
+ * Not offered: the bottom-sited types 4 and 5, a siting per slice, siting for 4:2:2. */
+typedef struct m355_export_opts {
+  int32_t filter;                        /* M355_FILTER_* */
+  int32_t chroma_loc;                    /* chroma sample location type of the 4:2:0 source, 0..3 */
+  int32_t reserved[6];                   /* 0 */
+} m355_export_opts;                      /* (32 bytes) */
+M355_API int   m355_frame_export_rgb_opts(m355_ctx* ctx, int frame, const m355_rgb_desc* desc, const m355_export_opts* opts);
+M355_API int   m355_frame_export_resized_opts(m355_ctx* ctx, int frame, const m355_resize_desc* desc, const m355_export_opts* opts);
+M355_API int   m355_frame_export_resized_rgb_opts(m355_ctx* ctx, int frame, const m355_resize_rgb_desc* desc, const m355_export_opts* opts);
+M355_API int   m355_frames_export_tensor_opts(m355_ctx* ctx, const int* frames, int n, const m355_tensor_desc* desc, const m355_export_opts* opts);
+M355_API int   m355_frames_export_tensor_rois_opts(m355_ctx* ctx, const int* frames, const m355_tensor_roi* rois, int n,
+                                                   const m355_tensor_desc* desc, const m355_export_opts* opts);
 M355_API int   m355_frame_export_wait(m355_ctx* ctx, int frame);
 M355_API int   m355_frame_export_order(m355_ctx* ctx, int frame, void* consumer_hipStream);
 /* Device memory for export destinations and blocking copies out of / into it, for applications (and the tests) that keep a second HIP

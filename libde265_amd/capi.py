@@ -106,6 +106,11 @@ class TensorRoi(ctypes.Structure):
     _fields_ = [("x0", ctypes.c_int32), ("y0", ctypes.c_int32), ("width", ctypes.c_int32), ("height", ctypes.c_int32), ("flags", ctypes.c_int32)]
 
 
+class ExportOpts(ctypes.Structure):
+    """m355_export_opts: the filter (FILTER_*) and the chroma sample location type 0..3 of a 4:2:0 source; reserved stays 0"""
+    _fields_ = [("filter", ctypes.c_int32), ("chroma_loc", ctypes.c_int32), ("reserved", ctypes.c_int32 * 6)]
+
+
 class RgbCoeffs(ctypes.Structure):
     """m355_rgb_coeffs (include/de265_mi355x.h)"""
     _fields_ = [(n, ctypes.c_int32) for n in ("F", "y0", "c0", "cy", "crv", "cgu", "cgv", "cbu")]
@@ -192,6 +197,13 @@ class Library:
             L.m355_frames_export_tensor_filtered.argtypes = [vp, ctypes.POINTER(i), i, ctypes.POINTER(TensorDesc), i]
             L.m355_frames_export_tensor_rois_filtered.argtypes = [vp, ctypes.POINTER(i), ctypes.POINTER(TensorRoi), i, ctypes.POINTER(TensorDesc), i]
             L.m355_resize_taps_filtered.argtypes = [i, i, i, i, i, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]
+        if hasattr(L, "m355_frame_export_rgb_opts"):    # (absent from older builds loaded through M355_LIB for an A/B)
+            po = ctypes.POINTER(ExportOpts)
+            L.m355_frame_export_rgb_opts.argtypes = [vp, i, ctypes.POINTER(RgbDesc), po]
+            L.m355_frame_export_resized_opts.argtypes = [vp, i, ctypes.POINTER(ResizeDesc), po]
+            L.m355_frame_export_resized_rgb_opts.argtypes = [vp, i, ctypes.POINTER(ResizeRgbDesc), po]
+            L.m355_frames_export_tensor_opts.argtypes = [vp, ctypes.POINTER(i), i, ctypes.POINTER(TensorDesc), po]
+            L.m355_frames_export_tensor_rois_opts.argtypes = [vp, ctypes.POINTER(i), ctypes.POINTER(TensorRoi), i, ctypes.POINTER(TensorDesc), po]
         L.m355_host_alloc.argtypes = [ctypes.c_size_t]
         L.m355_host_alloc.restype = vp
         L.m355_host_free.argtypes = [vp]
@@ -479,11 +491,14 @@ class Context:
         """row i of one axis of the resize filter (m355_resize_taps) -> (first source index, [coefficients]), or None for arguments it rejects"""
         return self.L.resize_taps(src_n, dst_n, cosited, i, filter, filtered_entry)
 
-    def frame_export_resized(self, f, layout, samples, out_size, rect=None, host=False, pad=20, filter=0, filtered_entry=False):
+    def frame_export_resized(self, f, layout, samples, out_size, rect=None, host=False, pad=20, filter=0, filtered_entry=False, chroma_loc=0,
+                             opts_entry=False):
         """start m355_frame_export_resized of frame f to out_size = (out_width, out_height) luma samples (rect = the source rectangle (x0, y0, width,
         height) in luma samples, None: the whole frame) into buffers of its own, made as frame_export makes them: every byte holds DEVICE_FILL
         beforehand, the pitch is `pad` bytes larger than the row.  filter = FILTER_*: a filter other than 0, or filtered_entry, goes
-        through m355_frame_export_resized_filtered (so do the three helpers below through theirs).  -> token for frame_export_finish"""
+        through m355_frame_export_resized_filtered (so do the three helpers below through theirs).  chroma_loc = the chroma sample location
+        type: a type other than 0, or opts_entry, goes through m355_frame_export_resized_opts with an ExportOpts of filter and chroma_loc (so do
+        the four helpers below through theirs; opts_entry=None passes a NULL options pointer).  -> token for frame_export_finish"""
         shapes = self.export_shapes(f, layout, samples, (0, 0, out_size[0], out_size[1]))
         desc = ResizeDesc(layout=layout, samples=samples, out_width=out_size[0], out_height=out_size[1])
         if rect is not None:
@@ -501,7 +516,9 @@ class Context:
                     p = self.device_alloc(rows * pitch)
                 bufs.append(p)
                 desc.dst[k] = p; desc.pitch[k] = pitch
-            if filter != 0 or filtered_entry:
+            if chroma_loc != 0 or opts_entry or opts_entry is None:
+                self.L.check(self.L.lib.m355_frame_export_resized_opts(self.h, f, ctypes.byref(desc), self._opts(filter, chroma_loc, opts_entry)))
+            elif filter != 0 or filtered_entry:
                 self.L.check(self.L.lib.m355_frame_export_resized_filtered(self.h, f, ctypes.byref(desc), filter))
             else:
                 self.L.check(self.L.lib.m355_frame_export_resized(self.h, f, ctypes.byref(desc)))
@@ -511,11 +528,16 @@ class Context:
             raise
         return (f, shapes, bufs, [int(desc.pitch[k]) for k in range(len(shapes))], host)
 
+    @staticmethod
+    def _opts(filter, chroma_loc, opts_entry):
+        """the options argument of an _opts entry point: an ExportOpts by reference, or NULL for opts_entry=None"""
+        return None if opts_entry is None else ctypes.byref(ExportOpts(filter=filter, chroma_loc=chroma_loc))
+
     def rgb_coefficients(self, matrix, full_range, bit_depth_luma, bit_depth_chroma, samples):
         """the integers of the R'G'B' conversion (m355_rgb_coefficients) -> dict F, y0, c0, cy, crv, cgu, cgv, cbu"""
         return self.L.rgb_coefficients(matrix, full_range, bit_depth_luma, bit_depth_chroma, samples)
 
-    def frame_export_rgb(self, f, layout, samples, matrix, full_range, rect=None, host=False, pad=20):
+    def frame_export_rgb(self, f, layout, samples, matrix, full_range, rect=None, host=False, pad=20, chroma_loc=0, opts_entry=False):
         """start m355_frame_export_rgb of frame f (rect = (x0, y0, width, height) in luma samples, None: the whole frame) into buffers of its own,
         made as frame_export makes them: every byte holds DEVICE_FILL beforehand, the pitch is `pad` bytes larger than the row.  Packed: one plane
         of 3 * width elements per row; planar: R, G, B.  -> token for frame_export_finish"""
@@ -540,14 +562,18 @@ class Context:
                     p = self.device_alloc(rows * pitch)
                 bufs.append(p)
                 desc.dst[k] = p; desc.pitch[k] = pitch
-            self.L.check(self.L.lib.m355_frame_export_rgb(self.h, f, ctypes.byref(desc)))
+            if chroma_loc != 0 or opts_entry or opts_entry is None:
+                self.L.check(self.L.lib.m355_frame_export_rgb_opts(self.h, f, ctypes.byref(desc), self._opts(0, chroma_loc, opts_entry)))
+            else:
+                self.L.check(self.L.lib.m355_frame_export_rgb(self.h, f, ctypes.byref(desc)))
         except Exception:
             for p in bufs:
                 self.L.lib.m355_host_free(p) if host else self.device_free(p)
             raise
         return (f, shapes, bufs, [int(desc.pitch[k]) for k in range(len(shapes))], host)
 
-    def frame_export_resized_rgb(self, f, layout, samples, matrix, full_range, out_size, rect=None, host=False, pad=20, filter=0, filtered_entry=False):
+    def frame_export_resized_rgb(self, f, layout, samples, matrix, full_range, out_size, rect=None, host=False, pad=20, filter=0, filtered_entry=False,
+                                 chroma_loc=0, opts_entry=False):
         """start m355_frame_export_resized_rgb of frame f to out_size = (out_width, out_height) luma samples (rect = the source rectangle (x0, y0,
         width, height) in luma samples, None: the whole frame) into buffers of its own, made as frame_export_rgb makes them: every byte holds
         DEVICE_FILL beforehand, the pitch is `pad` bytes larger than the row.  Packed: one plane of 3 * out_width elements per row; planar: R, G, B.
@@ -571,7 +597,9 @@ class Context:
                     p = self.device_alloc(rows * pitch)
                 bufs.append(p)
                 desc.dst[k] = p; desc.pitch[k] = pitch
-            if filter != 0 or filtered_entry:
+            if chroma_loc != 0 or opts_entry or opts_entry is None:
+                self.L.check(self.L.lib.m355_frame_export_resized_rgb_opts(self.h, f, ctypes.byref(desc), self._opts(filter, chroma_loc, opts_entry)))
+            elif filter != 0 or filtered_entry:
                 self.L.check(self.L.lib.m355_frame_export_resized_rgb_filtered(self.h, f, ctypes.byref(desc), filter))
             else:
                 self.L.check(self.L.lib.m355_frame_export_resized_rgb(self.h, f, ctypes.byref(desc)))
@@ -586,24 +614,26 @@ class Context:
         return self.L.tensor_element(v, scale, bias, dtype)
 
     def frames_export_tensor(self, frames, layout, dtype, samples, matrix, full_range, out_size, scale, bias, rect=None, host=False, pad=20, filter=0,
-                             filtered_entry=False):
+                             filtered_entry=False, chroma_loc=0, opts_entry=False):
         """start m355_frames_export_tensor of the frames (handles; the same one may repeat) to out_size = (out_width, out_height) luma samples each
         (rect = the source rectangle (x0, y0, width, height) in luma samples, the same in every frame; None: the whole frame) into ONE buffer of its
         own, made as frame_export_resized_rgb makes its buffers: every byte holds DEVICE_FILL beforehand, and every stride is `pad` bytes (a multiple
         of the element size) above the smallest one the call accepts — stride_h above the row, stride_c above a plane, stride_n above a slice.
         scale, bias: three floats each (R, G, B).  -> token for tensor_export_finish"""
         return self._frames_export_tensor(frames, None, layout, dtype, samples, matrix, full_range, out_size, scale, bias, rect, host, pad,
-                                          filter if filter != 0 or filtered_entry else None)
+                                          filter if filter != 0 or filtered_entry else None,
+                                          (filter, chroma_loc, opts_entry) if chroma_loc != 0 or opts_entry or opts_entry is None else None)
 
     def frames_export_tensor_rois(self, frames, rois, layout, dtype, samples, matrix, full_range, out_size, scale, bias, host=False, pad=20, filter=0,
-                                  filtered_entry=False):
+                                  filtered_entry=False, chroma_loc=0, opts_entry=False):
         """start m355_frames_export_tensor_rois: slice i is the rectangle rois[i] = (x0, y0, width, height, flags) of frames[i] (None or width 0: the
         whole of that frame; flags: 0 or ROI_MIRROR), resized to out_size.  The buffer is made as frames_export_tensor makes it: DEVICE_FILL in every
         byte, every stride `pad` bytes above the smallest one the call accepts.  -> token for tensor_export_finish"""
         return self._frames_export_tensor(frames, [r if r is not None else (0, 0, 0, 0, 0) for r in rois], layout, dtype, samples, matrix, full_range,
-                                          out_size, scale, bias, None, host, pad, filter if filter != 0 or filtered_entry else None)
+                                          out_size, scale, bias, None, host, pad, filter if filter != 0 or filtered_entry else None,
+                                          (filter, chroma_loc, opts_entry) if chroma_loc != 0 or opts_entry or opts_entry is None else None)
 
-    def _frames_export_tensor(self, frames, rois, layout, dtype, samples, matrix, full_range, out_size, scale, bias, rect, host, pad, filter=None):
+    def _frames_export_tensor(self, frames, rois, layout, dtype, samples, matrix, full_range, out_size, scale, bias, rect, host, pad, filter=None, opts=None):
         w, h = out_size
         n, eb = len(frames), (4 if dtype == TENSOR_F32 else 2)
         row = w * eb * (3 if layout == TENSOR_NHWC else 1)
@@ -628,14 +658,18 @@ class Context:
         desc.dst = p
         try:
             if rois is None:
-                if filter is not None:
+                if opts is not None:
+                    self.L.check(self.L.lib.m355_frames_export_tensor_opts(self.h, (ctypes.c_int * n)(*frames), n, ctypes.byref(desc), self._opts(*opts)))
+                elif filter is not None:
                     self.L.check(self.L.lib.m355_frames_export_tensor_filtered(self.h, (ctypes.c_int * n)(*frames), n, ctypes.byref(desc), filter))
                 else:
                     self.L.check(self.L.lib.m355_frames_export_tensor(self.h, (ctypes.c_int * n)(*frames), n, ctypes.byref(desc)))
             else:
                 assert len(rois) == n
                 arr = (TensorRoi * n)(*[TensorRoi(*r) for r in rois])
-                if filter is not None:
+                if opts is not None:
+                    self.L.check(self.L.lib.m355_frames_export_tensor_rois_opts(self.h, (ctypes.c_int * n)(*frames), arr, n, ctypes.byref(desc), self._opts(*opts)))
+                elif filter is not None:
                     self.L.check(self.L.lib.m355_frames_export_tensor_rois_filtered(self.h, (ctypes.c_int * n)(*frames), arr, n, ctypes.byref(desc), filter))
                 else:
                     self.L.check(self.L.lib.m355_frames_export_tensor_rois(self.h, (ctypes.c_int * n)(*frames), arr, n, ctypes.byref(desc)))

@@ -317,12 +317,14 @@ struct ExportRgbArgs {
   const uint32_t* timeout;
   uint32_t epoch;
 };
-/* src_bytes / dst_bytes: 1 or 2 per sample / channel; chroma_format: 0..3 */
-void m355_launch_export_rgb(const ExportRgbArgs& a, int src_bytes, int dst_bytes, bool planar, int chroma_format, hipStream_t st);
+/* src_bytes / dst_bytes: 1 or 2 per sample / channel; chroma_format: 0..3; chroma_loc: the chroma sample location type 0..3 of a 4:2:0 frame
+   (m355_export_opts), 0 for every other chroma format — a template parameter of the kernel */
+void m355_launch_export_rgb(const ExportRgbArgs& a, int src_bytes, int dst_bytes, bool planar, int chroma_format, int chroma_loc, hipStream_t st);
 
 /* one m355_frame_export_resized (k_export_resized.hip), planes as in ExportArgs (semi-planar: plane 1 = Cb and Cr, read from src[1] and src[2] and
    stored interleaved).  Plane k maps the rectangle's sn_x[k] x sn_y[k] source samples to dn_x[k] x dn_y[k] output samples; cosited[k]: the
-   horizontal axis is co-sited (4:2:0 / 4:2:2 chroma), every other axis centre-aligned.  A workgroup resizes a tile of tile_w[k] <= M355_RESIZE_TILE_W
+   horizontal axis is co-sited (4:2:0 / 4:2:2 chroma unless the siting is CENTRE), cosited_y[k]: the vertical axis is (4:2:0 chroma sited TOP:
+   m355_export_opts), every other axis centre-aligned.  A workgroup resizes a tile of tile_w[k] <= M355_RESIZE_TILE_W
    output columns x M355_RESIZE_TILE_H output rows: tiles_x[k] = tiles per row of tiles, unit_end[k] = the tiles of planes 0..k.  tshift[k] = bit depth - 4
    (the rounding to the 18-bit intermediate), an output sample is min(clip, ((v >> 1) + (1 << (oshift - 1))) >> oshift) << lshift with
    oshift[k] = 31 - bit depth (U8: 23, clip = 255), lshift[k] = 16 - bit depth for MSB16, else 0.  timeout / epoch: the gate (M355_GATE). */
@@ -332,7 +334,7 @@ struct ExportResizedArgs {
   const uint8_t* src[3];
   uint8_t* dst[3];
   long long src_pitch[3], dst_pitch[3];
-  uint32_t sn_x[3], sn_y[3], dn_x[3], dn_y[3], cosited[3];
+  uint32_t sn_x[3], sn_y[3], dn_x[3], dn_y[3], cosited[3], cosited_y[3];
   uint32_t tile_w[3], tiles_x[3], unit_end[3];
   int32_t tshift[3], oshift[3], lshift[3];
   const uint32_t* timeout;
@@ -344,7 +346,8 @@ void m355_launch_export_resized(const ExportResizedArgs& a, int src_bytes, int d
 /* one m355_frame_export_resized_rgb (k_export_resized_rgb.hip, RR_FRAME).  src[] = the rectangle's first sample of Y, Cb, Cr (the resize clamps to the rectangle),
    pitches in BYTES (src_pitch[0] luma, [1] both chroma planes); dst[0] alone for the packed layout, else R, G, B.  Index 0 of sn / dn is the luma
    grid, 1 the chroma grid (zeros for a monochrome frame): sn_x x sn_y source samples of the rectangle to dn_x x dn_y output samples; the horizontal
-   chroma axis of 4:2:0 / 4:2:2 is co-sited.  A workgroup owns a tile of tile_w <= M355_RESIZE_TILE_W luma output columns (even for 4:2:0 / 4:2:2)
+   chroma axis of 4:2:0 / 4:2:2 is co-sited unless chroma_loc & 1 (CENTRE), the vertical one of 4:2:0 iff chroma_loc >> 1 (TOP): chroma_loc is
+   m355_export_opts' (0 unless 4:2:0), and it selects the reconstruction filter's weights too.  A workgroup owns a tile of tile_w <= M355_RESIZE_TILE_W luma output columns (even for 4:2:0 / 4:2:2)
    x M355_RESIZE_TILE_H rows: tiles_x tiles per row of tiles, units tiles in all.  cf: chroma format 0..3; planar: 0 / 1; bdl / bdc: the bit depths;
    k: the integers of m355_rgb_coefficients.  timeout / epoch: the gate (M355_GATE). */
 struct ExportResizedRgbArgs {
@@ -357,6 +360,7 @@ struct ExportResizedRgbArgs {
   m355_rgb_coeffs k;
   const uint32_t* timeout;
   uint32_t epoch;
+  int32_t chroma_loc;
 };
 /* src_bytes / dst_bytes: 1 or 2 per sample / channel */
 void m355_launch_export_resized_rgb(const ExportResizedRgbArgs& a, int src_bytes, int dst_bytes, int filter, hipStream_t st);
@@ -381,6 +385,7 @@ struct ExportTensorArgs {
   float scale[3], bias[3];
   m355_rgb_coeffs k;
   ExportTensorFrame fr[M355_TENSOR_MAX_FRAMES];
+  int32_t chroma_loc, pad;                /* the batch's siting (ExportResizedRgbArgs); behind the records, whose offsets stay what they were */
 };
 /* src_bytes: 1 or 2 per sample; elem_bytes: 2 (F16 / BF16) or 4 (F32) */
 void m355_launch_export_tensor(const ExportTensorArgs& a, int src_bytes, int elem_bytes, int filter, hipStream_t st);
@@ -409,6 +414,7 @@ struct ExportTensorRoisArgs {
   float scale[3], bias[3];
   m355_rgb_coeffs k;
   ExportTensorRoi fr[M355_TENSOR_MAX_FRAMES];
+  int32_t chroma_loc, pad;                /* the batch's siting, kept out of the slices' records and behind them */
 };
 static_assert(sizeof(ExportTensorRoi) == 88 && sizeof(ExportTensorRoisArgs) <= 4096, "the records of a batch of regions must fit the kernel arguments");
 void m355_launch_export_tensor_rois(const ExportTensorRoisArgs& a, int src_bytes, int elem_bytes, int filter, hipStream_t st);

@@ -4,6 +4,8 @@
  * ratio, coefficients of 14 bits from resize_taps.h — the function m355_resize_taps is —, vertical pass, ONE rounding to an 18-bit intermediate t,
  * horizontal pass, the sample formats of k_export.hip applied to the horizontal sum (one rounding).  Integer-exact.  The filter is a template parameter:
  * M355_FILTER_CUBIC (Catmull-Rom, m355_frame_export_resized_filtered) runs the same procedure in signed arithmetic, as the comment at the template says.
+ * Which axes of a plane are co-sited are two flags per plane of the kernel arguments (cosited, cosited_y: the chroma sample location type of
+ * m355_export_opts), wave-uniform, read where the filter rows are derived.
  *
  * ONE launch covers every plane.  A workgroup of 256 lanes owns a tile of up to 256 output columns x 16 output rows of one plane (of Cb AND Cr for an
  * interleaved plane).  Prologue: lane i derives the horizontal row of output column i into registers (through LDS: the row function indexes its
@@ -77,8 +79,8 @@ __global__ void __launch_bounds__(256) k_export_resized(ExportResizedArgs a)
   }
   if (tid >= 256u - RS_TH && tid - (256u - RS_TH) < nrows) {
     const uint32_t jj = tid - (256u - RS_TH);
-    if constexpr (CUBIC) s_vy[jj][1] = m355_resize_row_cubic(sny, dny, 0, j0 + jj, &s_vy[jj][0], &s_vy[jj][2], 1);
-    else s_vy[jj][1] = m355_resize_row(sny, dny, 0, j0 + jj, &s_vy[jj][0], &s_vy[jj][2], 1);
+    if constexpr (CUBIC) s_vy[jj][1] = m355_resize_row_cubic(sny, dny, (int)M355_EXPORT_SEL(a.cosited_y), j0 + jj, &s_vy[jj][0], &s_vy[jj][2], 1);
+    else s_vy[jj][1] = m355_resize_row(sny, dny, (int)M355_EXPORT_SEL(a.cosited_y), j0 + jj, &s_vy[jj][0], &s_vy[jj][2], 1);
   }
 #pragma unroll
   for (int k = 0; k < M355_RESIZE_MAX_TAPS; k++) hq[k] = tid < ncols ? (unsigned)hrow[k * RS_TW + tid] : 0u;

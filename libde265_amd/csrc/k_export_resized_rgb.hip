@@ -6,7 +6,8 @@
  *   RR_BATCH  n frames, one rectangle, as one float tensor of EB = 2 (F16 / BF16) or 4 (F32) bytes per element (m355_frames_export_tensor);
  *   RR_ROIS   n frames, a rectangle per slice, as one float tensor (m355_frames_export_tensor_rois).
  * No new arithmetic: the filter rows are those of resize_taps.h, the passes those of k_export_resized.hip, the chroma filter and the matrix those of
- * k_export_rgb.hip, the float stage that of tensor_element.h.  The filter (M355_FILTER_TRIANGLE, or M355_FILTER_CUBIC of the _filtered entry points) is a
+ * k_export_rgb.hip — for the chroma sample location types 1..3 of m355_export_opts the template parameter SITED is set and the type is a wave-uniform
+ * kernel argument, which sets which chroma axes are co-sited and the weights of the chroma filter; type 0 runs the instantiations it always ran —, the float stage that of tensor_element.h.  The filter (M355_FILTER_TRIANGLE, or M355_FILTER_CUBIC of the _filtered entry points) is a
  * template parameter of the tile procedure — d_rr_row, d_rr_vertical, d_rr_horizontal — and so of every mode; the cubic passes are those of the cubic
  * k_export_resized: signed, 16 bits of fraction in t, luma and chroma clipped to a sample behind the horizontal pass.
  *
@@ -20,12 +21,13 @@
  *   own inside one row of s_t: a workgroup's time follows its number of passes (each is a chain of load, LDS and barrier latencies), not the work
  *   in them.  Segments share a pass where their spans fit the row of s_t AND their vectors the 256 lanes (a lane with a second vector would load
  *   it behind the first instead of a pass ahead); the host picks the tile width so that they do (runtime.hip resize_rgb_tile_w).
- *   Chroma phase (not for monochrome): the resized chroma columns cc0 = c0 / SubWidthC .. (c0 + ncols - 1) / SubWidthC + 1 (4:4:4: the tile's own
- *   columns) and rows j0 / 2 - 1 .. (j0 + nrows - 1) / 2 + 1 (4:2:0: at most 10; else the tile's own 16), both clamped to the RESIZED plane, are
+ *   Chroma phase (not for monochrome): the resized chroma columns cc0 = c0 / SubWidthC (CENTRE: one more on the left) .. (c0 + ncols - 1) / SubWidthC + 1
+ *   (4:4:4: the tile's own columns; subsampled: at most 128 + 2) and rows j0 / 2 - 1 (TOP: j0 / 2) .. (j0 + nrows - 1) / 2 + 1 (4:2:0: at most 10; else
+ *   the tile's own 16), both clamped to the RESIZED plane, are
  *   produced and kept as NATIVE 16-bit entries in LDS (2 planes x 16 rows x 258 entries): two rows of Cb and of Cr per pass, or one row of both,
  *   or — where not even two spans fit — Cb's rows first, then Cr's.
  *   Luma phase: two output rows per pass where they fit, else one; the horizontal sum is rounded to a sample in a register; the lane's chroma comes
- *   from the LDS tile through the filter of k_export_rgb.hip (T = 3 C[j] + C[jn], even / odd column forms, c0 folded into the rounding constant),
+ *   from the LDS tile through the filter of the header (weights in quarters per axis, (sum + 8) >> 4, c0 folded into the rounding constant),
  *   then the five v_mad_i32_i24 of the matrix, the shift and the clip.
  *   Stores: a lane holds one pixel of each row of the pass; the rows' channels are staged in LDS as EB-byte elements (packed / NHWC: the three of a
  *   pixel side by side; planar / NCHW: three segments) and leave as dwords, a lane per dword of consecutive addresses; only the valid bytes at the
@@ -47,7 +49,7 @@
  *   Mirror (RR_ROIS, M355_ROI_MIRROR) touches the epilogue only: the lane of tile column t stages its pixel at position ncols - 1 - t of the
  *   staged row (the channels of an NHWC pixel keep their order), and the tile's first destination column is out_width - c0 - ncols.
  * Layout, chroma format, F16 against BF16 and U8 against U16 of the tensors' integer stage are wave-uniform run-time switches (kernel arguments in
- * scalar registers): source sample bytes, element bytes, the mode and the filter are the template parameters, twelve instantiations per filter.
+ * scalar registers): source sample bytes, element bytes, the mode, the filter and SITED are the template parameters, twelve instantiations per filter and value of SITED.
  *
  * Reads stay inside the planes' allocations, by the argument of k_export_resized.hip for every plane of every slice: the host admits a frame only
  * if it contains the slice's rectangle (export_plan per frame), whose size is the source size the slice's rows are derived from.  A filter row's
@@ -180,7 +182,7 @@ template <> struct RrArgs<RR_ROIS> { typedef ExportTensorRoisArgs T; };
 #define RR_PITCH(i) ({ uint32_t g_; if constexpr (MODE == RR_FRAME) g_ = (uint32_t)a.src_pitch[i]; else g_ = (uint32_t)a.fr[slice].src_pitch[i]; g_; })
 #define RR_GEOM(field) ({ uint32_t g_; if constexpr (MODE == RR_ROIS) g_ = a.fr[slice].field; else g_ = a.field; g_; })
 
-template <int SB, int EB, int MODE, int FILTER>
+template <int SB, int EB, int MODE, int FILTER, bool SITED>
 __global__ void __launch_bounds__(256) k_export_resized_rgb(typename RrArgs<MODE>::T a)
 {
   constexpr bool CUBIC = FILTER == M355_FILTER_CUBIC;
@@ -211,15 +213,21 @@ __global__ void __launch_bounds__(256) k_export_resized_rgb(typename RrArgs<MODE
   bool planar;                                                  /* planar R'G'B' / NCHW: three staged segments */
   if constexpr (MODE == RR_FRAME) planar = a.planar != 0; else planar = a.nhwc == 0;
   const uint32_t swl = (cf == 1 || cf == 2) ? 1u : 0u, shl = cf == 1 ? 1u : 0u;
+  /* the siting of 4:2:0 chroma (m355_export_opts; the host passes 0 for every other format): horizontally CENTRE, vertically TOP.  SITED = false is
+     type 0, whose statements stand as they were in the other branch of each `if constexpr`: those instantiations are what they were before */
+  bool centre = false, top_sited = false;
+  if constexpr (SITED) { centre = (a.chroma_loc & 1) != 0; top_sited = (a.chroma_loc & 2) != 0; }
   /* the chroma tile: columns cc0 .. cc1 and rows cj0 .. cj1 of the resized chroma planes */
   uint32_t cc0 = 0, ncc = 0, cj0 = 0, ncr = 0;
   if (cf != 0) {
     cc0 = c0 >> swl;
+    if constexpr (SITED) { if (centre && cc0) cc0--; }          /* CENTRE: the left neighbour of the tile's first column */
     uint32_t cc1 = ((c0 + ncols - 1) >> swl) + swl;
     if (cc1 > cdx - 1) cc1 = cdx - 1;
     cj0 = j0;
     uint32_t cj1 = j0 + nrows - 1;
     if (shl) { cj0 = (j0 >> 1) ? (j0 >> 1) - 1 : 0u; cj1 = ((j0 + nrows - 1) >> 1) + 1; }
+    if constexpr (SITED) { if (shl && top_sited) cj0 = j0 >> 1; }   /* (TOP reads no row above j) */
     if (cj1 > cdy - 1) cj1 = cdy - 1;
     ncc = cc1 - cc0 + 1; ncr = cj1 - cj0 + 1;
   }
@@ -228,7 +236,7 @@ __global__ void __launch_bounds__(256) k_export_resized_rgb(typename RrArgs<MODE
   int32_t* hrow = (int32_t*)&s_t[0][0];                        /* coefficient k of lane i at [k * RR_TW + i] */
   int32_t hfirst = 0, cfirst = 0;
   if (tid < ncc) {
-    const int hn = d_rr_row<FILTER>(RR_GEOM(sn_x[1]), cdx, (int)swl, cc0 + tid, &cfirst, hrow + tid, RR_TW);
+    const int hn = d_rr_row<FILTER>(RR_GEOM(sn_x[1]), cdx, SITED && centre ? 0 : (int)swl, cc0 + tid, &cfirst, hrow + tid, RR_TW);
     if (tid == 0) s_span[1][0] = cfirst;
     if (tid == ncc - 1) s_span[1][1] = cfirst + hn - 1;
   }
@@ -238,7 +246,7 @@ __global__ void __launch_bounds__(256) k_export_resized_rgb(typename RrArgs<MODE
   }
   if (tid >= 256u - 2 * RR_TH && tid - (256u - 2 * RR_TH) < ncr) {
     const uint32_t jj = tid - (256u - 2 * RR_TH);
-    s_vy[1][jj][1] = d_rr_row<FILTER>(RR_GEOM(sn_y[1]), cdy, 0, cj0 + jj, &s_vy[1][jj][0], &s_vy[1][jj][2], 1);
+    s_vy[1][jj][1] = d_rr_row<FILTER>(RR_GEOM(sn_y[1]), cdy, SITED && top_sited ? 1 : 0, cj0 + jj, &s_vy[1][jj][0], &s_vy[1][jj][2], 1);
   }
   __syncthreads();
 
@@ -313,11 +321,14 @@ __global__ void __launch_bounds__(256) k_export_resized_rgb(typename RrArgs<MODE
   /* the constants of the launch (scalar): the rounding term and the luma offset in one, c0 folded into the chroma filter's rounding constants */
   const int F = a.k.F, ky = (int)((1u << (F - 1)) - (unsigned)a.k.cy * (unsigned)a.k.y0);
   const int cy = a.k.cy, crv = a.k.crv, ncgu = -a.k.cgu, ncgv = -a.k.cgv, cbu = a.k.cbu, kc0 = a.k.c0;
-  /* this lane's columns of the chroma tile: column i of its pixel and the clamped neighbour to the right */
+  /* this lane's columns of the chroma tile: column i of its pixel and the clamped neighbour to the right.  SITED: the neighbour is to the left for an
+     even luma column under CENTRE (LEFT: none, weight 0), and wh0, 4 - wh0 are the two columns' weights in quarters */
   const uint32_t X = c0 + tid;
   uint32_t ci = 0, cin = 0;
   if (cf != 0 && tid < ncols) {
-    const uint32_t i = X >> swl, in = i + 1 < cdx ? i + 1 : cdx - 1;
+    const uint32_t i = X >> swl;
+    uint32_t in = i + 1 < cdx ? i + 1 : cdx - 1;
+    if constexpr (SITED) { if (centre && !(X & 1u)) in = i ? i - 1 : 0u; }
     ci = i - cc0; cin = swl ? in - cc0 : ci;
   }
   const bool odd = swl && (X & 1u);
@@ -385,7 +396,23 @@ __global__ void __launch_bounds__(256) k_export_resized_rgb(typename RrArgs<MODE
         int r = base, g = base, b = base;
         if (cf != 0) {
           int uv[2];
-          if (cf == 1) {
+          if constexpr (SITED) {
+            /* types 1..3 (4:2:0): the reconstruction filter of the header with weights in quarters per axis, one rounding, c0 folded into its
+               constant.  The rows and their weights are wave-uniform: MID {j: 3, j -+ 1: 1}, TOP {j: 4} on even and {j: 2, j + 1: 2} on odd luma rows */
+            const uint32_t Y = j0 + jj, j = Y >> 1, jn = ((Y & 1u) || top_sited) ? (j + 1 < cdy ? j + 1 : cdy - 1) : (j ? j - 1 : 0u);
+            const uint32_t rj = j - cj0, rn = jn - cj0;
+            const int wv0 = top_sited ? ((Y & 1u) ? 2 : 4) : 3, wh0 = centre ? 3 : (odd ? 2 : 4), wh1 = 4 - wh0;
+            if (wv0 != 4) {
+#pragma unroll
+              for (int c = 0; c < 2; c++) {
+                const int t0 = wv0 * (int)s_c[c][rj][ci] + (4 - wv0) * (int)s_c[c][rn][ci], t1 = wv0 * (int)s_c[c][rj][cin] + (4 - wv0) * (int)s_c[c][rn][cin];
+                uv[c] = (wh0 * t0 + wh1 * t1 + 8 - 16 * kc0) >> 4;
+              }
+            } else {
+#pragma unroll
+              for (int c = 0; c < 2; c++) uv[c] = (4 * (wh0 * (int)s_c[c][rj][ci] + wh1 * (int)s_c[c][rj][cin]) + 8 - 16 * kc0) >> 4;
+            }
+          } else if (cf == 1) {
             const uint32_t Y = j0 + jj, j = Y >> 1, jn = (Y & 1u) ? (j + 1 < cdy ? j + 1 : cdy - 1) : (j ? j - 1 : 0u);
             const uint32_t rj = j - cj0, rn = jn - cj0;
 #pragma unroll
@@ -433,11 +460,14 @@ __global__ void __launch_bounds__(256) k_export_resized_rgb(typename RrArgs<MODE
 #undef RR_LOAD_BATCH
 
 /* src_bytes: 1 or 2 per sample; elem_bytes: 1 or 2 per channel of a frame, 2 or 4 per element of a tensor */
+#define RR_LAUNCH_S(MODE, B0, B1, F, S) \
+  if (src_bytes == 1 && elem_bytes == B0) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_export_resized_rgb<1, B0, MODE, F, S>), g_, block, 0, st, a); \
+  if (src_bytes == 1 && elem_bytes == B1) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_export_resized_rgb<1, B1, MODE, F, S>), g_, block, 0, st, a); \
+  if (src_bytes == 2 && elem_bytes == B0) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_export_resized_rgb<2, B0, MODE, F, S>), g_, block, 0, st, a); \
+  if (src_bytes == 2 && elem_bytes == B1) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_export_resized_rgb<2, B1, MODE, F, S>), g_, block, 0, st, a);
 #define RR_LAUNCH_F(MODE, B0, B1, F) \
-  if (src_bytes == 1 && elem_bytes == B0) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_export_resized_rgb<1, B0, MODE, F>), g_, block, 0, st, a); \
-  if (src_bytes == 1 && elem_bytes == B1) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_export_resized_rgb<1, B1, MODE, F>), g_, block, 0, st, a); \
-  if (src_bytes == 2 && elem_bytes == B0) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_export_resized_rgb<2, B0, MODE, F>), g_, block, 0, st, a); \
-  if (src_bytes == 2 && elem_bytes == B1) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_export_resized_rgb<2, B1, MODE, F>), g_, block, 0, st, a);
+  if (a.chroma_loc != 0) { RR_LAUNCH_S(MODE, B0, B1, F, true) } \
+  else { RR_LAUNCH_S(MODE, B0, B1, F, false) }
 #define RR_LAUNCH(MODE, B0, B1, grid) \
   const dim3 g_ grid, block(256); \
   if (filter == M355_FILTER_CUBIC) { RR_LAUNCH_F(MODE, B0, B1, M355_FILTER_CUBIC) } \
@@ -460,3 +490,4 @@ void m355_launch_export_tensor_rois(const ExportTensorRoisArgs& a, int src_bytes
 }
 #undef RR_LAUNCH
 #undef RR_LAUNCH_F
+#undef RR_LAUNCH_S

@@ -1,7 +1,8 @@
 /*
  * k_export_rgb.hip — a decoded frame (or a rectangle of it) into memory of the caller as R'G'B', packed or planar, 8 or 16 bits per channel
  * (m355_frame_export_rgb, include/de265_mi355x.h).  Integer-exact: chroma is brought to the luma positions by the one bilinear filter of the
- * header (chroma sample location type 0), then the eight integers of m355_rgb_coefficients are applied in signed 32-bit arithmetic.
+ * header (chroma sample location type 0, or the type 1..3 of m355_export_opts: a template parameter), then the eight integers of
+ * m355_rgb_coefficients are applied in signed 32-bit arithmetic.
  *
  * ONE launch per export.  The destination is the larger side of the traffic, so units follow destination rows: a wavefront converts one
  * 64-lane chunk of one row of the rectangle — row and chunk are decided once per wavefront, in scalar registers —, a lane the NP = 16 / SB
@@ -10,6 +11,10 @@
  * first pixel.  A subsampled lane needs NP / 2 chroma samples and the one to their right: the vector holds NP, so the right neighbour comes
  * with the same load — neither a neighbour lane nor an extra load is needed —, and where the frame's plane ends inside the vector the sample
  * of column CW - 1 stands for it (the clamp of the definition).  No LDS, no atomics.
+ * Types 1 and 3 (CENTRE) also need the sample to the LEFT of the lane's first one: the vector then starts at column i0 - 1 — for the lane at
+ * column 0 at i0 itself, where the clamp makes sample 0 its own left neighbour — and holds columns i0 - 1 .. i0 + NP / 2, NP / 2 + 2 <= NP
+ * samples, so it is still one load without a neighbour lane.  Types 2 and 3 (TOP) need chroma row j alone on even luma rows and rows j, j + 1 on odd
+ * ones; the row's parity is wave-uniform, so even rows skip the second load.
  * Arithmetic: 4:2:0 sums T = 3 C[j] + C[jn] and their pairs stay below 2^19 and are kept in 32-bit registers; the offset c0 is folded into
  * the rounding constant of the filter's shift ((T + 2 - 4 c0) >> 2 = ((T + 2) >> 2) - c0, arithmetic shift), so u and v come out signed.
  * The matrix is five v_mad_i32_i24 per pixel (coefficients < 2^23, |u|, |v|, Y < 2^16), a shift and a clip per channel.  The luma offset and
@@ -21,9 +26,9 @@
  * lane here has up to 96), so nothing beyond the exported row is written.
  *
  * No out-of-bounds read.  Every load is 16 bytes from a sample INSIDE a row of the frame's plane: luma column x0 + p0 < W of row y0 + row <
- * H; chroma column i0 = (x0 + p0) / SubWidthC <= CW - 1 of a row clamped to 0 .. CH - 1.  Rows are padded to 128 bytes and a plane's
- * allocation ends with a 256-byte tail (runtime_internal.h frame_alloc), so even the vector of the last sample of the last row ends inside
- * the allocation — half the span k_export.hip argues for.  Bytes of a vector beyond column CW - 1 (padding, or the next row's start) are
+ * H; chroma column i0 = (x0 + p0) / SubWidthC <= CW - 1 — CENTRE: column max(i0 - 1, 0), which is no less inside the row — of a row clamped to
+ * 0 .. CH - 1 (TOP: row min(j + 1, CH - 1)).  Rows are padded to 128 bytes and a plane's allocation ends with a 256-byte tail
+ * (runtime_internal.h frame_alloc), so even the vector of the last sample of the last row ends inside the allocation — half the span k_export.hip argues for.  Bytes of a vector beyond column CW - 1 (padding, or the next row's start) are
  * loaded and never used: every use is indexed through the clamp.
  * Roofline: traffic (every luma byte read once, every chroma row once or twice, every destination byte written once) against ~40 VALU
  * issues per pixel — profiles/export_rgb_bench.txt.
@@ -45,13 +50,48 @@ template <int SB> __device__ __forceinline__ int d_rgb_sample(const unsigned* w,
 
 /* the NP chroma samples of one plane at the lane's luma positions, minus c0.  r0 / r1: the vectors of chroma rows j / jn (4:2:0; else r0 only),
    last = CW - 1 - i0 >= 0: the index inside the vector of the plane's last column */
-template <int SB, int CF>
-__device__ __forceinline__ void d_rgb_chroma(const unsigned* r0, const unsigned* r1, int last, int c0, int* out)
+template <int SB, int CF, int LOC>
+__device__ __forceinline__ void d_rgb_chroma(const unsigned* r0, const unsigned* r1, int last, int c0, int* out, bool yodd, bool lead)
 {
   constexpr int NP = 16 / SB, NC = NP / 2;
   if (CF == 3) {
 #pragma unroll
     for (int k = 0; k < NP; k++) out[k] = d_rgb_sample<SB>(r0, k) - c0;
+    return;
+  }
+  if constexpr (LOC != 0) {
+    /* chroma sample location types 1..3 (4:2:0 only): the vertical sums T in quarters — MID 3 C[j] + C[jn], TOP 4 C[j] on an even luma row (yodd,
+       wave-uniform: a wave is one row) and 2 C[j] + 2 C[j + 1] on an odd one —, then LEFT as type 0, or CENTRE {i: 3, i -+ 1: 1} with one
+       rounding, (sum + 8) >> 4, c0 folded into the constant.  CENTRE: the vectors start at column i0 - 1 (lead) or, for the lane at column 0, at
+       i0 = 0, where the clamp makes sample 0 its own left neighbour: s[m] is column max(i0 - 1 + m, 0), m = 0 .. NC + 1 <= NP - 1 */
+    constexpr bool CENTRE = (LOC & 1) != 0, TOP = (LOC >> 1) != 0;
+    constexpr int NT = NC + 1 + (CENTRE ? 1 : 0);
+    int t[NT];
+    if (TOP && !yodd) {
+#pragma unroll
+      for (int k = 0; k < NT; k++) t[k] = 4 * d_rgb_sample<SB>(r0, k);
+    } else {
+#pragma unroll
+      for (int k = 0; k < NT; k++) t[k] = TOP ? 2 * (d_rgb_sample<SB>(r0, k) + d_rgb_sample<SB>(r1, k)) : 3 * d_rgb_sample<SB>(r0, k) + d_rgb_sample<SB>(r1, k);
+    }
+    if (!CENTRE) {
+#pragma unroll
+      for (int k = 0; k < NC; k++) {
+        const int tn = k < last ? t[k + 1] : t[k];
+        out[2 * k] = (t[k] + 2 - 4 * c0) >> 2;
+        out[2 * k + 1] = (t[k] + tn + 4 - 8 * c0) >> 3;
+      }
+    } else {
+      int s[NT];
+#pragma unroll
+      for (int m = 0; m < NT; m++) s[m] = lead ? t[m] : t[m ? m - 1 : 0];
+#pragma unroll
+      for (int k = 0; k < NC; k++) {
+        const int tr = k < last ? s[k + 2] : s[k + 1];            /* column min(i + 1, CW - 1) */
+        out[2 * k] = (3 * s[k + 1] + s[k] + 8 - 16 * c0) >> 4;
+        out[2 * k + 1] = (3 * s[k + 1] + tr + 8 - 16 * c0) >> 4;
+      }
+    }
     return;
   }
   int t[NC + 1];
@@ -97,7 +137,7 @@ template <int ND> __device__ __forceinline__ void d_rgb_store(M355_GLOBAL uint8_
   }
 }
 
-template <int SB, int DB, int PLANAR, int CF>
+template <int SB, int DB, int PLANAR, int CF, int LOC>
 __global__ void __launch_bounds__(256) k_export_rgb(ExportRgbArgs a)
 {
   M355_GATE(a);
@@ -113,19 +153,26 @@ __global__ void __launch_bounds__(256) k_export_rgb(ExportRgbArgs a)
   unsigned ry[4], rc[2][2][4];
   d_ldg16((const M355_GLOBAL uint8_t*)a.src[0] + (size_t)Y * a.src_pitch[0] + (size_t)X0 * SB, ry);
   int last = 0;
+  bool lead = false;                                            /* CENTRE: the chroma vectors start one column before i0 */
+  bool yodd = false;                                            /* TOP: an odd luma row (wave-uniform: a wave is one row) */
+  if constexpr ((LOC >> 1) != 0) yodd = (Y & 1u) != 0;
   if (CF != 0) {
     const uint32_t i0 = CF == 3 ? X0 : X0 >> 1;
     uint32_t j = Y, jn = Y;
     if (CF == 1) {
       j = Y >> 1;
-      jn = (Y & 1u) ? (j + 1 < a.ch ? j + 1 : a.ch - 1) : (j ? j - 1 : 0u);
+      if constexpr ((LOC >> 1) != 0) jn = j + 1 < a.ch ? j + 1 : a.ch - 1;   /* TOP: row j + 1, read on odd rows only */
+      else jn = (Y & 1u) ? (j + 1 < a.ch ? j + 1 : a.ch - 1) : (j ? j - 1 : 0u);
     }
     last = (int)(a.cw - 1u - i0);
+    uint32_t is = i0;
+    if constexpr ((LOC & 1) != 0) { lead = i0 != 0u; is = lead ? i0 - 1u : 0u; }
 #pragma unroll
     for (int c = 0; c < 2; c++) {
-      const M355_GLOBAL uint8_t* s = (const M355_GLOBAL uint8_t*)a.src[1 + c] + (size_t)i0 * SB;
+      const M355_GLOBAL uint8_t* s = (const M355_GLOBAL uint8_t*)a.src[1 + c] + (size_t)is * SB;
       d_ldg16(s + (size_t)j * a.src_pitch[1], rc[c][0]);
-      if (CF == 1) d_ldg16(s + (size_t)jn * a.src_pitch[1], rc[c][1]);
+      if constexpr ((LOC >> 1) != 0) { if (yodd) d_ldg16(s + (size_t)jn * a.src_pitch[1], rc[c][1]); }
+      else if (CF == 1) d_ldg16(s + (size_t)jn * a.src_pitch[1], rc[c][1]);
     }
   }
   /* the constants of the launch (scalar): the rounding term and the luma offset in one */
@@ -133,8 +180,8 @@ __global__ void __launch_bounds__(256) k_export_rgb(ExportRgbArgs a)
   const int cy = a.k.cy, crv = a.k.crv, ncgu = -a.k.cgu, ncgv = -a.k.cgv, cbu = a.k.cbu;
   int u[NP], v[NP];
   if (CF != 0) {
-    d_rgb_chroma<SB, CF>(rc[0][0], rc[0][1], last, a.k.c0, u);
-    d_rgb_chroma<SB, CF>(rc[1][0], rc[1][1], last, a.k.c0, v);
+    d_rgb_chroma<SB, CF, LOC>(rc[0][0], rc[0][1], last, a.k.c0, u, yodd, lead);
+    d_rgb_chroma<SB, CF, LOC>(rc[1][0], rc[1][1], last, a.k.c0, v, yodd, lead);
   }
   unsigned e[3][NP];
 #pragma unroll
@@ -168,18 +215,23 @@ __global__ void __launch_bounds__(256) k_export_rgb(ExportRgbArgs a)
   }
 }
 
-void m355_launch_export_rgb(const ExportRgbArgs& a, int src_bytes, int dst_bytes, bool planar, int chroma_format, hipStream_t st)
+void m355_launch_export_rgb(const ExportRgbArgs& a, int src_bytes, int dst_bytes, bool planar, int chroma_format, int chroma_loc, hipStream_t st)
 {
   if (!a.units) return;
   const dim3 grid((a.units + 3) / 4), block(256);
-#define M355_EXPORT_RGB_CF(SB, DB, PL, CF) \
-  if (chroma_format == CF) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_export_rgb<SB, DB, PL, CF>), grid, block, 0, st, a);
+  const int loc = chroma_format == 1 ? chroma_loc : 0;          /* (the siting is 4:2:0's alone) */
+#define M355_EXPORT_RGB_CF(SB, DB, PL, CF, LOC) \
+  if (chroma_format == CF && loc == LOC) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_export_rgb<SB, DB, PL, CF, LOC>), grid, block, 0, st, a);
+#define M355_EXPORT_RGB_PL(SB, DB, PL) \
+  M355_EXPORT_RGB_CF(SB, DB, PL, 0, 0) M355_EXPORT_RGB_CF(SB, DB, PL, 1, 0) M355_EXPORT_RGB_CF(SB, DB, PL, 2, 0) M355_EXPORT_RGB_CF(SB, DB, PL, 3, 0) \
+  M355_EXPORT_RGB_CF(SB, DB, PL, 1, 1) M355_EXPORT_RGB_CF(SB, DB, PL, 1, 2) M355_EXPORT_RGB_CF(SB, DB, PL, 1, 3)
 #define M355_EXPORT_RGB_CASE(SB, DB) \
   if (src_bytes == SB && dst_bytes == DB) { \
-    if (planar) { M355_EXPORT_RGB_CF(SB, DB, 1, 0) M355_EXPORT_RGB_CF(SB, DB, 1, 1) M355_EXPORT_RGB_CF(SB, DB, 1, 2) M355_EXPORT_RGB_CF(SB, DB, 1, 3) } \
-    else { M355_EXPORT_RGB_CF(SB, DB, 0, 0) M355_EXPORT_RGB_CF(SB, DB, 0, 1) M355_EXPORT_RGB_CF(SB, DB, 0, 2) M355_EXPORT_RGB_CF(SB, DB, 0, 3) } \
+    if (planar) { M355_EXPORT_RGB_PL(SB, DB, 1) } \
+    else { M355_EXPORT_RGB_PL(SB, DB, 0) } \
   }
   M355_EXPORT_RGB_CASE(1, 1) M355_EXPORT_RGB_CASE(1, 2) M355_EXPORT_RGB_CASE(2, 1) M355_EXPORT_RGB_CASE(2, 2)
 #undef M355_EXPORT_RGB_CASE
+#undef M355_EXPORT_RGB_PL
 #undef M355_EXPORT_RGB_CF
 }

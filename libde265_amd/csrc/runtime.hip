@@ -613,15 +613,32 @@ int m355_rgb_coefficients(int matrix, int full_range, int bdl, int bdc, int samp
   out->cgv = (int32_t)rdiv(2 * kr * (10000 - kr) * mf, 10000 * kg * cs);
   return M355_OK;
 }
+/* m355_export_opts behind the plan of a frame like f (a batch: frames[0], whose chroma format every frame shares): null = the defaults; the reserved
+ * entries and the chroma sample location type, which is 4:2:0's alone.  The filter is checked where it is used (resize_check); resizes = false: the
+ * call has no filter to choose. */
+static int opts_check(const char* who, const m355_export_opts* o, const Frame* f, bool resizes, m355_export_opts& out)
+{
+  out = m355_export_opts{};
+  if (!o) return M355_OK;
+  for (int i = 0; i < 6; i++) if (o->reserved[i]) return fail(M355_ERR_INVALID, "%s: reserved[%d] of the options is %d, not 0", who, i, o->reserved[i]);
+  if (!resizes && o->filter != M355_FILTER_TRIANGLE) return fail(M355_ERR_INVALID, "%s: filter %d where nothing is resized", who, o->filter);
+  if (o->chroma_loc < 0 || o->chroma_loc > 3) return fail(M355_ERR_INVALID, "%s: chroma sample location type %d is not 0..3", who, o->chroma_loc);
+  if (o->chroma_loc && f->cf != 1) return fail(M355_ERR_INVALID, "%s: chroma sample location type %d for a frame that is not 4:2:0", who, o->chroma_loc);
+  out = *o;
+  return M355_OK;
+}
 /* The frame, or a rectangle of it, as R'G'B' (k_export_rgb.hip): the frame handle and the rectangle are checked by export_plan — as a planar NATIVE
  * export whose destinations cannot fail —, the destinations here.  A reader of the kind RD_EXPORT, like the two above. */
-int m355_frame_export_rgb(m355_ctx* c, int h, const m355_rgb_desc* e)
+int m355_frame_export_rgb_opts(m355_ctx* c, int h, const m355_rgb_desc* e, const m355_export_opts* opts)
 {
   const char* who = "m355_frame_export_rgb";
   ExportPlan P;
   int rc = export_plan_rect(c, h, e, e ? e->dst[0] : nullptr, who, P);
   if (rc) return rc;
   Frame* f = P.f;
+  m355_export_opts o;
+  rc = opts_check(who, opts, f, false, o);
+  if (rc) return rc;
   ExportRgbArgs a = {};
   bool planar = false;
   int db = 1;
@@ -639,10 +656,11 @@ int m355_frame_export_rgb(m355_ctx* c, int h, const m355_rgb_desc* e)
   a.units = a.chunks * a.height;
   hipSetDevice(c->device);
   const hipStream_t cs = reader_begin(c, f, RD_EXPORT, &a.timeout, &a.epoch);
-  m355_launch_export_rgb(a, sb, db, planar, f->cf, cs);
+  m355_launch_export_rgb(a, sb, db, planar, f->cf, o.chroma_loc, cs);
   HIPCHK(hipGetLastError());
   return reader_end(c, f, RD_EXPORT, cs);
 }
+int m355_frame_export_rgb(m355_ctx* c, int h, const m355_rgb_desc* e) { return m355_frame_export_rgb_opts(c, h, e, nullptr); }
 /* row i of one axis of the resize filter (resize_taps.h: the function k_export_resized.hip derives its rows with) */
 int m355_resize_taps_filtered(int filter, int src_n, int dst_n, int cosited, int i, int32_t* first, int32_t coeff[M355_RESIZE_MAX_TAPS])
 {
@@ -689,13 +707,17 @@ static int resize_check(const char* who, const ExportPlan* P, int entries, int o
 /* The frame, or a rectangle of it, resized to out_width x out_height luma samples (k_export_resized.hip): the frame handle, the rectangle, the layout and
  * the samples are checked by export_plan — with destinations that cannot fail, as for the R'G'B' export —, the output size, the ratio and the destinations
  * here.  A reader of the kind RD_EXPORT, like the three above. */
-int m355_frame_export_resized_filtered(m355_ctx* c, int h, const m355_resize_desc* e, int filter)
+int m355_frame_export_resized_opts(m355_ctx* c, int h, const m355_resize_desc* e, const m355_export_opts* opts)
 {
   const char* who = "m355_frame_export_resized";
   ExportPlan P;
   int rc = export_plan_rect(c, h, e, e, who, P, e ? e->layout : 0, e ? e->samples : 0);
   if (rc) return rc;
   Frame* f = P.f;
+  m355_export_opts o;
+  rc = opts_check(who, opts, f, true, o);
+  if (rc) return rc;
+  const int filter = o.filter;
   const int sw = (f->cf == 1 || f->cf == 2) ? 2 : 1, sh = f->cf == 1 ? 2 : 1;
   rc = resize_check(who, &P, 0, e->out_width, e->out_height, filter);
   if (rc) return rc;
@@ -714,7 +736,8 @@ int m355_frame_export_resized_filtered(m355_ctx* c, int h, const m355_resize_des
       a.dst[p] = (uint8_t*)e->dst[p]; a.dst_pitch[p] = e->pitch[p];
       a.src_pitch[p] = q.src_pitch;
       a.sn_x[p] = (uint32_t)q.pw; a.sn_y[p] = (uint32_t)q.ph; a.dn_x[p] = (uint32_t)ow; a.dn_y[p] = (uint32_t)oh;
-      a.cosited[p] = p && sw == 2;
+      a.cosited[p] = p && sw == 2 && !(o.chroma_loc & 1);        /* chroma: horizontally co-sited iff LEFT, vertically iff TOP (4:2:0 only) */
+      a.cosited_y[p] = p && (o.chroma_loc & 2);
       a.tile_w[p] = resize_tile_w(filter, q.pw, ow, q.sb);
       a.tiles_x[p] = ((uint32_t)ow + a.tile_w[p] - 1) / a.tile_w[p];
       a.tshift[p] = q.bd - (cubic ? 2 : 4);
@@ -730,15 +753,24 @@ int m355_frame_export_resized_filtered(m355_ctx* c, int h, const m355_resize_des
   HIPCHK(hipGetLastError());
   return reader_end(c, f, RD_EXPORT, cs);
 }
-int m355_frame_export_resized(m355_ctx* c, int h, const m355_resize_desc* e) { return m355_frame_export_resized_filtered(c, h, e, M355_FILTER_TRIANGLE); }
+extern "C++" {
+/* the options of a _filtered call: that filter, chroma sample location type 0 */
+static m355_export_opts filter_opts(int filter) { m355_export_opts o = {}; o.filter = filter; return o; }
+}
+int m355_frame_export_resized_filtered(m355_ctx* c, int h, const m355_resize_desc* e, int filter)
+{
+  const m355_export_opts o = filter_opts(filter);
+  return m355_frame_export_resized_opts(c, h, e, &o);
+}
+int m355_frame_export_resized(m355_ctx* c, int h, const m355_resize_desc* e) { return m355_frame_export_resized_opts(c, h, e, nullptr); }
 /* The width of k_export_resized_rgb's tiles: a pass of that kernel takes two luma rows, or two rows of Cb and of Cr, where their source vectors fit
  * the workgroup's 256 lanes, and a workgroup's time follows its number of passes — so the widest width (even for 4:2:0 / 4:2:2: a tile's first column
  * is a chroma column) not above resize_tile_w's at which they fit, but at least 64 columns, then the narrowest one with the same number of tiles. */
-static uint32_t resize_rgb_tile_w(int filter, int64_t sn, int64_t dn, int64_t csn, int64_t cdn, int sb, int sw)
+static uint32_t resize_rgb_tile_w(int filter, int64_t sn, int64_t dn, int64_t csn, int64_t cdn, int sb, int sw, int centre)
 {
   const int64_t S = 16 / sb;
   const auto vectors = [&](int64_t w, int64_t s, int64_t d) { return ((w - 1) * s / d + 2 + m355_resize_max_taps_filtered(filter, s, d) + S - 1) / S; };   /* (an upper bound) */
-  const auto fits = [&](int64_t w) { return 2 * vectors(w, sn, dn) <= 256 && (sw != 2 || 4 * vectors(w / 2 + 1, csn, cdn) <= 256); };
+  const auto fits = [&](int64_t w) { return 2 * vectors(w, sn, dn) <= 256 && (sw != 2 || 4 * vectors(w / 2 + 1 + centre, csn, cdn) <= 256); };   /* (CENTRE: a chroma column more) */
   int64_t w = resize_tile_w(filter, sn, dn, sb);
   if (sw == 2) w = w > 2 ? w & ~(int64_t)1 : 2;
   int64_t t = w;
@@ -758,13 +790,13 @@ template <class R> static void plan_sources(const ExportPlan& Q, R& r)
   for (int p = 0; p < Q.np; p++) r.src[p] = Q.p[p].src[0];
   r.src_pitch[0] = Q.p[0].src_pitch; r.src_pitch[1] = Q.np > 1 ? Q.p[1].src_pitch : 0;
 }
-template <class G, class D> static void plan_geometry(const ExportPlan& Q, int ow, int oh, int filter, G& g, D& d)
+template <class G, class D> static void plan_geometry(const ExportPlan& Q, int ow, int oh, int filter, int chroma_loc, G& g, D& d)
 {
   const Frame* f = Q.f;
   const int sw = (f->cf == 1 || f->cf == 2) ? 2 : 1, sh = f->cf == 1 ? 2 : 1;
   g.sn_x[0] = (uint32_t)Q.p[0].pw; g.sn_y[0] = (uint32_t)Q.p[0].ph; d.dn_x[0] = (uint32_t)ow; d.dn_y[0] = (uint32_t)oh;
   if (Q.np > 1) { g.sn_x[1] = (uint32_t)Q.p[1].pw; g.sn_y[1] = (uint32_t)Q.p[1].ph; d.dn_x[1] = (uint32_t)(ow / sw); d.dn_y[1] = (uint32_t)(oh / sh); }
-  g.tile_w = resize_rgb_tile_w(filter, Q.p[0].pw, ow, Q.np > 1 ? Q.p[1].pw : 0, ow / sw, f->bpp[0], sw);
+  g.tile_w = resize_rgb_tile_w(filter, Q.p[0].pw, ow, Q.np > 1 ? Q.p[1].pw : 0, ow / sw, f->bpp[0], sw, chroma_loc & 1);
   g.tiles_x = ((uint32_t)ow + g.tile_w - 1) / g.tile_w;
   g.units = g.tiles_x * (((uint32_t)oh + M355_RESIZE_TILE_H - 1) / M355_RESIZE_TILE_H);
 }
@@ -772,13 +804,17 @@ template <class G, class D> static void plan_geometry(const ExportPlan& Q, int o
 /* The same resize with the R'G'B' conversion of the resized picture behind it, in one launch (k_export_resized_rgb.hip, RR_FRAME): the frame handle and
  * the rectangle are checked by export_plan — with destinations that cannot fail —, the output size and the ratio as for the resized export, the
  * conversion and the destinations as for the R'G'B' export, with the OUTPUT width.  A reader of the kind RD_EXPORT, like the four above. */
-int m355_frame_export_resized_rgb_filtered(m355_ctx* c, int h, const m355_resize_rgb_desc* e, int filter)
+int m355_frame_export_resized_rgb_opts(m355_ctx* c, int h, const m355_resize_rgb_desc* e, const m355_export_opts* opts)
 {
   const char* who = "m355_frame_export_resized_rgb";
   ExportPlan P;
   int rc = export_plan_rect(c, h, e, e, who, P);
   if (rc) return rc;
   Frame* f = P.f;
+  m355_export_opts o;
+  rc = opts_check(who, opts, f, true, o);
+  if (rc) return rc;
+  const int filter = o.filter;
   rc = resize_check(who, &P, 0, e->out_width, e->out_height, filter);
   if (rc) return rc;
   ExportResizedRgbArgs a = {};
@@ -787,15 +823,20 @@ int m355_frame_export_resized_rgb_filtered(m355_ctx* c, int h, const m355_resize
   rc = rgb_desc_check(who, e, f, e->out_width, a, &planar, &db);
   if (rc) return rc;
   plan_sources(P, a);
-  plan_geometry(P, e->out_width, e->out_height, filter, a, a);
-  a.cf = f->cf; a.planar = planar; a.bdl = f->bdl; a.bdc = f->bdc;
+  plan_geometry(P, e->out_width, e->out_height, filter, o.chroma_loc, a, a);
+  a.cf = f->cf; a.planar = planar; a.bdl = f->bdl; a.bdc = f->bdc; a.chroma_loc = o.chroma_loc;
   hipSetDevice(c->device);
   const hipStream_t cs = reader_begin(c, f, RD_EXPORT, &a.timeout, &a.epoch);
   m355_launch_export_resized_rgb(a, f->bpp[0], db, filter, cs);
   HIPCHK(hipGetLastError());
   return reader_end(c, f, RD_EXPORT, cs);
 }
-int m355_frame_export_resized_rgb(m355_ctx* c, int h, const m355_resize_rgb_desc* e) { return m355_frame_export_resized_rgb_filtered(c, h, e, M355_FILTER_TRIANGLE); }
+int m355_frame_export_resized_rgb_filtered(m355_ctx* c, int h, const m355_resize_rgb_desc* e, int filter)
+{
+  const m355_export_opts o = filter_opts(filter);
+  return m355_frame_export_resized_rgb_opts(c, h, e, &o);
+}
+int m355_frame_export_resized_rgb(m355_ctx* c, int h, const m355_resize_rgb_desc* e) { return m355_frame_export_resized_rgb_opts(c, h, e, nullptr); }
 /* the float stage of m355_frames_export_tensor for one value (tensor_element.h: the function the kernel calls) */
 int m355_tensor_element(uint32_t v, float scale, float bias, int dtype, uint32_t* bits)
 {
@@ -882,7 +923,7 @@ static int batch_reader_end(m355_ctx* c, const ExportPlan* P, int n, hipStream_t
 /* A batch of frames resized, converted, normalised and delivered as one float tensor in one launch (k_export_resized_rgb.hip, RR_BATCH).  Every frame's
  * handle and the rectangle in it are checked by export_plan — with destinations that cannot fail —, the output size, the ratio and the conversion as for
  * m355_frame_export_resized_rgb, the tensor's layout by tensor_desc_check. */
-int m355_frames_export_tensor_filtered(m355_ctx* c, const int* frames, int n, const m355_tensor_desc* e, int filter)
+int m355_frames_export_tensor_opts(m355_ctx* c, const int* frames, int n, const m355_tensor_desc* e, const m355_export_opts* opts)
 {
   const char* who = "m355_frames_export_tensor";
   if (!c || !frames || !e || n < 1 || n > M355_TENSOR_MAX_FRAMES) return fail(M355_ERR_INVALID, "%s: no context / frames / descriptor, or %d frames are not 1..%d", who, n, M355_TENSOR_MAX_FRAMES);
@@ -892,10 +933,14 @@ int m355_frames_export_tensor_filtered(m355_ctx* c, const int* frames, int n, co
     if ((rc = export_plan_rect(c, frames[i], e, e, who, P[i])) != 0) return rc;
     if ((rc = batch_frame_check(who, frames, i, P, e->width == 0)) != 0) return rc;
   }
+  m355_export_opts o;
+  if ((rc = opts_check(who, opts, P[0].f, true, o)) != 0) return rc;
+  const int filter = o.filter;
   if ((rc = resize_check(who, P, 0, e->out_width, e->out_height, filter)) != 0) return rc;
   ExportTensorArgs a = {};
   if ((rc = tensor_desc_check(who, e, n, P[0].f, a, &eb)) != 0) return rc;
-  plan_geometry(P[0], e->out_width, e->out_height, filter, a, a);
+  plan_geometry(P[0], e->out_width, e->out_height, filter, o.chroma_loc, a, a);
+  a.chroma_loc = o.chroma_loc;
   for (int i = 0; i < n; i++) plan_sources(P[i], a.fr[i]);
   hipSetDevice(c->device);
   const hipStream_t cs = batch_reader_begin(c, P, n, a.fr);
@@ -903,12 +948,17 @@ int m355_frames_export_tensor_filtered(m355_ctx* c, const int* frames, int n, co
   HIPCHK(hipGetLastError());
   return batch_reader_end(c, P, n, cs);
 }
-int m355_frames_export_tensor(m355_ctx* c, const int* frames, int n, const m355_tensor_desc* e) { return m355_frames_export_tensor_filtered(c, frames, n, e, M355_FILTER_TRIANGLE); }
+int m355_frames_export_tensor_filtered(m355_ctx* c, const int* frames, int n, const m355_tensor_desc* e, int filter)
+{
+  const m355_export_opts o = filter_opts(filter);
+  return m355_frames_export_tensor_opts(c, frames, n, e, &o);
+}
+int m355_frames_export_tensor(m355_ctx* c, const int* frames, int n, const m355_tensor_desc* e) { return m355_frames_export_tensor_opts(c, frames, n, e, nullptr); }
 /* A batch of REGIONS, one rectangle per slice, as one float tensor in one launch (k_export_resized_rgb.hip, RR_ROIS): slice i is what
  * m355_frames_export_tensor delivers for frames[i] alone with rois[i] as the rectangle, its columns reversed under M355_ROI_MIRROR.  Every entry's
  * handle and rectangle are checked by export_plan against ITS frame, the ratio per entry; tile width, tiles and units are resize_rgb_tile_w's for the
  * entry's own source size. */
-int m355_frames_export_tensor_rois_filtered(m355_ctx* c, const int* frames, const m355_tensor_roi* rois, int n, const m355_tensor_desc* e, int filter)
+int m355_frames_export_tensor_rois_opts(m355_ctx* c, const int* frames, const m355_tensor_roi* rois, int n, const m355_tensor_desc* e, const m355_export_opts* opts)
 {
   const char* who = "m355_frames_export_tensor_rois";
   if (!c || !frames || !rois || !e || n < 1 || n > M355_TENSOR_MAX_FRAMES)
@@ -922,13 +972,17 @@ int m355_frames_export_tensor_rois_filtered(m355_ctx* c, const int* frames, cons
     if ((rc = export_plan_rect(c, frames[i], &rois[i], e, who, P[i])) != 0) return rc;
     if ((rc = batch_frame_check(who, frames, i, P, false)) != 0) return rc;
   }
+  m355_export_opts o;
+  if ((rc = opts_check(who, opts, P[0].f, true, o)) != 0) return rc;
+  const int filter = o.filter;
   if ((rc = resize_check(who, P, n, e->out_width, e->out_height, filter)) != 0) return rc;
   ExportTensorRoisArgs a = {};
   if ((rc = tensor_desc_check(who, e, n, P[0].f, a, &eb)) != 0) return rc;
+  a.chroma_loc = o.chroma_loc;
   for (int i = 0; i < n; i++) {
     ExportTensorRoi& r = a.fr[i];
     plan_sources(P[i], r);
-    plan_geometry(P[i], e->out_width, e->out_height, filter, r, a);
+    plan_geometry(P[i], e->out_width, e->out_height, filter, o.chroma_loc, r, a);
     r.flags = (uint32_t)rois[i].flags;
     if (r.units > a.max_units) a.max_units = r.units;
   }
@@ -938,9 +992,14 @@ int m355_frames_export_tensor_rois_filtered(m355_ctx* c, const int* frames, cons
   HIPCHK(hipGetLastError());
   return batch_reader_end(c, P, n, cs);
 }
+int m355_frames_export_tensor_rois_filtered(m355_ctx* c, const int* frames, const m355_tensor_roi* rois, int n, const m355_tensor_desc* e, int filter)
+{
+  const m355_export_opts o = filter_opts(filter);
+  return m355_frames_export_tensor_rois_opts(c, frames, rois, n, e, &o);
+}
 int m355_frames_export_tensor_rois(m355_ctx* c, const int* frames, const m355_tensor_roi* rois, int n, const m355_tensor_desc* e)
 {
-  return m355_frames_export_tensor_rois_filtered(c, frames, rois, n, e, M355_FILTER_TRIANGLE);
+  return m355_frames_export_tensor_rois_opts(c, frames, rois, n, e, nullptr);
 }
 /* the host waits until this frame's last export has landed */
 int m355_frame_export_wait(m355_ctx* c, int h)

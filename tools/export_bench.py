@@ -32,6 +32,8 @@
       exactly 4, the most M355_FILTER_CUBIC takes
   --filter cubic adds, beside (m), (n), (q), (w), (Q8), (Q32), the same calls through the _filtered entry points with M355_FILTER_CUBIC as (Cm), (Cn),
       (Cq), (Cw), (CQ8), (CQ32) — 8K to 1080p is ratio exactly 4 — and their ratios to the triangle's rows in the result line; no bar is set for them
+  --chroma-loc N (1, 2 or 3; may repeat) adds, beside (k), (l), (m), (n), (q), (w), (Q8), (Q32), the same calls through the _opts entry points with
+      chroma sample location type N as (LNk), (LNl), (LNm), (LNn), (LNq), (LNw), (LNQ8), (LNQ32), and their ratios to the type-0 rows; no bar is set
 
 and, beside them, m355_measure_copy_rate for the frame's byte count.  Every figure is the median of --iters launches; (b) is measured in
 --rounds separate rounds spread over the run, and the spread of their medians is the margin (c), (d), (g)-(j) and (m)-(p) are held against: a scaled or resized export reads exactly (b)'s source bytes and writes at most a
@@ -72,6 +74,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--out", default=None, help="append the result lines to this file")
     ap.add_argument("--filter", choices=("triangle", "cubic"), default="triangle", help="cubic: also measure the cubic filter's rows beside the triangle's")
+    ap.add_argument("--chroma-loc", type=int, choices=(1, 2, 3), action="append", default=[],
+                    help="also measure this chroma sample location type's rows beside the type-0 rows (may repeat)")
     args = ap.parse_args()
 
     lib = capi.Library()
@@ -125,28 +129,40 @@ def main():
             return lambda: lib.check(lib.lib.m355_frame_export_scaled(ctx.h, frame, ctypes.byref(d), log2_scale))
         return lambda: lib.check(lib.lib.m355_frame_export(ctx.h, frame, ctypes.byref(d)))
 
-    def export_resized(layout, samples, out_size, elem, filter=0):
+    def opts_of(filter, loc):
+        return capi.ExportOpts(filter=filter, chroma_loc=loc)
+
+    def export_resized(layout, samples, out_size, elem, filter=0, loc=0):
         d = capi.ResizeDesc(layout=layout, samples=samples, out_width=out_size[0], out_height=out_size[1])
         w = out_size[0]
         rows = [w * elem, w * elem if layout else w // 2 * elem, w // 2 * elem]
         for k in range(3):
             d.dst[k] = dst[k]; d.pitch[k] = rows[k]
+        if loc:
+            o = opts_of(filter, loc)
+            return lambda: lib.check(lib.lib.m355_frame_export_resized_opts(ctx.h, frame, ctypes.byref(d), ctypes.byref(o)))
         if filter:
             return lambda: lib.check(lib.lib.m355_frame_export_resized_filtered(ctx.h, frame, ctypes.byref(d), filter))
         return lambda: lib.check(lib.lib.m355_frame_export_resized(ctx.h, frame, ctypes.byref(d)))
 
     rgb_dst = [ctx.device_alloc(n, fill=None) for n in (W * 3 * H, W * 2 * H, W * 2 * H)]
 
-    def export_rgb(layout, samples, elem):
+    def export_rgb(layout, samples, elem, loc=0):
         d = capi.RgbDesc(layout=layout, samples=samples, matrix=capi.MATRIX_BT709, full_range=0)
         for k in range(3):
             d.dst[k] = rgb_dst[k]; d.pitch[k] = W * elem * (1 if layout == capi.RGB_PLANAR else 3)
+        if loc:
+            o = opts_of(0, loc)
+            return lambda: lib.check(lib.lib.m355_frame_export_rgb_opts(ctx.h, frame, ctypes.byref(d), ctypes.byref(o)))
         return lambda: lib.check(lib.lib.m355_frame_export_rgb(ctx.h, frame, ctypes.byref(d)))
 
-    def export_resized_rgb(layout, samples, out_size, elem, filter=0):
+    def export_resized_rgb(layout, samples, out_size, elem, filter=0, loc=0):
         d = capi.ResizeRgbDesc(layout=layout, samples=samples, matrix=capi.MATRIX_BT709, full_range=0, out_width=out_size[0], out_height=out_size[1])
         for k in range(3):
             d.dst[k] = rgb_dst[k]; d.pitch[k] = out_size[0] * elem * (1 if layout == capi.RGB_PLANAR else 3)
+        if loc:
+            o = opts_of(filter, loc)
+            return lambda: lib.check(lib.lib.m355_frame_export_resized_rgb_opts(ctx.h, frame, ctypes.byref(d), ctypes.byref(o)))
         if filter:
             return lambda: lib.check(lib.lib.m355_frame_export_resized_rgb_filtered(ctx.h, frame, ctypes.byref(d), filter))
         return lambda: lib.check(lib.lib.m355_frame_export_resized_rgb(ctx.h, frame, ctypes.byref(d)))
@@ -163,7 +179,7 @@ def main():
             d.dst[k] = rgb_dst[k]; d.pitch[k] = size[0] * elem * (1 if layout == capi.RGB_PLANAR else 3)
         return lambda: lib.check(lib.lib.m355_frame_export_rgb(ctx.h, small[size], ctypes.byref(d)))
 
-    def export_tensor(frames, layout, dtype, samples, out_size, rect=None, filter=0):
+    def export_tensor(frames, layout, dtype, samples, out_size, rect=None, filter=0, loc=0):
         eb = 4 if dtype == capi.TENSOR_F32 else 2
         ow, oh = out_size
         row = ow * eb * (3 if layout == capi.TENSOR_NHWC else 1)
@@ -178,11 +194,14 @@ def main():
         assert len(frames) * 3 * ow * oh * eb <= W * 3 * H
         d.dst = rgb_dst[0]
         arr = (ctypes.c_int * len(frames))(*frames)
+        if loc:
+            o = opts_of(filter, loc)
+            return lambda: lib.check(lib.lib.m355_frames_export_tensor_opts(ctx.h, arr, len(frames), ctypes.byref(d), ctypes.byref(o)))
         if filter:
             return lambda: lib.check(lib.lib.m355_frames_export_tensor_filtered(ctx.h, arr, len(frames), ctypes.byref(d), filter))
         return lambda: lib.check(lib.lib.m355_frames_export_tensor(ctx.h, arr, len(frames), ctypes.byref(d)))
 
-    def export_tensor_rois(frames, rois, layout, dtype, samples, out_size, filter=0):
+    def export_tensor_rois(frames, rois, layout, dtype, samples, out_size, filter=0, loc=0):
         eb = 4 if dtype == capi.TENSOR_F32 else 2
         ow, oh = out_size
         row = ow * eb * (3 if layout == capi.TENSOR_NHWC else 1)
@@ -196,6 +215,9 @@ def main():
         d.dst = rgb_dst[0]
         arr = (ctypes.c_int * len(frames))(*frames)
         ra = (capi.TensorRoi * len(rois))(*[capi.TensorRoi(*r) for r in rois])
+        if loc:
+            o = opts_of(filter, loc)
+            return lambda: lib.check(lib.lib.m355_frames_export_tensor_rois_opts(ctx.h, arr, ra, len(frames), ctypes.byref(d), ctypes.byref(o)))
         if filter:
             return lambda: lib.check(lib.lib.m355_frames_export_tensor_rois_filtered(ctx.h, arr, ra, len(frames), ctypes.byref(d), filter))
         return lambda: lib.check(lib.lib.m355_frames_export_tensor_rois(ctx.h, arr, ra, len(frames), ctypes.byref(d)))
@@ -283,9 +305,9 @@ def main():
         "T32_tensor_rois_f16_nchw_224_32_regions": export_tensor_rois([batch[0]] * 32, [r + (capi.ROI_MIRROR if k % 4 == 3 else 0,) for k, r in enumerate(roi_list)],
                                                                       capi.TENSOR_NCHW, capi.TENSOR_F16, capi.RGB_U8, (224, 224)),
     }
-    def region_rows(prefix, filter):
+    def region_rows(prefix, filter, loc=0):
         return {"%sQ%d_tensor_rois_f16_nchw_224_of_896_batch%d" % (prefix, n, n):
-                export_tensor_rois(batch[:n], [SQUARE4 + (0,)] * n, capi.TENSOR_NCHW, capi.TENSOR_F16, capi.RGB_U8, (224, 224), filter) for n in (8, 32)}
+                export_tensor_rois(batch[:n], [SQUARE4 + (0,)] * n, capi.TENSOR_NCHW, capi.TENSOR_F16, capi.RGB_U8, (224, 224), filter, loc) for n in (8, 32)}
 
     variants.update(region_rows("", 0))
     cubic_of = {}                      # a cubic row -> the triangle's row of the same call
@@ -302,6 +324,22 @@ def main():
             if n[0] == "C":
                 key = n[1:].split("_")[0] + "_"
                 cubic_of[n] = [t for t in variants if t.startswith(key)][0]
+    sited_of = {}                      # a row of another chroma sample location type -> the type-0 row of the same call
+    for loc in sorted(set(args.chroma_loc)):
+        L = "L%d" % loc
+        rows = {
+            L + "k_sited_rgb_u8_packed": export_rgb(capi.RGB_PACKED, capi.RGB_U8, 1, loc),
+            L + "l_sited_rgb_u16_planar": export_rgb(capi.RGB_PLANAR, capi.RGB_U16, 2, loc),
+            L + "m_sited_resized_native_planar_1080p": export_resized(capi.EXPORT_PLANAR, capi.EXPORT_NATIVE, (1920, 1080), 2, 0, loc),
+            L + "n_sited_resized_u8_semiplanar_1080p": export_resized(capi.EXPORT_SEMIPLANAR, capi.EXPORT_U8, (1920, 1080), 1, 0, loc),
+            L + "q_sited_resized_rgb_u8_packed_1080p": export_resized_rgb(capi.RGB_PACKED, capi.RGB_U8, (1920, 1080), 1, 0, loc),
+            L + "w_sited_tensor_f16_nhwc_1080p": export_tensor([frame], capi.TENSOR_NHWC, capi.TENSOR_F16, capi.RGB_U16, (1920, 1080), None, 0, loc),
+        }
+        rows.update(region_rows(L, 0, loc))
+        for n in rows:
+            key = n[2:].split("_")[0] + "_"
+            sited_of[n] = [t for t in variants if t.startswith(key)][0]
+        variants.update(rows)
     scaled = [n for n in variants if n[0] in "ghijmnop"]
     ms = {n: [] for n in variants}
     for _ in range(args.rounds):
@@ -337,6 +375,7 @@ def main():
                         "T32_over_S32": res["T32_tensor_rois_f16_nchw_224_32_regions"] / res["S32_tensor_f16_nchw_224_x32_regions"],
                         "us_per_region": {n: 1e3 * res[n] / 32 for n in ("S32_tensor_f16_nchw_224_x32_regions", "T32_tensor_rois_f16_nchw_224_32_regions")}},
         "cubic_over_triangle": {n: res[n] / res[t] for n, t in cubic_of.items()},
+        "sited_over_type_0": {n: res[n] / res[t] for n, t in sited_of.items()},
         "copy_rate_GBps_same_bytes": ctx.measure_copy_rate(frame_bytes, 9),
         "bars": {"b_le_a": res["b_native_planar"] <= res["a_memcpy2d_x3"],
                  "c_le_b_plus_spread": res["c_msb16_semiplanar_crop8"] <= res["b_native_planar"] + spread,
