@@ -86,7 +86,7 @@ namespace {
   X(m355_last_error) X(m355_device_count) X(m355_create) X(m355_destroy) X(m355_frame_create) X(m355_frame_destroy) \
   X(m355_frame_upload) X(m355_frame_download) X(m355_submit_picture) X(m355_wait) X(m355_set_pipeline_depth) \
   X(m355_host_alloc) X(m355_host_free) X(m355_frame_hash) X(m355_arena_begin) X(m355_last_serial) X(m355_decode_status) \
-  X(m355_frame_download_async) X(m355_frame_download_wait) X(m355_frame_export) X(m355_frame_export_scaled) X(m355_frame_export_rgb_opts) X(m355_frame_export_resized_opts) X(m355_frame_export_resized_rgb_opts) X(m355_frames_export_tensor_opts) X(m355_frames_export_tensor_rois_opts) X(m355_frame_export_order) \
+  X(m355_frame_download_async) X(m355_frame_download_wait) X(m355_frame_export) X(m355_frame_export_scaled) X(m355_frame_export_rgb_opts) X(m355_frame_export_resized_opts) X(m355_frame_export_resized_rgb_opts) X(m355_frames_export_tensor_opts) X(m355_frames_export_tensor_rois_opts) X(m355_frame_export_order) X(m355_colour_create) X(m355_colour_destroy) X(m355_colour_preset) \
   X(m355_group_create) X(m355_group_destroy) X(m355_group_decode) X(m355_picture_upload) X(m355_picture_replace) X(m355_shard_owner_of_tile) \
   X(m355_picture_arena_begin) X(m355_frame_hash_async) X(m355_frame_hash_result) X(m355_frame_measure_async) X(m355_frame_measure_result)
 
@@ -1753,6 +1753,54 @@ LIBDE265_API int m355_glue_image_chroma_loc(const struct de265_image* img)
   if (sps.chroma_format_idc != 1 || !sps.vui_parameters_present_flag || !sps.vui.chroma_loc_info_present_flag) return 0;
   return sps.vui.chroma_sample_loc_type_top_field;
 }
+/* The colour description the picture's stream signals: its SPS' vui.colour_primaries and vui.transfer_characteristics (the H.265 code points of Tables E.3 /
+ * E.4), or 2 / 2, unspecified, where the SPS has no VUI or the VUI no colour description.  -> M355_OK, or M355_ERR_INVALID for null pointers. */
+LIBDE265_API int m355_glue_image_colour(const struct de265_image* img, int* primaries, int* transfer)
+{
+  if (!img || !primaries || !transfer) return M355_ERR_INVALID;
+  *primaries = *transfer = 2;
+  if (!img->has_sps()) return M355_OK;
+  const seq_parameter_set& sps = img->get_sps();
+  if (!sps.vui_parameters_present_flag || !sps.vui.video_signal_type_present_flag || !sps.vui.colour_description_present_flag) return M355_OK;
+  *primaries = sps.vui.colour_primaries; *transfer = sps.vui.transfer_characteristics;
+  return M355_OK;
+}
+/* Colour transform objects of the decoder's backend context (m355_colour_create / m355_colour_destroy): the handle is what the _colour forms of the three
+ * composed exports below take.  M355_ERR_INVALID for a decoder without the backend, and for one that shards its pictures over several ranks, like the exports. */
+LIBDE265_API int m355_glue_colour_create(de265_decoder_context* ctx, const m355_colour_tables* tables, int* handle)
+{
+  Api* A = api();
+  if (!A) return M355_ERR_NO_DEVICE;
+  Glue* g = ctx ? glue_of((const decoder_context*)ctx) : nullptr;
+  if (!g || g->n_ranks > 1) return M355_ERR_INVALID;
+  std::lock_guard<std::mutex> api_lock(g->api_mu);
+  const int rc = A->m355_colour_create(g->mctx, tables, handle);
+  if (rc != M355_OK) g->error = A->m355_last_error();
+  return rc;
+}
+LIBDE265_API int m355_glue_colour_destroy(de265_decoder_context* ctx, int handle)
+{
+  Api* A = api();
+  if (!A) return M355_ERR_NO_DEVICE;
+  Glue* g = ctx ? glue_of((const decoder_context*)ctx) : nullptr;
+  if (!g || g->n_ranks > 1) return M355_ERR_INVALID;
+  std::lock_guard<std::mutex> api_lock(g->api_mu);
+  const int rc = A->m355_colour_destroy(g->mctx, handle);
+  if (rc != M355_OK) g->error = A->m355_last_error();
+  return rc;
+}
+/* m355_colour_preset from what the picture's stream signals (m355_glue_image_colour) to out_transfer / out_primaries */
+LIBDE265_API int m355_glue_colour_preset_for_image(const struct de265_image* img, int out_transfer, int out_primaries, int tone, int white_nits, int peak_nits,
+                                                   m355_colour_tables* tables)
+{
+  Api* A = api();
+  if (!A) return M355_ERR_NO_DEVICE;
+  m355_colour_preset_desc d;
+  memset(&d, 0, sizeof(d));
+  if (m355_glue_image_colour(img, &d.in_primaries, &d.in_transfer) != M355_OK) return M355_ERR_INVALID;
+  d.out_transfer = out_transfer; d.out_primaries = out_primaries; d.tone = tone; d.white_nits = white_nits; d.peak_nits = peak_nits;
+  return A->m355_colour_preset(&d, tables);
+}
 /* the options of a _sited call: chroma_loc = -1 is what the stream signals (of imgs[0] for a batch, like matrix = -1), where the bottom-sited types 4
  * and 5 are M355_ERR_INVALID like an unmapped matrix; every other value is the backend's to judge */
 static int sited_opts(const de265_image* img, int filter, int chroma_loc, m355_export_opts* o)
@@ -1772,7 +1820,9 @@ static int sited_opts(const de265_image* img, int filter, int chroma_loc, m355_e
  * and pitch[0] only.
  * The _sited form — of this call and of the four below — takes `filter` (M355_FILTER_*; 0 here, where nothing is resized) and `chroma_loc`, the chroma
  * sample location type 0..3 of m355_export_opts, or -1: what the stream signals (m355_glue_image_chroma_loc; of imgs[0] for a batch; a signalled 4 or 5 is
- * M355_ERR_INVALID).  The plain and the _filtered forms keep type 0. */
+ * M355_ERR_INVALID).  The plain and the _filtered forms keep type 0.
+ * The _colour form — of the three composed exports: resized R'G'B', tensor, tensor of regions — takes `colour` too, 0 or a handle of
+ * m355_glue_colour_create (m355_export_opts.colour); each _sited form of those three is its _colour form with 0. */
 LIBDE265_API int m355_glue_export_image_rgb_sited(const struct de265_image* img, int layout, int samples, int matrix, int full_range, const int rect[4],
                                                   void* const dst[3], const int64_t pitch[3], int filter, int chroma_loc, void* consumer_stream)
 {
@@ -1856,9 +1906,9 @@ LIBDE265_API int m355_glue_export_image_resized(const struct de265_image* img, i
  * resized export and the R'G'B' export of the resized picture composed, integer-exact), with the waiting behaviour of m355_glue_export_image.  The frame,
  * the rectangle (NULL: the image's conformance window), matrix == -1 and full_range == -1 are resolved as in m355_glue_export_image_rgb, out_size as in
  * m355_glue_export_image_resized.  PACKED uses dst[0] and pitch[0] only. */
-LIBDE265_API int m355_glue_export_image_resized_rgb_sited(const struct de265_image* img, int layout, int samples, int matrix, int full_range, const int rect[4],
-                                                          const int out_size[2], void* const dst[3], const int64_t pitch[3], int filter, int chroma_loc,
-                                                          void* consumer_stream)
+LIBDE265_API int m355_glue_export_image_resized_rgb_colour(const struct de265_image* img, int layout, int samples, int matrix, int full_range, const int rect[4],
+                                                           const int out_size[2], void* const dst[3], const int64_t pitch[3], int filter, int chroma_loc,
+                                                           int colour, void* consumer_stream)
 {
   Api* A = api();
   if (!A) return M355_ERR_NO_DEVICE;
@@ -1875,6 +1925,7 @@ LIBDE265_API int m355_glue_export_image_resized_rgb_sited(const struct de265_ima
   if (full_range == -1) full_range = de265_get_image_full_range_flag(img) ? 1 : 0;
   m355_export_opts o;
   if (sited_opts(img, filter, chroma_loc, &o) != M355_OK) return M355_ERR_INVALID;
+  o.colour = colour;
   wait_submitted(g, img->get_ID());
   std::lock_guard<std::mutex> api_lock(g->api_mu);
   int r[4];
@@ -1891,6 +1942,12 @@ LIBDE265_API int m355_glue_export_image_resized_rgb_sited(const struct de265_ima
   if (rc != M355_OK) g->error = A->m355_last_error();
   return rc;
 }
+LIBDE265_API int m355_glue_export_image_resized_rgb_sited(const struct de265_image* img, int layout, int samples, int matrix, int full_range, const int rect[4],
+                                                          const int out_size[2], void* const dst[3], const int64_t pitch[3], int filter, int chroma_loc,
+                                                          void* consumer_stream)
+{
+  return m355_glue_export_image_resized_rgb_colour(img, layout, samples, matrix, full_range, rect, out_size, dst, pitch, filter, chroma_loc, 0, consumer_stream);
+}
 LIBDE265_API int m355_glue_export_image_resized_rgb_filtered(const struct de265_image* img, int layout, int samples, int matrix, int full_range, const int rect[4],
                                                              const int out_size[2], void* const dst[3], const int64_t pitch[3], int filter, void* consumer_stream)
 {
@@ -1906,9 +1963,10 @@ LIBDE265_API int m355_glue_export_image_resized_rgb(const struct de265_image* im
  * BYTES as in m355_tensor_desc), with the waiting behaviour of m355_glue_export_image: the only wait is for the worker to have enqueued every picture of
  * the batch, and the consumer's stream is ordered behind the one launch.  The rectangle (NULL: the conformance window of imgs[0]), matrix == -1 and
  * full_range == -1 are resolved from imgs[0] as in m355_glue_export_image_resized_rgb and hold for every picture; out_size as there. */
-LIBDE265_API int m355_glue_export_images_tensor_sited(const struct de265_image* const* imgs, int n, int layout, int dtype, int samples, int matrix, int full_range,
-                                                      const int rect[4], const int out_size[2], const float scale[3], const float bias[3], void* dst,
-                                                      int64_t stride_n, int64_t stride_c, int64_t stride_h, int filter, int chroma_loc, void* consumer_stream)
+LIBDE265_API int m355_glue_export_images_tensor_colour(const struct de265_image* const* imgs, int n, int layout, int dtype, int samples, int matrix, int full_range,
+                                                       const int rect[4], const int out_size[2], const float scale[3], const float bias[3], void* dst,
+                                                       int64_t stride_n, int64_t stride_c, int64_t stride_h, int filter, int chroma_loc, int colour,
+                                                       void* consumer_stream)
 {
   Api* A = api();
   if (!A) return M355_ERR_NO_DEVICE;
@@ -1926,6 +1984,7 @@ LIBDE265_API int m355_glue_export_images_tensor_sited(const struct de265_image* 
   if (full_range == -1) full_range = de265_get_image_full_range_flag(imgs[0]) ? 1 : 0;
   m355_export_opts o;
   if (sited_opts(imgs[0], filter, chroma_loc, &o) != M355_OK) return M355_ERR_INVALID;
+  o.colour = colour;
   for (int i = 0; i < n; i++) wait_submitted(g, imgs[i]->get_ID());
   std::lock_guard<std::mutex> api_lock(g->api_mu);
   int r[4], frames[M355_TENSOR_MAX_FRAMES];
@@ -1945,6 +2004,13 @@ LIBDE265_API int m355_glue_export_images_tensor_sited(const struct de265_image* 
   if (rc != M355_OK) g->error = A->m355_last_error();
   return rc;
 }
+LIBDE265_API int m355_glue_export_images_tensor_sited(const struct de265_image* const* imgs, int n, int layout, int dtype, int samples, int matrix, int full_range,
+                                                      const int rect[4], const int out_size[2], const float scale[3], const float bias[3], void* dst,
+                                                      int64_t stride_n, int64_t stride_c, int64_t stride_h, int filter, int chroma_loc, void* consumer_stream)
+{
+  return m355_glue_export_images_tensor_colour(imgs, n, layout, dtype, samples, matrix, full_range, rect, out_size, scale, bias, dst, stride_n, stride_c, stride_h,
+                                               filter, chroma_loc, 0, consumer_stream);
+}
 LIBDE265_API int m355_glue_export_images_tensor_filtered(const struct de265_image* const* imgs, int n, int layout, int dtype, int samples, int matrix, int full_range,
                                                          const int rect[4], const int out_size[2], const float scale[3], const float bias[3], void* dst,
                                                          int64_t stride_n, int64_t stride_c, int64_t stride_h, int filter, void* consumer_stream)
@@ -1963,9 +2029,10 @@ LIBDE265_API int m355_glue_export_images_tensor(const struct de265_image* const*
  * waiting and ordering of m355_glue_export_images_tensor.  rois: n x {x0, y0, width, height, flags} in luma samples of the coded picture, flags = 0 or
  * M355_ROI_MIRROR; an entry whose four rectangle fields are 0 means THAT picture's conformance window.  Every rectangle is resolved against ITS
  * picture; the same picture may appear any number of times.  matrix == -1 and full_range == -1 are resolved from imgs[0]. */
-LIBDE265_API int m355_glue_export_images_tensor_rois_sited(const struct de265_image* const* imgs, const int (*rois)[5], int n, int layout, int dtype, int samples,
-                                                           int matrix, int full_range, const int out_size[2], const float scale[3], const float bias[3], void* dst,
-                                                           int64_t stride_n, int64_t stride_c, int64_t stride_h, int filter, int chroma_loc, void* consumer_stream)
+LIBDE265_API int m355_glue_export_images_tensor_rois_colour(const struct de265_image* const* imgs, const int (*rois)[5], int n, int layout, int dtype, int samples,
+                                                            int matrix, int full_range, const int out_size[2], const float scale[3], const float bias[3], void* dst,
+                                                            int64_t stride_n, int64_t stride_c, int64_t stride_h, int filter, int chroma_loc, int colour,
+                                                            void* consumer_stream)
 {
   Api* A = api();
   if (!A) return M355_ERR_NO_DEVICE;
@@ -1983,6 +2050,7 @@ LIBDE265_API int m355_glue_export_images_tensor_rois_sited(const struct de265_im
   if (full_range == -1) full_range = de265_get_image_full_range_flag(imgs[0]) ? 1 : 0;
   m355_export_opts o;
   if (sited_opts(imgs[0], filter, chroma_loc, &o) != M355_OK) return M355_ERR_INVALID;
+  o.colour = colour;
   for (int i = 0; i < n; i++) wait_submitted(g, imgs[i]->get_ID());
   std::lock_guard<std::mutex> api_lock(g->api_mu);
   int frames[M355_TENSOR_MAX_FRAMES];
@@ -2005,6 +2073,13 @@ LIBDE265_API int m355_glue_export_images_tensor_rois_sited(const struct de265_im
   if (rc == M355_OK) rc = A->m355_frame_export_order(g->mctx, frames[0], consumer_stream);
   if (rc != M355_OK) g->error = A->m355_last_error();
   return rc;
+}
+LIBDE265_API int m355_glue_export_images_tensor_rois_sited(const struct de265_image* const* imgs, const int (*rois)[5], int n, int layout, int dtype, int samples,
+                                                           int matrix, int full_range, const int out_size[2], const float scale[3], const float bias[3], void* dst,
+                                                           int64_t stride_n, int64_t stride_c, int64_t stride_h, int filter, int chroma_loc, void* consumer_stream)
+{
+  return m355_glue_export_images_tensor_rois_colour(imgs, rois, n, layout, dtype, samples, matrix, full_range, out_size, scale, bias, dst, stride_n, stride_c,
+                                                    stride_h, filter, chroma_loc, 0, consumer_stream);
 }
 LIBDE265_API int m355_glue_export_images_tensor_rois_filtered(const struct de265_image* const* imgs, const int (*rois)[5], int n, int layout, int dtype, int samples,
                                                               int matrix, int full_range, const int out_size[2], const float scale[3], const float bias[3], void* dst,

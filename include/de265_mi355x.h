@@ -720,7 +720,8 @@ M355_API int   m355_frames_export_tensor_rois_filtered(m355_ctx* ctx, const int*
  * cosited = 1.  Luma, both filters, every rounding, the clamp to the rectangle and all limits are unchanged, and the composed exports remain
  * compositions: resize every plane on these grids, reconstruct on the resized chroma with the filter above, then the matrix / m355_tensor_element.
  * For a batch chroma_loc is the batch's, like the filter.
- * M355_ERR_INVALID (nothing is enqueued, no destination byte written) beyond what the plain call rejects: a non-zero `reserved` entry; an unknown
+ * M355_ERR_INVALID (nothing is enqueued, no destination byte written) beyond what the plain call rejects: a non-zero `reserved` entry — reserved[0] is
+ * `colour`, for which the rule reads: any value that is not 0 or a live colour transform of this context in a call that has the stage (COLOUR TRANSFORM below); an unknown
  * filter, and for m355_frame_export_rgb_opts, which resizes nothing, any filter but 0; chroma_loc outside 0..3 (4 and 5, bottom-sited, included);
  * a non-zero chroma_loc for a frame that is not 4:2:0 (the standard defines the field for 4:2:0 alone).
  * m355_frame_export, m355_frame_export_scaled (a box average without siting correction), the hashes, the measurements and the downloads deliver
@@ -729,7 +730,10 @@ M355_API int   m355_frames_export_tensor_rois_filtered(m355_ctx* ctx, const int*
 typedef struct m355_export_opts {
   int32_t filter;                        /* M355_FILTER_* */
   int32_t chroma_loc;                    /* chroma sample location type of the 4:2:0 source, 0..3 */
-  int32_t reserved[6];                   /* 0 */
+  union {
+    int32_t reserved[6];                 /* 0, but for reserved[0], which IS `colour` */
+    int32_t colour;                      /* 0: none; else a handle of m355_colour_create of THIS context (COLOUR TRANSFORM below) */
+  };
 } m355_export_opts;                      /* (32 bytes) */
 M355_API int   m355_frame_export_rgb_opts(m355_ctx* ctx, int frame, const m355_rgb_desc* desc, const m355_export_opts* opts);
 M355_API int   m355_frame_export_resized_opts(m355_ctx* ctx, int frame, const m355_resize_desc* desc, const m355_export_opts* opts);
@@ -737,6 +741,64 @@ M355_API int   m355_frame_export_resized_rgb_opts(m355_ctx* ctx, int frame, cons
 M355_API int   m355_frames_export_tensor_opts(m355_ctx* ctx, const int* frames, int n, const m355_tensor_desc* desc, const m355_export_opts* opts);
 M355_API int   m355_frames_export_tensor_rois_opts(m355_ctx* ctx, const int* frames, const m355_tensor_roi* rois, int n,
                                                    const m355_tensor_desc* desc, const m355_export_opts* opts);
+/* COLOUR TRANSFORM of the composed exports: a stage between the YCbCr -> R'G'B' matrix and the output of m355_frame_export_resized_rgb_opts,
+ * m355_frames_export_tensor_opts and m355_frames_export_tensor_rois_opts — 1-D table -> 3x3 matrix -> 1-D table (shaper / matrix / shaper), in integers —
+ * which maps, e.g., PQ or HLG code values in BT.2020 primaries to BT.709 / sRGB values for an SDR consumer.  m355_export_opts.colour = 0 is every
+ * call as it is without the stage, byte for byte.
+ * PER PIXEL (m355_colour_pixel; host only; csrc/colour_transform.h is the one definition, compiled into the kernel too).  rgb16 = the clipped 16-bit
+ * full-scale R'G'B' of the pixel, 0..65535:
+ *   1. linearise, per channel, k = v >> 6, f = v & 63:  L = (lut_in[k] (64 - f) + lut_in[k + 1] f + 32) >> 6.  Knot k stands for v = 64 k; knot
+ *      1024 is reached only as the upper neighbour.  L <= M355_COLOUR_ONE.
+ *   2. matrix, per output channel c, in exact integers (>> arithmetic):
+ *      P_c = clip(0, ONE, (m[c][0] L_r + m[c][1] L_g + m[c][2] L_b + (1 << 13)) >> 14).
+ *   3. encode, per channel, through a table indexed like a small float (accurate at the black end, where an inverse gamma is steep):
+ *      P < 64: idx = P, fr = 0.  Otherwise e = floor(log2 P) (6..24), n = P << (24 - e), idx = 64 (e - 5) + ((n >> 18) & 63), fr = (n >> 10) & 255;
+ *      P = ONE gives idx = 1216, fr = 0.  Knot idx stands for P = idx below 64 and for (64 + idx % 64) << (idx / 64 - 1) from 64 up.
+ *      o = (lut_out[idx] (256 - fr) + lut_out[min(idx + 1, 1216)] fr + 128) >> 8.
+ *   4. deliver.  M355_RGB_U16: o.  M355_RGB_U8: (2 o + 257) / 514, which is o / 257 rounded.
+ * THE COMPOSED EXPORTS WITH A COLOUR TRANSFORM: for each pixel, the (R, G, B) the same call delivers with samples = M355_RGB_U16 and no colour
+ * transform goes through m355_colour_pixel with the descriptor's `samples` — the matrix coefficients are those of m355_rgb_coefficients(...,
+ * M355_RGB_U16, ...) whatever `samples` says, which only picks step 4.  Resize, siting, filter, mirror, m355_tensor_element, layouts, strides,
+ * ordering and gates are unchanged.  A monochrome frame, or neutral chroma, gives three equal channels whenever every matrix row sums to 1 << 14.
+ * out size == rectangle of m355_frame_export_resized_rgb_opts is the unresized R'G'B' export with colour: m355_frame_export_rgb_opts and
+ * m355_frame_export_resized_opts reject a non-zero colour (M355_ERR_INVALID, nothing enqueued).
+ * OBJECTS.  m355_colour_create checks the bounds stated at the fields and pad == 0 (else M355_ERR_INVALID, as for null pointers), copies the tables
+ * into device memory the context owns and returns a handle >= 0x100 in *handle; at most M355_COLOUR_OBJECTS objects live per context (one more:
+ * M355_ERR_BUSY).  A value that is not a live handle of THIS context — a destroyed one, another context's, 1 — is M355_ERR_INVALID in every export.
+ * m355_colour_destroy waits for the context's work first, as m355_device_free does, so it may follow an export directly.
+ * PRESETS (m355_colour_preset; host only, no context, double arithmetic).  Transfers and primaries are the H.265 code points of Tables E.3 / E.4; code
+ * 2, unspecified, counts as 1.  white = white_nits, or 203 for 0.
+ *   lut_in[k], E = min(64 k, 65535) / 65535 -> nits:  in_transfer 1 / 6 / 14 / 15: white E^2.4;  13: white * inverse sRGB;  8: white E;
+ *     16: 10000 * ST 2084 EOTF;  18: 1000 * (inverse HLG OETF)^1.2 — the HLG OOTF per channel with gamma 1.2, a stated simplification.
+ *     S = the nits at E = 1; the entry is min(ONE, floor(nits / S * ONE + 0.5)).
+ *   matrix: RGB -> XYZ of in_primaries, then XYZ -> RGB of out_primaries; primaries 1, 5, 6 and 9, white D65 (0.3127, 0.3290), from the xy
+ *     chromaticities of Table E.3.  Each coefficient is floor(c * 16384 + 0.5); then the largest-magnitude entry of each row is adjusted so that the
+ *     row sums to exactly 1 << 14.  Equal primaries give the exact identity.
+ *   lut_out[i]: nits = knot(i) / ONE * S, x = nits / white, peak = peak_nits or S for 0, w = max(1, peak / white);
+ *     M355_TONE_CLIP y = min(1, x);  M355_TONE_REINHARD y = min(1, x (1 + x / w^2) / (1 + x));
+ *     the inverse of out_transfer: 1 / 6 / 14 / 15 y^(1 / 2.4), 13 sRGB, 8 y; the entry is floor(y' * 65535 + 0.5).
+ *   M355_ERR_INVALID: any other code point; out_transfer 16 or 18; a non-zero `reserved`; negative nits; peak < white when given; null pointers.
+ * Not offered: HDR outputs (PQ / HLG out, linear above SDR white); luminance- or maxRGB-based tone mapping; the luminance-dependent HLG OOTF; 3-D
+ * LUTs; dynamic metadata; colour in m355_frame_export_rgb_opts; a transform per slice. */
+#define M355_COLOUR_ONE        (1 << 24)     /* linear light, full scale */
+#define M355_COLOUR_IN_KNOTS   1025
+#define M355_COLOUR_OUT_KNOTS  1217
+#define M355_COLOUR_OBJECTS    16
+#define M355_TONE_CLIP         0
+#define M355_TONE_REINHARD     1
+typedef struct m355_colour_tables {
+  uint32_t lut_in[M355_COLOUR_IN_KNOTS];     /* every entry <= M355_COLOUR_ONE */
+  int32_t  matrix[9];                        /* row-major, Q14, every |entry| <= 65535 */
+  uint16_t lut_out[M355_COLOUR_OUT_KNOTS];
+  uint16_t pad;                              /* 0 */
+} m355_colour_tables;                        /* (6572 bytes) */
+typedef struct m355_colour_preset_desc {
+  int32_t in_transfer, in_primaries, out_transfer, out_primaries, tone, white_nits, peak_nits, reserved;
+} m355_colour_preset_desc;
+M355_API int   m355_colour_create(m355_ctx* ctx, const m355_colour_tables* tables, int* handle);
+M355_API int   m355_colour_destroy(m355_ctx* ctx, int handle);
+M355_API int   m355_colour_preset(const m355_colour_preset_desc* desc, m355_colour_tables* out);
+M355_API int   m355_colour_pixel(const m355_colour_tables* tables, const uint32_t rgb16[3], int samples, uint32_t out[3]);
 M355_API int   m355_frame_export_wait(m355_ctx* ctx, int frame);
 M355_API int   m355_frame_export_order(m355_ctx* ctx, int frame, void* consumer_hipStream);
 /* Device memory for export destinations and blocking copies out of / into it, for applications (and the tests) that keep a second HIP

@@ -107,8 +107,34 @@ class TensorRoi(ctypes.Structure):
 
 
 class ExportOpts(ctypes.Structure):
-    """m355_export_opts: the filter (FILTER_*) and the chroma sample location type 0..3 of a 4:2:0 source; reserved stays 0"""
+    """m355_export_opts: the filter (FILTER_*) and the chroma sample location type 0..3 of a 4:2:0 source; reserved stays 0, but for reserved[0],
+    which is the header's `colour`: 0 or a handle of Context.colour_create"""
     _fields_ = [("filter", ctypes.c_int32), ("chroma_loc", ctypes.c_int32), ("reserved", ctypes.c_int32 * 6)]
+
+
+COLOUR_ONE, COLOUR_IN_KNOTS, COLOUR_OUT_KNOTS, COLOUR_OBJECTS = 1 << 24, 1025, 1217, 16   # M355_COLOUR_*
+TONE_CLIP, TONE_REINHARD = 0, 1               # M355_TONE_*
+
+
+class ColourTables(ctypes.Structure):
+    """m355_colour_tables (include/de265_mi355x.h)"""
+    _fields_ = [("lut_in", ctypes.c_uint32 * COLOUR_IN_KNOTS), ("matrix", ctypes.c_int32 * 9), ("lut_out", ctypes.c_uint16 * COLOUR_OUT_KNOTS),
+                ("pad", ctypes.c_uint16)]
+
+
+class ColourPresetDesc(ctypes.Structure):
+    """m355_colour_preset_desc (include/de265_mi355x.h)"""
+    _fields_ = [(n, ctypes.c_int32) for n in ("in_transfer", "in_primaries", "out_transfer", "out_primaries", "tone", "white_nits", "peak_nits",
+                                              "reserved")]
+
+
+def colour_tables(lut_in, matrix, lut_out, pad=0):
+    """a ColourTables from three sequences (1025, 9 and 1217 entries)"""
+    t = ColourTables(pad=pad)
+    t.lut_in[:] = [int(v) for v in lut_in]
+    t.matrix[:] = [int(v) for v in matrix]
+    t.lut_out[:] = [int(v) for v in lut_out]
+    return t
 
 
 class RgbCoeffs(ctypes.Structure):
@@ -204,6 +230,11 @@ class Library:
             L.m355_frame_export_resized_rgb_opts.argtypes = [vp, i, ctypes.POINTER(ResizeRgbDesc), po]
             L.m355_frames_export_tensor_opts.argtypes = [vp, ctypes.POINTER(i), i, ctypes.POINTER(TensorDesc), po]
             L.m355_frames_export_tensor_rois_opts.argtypes = [vp, ctypes.POINTER(i), ctypes.POINTER(TensorRoi), i, ctypes.POINTER(TensorDesc), po]
+        if hasattr(L, "m355_colour_create"):
+            L.m355_colour_create.argtypes = [vp, ctypes.POINTER(ColourTables), ctypes.POINTER(i)]
+            L.m355_colour_destroy.argtypes = [vp, i]
+            L.m355_colour_preset.argtypes = [ctypes.POINTER(ColourPresetDesc), ctypes.POINTER(ColourTables)]
+            L.m355_colour_pixel.argtypes = [ctypes.POINTER(ColourTables), ctypes.POINTER(ctypes.c_uint32), i, ctypes.POINTER(ctypes.c_uint32)]
         L.m355_host_alloc.argtypes = [ctypes.c_size_t]
         L.m355_host_alloc.restype = vp
         L.m355_host_free.argtypes = [vp]
@@ -288,6 +319,19 @@ class Library:
         bits = ctypes.c_uint32(0)
         self.check(self.lib.m355_tensor_element(v, scale, bias, dtype, ctypes.byref(bits)))
         return int(bits.value)
+
+    def colour_preset(self, in_transfer, in_primaries, out_transfer, out_primaries, tone=TONE_CLIP, white_nits=0, peak_nits=0, reserved=0):
+        """the tables of a preset (m355_colour_preset; host only) -> ColourTables"""
+        d = ColourPresetDesc(in_transfer, in_primaries, out_transfer, out_primaries, tone, white_nits, peak_nits, reserved)
+        t = ColourTables()
+        self.check(self.lib.m355_colour_preset(ctypes.byref(d), ctypes.byref(t)))
+        return t
+
+    def colour_pixel(self, tables, rgb16, samples):
+        """the colour transform stage for one pixel (m355_colour_pixel; host only) -> (R, G, B)"""
+        out = (ctypes.c_uint32 * 3)()
+        self.check(self.lib.m355_colour_pixel(ctypes.byref(tables), (ctypes.c_uint32 * 3)(*[int(v) for v in rgb16]), samples, out))
+        return tuple(int(v) for v in out)
 
     def pack_narrow(self, pic):
         """m355_pack_narrow on a picture's residual records and coefficient list (host only; worklist.pack_narrow is the numpy
@@ -492,7 +536,7 @@ class Context:
         return self.L.resize_taps(src_n, dst_n, cosited, i, filter, filtered_entry)
 
     def frame_export_resized(self, f, layout, samples, out_size, rect=None, host=False, pad=20, filter=0, filtered_entry=False, chroma_loc=0,
-                             opts_entry=False):
+                             opts_entry=False, colour=0):
         """start m355_frame_export_resized of frame f to out_size = (out_width, out_height) luma samples (rect = the source rectangle (x0, y0, width,
         height) in luma samples, None: the whole frame) into buffers of its own, made as frame_export makes them: every byte holds DEVICE_FILL
         beforehand, the pitch is `pad` bytes larger than the row.  filter = FILTER_*: a filter other than 0, or filtered_entry, goes
@@ -516,8 +560,8 @@ class Context:
                     p = self.device_alloc(rows * pitch)
                 bufs.append(p)
                 desc.dst[k] = p; desc.pitch[k] = pitch
-            if chroma_loc != 0 or opts_entry or opts_entry is None:
-                self.L.check(self.L.lib.m355_frame_export_resized_opts(self.h, f, ctypes.byref(desc), self._opts(filter, chroma_loc, opts_entry)))
+            if chroma_loc != 0 or colour != 0 or opts_entry or opts_entry is None:
+                self.L.check(self.L.lib.m355_frame_export_resized_opts(self.h, f, ctypes.byref(desc), self._opts(filter, chroma_loc, opts_entry, colour)))
             elif filter != 0 or filtered_entry:
                 self.L.check(self.L.lib.m355_frame_export_resized_filtered(self.h, f, ctypes.byref(desc), filter))
             else:
@@ -529,15 +573,29 @@ class Context:
         return (f, shapes, bufs, [int(desc.pitch[k]) for k in range(len(shapes))], host)
 
     @staticmethod
-    def _opts(filter, chroma_loc, opts_entry):
+    def _opts(filter, chroma_loc, opts_entry, colour=0):
         """the options argument of an _opts entry point: an ExportOpts by reference, or NULL for opts_entry=None"""
-        return None if opts_entry is None else ctypes.byref(ExportOpts(filter=filter, chroma_loc=chroma_loc))
+        if opts_entry is None:
+            return None
+        o = ExportOpts(filter=filter, chroma_loc=chroma_loc)
+        o.reserved[0] = colour
+        return ctypes.byref(o)
+
+    def colour_create(self, tables):
+        """m355_colour_create: the tables (ColourTables, or None for a NULL pointer) as an object of this context -> its handle (>= 0x100), which
+        the `colour` keyword of the composed exports takes"""
+        h = ctypes.c_int(0)
+        self.L.check(self.L.lib.m355_colour_create(self.h, None if tables is None else ctypes.byref(tables), ctypes.byref(h)))
+        return int(h.value)
+
+    def colour_destroy(self, handle):
+        self.L.check(self.L.lib.m355_colour_destroy(self.h, handle))
 
     def rgb_coefficients(self, matrix, full_range, bit_depth_luma, bit_depth_chroma, samples):
         """the integers of the R'G'B' conversion (m355_rgb_coefficients) -> dict F, y0, c0, cy, crv, cgu, cgv, cbu"""
         return self.L.rgb_coefficients(matrix, full_range, bit_depth_luma, bit_depth_chroma, samples)
 
-    def frame_export_rgb(self, f, layout, samples, matrix, full_range, rect=None, host=False, pad=20, chroma_loc=0, opts_entry=False):
+    def frame_export_rgb(self, f, layout, samples, matrix, full_range, rect=None, host=False, pad=20, chroma_loc=0, opts_entry=False, colour=0):
         """start m355_frame_export_rgb of frame f (rect = (x0, y0, width, height) in luma samples, None: the whole frame) into buffers of its own,
         made as frame_export makes them: every byte holds DEVICE_FILL beforehand, the pitch is `pad` bytes larger than the row.  Packed: one plane
         of 3 * width elements per row; planar: R, G, B.  -> token for frame_export_finish"""
@@ -562,8 +620,8 @@ class Context:
                     p = self.device_alloc(rows * pitch)
                 bufs.append(p)
                 desc.dst[k] = p; desc.pitch[k] = pitch
-            if chroma_loc != 0 or opts_entry or opts_entry is None:
-                self.L.check(self.L.lib.m355_frame_export_rgb_opts(self.h, f, ctypes.byref(desc), self._opts(0, chroma_loc, opts_entry)))
+            if chroma_loc != 0 or colour != 0 or opts_entry or opts_entry is None:
+                self.L.check(self.L.lib.m355_frame_export_rgb_opts(self.h, f, ctypes.byref(desc), self._opts(0, chroma_loc, opts_entry, colour)))
             else:
                 self.L.check(self.L.lib.m355_frame_export_rgb(self.h, f, ctypes.byref(desc)))
         except Exception:
@@ -573,11 +631,12 @@ class Context:
         return (f, shapes, bufs, [int(desc.pitch[k]) for k in range(len(shapes))], host)
 
     def frame_export_resized_rgb(self, f, layout, samples, matrix, full_range, out_size, rect=None, host=False, pad=20, filter=0, filtered_entry=False,
-                                 chroma_loc=0, opts_entry=False):
+                                 chroma_loc=0, opts_entry=False, colour=0):
         """start m355_frame_export_resized_rgb of frame f to out_size = (out_width, out_height) luma samples (rect = the source rectangle (x0, y0,
         width, height) in luma samples, None: the whole frame) into buffers of its own, made as frame_export_rgb makes them: every byte holds
         DEVICE_FILL beforehand, the pitch is `pad` bytes larger than the row.  Packed: one plane of 3 * out_width elements per row; planar: R, G, B.
-        -> token for frame_export_finish"""
+        colour: 0, or the handle of a colour transform (colour_create), which goes through the _opts entry point like a chroma_loc other than 0 —
+        so it does in the two tensor calls below.  -> token for frame_export_finish"""
         w, h = out_size
         dt = np.dtype(np.uint16 if samples == RGB_U16 else np.uint8)
         shapes = [(h, 3 * w, dt)] if layout == RGB_PACKED else [(h, w, dt)] * 3
@@ -597,8 +656,8 @@ class Context:
                     p = self.device_alloc(rows * pitch)
                 bufs.append(p)
                 desc.dst[k] = p; desc.pitch[k] = pitch
-            if chroma_loc != 0 or opts_entry or opts_entry is None:
-                self.L.check(self.L.lib.m355_frame_export_resized_rgb_opts(self.h, f, ctypes.byref(desc), self._opts(filter, chroma_loc, opts_entry)))
+            if chroma_loc != 0 or colour != 0 or opts_entry or opts_entry is None:
+                self.L.check(self.L.lib.m355_frame_export_resized_rgb_opts(self.h, f, ctypes.byref(desc), self._opts(filter, chroma_loc, opts_entry, colour)))
             elif filter != 0 or filtered_entry:
                 self.L.check(self.L.lib.m355_frame_export_resized_rgb_filtered(self.h, f, ctypes.byref(desc), filter))
             else:
@@ -614,7 +673,7 @@ class Context:
         return self.L.tensor_element(v, scale, bias, dtype)
 
     def frames_export_tensor(self, frames, layout, dtype, samples, matrix, full_range, out_size, scale, bias, rect=None, host=False, pad=20, filter=0,
-                             filtered_entry=False, chroma_loc=0, opts_entry=False):
+                             filtered_entry=False, chroma_loc=0, opts_entry=False, colour=0):
         """start m355_frames_export_tensor of the frames (handles; the same one may repeat) to out_size = (out_width, out_height) luma samples each
         (rect = the source rectangle (x0, y0, width, height) in luma samples, the same in every frame; None: the whole frame) into ONE buffer of its
         own, made as frame_export_resized_rgb makes its buffers: every byte holds DEVICE_FILL beforehand, and every stride is `pad` bytes (a multiple
@@ -622,16 +681,16 @@ class Context:
         scale, bias: three floats each (R, G, B).  -> token for tensor_export_finish"""
         return self._frames_export_tensor(frames, None, layout, dtype, samples, matrix, full_range, out_size, scale, bias, rect, host, pad,
                                           filter if filter != 0 or filtered_entry else None,
-                                          (filter, chroma_loc, opts_entry) if chroma_loc != 0 or opts_entry or opts_entry is None else None)
+                                          (filter, chroma_loc, opts_entry, colour) if chroma_loc != 0 or colour != 0 or opts_entry or opts_entry is None else None)
 
     def frames_export_tensor_rois(self, frames, rois, layout, dtype, samples, matrix, full_range, out_size, scale, bias, host=False, pad=20, filter=0,
-                                  filtered_entry=False, chroma_loc=0, opts_entry=False):
+                                  filtered_entry=False, chroma_loc=0, opts_entry=False, colour=0):
         """start m355_frames_export_tensor_rois: slice i is the rectangle rois[i] = (x0, y0, width, height, flags) of frames[i] (None or width 0: the
         whole of that frame; flags: 0 or ROI_MIRROR), resized to out_size.  The buffer is made as frames_export_tensor makes it: DEVICE_FILL in every
         byte, every stride `pad` bytes above the smallest one the call accepts.  -> token for tensor_export_finish"""
         return self._frames_export_tensor(frames, [r if r is not None else (0, 0, 0, 0, 0) for r in rois], layout, dtype, samples, matrix, full_range,
                                           out_size, scale, bias, None, host, pad, filter if filter != 0 or filtered_entry else None,
-                                          (filter, chroma_loc, opts_entry) if chroma_loc != 0 or opts_entry or opts_entry is None else None)
+                                          (filter, chroma_loc, opts_entry, colour) if chroma_loc != 0 or colour != 0 or opts_entry or opts_entry is None else None)
 
     def _frames_export_tensor(self, frames, rois, layout, dtype, samples, matrix, full_range, out_size, scale, bias, rect, host, pad, filter=None, opts=None):
         w, h = out_size

@@ -343,6 +343,13 @@ struct ExportResizedArgs {
 /* src_bytes / dst_bytes: 1 or 2 per sample */
 void m355_launch_export_resized(const ExportResizedArgs& a, int src_bytes, int dst_bytes, bool semiplanar, int filter, hipStream_t st);
 
+/* the colour transform stage of a launch of k_export_resized_rgb.hip (m355_export_opts.colour; colour_transform.h): t = the object's tables in device
+   memory (m355_colour_tables; null: no stage, and the instantiations without it run), m = its matrix, wave-uniform like t.  With a stage, k are the
+   coefficients of M355_RGB_U16 whatever the descriptor's samples, which pick the delivery (RR_FRAME: the element bytes; tensors: u16). */
+struct ColourArgs {
+  const uint8_t* t;
+  int32_t m[9], pad;
+};
 /* one m355_frame_export_resized_rgb (k_export_resized_rgb.hip, RR_FRAME).  src[] = the rectangle's first sample of Y, Cb, Cr (the resize clamps to the rectangle),
    pitches in BYTES (src_pitch[0] luma, [1] both chroma planes); dst[0] alone for the packed layout, else R, G, B.  Index 0 of sn / dn is the luma
    grid, 1 the chroma grid (zeros for a monochrome frame): sn_x x sn_y source samples of the rectangle to dn_x x dn_y output samples; the horizontal
@@ -361,6 +368,7 @@ struct ExportResizedRgbArgs {
   const uint32_t* timeout;
   uint32_t epoch;
   int32_t chroma_loc;
+  ColourArgs colour;                      /* behind everything that was here: no offset moves */
 };
 /* src_bytes / dst_bytes: 1 or 2 per sample / channel */
 void m355_launch_export_resized_rgb(const ExportResizedRgbArgs& a, int src_bytes, int dst_bytes, int filter, hipStream_t st);
@@ -386,6 +394,7 @@ struct ExportTensorArgs {
   m355_rgb_coeffs k;
   ExportTensorFrame fr[M355_TENSOR_MAX_FRAMES];
   int32_t chroma_loc, pad;                /* the batch's siting (ExportResizedRgbArgs); behind the records, whose offsets stay what they were */
+  ColourArgs colour;
 };
 /* src_bytes: 1 or 2 per sample; elem_bytes: 2 (F16 / BF16) or 4 (F32) */
 void m355_launch_export_tensor(const ExportTensorArgs& a, int src_bytes, int elem_bytes, int filter, hipStream_t st);
@@ -415,6 +424,7 @@ struct ExportTensorRoisArgs {
   m355_rgb_coeffs k;
   ExportTensorRoi fr[M355_TENSOR_MAX_FRAMES];
   int32_t chroma_loc, pad;                /* the batch's siting, kept out of the slices' records and behind them */
+  ColourArgs colour;
 };
 static_assert(sizeof(ExportTensorRoi) == 88 && sizeof(ExportTensorRoisArgs) <= 4096, "the records of a batch of regions must fit the kernel arguments");
 void m355_launch_export_tensor_rois(const ExportTensorRoisArgs& a, int src_bytes, int elem_bytes, int filter, hipStream_t st);

@@ -49,7 +49,14 @@
  *   Mirror (RR_ROIS, M355_ROI_MIRROR) touches the epilogue only: the lane of tile column t stages its pixel at position ncols - 1 - t of the
  *   staged row (the channels of an NHWC pixel keep their order), and the tile's first destination column is out_width - c0 - ncols.
  * Layout, chroma format, F16 against BF16 and U8 against U16 of the tensors' integer stage are wave-uniform run-time switches (kernel arguments in
- * scalar registers): source sample bytes, element bytes, the mode, the filter and SITED are the template parameters, twelve instantiations per filter and value of SITED.
+ * scalar registers): source sample bytes, element bytes, the mode, the filter, SITED and COLOUR are the template parameters, twelve instantiations per filter and
+ * value of SITED and of COLOUR.
+ * COLOUR (m355_export_opts.colour; colour_transform.h, k_colour_dev.h) puts the colour transform stage between the clip and the staging: the launch's
+ *   coefficients are then those of M355_RGB_U16 and the clip is to 65 535 whatever the samples; the pixel's three 16-bit values go through the input
+ *   table (global memory, two neighbouring knots per channel in one load), the 3 x 3 matrix (wave-uniform kernel arguments, 24-bit multiplies) and the
+ *   output table (LDS: 2 436 bytes more, filled behind the gate and ahead of the prologue's barrier), and the delivery the samples ask for (U8: one
+ *   rounding division) hands the integer to the pack or to tensor_element.h as before.  COLOUR = false compiles none of it: those instantiations are
+ *   what they were.
  *
  * Reads stay inside the planes' allocations, by the argument of k_export_resized.hip for every plane of every slice: the host admits a frame only
  * if it contains the slice's rectangle (export_plan per frame), whose size is the source size the slice's rows are derived from.  A filter row's
@@ -71,6 +78,7 @@
 #include "resize_taps.h"
 #include "tensor_element.h"
 #include "k_resize_dev.h"
+#include "k_colour_dev.h"
 
 #define RR_TW M355_RESIZE_TILE_W
 #define RR_TH M355_RESIZE_TILE_H
@@ -182,7 +190,7 @@ template <> struct RrArgs<RR_ROIS> { typedef ExportTensorRoisArgs T; };
 #define RR_PITCH(i) ({ uint32_t g_; if constexpr (MODE == RR_FRAME) g_ = (uint32_t)a.src_pitch[i]; else g_ = (uint32_t)a.fr[slice].src_pitch[i]; g_; })
 #define RR_GEOM(field) ({ uint32_t g_; if constexpr (MODE == RR_ROIS) g_ = a.fr[slice].field; else g_ = a.field; g_; })
 
-template <int SB, int EB, int MODE, int FILTER, bool SITED>
+template <int SB, int EB, int MODE, int FILTER, bool SITED, bool COLOUR>
 __global__ void __launch_bounds__(256) k_export_resized_rgb(typename RrArgs<MODE>::T a)
 {
   constexpr bool CUBIC = FILTER == M355_FILTER_CUBIC;
@@ -205,6 +213,13 @@ __global__ void __launch_bounds__(256) k_export_resized_rgb(typename RrArgs<MODE
   if constexpr (MODE == RR_FRAME) { if (unit >= a.units) return; }   /* (here, not beside the gate: there the two exits become one branch and the code another) */
   if constexpr (MODE == RR_BATCH) unit -= slice * a.units;
   const uint32_t tid = threadIdx.x;
+  /* the colour transform stage (m355_export_opts.colour): its output table goes to LDS here, behind the gate and ahead of the prologue's barrier */
+  const unsigned short* s_lo = nullptr;
+  if constexpr (COLOUR) {
+    __shared__ unsigned s_lut[M355_COLOUR_LDS_DWORDS];
+    d_colour_fill(a.colour.t, s_lut, tid);
+    s_lo = (const unsigned short*)s_lut;
+  }
   const uint32_t run = unit / RR_GEOM(tiles_x), tile = unit - run * RR_GEOM(tiles_x);
   const uint32_t tw = RR_GEOM(tile_w), c0 = tile * tw, j0 = run * RR_TH;
   const uint32_t dnx = a.dn_x[0], dny = a.dn_y[0], cdx = a.dn_x[1], cdy = a.dn_y[1];
@@ -334,7 +349,8 @@ __global__ void __launch_bounds__(256) k_export_resized_rgb(typename RrArgs<MODE
   const bool odd = swl && (X & 1u);
   /* the epilogue of the launch (scalar): the clip of the integer stage; tensors: the element format, scale and bias per channel (RR_TE: 0 for a frame) */
 #define RR_TE(T, expr) ({ T g_ = 0; if constexpr (MODE != RR_FRAME) g_ = (expr); g_; })
-  const int M = MODE == RR_FRAME ? (EB == 1 ? 255 : 65535) : (RR_TE(int, a.u16) ? 65535 : 255);
+  const int M = COLOUR ? 65535 : (MODE == RR_FRAME ? (EB == 1 ? 255 : 65535) : (RR_TE(int, a.u16) ? 65535 : 255));   /* (COLOUR: k is the U16 set) */
+  const bool deliver_u8 = MODE == RR_FRAME ? EB == 1 : !RR_TE(int, a.u16);   /* COLOUR: step 4 of colour_transform.h */
   const uint32_t bf16_mask = RR_TE(int, a.bf16) ? 0xFFFFFFFFu : 0u;
   const float sc[3] = {RR_TE(float, a.scale[0]), RR_TE(float, a.scale[1]), RR_TE(float, a.scale[2])};
   const float bi[3] = {RR_TE(float, a.bias[0]), RR_TE(float, a.bias[1]), RR_TE(float, a.bias[2])};
@@ -431,7 +447,12 @@ __global__ void __launch_bounds__(256) k_export_resized_rgb(typename RrArgs<MODE
           g = d_mad24(ncgv, uv[1], d_mad24(ncgu, uv[0], base));
           b = d_mad24(cbu, uv[0], base);
         }
-        const unsigned e[3] = {(unsigned)d_clip3(0, M, r >> F), (unsigned)d_clip3(0, M, g >> F), (unsigned)d_clip3(0, M, b >> F)};
+        unsigned e[3] = {(unsigned)d_clip3(0, M, r >> F), (unsigned)d_clip3(0, M, g >> F), (unsigned)d_clip3(0, M, b >> F)};
+        if constexpr (COLOUR) {                                /* table, matrix, table on the 16-bit R'G'B', then the delivery the samples ask for */
+          d_colour_pixel(a.colour.t, s_lo, a.colour.m, e);
+#pragma unroll
+          for (int c = 0; c < 3; c++) e[c] = m355_ct_deliver(e[c], deliver_u8);
+        }
         uint8_t* o = s_o[par][ri];
 #pragma unroll
         for (int c = 0; c < 3; c++) {
@@ -460,11 +481,14 @@ __global__ void __launch_bounds__(256) k_export_resized_rgb(typename RrArgs<MODE
 #undef RR_LOAD_BATCH
 
 /* src_bytes: 1 or 2 per sample; elem_bytes: 1 or 2 per channel of a frame, 2 or 4 per element of a tensor */
+#define RR_LAUNCH_C(MODE, B0, B1, F, S, C) \
+  if (src_bytes == 1 && elem_bytes == B0) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_export_resized_rgb<1, B0, MODE, F, S, C>), g_, block, 0, st, a); \
+  if (src_bytes == 1 && elem_bytes == B1) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_export_resized_rgb<1, B1, MODE, F, S, C>), g_, block, 0, st, a); \
+  if (src_bytes == 2 && elem_bytes == B0) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_export_resized_rgb<2, B0, MODE, F, S, C>), g_, block, 0, st, a); \
+  if (src_bytes == 2 && elem_bytes == B1) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_export_resized_rgb<2, B1, MODE, F, S, C>), g_, block, 0, st, a);
 #define RR_LAUNCH_S(MODE, B0, B1, F, S) \
-  if (src_bytes == 1 && elem_bytes == B0) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_export_resized_rgb<1, B0, MODE, F, S>), g_, block, 0, st, a); \
-  if (src_bytes == 1 && elem_bytes == B1) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_export_resized_rgb<1, B1, MODE, F, S>), g_, block, 0, st, a); \
-  if (src_bytes == 2 && elem_bytes == B0) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_export_resized_rgb<2, B0, MODE, F, S>), g_, block, 0, st, a); \
-  if (src_bytes == 2 && elem_bytes == B1) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_export_resized_rgb<2, B1, MODE, F, S>), g_, block, 0, st, a);
+  if (a.colour.t) { RR_LAUNCH_C(MODE, B0, B1, F, S, true) } \
+  else { RR_LAUNCH_C(MODE, B0, B1, F, S, false) }
 #define RR_LAUNCH_F(MODE, B0, B1, F) \
   if (a.chroma_loc != 0) { RR_LAUNCH_S(MODE, B0, B1, F, true) } \
   else { RR_LAUNCH_S(MODE, B0, B1, F, false) }
@@ -491,3 +515,4 @@ void m355_launch_export_tensor_rois(const ExportTensorRoisArgs& a, int src_bytes
 #undef RR_LAUNCH
 #undef RR_LAUNCH_F
 #undef RR_LAUNCH_S
+#undef RR_LAUNCH_C

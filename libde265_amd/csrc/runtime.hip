@@ -12,6 +12,8 @@
 #include "runtime_internal.h"
 #include "resize_taps.h"
 #include "tensor_element.h"
+#include "colour_transform.h"
+#include "colour_preset.h"
 
 thread_local std::string g_err;
 int fail(int code, const char* fmt, ...)
@@ -310,6 +312,7 @@ void m355_destroy(m355_ctx* c)
   if (c->rccl && g_rccl.CommDestroy) g_rccl.CommDestroy(c->rccl);
   for (auto& e_ : c->evring) if (e_.ev) hipEventDestroy(e_.ev);
   if (c->status_words) hipHostFree(c->status_words);
+  for (auto& q : c->colour) if (q.dev) hipFree(q.dev);
   if (c->stage) hipHostFree(c->stage);
   for (Lane& l : c->lanes) lane_destroy(l);
   delete c;
@@ -614,13 +617,22 @@ int m355_rgb_coefficients(int matrix, int full_range, int bdl, int bdc, int samp
   return M355_OK;
 }
 /* m355_export_opts behind the plan of a frame like f (a batch: frames[0], whose chroma format every frame shares): null = the defaults; the reserved
- * entries and the chroma sample location type, which is 4:2:0's alone.  The filter is checked where it is used (resize_check); resizes = false: the
+ * entries, the colour transform and the chroma sample location type, which is 4:2:0's alone.  The filter is checked where it is used (resize_check); resizes = false: the
  * call has no filter to choose. */
-static int opts_check(const char* who, const m355_export_opts* o, const Frame* f, bool resizes, m355_export_opts& out)
+static int opts_check(const char* who, m355_ctx* c, const m355_export_opts* o, const Frame* f, bool resizes, m355_export_opts& out, ColourArgs* colour = nullptr)
 {
   out = m355_export_opts{};
   if (!o) return M355_OK;
-  for (int i = 0; i < 6; i++) if (o->reserved[i]) return fail(M355_ERR_INVALID, "%s: reserved[%d] of the options is %d, not 0", who, i, o->reserved[i]);
+  for (int i = 1; i < 6; i++) if (o->reserved[i]) return fail(M355_ERR_INVALID, "%s: reserved[%d] of the options is %d, not 0", who, i, o->reserved[i]);
+  /* reserved[0] is the colour transform: a live object of this context, where the call has the stage (colour != null) */
+  if (o->colour) {
+    if (!colour) return fail(M355_ERR_INVALID, "%s: colour %d (reserved[0]) in a call without a colour transform stage", who, o->colour);
+    const m355_ctx::ColourObj* obj = nullptr;
+    for (const auto& q : c->colour) if (q.handle == o->colour) obj = &q;
+    if (!obj) return fail(M355_ERR_INVALID, "%s: colour %d (reserved[0]) is no live colour transform of this context", who, o->colour);
+    colour->t = obj->dev;
+    for (int k = 0; k < 9; k++) colour->m[k] = obj->matrix[k];
+  }
   if (!resizes && o->filter != M355_FILTER_TRIANGLE) return fail(M355_ERR_INVALID, "%s: filter %d where nothing is resized", who, o->filter);
   if (o->chroma_loc < 0 || o->chroma_loc > 3) return fail(M355_ERR_INVALID, "%s: chroma sample location type %d is not 0..3", who, o->chroma_loc);
   if (o->chroma_loc && f->cf != 1) return fail(M355_ERR_INVALID, "%s: chroma sample location type %d for a frame that is not 4:2:0", who, o->chroma_loc);
@@ -637,7 +649,7 @@ int m355_frame_export_rgb_opts(m355_ctx* c, int h, const m355_rgb_desc* e, const
   if (rc) return rc;
   Frame* f = P.f;
   m355_export_opts o;
-  rc = opts_check(who, opts, f, false, o);
+  rc = opts_check(who, c, opts, f, false, o);
   if (rc) return rc;
   ExportRgbArgs a = {};
   bool planar = false;
@@ -715,7 +727,7 @@ int m355_frame_export_resized_opts(m355_ctx* c, int h, const m355_resize_desc* e
   if (rc) return rc;
   Frame* f = P.f;
   m355_export_opts o;
-  rc = opts_check(who, opts, f, true, o);
+  rc = opts_check(who, c, opts, f, true, o);
   if (rc) return rc;
   const int filter = o.filter;
   const int sw = (f->cf == 1 || f->cf == 2) ? 2 : 1, sh = f->cf == 1 ? 2 : 1;
@@ -781,6 +793,68 @@ static uint32_t resize_rgb_tile_w(int filter, int64_t sn, int64_t dn, int64_t cs
   if (sw == 2) even = (even + 1) & ~(int64_t)1;
   return (uint32_t)(even < w ? even : w);
 }
+extern "C++" {
+/* The colour transform stage of a composed export into its kernel arguments: the object's tables and matrix, and the coefficients of M355_RGB_U16
+ * in place of the descriptor's samples', which then only pick the delivery (the kernel's element bytes, or the tensors' u16) */
+template <class D, class A> static int colour_apply(const ColourArgs& colour, const D* e, const Frame* f, A& a)
+{
+  if (!colour.t) return M355_OK;
+  a.colour = colour;
+  return m355_rgb_coefficients(e->matrix, e->full_range, f->bdl, f->bdc, M355_RGB_U16, &a.k);
+}
+}
+/* The colour transform objects (include/de265_mi355x.h, COLOUR TRANSFORM): the tables go to device memory of the context through its pinned staging
+ * buffer and the active lane's stream, like m355_device_write's bytes; the exports find an object by its handle (opts_check). */
+static std::atomic<int> g_colour_handle{0x100};
+int m355_colour_create(m355_ctx* c, const m355_colour_tables* t, int* handle)
+{
+  if (!c || !t || !handle) return fail(M355_ERR_INVALID, "m355_colour_create: no context / tables / handle");
+  const int bad = m355_ct_tables_check(t);
+  if (bad) return fail(M355_ERR_INVALID, "m355_colour_create: %s", bad == 1 ? "an entry of lut_in is above M355_COLOUR_ONE" : (bad == 2 ? "a matrix entry is outside -65535..65535" : "pad is not 0"));
+  m355_ctx::ColourObj* obj = nullptr;
+  for (auto& q : c->colour) if (!q.handle && !obj) obj = &q;
+  if (!obj) return fail(M355_ERR_BUSY, "m355_colour_create: %d colour transforms live (destroy one: m355_colour_destroy)", M355_COLOUR_OBJECTS);
+  hipSetDevice(c->device);
+  int rc = stage_reserve(c, sizeof(*t));
+  if (rc) return rc;
+  uint8_t* dev = nullptr;
+  if (hipMalloc(&dev, sizeof(*t)) != hipSuccess) return fail(M355_ERR_NOMEM, "m355_colour_create: hipMalloc(%zu) failed", sizeof(*t));
+  memcpy(c->stage, t, sizeof(*t));
+  const hipStream_t st = lane(c).stream;
+  if (hipMemcpyAsync(dev, c->stage, sizeof(*t), hipMemcpyHostToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
+    hipFree(dev);
+    return fail(M355_ERR_HIP, "m355_colour_create: the copy of the tables failed");
+  }
+  obj->dev = dev;
+  for (int k = 0; k < 9; k++) obj->matrix[k] = t->matrix[k];
+  *handle = obj->handle = g_colour_handle.fetch_add(1);
+  return M355_OK;
+}
+int m355_colour_destroy(m355_ctx* c, int handle)
+{
+  if (!c) return fail(M355_ERR_INVALID, "m355_colour_destroy: no context");
+  for (auto& q : c->colour) {
+    if (!handle || q.handle != handle) continue;
+    hipSetDevice(c->device);
+    sync_all(c);                                              /* (an export may still be reading the tables) */
+    hipFree(q.dev);
+    q = m355_ctx::ColourObj();
+    return M355_OK;
+  }
+  return fail(M355_ERR_INVALID, "m355_colour_destroy: %d is no live colour transform of this context", handle);
+}
+int m355_colour_preset(const m355_colour_preset_desc* d, m355_colour_tables* out)
+{
+  if (m355_cp_build(d, out)) return fail(M355_ERR_INVALID, "m355_colour_preset: null pointer, unknown code point, tone or reserved, negative nits, or peak below white");
+  return M355_OK;
+}
+int m355_colour_pixel(const m355_colour_tables* t, const uint32_t rgb16[3], int samples, uint32_t out[3])
+{
+  if (!t || !rgb16 || !out || (samples != M355_RGB_U8 && samples != M355_RGB_U16) || m355_ct_tables_check(t))
+    return fail(M355_ERR_INVALID, "m355_colour_pixel: null pointer, unknown samples %d, or tables outside their bounds", samples);
+  m355_ct_pixel(t, rgb16, samples, out);
+  return M355_OK;
+}
 extern "C++" {             /* (templates over the descriptors and the kernel arguments) */
 /* What the kernel arguments of k_export_resized_rgb.hip take from a plan.  plan_sources: the rectangle's first samples and the two pitches, into the
  * launch's or the slice's record.  plan_geometry: the source size on both grids, the tile width, the tiles per row of tiles and the units into g (the
@@ -812,7 +886,8 @@ int m355_frame_export_resized_rgb_opts(m355_ctx* c, int h, const m355_resize_rgb
   if (rc) return rc;
   Frame* f = P.f;
   m355_export_opts o;
-  rc = opts_check(who, opts, f, true, o);
+  ColourArgs colour = {};
+  rc = opts_check(who, c, opts, f, true, o, &colour);
   if (rc) return rc;
   const int filter = o.filter;
   rc = resize_check(who, &P, 0, e->out_width, e->out_height, filter);
@@ -822,6 +897,7 @@ int m355_frame_export_resized_rgb_opts(m355_ctx* c, int h, const m355_resize_rgb
   int db = 1;
   rc = rgb_desc_check(who, e, f, e->out_width, a, &planar, &db);
   if (rc) return rc;
+  if ((rc = colour_apply(colour, e, f, a)) != 0) return rc;
   plan_sources(P, a);
   plan_geometry(P, e->out_width, e->out_height, filter, o.chroma_loc, a, a);
   a.cf = f->cf; a.planar = planar; a.bdl = f->bdl; a.bdc = f->bdc; a.chroma_loc = o.chroma_loc;
@@ -934,11 +1010,13 @@ int m355_frames_export_tensor_opts(m355_ctx* c, const int* frames, int n, const 
     if ((rc = batch_frame_check(who, frames, i, P, e->width == 0)) != 0) return rc;
   }
   m355_export_opts o;
-  if ((rc = opts_check(who, opts, P[0].f, true, o)) != 0) return rc;
+  ColourArgs colour = {};
+  if ((rc = opts_check(who, c, opts, P[0].f, true, o, &colour)) != 0) return rc;
   const int filter = o.filter;
   if ((rc = resize_check(who, P, 0, e->out_width, e->out_height, filter)) != 0) return rc;
   ExportTensorArgs a = {};
   if ((rc = tensor_desc_check(who, e, n, P[0].f, a, &eb)) != 0) return rc;
+  if ((rc = colour_apply(colour, e, P[0].f, a)) != 0) return rc;
   plan_geometry(P[0], e->out_width, e->out_height, filter, o.chroma_loc, a, a);
   a.chroma_loc = o.chroma_loc;
   for (int i = 0; i < n; i++) plan_sources(P[i], a.fr[i]);
@@ -973,11 +1051,13 @@ int m355_frames_export_tensor_rois_opts(m355_ctx* c, const int* frames, const m3
     if ((rc = batch_frame_check(who, frames, i, P, false)) != 0) return rc;
   }
   m355_export_opts o;
-  if ((rc = opts_check(who, opts, P[0].f, true, o)) != 0) return rc;
+  ColourArgs colour = {};
+  if ((rc = opts_check(who, c, opts, P[0].f, true, o, &colour)) != 0) return rc;
   const int filter = o.filter;
   if ((rc = resize_check(who, P, n, e->out_width, e->out_height, filter)) != 0) return rc;
   ExportTensorRoisArgs a = {};
   if ((rc = tensor_desc_check(who, e, n, P[0].f, a, &eb)) != 0) return rc;
+  if ((rc = colour_apply(colour, e, P[0].f, a)) != 0) return rc;
   a.chroma_loc = o.chroma_loc;
   for (int i = 0; i < n; i++) {
     ExportTensorRoi& r = a.fr[i];

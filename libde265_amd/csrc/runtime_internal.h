@@ -278,6 +278,10 @@ struct m355_ctx {
   /* pinned staging buffer of the blocking frame transfers (m355_frame_upload / _download / _fill, MD5 of m355_frame_hash): the copy itself is queued on the
      stream that last wrote the frame, between pinned memory and the frame (frame_stage_* in runtime.hip) */
   void* stage = nullptr; size_t stage_bytes = 0;
+  /* m355_colour_create: the colour transform objects of the composed exports — the tables in device memory, the matrix for the kernel arguments.
+     handle == 0: the slot is free; handles count up over all contexts of the process and are never given twice */
+  struct ColourObj { int handle = 0; uint8_t* dev = nullptr; int32_t matrix[9] = {}; };
+  ColourObj colour[M355_COLOUR_OBJECTS];
   /* m355_decode_batch: ring of picture-record arrays (pinned staging + device copy + the batch's ticket word); a slot's event is
      recorded behind the batch's k_intra — what the pictures' filter stages wait for, and what guards the slot's reuse */
   struct BatchSlot { DevPic* host = nullptr; DevPic* dev = nullptr; uint32_t* ticket = nullptr; hipEvent_t ev = nullptr; bool pending = false; };

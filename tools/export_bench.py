@@ -34,6 +34,10 @@
       (Cq), (Cw), (CQ8), (CQ32) — 8K to 1080p is ratio exactly 4 — and their ratios to the triangle's rows in the result line; no bar is set for them
   --chroma-loc N (1, 2 or 3; may repeat) adds, beside (k), (l), (m), (n), (q), (w), (Q8), (Q32), the same calls through the _opts entry points with
       chroma sample location type N as (LNk), (LNl), (LNm), (LNn), (LNq), (LNw), (LNQ8), (LNQ32), and their ratios to the type-0 rows; no bar is set
+  --colour adds, beside (q), (w), (z8), (z32), (T32), (Q8), (Q32), the same calls through the _opts entry points with a colour transform (the preset PQ /
+      BT.2020 -> gamma 2.4 / BT.709, Reinhard, 203 / 1000 nits) as (Kq), (Kw), (Kz8), (Kz32), (KT32), (KQ8), (KQ32), on frames of seeded RANDOM samples — the
+      stage gathers from its tables by the pixel's value, so a constant frame would show its best case —, the colour-off calls on those frames as (K0q),
+      (K0z32), and the ratios in the result line; no bar is set for them
 
 and, beside them, m355_measure_copy_rate for the frame's byte count.  Every figure is the median of --iters launches; (b) is measured in
 --rounds separate rounds spread over the run, and the spread of their medians is the margin (c), (d), (g)-(j) and (m)-(p) are held against: a scaled or resized export reads exactly (b)'s source bytes and writes at most a
@@ -76,6 +80,7 @@ def main():
     ap.add_argument("--filter", choices=("triangle", "cubic"), default="triangle", help="cubic: also measure the cubic filter's rows beside the triangle's")
     ap.add_argument("--chroma-loc", type=int, choices=(1, 2, 3), action="append", default=[],
                     help="also measure this chroma sample location type's rows beside the type-0 rows (may repeat)")
+    ap.add_argument("--colour", action="store_true", help="also measure the composed exports with a colour transform, on frames of random samples")
     args = ap.parse_args()
 
     lib = capi.Library()
@@ -129,8 +134,10 @@ def main():
             return lambda: lib.check(lib.lib.m355_frame_export_scaled(ctx.h, frame, ctypes.byref(d), log2_scale))
         return lambda: lib.check(lib.lib.m355_frame_export(ctx.h, frame, ctypes.byref(d)))
 
-    def opts_of(filter, loc):
-        return capi.ExportOpts(filter=filter, chroma_loc=loc)
+    def opts_of(filter, loc, colour=0):
+        o = capi.ExportOpts(filter=filter, chroma_loc=loc)
+        o.reserved[0] = colour
+        return o
 
     def export_resized(layout, samples, out_size, elem, filter=0, loc=0):
         d = capi.ResizeDesc(layout=layout, samples=samples, out_width=out_size[0], out_height=out_size[1])
@@ -156,12 +163,12 @@ def main():
             return lambda: lib.check(lib.lib.m355_frame_export_rgb_opts(ctx.h, frame, ctypes.byref(d), ctypes.byref(o)))
         return lambda: lib.check(lib.lib.m355_frame_export_rgb(ctx.h, frame, ctypes.byref(d)))
 
-    def export_resized_rgb(layout, samples, out_size, elem, filter=0, loc=0):
+    def export_resized_rgb(layout, samples, out_size, elem, filter=0, loc=0, colour=0, frame=frame):
         d = capi.ResizeRgbDesc(layout=layout, samples=samples, matrix=capi.MATRIX_BT709, full_range=0, out_width=out_size[0], out_height=out_size[1])
         for k in range(3):
             d.dst[k] = rgb_dst[k]; d.pitch[k] = out_size[0] * elem * (1 if layout == capi.RGB_PLANAR else 3)
-        if loc:
-            o = opts_of(filter, loc)
+        if loc or colour:
+            o = opts_of(filter, loc, colour)
             return lambda: lib.check(lib.lib.m355_frame_export_resized_rgb_opts(ctx.h, frame, ctypes.byref(d), ctypes.byref(o)))
         if filter:
             return lambda: lib.check(lib.lib.m355_frame_export_resized_rgb_filtered(ctx.h, frame, ctypes.byref(d), filter))
@@ -179,7 +186,7 @@ def main():
             d.dst[k] = rgb_dst[k]; d.pitch[k] = size[0] * elem * (1 if layout == capi.RGB_PLANAR else 3)
         return lambda: lib.check(lib.lib.m355_frame_export_rgb(ctx.h, small[size], ctypes.byref(d)))
 
-    def export_tensor(frames, layout, dtype, samples, out_size, rect=None, filter=0, loc=0):
+    def export_tensor(frames, layout, dtype, samples, out_size, rect=None, filter=0, loc=0, colour=0):
         eb = 4 if dtype == capi.TENSOR_F32 else 2
         ow, oh = out_size
         row = ow * eb * (3 if layout == capi.TENSOR_NHWC else 1)
@@ -194,14 +201,14 @@ def main():
         assert len(frames) * 3 * ow * oh * eb <= W * 3 * H
         d.dst = rgb_dst[0]
         arr = (ctypes.c_int * len(frames))(*frames)
-        if loc:
-            o = opts_of(filter, loc)
+        if loc or colour:
+            o = opts_of(filter, loc, colour)
             return lambda: lib.check(lib.lib.m355_frames_export_tensor_opts(ctx.h, arr, len(frames), ctypes.byref(d), ctypes.byref(o)))
         if filter:
             return lambda: lib.check(lib.lib.m355_frames_export_tensor_filtered(ctx.h, arr, len(frames), ctypes.byref(d), filter))
         return lambda: lib.check(lib.lib.m355_frames_export_tensor(ctx.h, arr, len(frames), ctypes.byref(d)))
 
-    def export_tensor_rois(frames, rois, layout, dtype, samples, out_size, filter=0, loc=0):
+    def export_tensor_rois(frames, rois, layout, dtype, samples, out_size, filter=0, loc=0, colour=0):
         eb = 4 if dtype == capi.TENSOR_F32 else 2
         ow, oh = out_size
         row = ow * eb * (3 if layout == capi.TENSOR_NHWC else 1)
@@ -215,8 +222,8 @@ def main():
         d.dst = rgb_dst[0]
         arr = (ctypes.c_int * len(frames))(*frames)
         ra = (capi.TensorRoi * len(rois))(*[capi.TensorRoi(*r) for r in rois])
-        if loc:
-            o = opts_of(filter, loc)
+        if loc or colour:
+            o = opts_of(filter, loc, colour)
             return lambda: lib.check(lib.lib.m355_frames_export_tensor_rois_opts(ctx.h, arr, ra, len(frames), ctypes.byref(d), ctypes.byref(o)))
         if filter:
             return lambda: lib.check(lib.lib.m355_frames_export_tensor_rois_filtered(ctx.h, arr, ra, len(frames), ctypes.byref(d), filter))
@@ -340,6 +347,35 @@ def main():
             key = n[2:].split("_")[0] + "_"
             sited_of[n] = [t for t in variants if t.startswith(key)][0]
         variants.update(rows)
+    colour_of, made = {}, []           # a row with a colour transform -> the colour-off row of the same call
+    if args.colour:
+        import numpy as np
+        rng_c = np.random.default_rng(ROI_SEED)
+
+        def random_frame(w, h):
+            f = ctx.frame_create(w, h, 1, BD, BD)
+            ctx.frame_upload(f, [rng_c.integers(0, 1 << BD, (ph, pw)).astype(np.uint16) for pw, ph in ((w, h), (w // 2, h // 2), (w // 2, h // 2))])
+            made.append(f)
+            return f
+
+        cframe, cbatch = random_frame(W, H), [random_frame(1920, 1088) for _ in range(32)]
+        K = ctx.colour_create(lib.colour_preset(16, 9, 1, 1, capi.TONE_REINHARD, 203, 1000))
+        rois32 = [r + (capi.ROI_MIRROR if k % 4 == 3 else 0,) for k, r in enumerate(roi_list)]
+        rows = {
+            "K0q_random_resized_rgb_u8_packed_1080p": export_resized_rgb(capi.RGB_PACKED, capi.RGB_U8, (1920, 1080), 1, frame=cframe),
+            "K0z32_random_tensor_f16_nchw_224_batch32": export_tensor(cbatch, capi.TENSOR_NCHW, capi.TENSOR_F16, capi.RGB_U8, (224, 224), SQUARE),
+            "Kq_colour_resized_rgb_u8_packed_1080p": export_resized_rgb(capi.RGB_PACKED, capi.RGB_U8, (1920, 1080), 1, colour=K, frame=cframe),
+            "Kw_colour_tensor_f16_nhwc_1080p": export_tensor([cframe], capi.TENSOR_NHWC, capi.TENSOR_F16, capi.RGB_U16, (1920, 1080), colour=K),
+            "Kz8_colour_tensor_f16_nchw_224_batch8": export_tensor(cbatch[:8], capi.TENSOR_NCHW, capi.TENSOR_F16, capi.RGB_U8, (224, 224), SQUARE, colour=K),
+            "Kz32_colour_tensor_f16_nchw_224_batch32": export_tensor(cbatch, capi.TENSOR_NCHW, capi.TENSOR_F16, capi.RGB_U8, (224, 224), SQUARE, colour=K),
+            "KT32_colour_tensor_rois_f16_nchw_224_32_regions": export_tensor_rois([cbatch[0]] * 32, rois32, capi.TENSOR_NCHW, capi.TENSOR_F16, capi.RGB_U8, (224, 224), colour=K),
+        }
+        rows.update({"KQ%d_colour_tensor_rois_f16_nchw_224_of_896_batch%d" % (n, n):
+                     export_tensor_rois(cbatch[:n], [SQUARE4 + (0,)] * n, capi.TENSOR_NCHW, capi.TENSOR_F16, capi.RGB_U8, (224, 224), colour=K) for n in (8, 32)})
+        for n in rows:
+            key = n[2 if n[1] == "0" else 1:].split("_")[0] + "_"
+            colour_of[n] = [t for t in variants if t.startswith(key)][0]
+        variants.update(rows)
     scaled = [n for n in variants if n[0] in "ghijmnop"]
     ms = {n: [] for n in variants}
     for _ in range(args.rounds):
@@ -376,6 +412,8 @@ def main():
                         "us_per_region": {n: 1e3 * res[n] / 32 for n in ("S32_tensor_f16_nchw_224_x32_regions", "T32_tensor_rois_f16_nchw_224_32_regions")}},
         "cubic_over_triangle": {n: res[n] / res[t] for n, t in cubic_of.items()},
         "sited_over_type_0": {n: res[n] / res[t] for n, t in sited_of.items()},
+        "colour_over_colour_off": {n: res[n] / res[t] for n, t in colour_of.items()},
+        "colour_rounds_ms": {n: ms[n] for n in colour_of},
         "copy_rate_GBps_same_bytes": ctx.measure_copy_rate(frame_bytes, 9),
         "bars": {"b_le_a": res["b_native_planar"] <= res["a_memcpy2d_x3"],
                  "c_le_b_plus_spread": res["c_msb16_semiplanar_crop8"] <= res["b_native_planar"] + spread,
@@ -400,7 +438,7 @@ def main():
             f.write(line + "\n")
     for p in src + dst + rgb_dst:
         ctx.device_free(p)
-    for f in list(small.values()) + batch:
+    for f in list(small.values()) + batch + made:
         ctx.frame_destroy(f)
     ctx.close()
 
