@@ -1701,6 +1701,85 @@ static int frame_and_rect(Glue* g, const de265_image* img, const int rect[4], in
   return g->frame_of_slot[slot];
 }
 
+/* The chroma sample location type the picture's stream signals: its SPS' vui.chroma_sample_loc_type_top_field (0..5), or 0 where the SPS has no VUI,
+ * the VUI no chroma_loc_info, or the picture is not 4:2:0 (the standard defines the field for 4:2:0 alone). */
+LIBDE265_API int m355_glue_image_chroma_loc(const struct de265_image* img)
+{
+  if (!img || !img->has_sps()) return 0;
+  const seq_parameter_set& sps = img->get_sps();
+  if (sps.chroma_format_idc != 1 || !sps.vui_parameters_present_flag || !sps.vui.chroma_loc_info_present_flag) return 0;
+  return sps.vui.chroma_sample_loc_type_top_field;
+}
+
+/* What the six export bodies below share.  begin: every check that needs neither the worker nor the lock, in this order — the backend
+ * (M355_ERR_NO_DEVICE), the call's own pointers (`args`: what the body found of its arrays), the n images of ONE decoder, that decoder's glue and its
+ * single rank —, then what the call leaves to the stream, resolved from imgs[0]: *matrix == -1 (de265_get_image_matrix_coefficients: 1, 2 -> BT.709;
+ * 5, 6 -> BT.601; 9 -> BT.2020; anything else is M355_ERR_INVALID), *full_range == -1 and chroma_loc == -1 (the bottom-sited types 4 and 5 are
+ * M355_ERR_INVALID like an unmapped matrix; every other value is the backend's to judge), into the call's options `o`.  Only then does it wait for the
+ * worker to have enqueued every image and take api_mu, which the object holds until it goes: a call these checks reject has waited for nothing.
+ * finish: the consumer's stream ordered behind the export of `frame`; the decoder's error text is written only when the backend failed. */
+extern "C++" {
+namespace {
+struct ExportCall {
+  Api* A = nullptr;
+  Glue* g = nullptr;
+  m355_export_opts o;
+  std::unique_lock<std::mutex> api_lock;
+
+  int begin(const de265_image* const* imgs, int n, bool args, int* matrix = nullptr, int* full_range = nullptr, int filter = 0, int chroma_loc = 0, int colour = 0)
+  {
+    A = api();
+    if (!A) return M355_ERR_NO_DEVICE;
+    if (!args || !imgs || n < 1 || n > M355_TENSOR_MAX_FRAMES) return M355_ERR_INVALID;
+    for (int i = 0; i < n; i++) if (!imgs[i] || !imgs[i]->decctx || imgs[i]->decctx != imgs[0]->decctx) return M355_ERR_INVALID;
+    g = glue_of(imgs[0]->decctx);
+    if (!g || g->n_ranks > 1) return M355_ERR_INVALID;
+    if (matrix && *matrix == -1) {
+      const int mc = de265_get_image_matrix_coefficients(imgs[0]);
+      if (mc == 1 || mc == 2) *matrix = M355_MATRIX_BT709;
+      else if (mc == 5 || mc == 6) *matrix = M355_MATRIX_BT601;
+      else if (mc == 9) *matrix = M355_MATRIX_BT2020;
+      else return M355_ERR_INVALID;
+    }
+    if (full_range && *full_range == -1) *full_range = de265_get_image_full_range_flag(imgs[0]) ? 1 : 0;
+    if (chroma_loc == -1) {
+      chroma_loc = m355_glue_image_chroma_loc(imgs[0]);
+      if (chroma_loc > 3) return M355_ERR_INVALID;
+    }
+    memset(&o, 0, sizeof(o));
+    o.filter = filter; o.chroma_loc = chroma_loc; o.colour = colour;
+    for (int i = 0; i < n; i++) wait_submitted(g, imgs[i]->get_ID());
+    api_lock = std::unique_lock<std::mutex>(g->api_mu);
+    return M355_OK;
+  }
+  int finish(int rc, int frame, void* consumer_stream)
+  {
+    if (rc == M355_OK) rc = A->m355_frame_export_order(g->mctx, frame, consumer_stream);
+    if (rc != M355_OK) g->error = A->m355_last_error();
+    return rc;
+  }
+};
+/* the luma rectangle r and the destination planes into a descriptor of the single-image exports */
+template <class D> void rect_and_planes(D& d, const int r[4], void* const dst[3], const int64_t pitch[3])
+{
+  d.x0 = r[0]; d.y0 = r[1]; d.width = r[2]; d.height = r[3];
+  for (int c = 0; c < 3; c++) { d.dst[c] = dst[c]; d.pitch[c] = pitch[c]; }
+}
+/* the descriptor of the two tensor exports but for its rectangle, which stays zero */
+m355_tensor_desc tensor_desc(int layout, int dtype, int samples, int matrix, int full_range, const int out_size[2], const float scale[3], const float bias[3],
+                             void* dst, int64_t stride_n, int64_t stride_c, int64_t stride_h)
+{
+  m355_tensor_desc d;
+  memset(&d, 0, sizeof(d));
+  d.layout = layout; d.dtype = dtype; d.samples = samples; d.matrix = matrix; d.full_range = full_range;
+  d.out_width = out_size[0]; d.out_height = out_size[1];
+  for (int c = 0; c < 3; c++) { d.scale[c] = scale[c]; d.bias[c] = bias[c]; }
+  d.dst = dst; d.stride_n = stride_n; d.stride_c = stride_c; d.stride_h = stride_h;
+  return d;
+}
+}
+}
+
 /* The other way out of the decoder, for a consumer on the same GPU (not part of de265.h, which stays as it is): the picture's DEVICE frame
  * exported into device memory of the caller (m355_frame_export: layout / samples = M355_EXPORT_*; rect = {x0, y0, width, height} in luma
  * samples, NULL: the image's conformance window), and the consumer's stream ordered behind the export (m355_frame_export_order).  Nothing
@@ -1711,25 +1790,17 @@ static int frame_and_rect(Glue* g, const de265_image* img, const int rect[4], in
 static int export_image(const struct de265_image* img, int layout, int samples, const int rect[4], int log2_scale, void* const dst[3],
                         const int64_t pitch[3], void* consumer_stream)
 {
-  Api* A = api();
-  if (!A) return M355_ERR_NO_DEVICE;
-  if (!img || !img->decctx || !dst || !pitch) return M355_ERR_INVALID;
-  Glue* g = glue_of(img->decctx);
-  if (!g || g->n_ranks > 1) return M355_ERR_INVALID;
-  wait_submitted(g, img->get_ID());
-  std::lock_guard<std::mutex> api_lock(g->api_mu);
+  ExportCall x;
+  const int rc = x.begin(&img, 1, dst && pitch);
+  if (rc != M355_OK) return rc;
   int r[4];
-  const int frame = frame_and_rect(g, img, rect, r);
+  const int frame = frame_and_rect(x.g, img, rect, r);
   if (frame < 0) return M355_ERR_INVALID;
   m355_export_desc d;
   memset(&d, 0, sizeof(d));
   d.layout = layout; d.samples = samples;
-  d.x0 = r[0]; d.y0 = r[1]; d.width = r[2]; d.height = r[3];
-  for (int c = 0; c < 3; c++) { d.dst[c] = dst[c]; d.pitch[c] = pitch[c]; }
-  int rc = log2_scale ? A->m355_frame_export_scaled(g->mctx, frame, &d, log2_scale) : A->m355_frame_export(g->mctx, frame, &d);
-  if (rc == M355_OK) rc = A->m355_frame_export_order(g->mctx, frame, consumer_stream);
-  if (rc != M355_OK) g->error = A->m355_last_error();
-  return rc;
+  rect_and_planes(d, r, dst, pitch);
+  return x.finish(log2_scale ? x.A->m355_frame_export_scaled(x.g->mctx, frame, &d, log2_scale) : x.A->m355_frame_export(x.g->mctx, frame, &d), frame, consumer_stream);
 }
 LIBDE265_API int m355_glue_export_image(const struct de265_image* img, int layout, int samples, const int rect[4], void* const dst[3],
                                         const int64_t pitch[3], void* consumer_stream)
@@ -1743,15 +1814,6 @@ LIBDE265_API int m355_glue_export_image_scaled(const struct de265_image* img, in
 {
   if (log2_scale < 0 || log2_scale > 3) return M355_ERR_INVALID;
   return export_image(img, layout, samples, rect, log2_scale, dst, pitch, consumer_stream);
-}
-/* The chroma sample location type the picture's stream signals: its SPS' vui.chroma_sample_loc_type_top_field (0..5), or 0 where the SPS has no VUI,
- * the VUI no chroma_loc_info, or the picture is not 4:2:0 (the standard defines the field for 4:2:0 alone). */
-LIBDE265_API int m355_glue_image_chroma_loc(const struct de265_image* img)
-{
-  if (!img || !img->has_sps()) return 0;
-  const seq_parameter_set& sps = img->get_sps();
-  if (sps.chroma_format_idc != 1 || !sps.vui_parameters_present_flag || !sps.vui.chroma_loc_info_present_flag) return 0;
-  return sps.vui.chroma_sample_loc_type_top_field;
 }
 /* The colour description the picture's stream signals: its SPS' vui.colour_primaries and vui.transfer_characteristics (the H.265 code points of Tables E.3 /
  * E.4), or 2 / 2, unspecified, where the SPS has no VUI or the VUI no colour description.  -> M355_OK, or M355_ERR_INVALID for null pointers. */
@@ -1801,18 +1863,6 @@ LIBDE265_API int m355_glue_colour_preset_for_image(const struct de265_image* img
   d.out_transfer = out_transfer; d.out_primaries = out_primaries; d.tone = tone; d.white_nits = white_nits; d.peak_nits = peak_nits;
   return A->m355_colour_preset(&d, tables);
 }
-/* the options of a _sited call: chroma_loc = -1 is what the stream signals (of imgs[0] for a batch, like matrix = -1), where the bottom-sited types 4
- * and 5 are M355_ERR_INVALID like an unmapped matrix; every other value is the backend's to judge */
-static int sited_opts(const de265_image* img, int filter, int chroma_loc, m355_export_opts* o)
-{
-  memset(o, 0, sizeof(*o));
-  if (chroma_loc == -1) {
-    chroma_loc = m355_glue_image_chroma_loc(img);
-    if (chroma_loc > 3) return M355_ERR_INVALID;
-  }
-  o->filter = filter; o->chroma_loc = chroma_loc;
-  return M355_OK;
-}
 /* The picture as R'G'B' (m355_frame_export_rgb: layout / samples = M355_RGB_*, one chroma reconstruction filter, integer-exact), with the waiting
  * behaviour of m355_glue_export_image: the only wait is for the worker to have enqueued the picture.  matrix = M355_MATRIX_*, or -1: what the stream
  * signals (de265_get_image_matrix_coefficients: 1 -> BT.709; 5, 6 -> BT.601; 9 -> BT.2020 non-constant luminance; 2, unspecified -> BT.709; anything
@@ -1826,35 +1876,17 @@ static int sited_opts(const de265_image* img, int filter, int chroma_loc, m355_e
 LIBDE265_API int m355_glue_export_image_rgb_sited(const struct de265_image* img, int layout, int samples, int matrix, int full_range, const int rect[4],
                                                   void* const dst[3], const int64_t pitch[3], int filter, int chroma_loc, void* consumer_stream)
 {
-  Api* A = api();
-  if (!A) return M355_ERR_NO_DEVICE;
-  if (!img || !img->decctx || !dst || !pitch) return M355_ERR_INVALID;
-  Glue* g = glue_of(img->decctx);
-  if (!g || g->n_ranks > 1) return M355_ERR_INVALID;
-  if (matrix == -1) {
-    const int mc = de265_get_image_matrix_coefficients(img);
-    if (mc == 1 || mc == 2) matrix = M355_MATRIX_BT709;
-    else if (mc == 5 || mc == 6) matrix = M355_MATRIX_BT601;
-    else if (mc == 9) matrix = M355_MATRIX_BT2020;
-    else return M355_ERR_INVALID;
-  }
-  if (full_range == -1) full_range = de265_get_image_full_range_flag(img) ? 1 : 0;
-  m355_export_opts o;
-  if (sited_opts(img, filter, chroma_loc, &o) != M355_OK) return M355_ERR_INVALID;
-  wait_submitted(g, img->get_ID());
-  std::lock_guard<std::mutex> api_lock(g->api_mu);
+  ExportCall x;
+  const int rc = x.begin(&img, 1, dst && pitch, &matrix, &full_range, filter, chroma_loc);
+  if (rc != M355_OK) return rc;
   int r[4];
-  const int frame = frame_and_rect(g, img, rect, r);
+  const int frame = frame_and_rect(x.g, img, rect, r);
   if (frame < 0) return M355_ERR_INVALID;
   m355_rgb_desc d;
   memset(&d, 0, sizeof(d));
   d.layout = layout; d.samples = samples; d.matrix = matrix; d.full_range = full_range;
-  d.x0 = r[0]; d.y0 = r[1]; d.width = r[2]; d.height = r[3];
-  for (int c = 0; c < 3; c++) { d.dst[c] = dst[c]; d.pitch[c] = pitch[c]; }
-  int rc = A->m355_frame_export_rgb_opts(g->mctx, frame, &d, &o);
-  if (rc == M355_OK) rc = A->m355_frame_export_order(g->mctx, frame, consumer_stream);
-  if (rc != M355_OK) g->error = A->m355_last_error();
-  return rc;
+  rect_and_planes(d, r, dst, pitch);
+  return x.finish(x.A->m355_frame_export_rgb_opts(x.g->mctx, frame, &d, &x.o), frame, consumer_stream);
 }
 LIBDE265_API int m355_glue_export_image_rgb(const struct de265_image* img, int layout, int samples, int matrix, int full_range, const int rect[4],
                                             void* const dst[3], const int64_t pitch[3], void* consumer_stream)
@@ -1869,28 +1901,18 @@ LIBDE265_API int m355_glue_export_image_rgb(const struct de265_image* img, int l
 LIBDE265_API int m355_glue_export_image_resized_sited(const struct de265_image* img, int layout, int samples, const int rect[4], const int out_size[2],
                                                       void* const dst[3], const int64_t pitch[3], int filter, int chroma_loc, void* consumer_stream)
 {
-  Api* A = api();
-  if (!A) return M355_ERR_NO_DEVICE;
-  if (!img || !img->decctx || !out_size || !dst || !pitch) return M355_ERR_INVALID;
-  Glue* g = glue_of(img->decctx);
-  if (!g || g->n_ranks > 1) return M355_ERR_INVALID;
-  m355_export_opts o;
-  if (sited_opts(img, filter, chroma_loc, &o) != M355_OK) return M355_ERR_INVALID;
-  wait_submitted(g, img->get_ID());
-  std::lock_guard<std::mutex> api_lock(g->api_mu);
+  ExportCall x;
+  const int rc = x.begin(&img, 1, out_size && dst && pitch, nullptr, nullptr, filter, chroma_loc);
+  if (rc != M355_OK) return rc;
   int r[4];
-  const int frame = frame_and_rect(g, img, rect, r);
+  const int frame = frame_and_rect(x.g, img, rect, r);
   if (frame < 0) return M355_ERR_INVALID;
   m355_resize_desc d;
   memset(&d, 0, sizeof(d));
   d.layout = layout; d.samples = samples;
-  d.x0 = r[0]; d.y0 = r[1]; d.width = r[2]; d.height = r[3];
   d.out_width = out_size[0]; d.out_height = out_size[1];
-  for (int c = 0; c < 3; c++) { d.dst[c] = dst[c]; d.pitch[c] = pitch[c]; }
-  int rc = A->m355_frame_export_resized_opts(g->mctx, frame, &d, &o);
-  if (rc == M355_OK) rc = A->m355_frame_export_order(g->mctx, frame, consumer_stream);
-  if (rc != M355_OK) g->error = A->m355_last_error();
-  return rc;
+  rect_and_planes(d, r, dst, pitch);
+  return x.finish(x.A->m355_frame_export_resized_opts(x.g->mctx, frame, &d, &x.o), frame, consumer_stream);
 }
 LIBDE265_API int m355_glue_export_image_resized_filtered(const struct de265_image* img, int layout, int samples, const int rect[4], const int out_size[2],
                                                          void* const dst[3], const int64_t pitch[3], int filter, void* consumer_stream)
@@ -1910,37 +1932,18 @@ LIBDE265_API int m355_glue_export_image_resized_rgb_colour(const struct de265_im
                                                            const int out_size[2], void* const dst[3], const int64_t pitch[3], int filter, int chroma_loc,
                                                            int colour, void* consumer_stream)
 {
-  Api* A = api();
-  if (!A) return M355_ERR_NO_DEVICE;
-  if (!img || !img->decctx || !out_size || !dst || !pitch) return M355_ERR_INVALID;
-  Glue* g = glue_of(img->decctx);
-  if (!g || g->n_ranks > 1) return M355_ERR_INVALID;
-  if (matrix == -1) {
-    const int mc = de265_get_image_matrix_coefficients(img);
-    if (mc == 1 || mc == 2) matrix = M355_MATRIX_BT709;
-    else if (mc == 5 || mc == 6) matrix = M355_MATRIX_BT601;
-    else if (mc == 9) matrix = M355_MATRIX_BT2020;
-    else return M355_ERR_INVALID;
-  }
-  if (full_range == -1) full_range = de265_get_image_full_range_flag(img) ? 1 : 0;
-  m355_export_opts o;
-  if (sited_opts(img, filter, chroma_loc, &o) != M355_OK) return M355_ERR_INVALID;
-  o.colour = colour;
-  wait_submitted(g, img->get_ID());
-  std::lock_guard<std::mutex> api_lock(g->api_mu);
+  ExportCall x;
+  const int rc = x.begin(&img, 1, out_size && dst && pitch, &matrix, &full_range, filter, chroma_loc, colour);
+  if (rc != M355_OK) return rc;
   int r[4];
-  const int frame = frame_and_rect(g, img, rect, r);
+  const int frame = frame_and_rect(x.g, img, rect, r);
   if (frame < 0) return M355_ERR_INVALID;
   m355_resize_rgb_desc d;
   memset(&d, 0, sizeof(d));
   d.layout = layout; d.samples = samples; d.matrix = matrix; d.full_range = full_range;
-  d.x0 = r[0]; d.y0 = r[1]; d.width = r[2]; d.height = r[3];
   d.out_width = out_size[0]; d.out_height = out_size[1];
-  for (int c = 0; c < 3; c++) { d.dst[c] = dst[c]; d.pitch[c] = pitch[c]; }
-  int rc = A->m355_frame_export_resized_rgb_opts(g->mctx, frame, &d, &o);
-  if (rc == M355_OK) rc = A->m355_frame_export_order(g->mctx, frame, consumer_stream);
-  if (rc != M355_OK) g->error = A->m355_last_error();
-  return rc;
+  rect_and_planes(d, r, dst, pitch);
+  return x.finish(x.A->m355_frame_export_resized_rgb_opts(x.g->mctx, frame, &d, &x.o), frame, consumer_stream);
 }
 LIBDE265_API int m355_glue_export_image_resized_rgb_sited(const struct de265_image* img, int layout, int samples, int matrix, int full_range, const int rect[4],
                                                           const int out_size[2], void* const dst[3], const int64_t pitch[3], int filter, int chroma_loc,
@@ -1968,41 +1971,17 @@ LIBDE265_API int m355_glue_export_images_tensor_colour(const struct de265_image*
                                                        int64_t stride_n, int64_t stride_c, int64_t stride_h, int filter, int chroma_loc, int colour,
                                                        void* consumer_stream)
 {
-  Api* A = api();
-  if (!A) return M355_ERR_NO_DEVICE;
-  if (!imgs || n < 1 || n > M355_TENSOR_MAX_FRAMES || !out_size || !scale || !bias) return M355_ERR_INVALID;
-  for (int i = 0; i < n; i++) if (!imgs[i] || !imgs[i]->decctx || imgs[i]->decctx != imgs[0]->decctx) return M355_ERR_INVALID;
-  Glue* g = glue_of(imgs[0]->decctx);
-  if (!g || g->n_ranks > 1) return M355_ERR_INVALID;
-  if (matrix == -1) {
-    const int mc = de265_get_image_matrix_coefficients(imgs[0]);
-    if (mc == 1 || mc == 2) matrix = M355_MATRIX_BT709;
-    else if (mc == 5 || mc == 6) matrix = M355_MATRIX_BT601;
-    else if (mc == 9) matrix = M355_MATRIX_BT2020;
-    else return M355_ERR_INVALID;
-  }
-  if (full_range == -1) full_range = de265_get_image_full_range_flag(imgs[0]) ? 1 : 0;
-  m355_export_opts o;
-  if (sited_opts(imgs[0], filter, chroma_loc, &o) != M355_OK) return M355_ERR_INVALID;
-  o.colour = colour;
-  for (int i = 0; i < n; i++) wait_submitted(g, imgs[i]->get_ID());
-  std::lock_guard<std::mutex> api_lock(g->api_mu);
+  ExportCall x;
+  const int rc = x.begin(imgs, n, out_size && scale && bias, &matrix, &full_range, filter, chroma_loc, colour);
+  if (rc != M355_OK) return rc;
   int r[4], frames[M355_TENSOR_MAX_FRAMES];
   for (int i = n - 1; i >= 0; i--) {                             /* (last: imgs[0], whose rectangle is the batch's) */
-    frames[i] = frame_and_rect(g, imgs[i], rect, r);
+    frames[i] = frame_and_rect(x.g, imgs[i], rect, r);
     if (frames[i] < 0) return M355_ERR_INVALID;
   }
-  m355_tensor_desc d;
-  memset(&d, 0, sizeof(d));
-  d.layout = layout; d.dtype = dtype; d.samples = samples; d.matrix = matrix; d.full_range = full_range;
+  m355_tensor_desc d = tensor_desc(layout, dtype, samples, matrix, full_range, out_size, scale, bias, dst, stride_n, stride_c, stride_h);
   d.x0 = r[0]; d.y0 = r[1]; d.width = r[2]; d.height = r[3];
-  d.out_width = out_size[0]; d.out_height = out_size[1];
-  for (int c = 0; c < 3; c++) { d.scale[c] = scale[c]; d.bias[c] = bias[c]; }
-  d.dst = dst; d.stride_n = stride_n; d.stride_c = stride_c; d.stride_h = stride_h;
-  int rc = A->m355_frames_export_tensor_opts(g->mctx, frames, n, &d, &o);
-  if (rc == M355_OK) rc = A->m355_frame_export_order(g->mctx, frames[0], consumer_stream);
-  if (rc != M355_OK) g->error = A->m355_last_error();
-  return rc;
+  return x.finish(x.A->m355_frames_export_tensor_opts(x.g->mctx, frames, n, &d, &x.o), frames[0], consumer_stream);
 }
 LIBDE265_API int m355_glue_export_images_tensor_sited(const struct de265_image* const* imgs, int n, int layout, int dtype, int samples, int matrix, int full_range,
                                                       const int rect[4], const int out_size[2], const float scale[3], const float bias[3], void* dst,
@@ -2034,45 +2013,21 @@ LIBDE265_API int m355_glue_export_images_tensor_rois_colour(const struct de265_i
                                                             int64_t stride_n, int64_t stride_c, int64_t stride_h, int filter, int chroma_loc, int colour,
                                                             void* consumer_stream)
 {
-  Api* A = api();
-  if (!A) return M355_ERR_NO_DEVICE;
-  if (!imgs || !rois || n < 1 || n > M355_TENSOR_MAX_FRAMES || !out_size || !scale || !bias) return M355_ERR_INVALID;
-  for (int i = 0; i < n; i++) if (!imgs[i] || !imgs[i]->decctx || imgs[i]->decctx != imgs[0]->decctx) return M355_ERR_INVALID;
-  Glue* g = glue_of(imgs[0]->decctx);
-  if (!g || g->n_ranks > 1) return M355_ERR_INVALID;
-  if (matrix == -1) {
-    const int mc = de265_get_image_matrix_coefficients(imgs[0]);
-    if (mc == 1 || mc == 2) matrix = M355_MATRIX_BT709;
-    else if (mc == 5 || mc == 6) matrix = M355_MATRIX_BT601;
-    else if (mc == 9) matrix = M355_MATRIX_BT2020;
-    else return M355_ERR_INVALID;
-  }
-  if (full_range == -1) full_range = de265_get_image_full_range_flag(imgs[0]) ? 1 : 0;
-  m355_export_opts o;
-  if (sited_opts(imgs[0], filter, chroma_loc, &o) != M355_OK) return M355_ERR_INVALID;
-  o.colour = colour;
-  for (int i = 0; i < n; i++) wait_submitted(g, imgs[i]->get_ID());
-  std::lock_guard<std::mutex> api_lock(g->api_mu);
+  ExportCall x;
+  const int rc = x.begin(imgs, n, rois && out_size && scale && bias, &matrix, &full_range, filter, chroma_loc, colour);
+  if (rc != M355_OK) return rc;
   int frames[M355_TENSOR_MAX_FRAMES];
   m355_tensor_roi rr[M355_TENSOR_MAX_FRAMES];
   for (int i = 0; i < n; i++) {
     const int* q = rois[i];
     const bool window = !q[0] && !q[1] && !q[2] && !q[3];
     int r[4];
-    frames[i] = frame_and_rect(g, imgs[i], window ? nullptr : q, r);
+    frames[i] = frame_and_rect(x.g, imgs[i], window ? nullptr : q, r);
     if (frames[i] < 0) return M355_ERR_INVALID;
     rr[i].x0 = r[0]; rr[i].y0 = r[1]; rr[i].width = r[2]; rr[i].height = r[3]; rr[i].flags = q[4];
   }
-  m355_tensor_desc d;
-  memset(&d, 0, sizeof(d));
-  d.layout = layout; d.dtype = dtype; d.samples = samples; d.matrix = matrix; d.full_range = full_range;
-  d.out_width = out_size[0]; d.out_height = out_size[1];
-  for (int c = 0; c < 3; c++) { d.scale[c] = scale[c]; d.bias[c] = bias[c]; }
-  d.dst = dst; d.stride_n = stride_n; d.stride_c = stride_c; d.stride_h = stride_h;
-  int rc = A->m355_frames_export_tensor_rois_opts(g->mctx, frames, rr, n, &d, &o);
-  if (rc == M355_OK) rc = A->m355_frame_export_order(g->mctx, frames[0], consumer_stream);
-  if (rc != M355_OK) g->error = A->m355_last_error();
-  return rc;
+  const m355_tensor_desc d = tensor_desc(layout, dtype, samples, matrix, full_range, out_size, scale, bias, dst, stride_n, stride_c, stride_h);
+  return x.finish(x.A->m355_frames_export_tensor_rois_opts(x.g->mctx, frames, rr, n, &d, &x.o), frames[0], consumer_stream);
 }
 LIBDE265_API int m355_glue_export_images_tensor_rois_sited(const struct de265_image* const* imgs, const int (*rois)[5], int n, int layout, int dtype, int samples,
                                                            int matrix, int full_range, const int out_size[2], const float scale[3], const float bias[3], void* dst,

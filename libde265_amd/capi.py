@@ -499,37 +499,63 @@ class Context:
             out.append((ph, pw * (2 if layout == EXPORT_SEMIPLANAR and c == 1 else 1), np.dtype(dt)))
         return out
 
+    def _buffer(self, nbytes, host):
+        """a destination buffer — device memory, or with host=True pinned host memory —, every byte of which holds DEVICE_FILL -> pointer"""
+        if not host:
+            return self.device_alloc(nbytes)
+        p = self.L.lib.m355_host_alloc(nbytes)
+        if not p:
+            raise M355Error(4, self.L.error())
+        ctypes.memset(p, DEVICE_FILL, nbytes)
+        return p
+
+    def _buffer_free(self, p, host):
+        self.L.lib.m355_host_free(p) if host else self.device_free(p)
+
+    def _export_into_planes(self, f, shapes, desc, host, pad, call):
+        """what the four frame exports do with their destinations: a _buffer per entry (rows, n, dtype) of shapes, its pitch `pad` bytes LARGER than
+        the row — so rows start at addresses that are no multiple of a vector —, into desc.dst[k] / desc.pitch[k]; then call(), the export itself; if
+        anything raises, every buffer is freed again.  -> token for frame_export_finish"""
+        bufs = []
+        try:
+            for k, (rows, n, dt) in enumerate(shapes):
+                pitch = n * dt.itemsize + pad
+                bufs.append(self._buffer(rows * pitch, host))
+                desc.dst[k] = bufs[-1]; desc.pitch[k] = pitch
+            call()
+        except Exception:
+            for p in bufs:
+                self._buffer_free(p, host)
+            raise
+        return (f, shapes, bufs, [int(desc.pitch[k]) for k in range(len(shapes))], host)
+
+    def _export_entry(self, base, args, filter=0, filtered_entry=False, chroma_loc=0, opts_entry=False, colour=0):
+        """one export through the entry point its keywords pick: a chroma_loc or colour other than 0, or opts_entry, goes through base + "_opts" with
+        an ExportOpts of filter, chroma_loc and colour (opts_entry=None: with a NULL options pointer); else a filter other than 0, or filtered_entry,
+        through base + "_filtered"; else through base"""
+        lib = self.L.lib
+        if chroma_loc != 0 or colour != 0 or opts_entry or opts_entry is None:
+            self.L.check(getattr(lib, base + "_opts")(*args, self._opts(filter, chroma_loc, opts_entry, colour)))
+        elif filter != 0 or filtered_entry:
+            self.L.check(getattr(lib, base + "_filtered")(*args, filter))
+        else:
+            self.L.check(getattr(lib, base)(*args))
+
     def frame_export(self, f, layout, samples, rect=None, host=False, pad=20, log2_scale=0, scaled_entry=False):
         """start m355_frame_export of frame f (rect = (x0, y0, width, height) in luma samples, None: the whole frame) into buffers of its
         own — device memory, or with host=True pinned host memory —, every byte of which holds DEVICE_FILL beforehand; the pitch is `pad`
         bytes LARGER than the row, so rows start at addresses that are no multiple of a vector.  log2_scale != 0: downscaled by 1 << log2_scale
         (m355_frame_export_scaled; scaled_entry=True takes that entry point for log2_scale 0 too).  -> token for frame_export_finish"""
-        shapes = self.export_shapes(f, layout, samples, rect, log2_scale)
         desc = ExportDesc(layout=layout, samples=samples)
         if rect is not None:
             desc.x0, desc.y0, desc.width, desc.height = rect
-        bufs = []
-        try:
-            for k, (rows, n, dt) in enumerate(shapes):
-                pitch = n * dt.itemsize + pad
-                if host:
-                    p = self.L.lib.m355_host_alloc(rows * pitch)
-                    if not p:
-                        raise M355Error(4, self.L.error())
-                    ctypes.memset(p, DEVICE_FILL, rows * pitch)
-                else:
-                    p = self.device_alloc(rows * pitch)
-                bufs.append(p)
-                desc.dst[k] = p; desc.pitch[k] = pitch
+
+        def call():
             if log2_scale or scaled_entry:
                 self.L.check(self.L.lib.m355_frame_export_scaled(self.h, f, ctypes.byref(desc), log2_scale))
             else:
                 self.L.check(self.L.lib.m355_frame_export(self.h, f, ctypes.byref(desc)))
-        except Exception:
-            for p in bufs:
-                self.L.lib.m355_host_free(p) if host else self.device_free(p)
-            raise
-        return (f, shapes, bufs, [int(desc.pitch[k]) for k in range(len(shapes))], host)
+        return self._export_into_planes(f, self.export_shapes(f, layout, samples, rect, log2_scale), desc, host, pad, call)
 
     def resize_taps(self, src_n, dst_n, cosited, i, filter=0, filtered_entry=False):
         """row i of one axis of the resize filter (m355_resize_taps) -> (first source index, [coefficients]), or None for arguments it rejects"""
@@ -539,38 +565,14 @@ class Context:
                              opts_entry=False, colour=0):
         """start m355_frame_export_resized of frame f to out_size = (out_width, out_height) luma samples (rect = the source rectangle (x0, y0, width,
         height) in luma samples, None: the whole frame) into buffers of its own, made as frame_export makes them: every byte holds DEVICE_FILL
-        beforehand, the pitch is `pad` bytes larger than the row.  filter = FILTER_*: a filter other than 0, or filtered_entry, goes
-        through m355_frame_export_resized_filtered (so do the three helpers below through theirs).  chroma_loc = the chroma sample location
-        type: a type other than 0, or opts_entry, goes through m355_frame_export_resized_opts with an ExportOpts of filter and chroma_loc (so do
-        the four helpers below through theirs; opts_entry=None passes a NULL options pointer).  -> token for frame_export_finish"""
-        shapes = self.export_shapes(f, layout, samples, (0, 0, out_size[0], out_size[1]))
+        beforehand, the pitch is `pad` bytes larger than the row.  filter, filtered_entry, chroma_loc, opts_entry and colour pick the plain, the
+        _filtered or the _opts entry point as _export_entry states it, here and in the three helpers below.  -> token for frame_export_finish"""
+        entry = (filter, filtered_entry, chroma_loc, opts_entry, colour)
         desc = ResizeDesc(layout=layout, samples=samples, out_width=out_size[0], out_height=out_size[1])
         if rect is not None:
             desc.x0, desc.y0, desc.width, desc.height = rect
-        bufs = []
-        try:
-            for k, (rows, n, dt) in enumerate(shapes):
-                pitch = n * dt.itemsize + pad
-                if host:
-                    p = self.L.lib.m355_host_alloc(rows * pitch)
-                    if not p:
-                        raise M355Error(4, self.L.error())
-                    ctypes.memset(p, DEVICE_FILL, rows * pitch)
-                else:
-                    p = self.device_alloc(rows * pitch)
-                bufs.append(p)
-                desc.dst[k] = p; desc.pitch[k] = pitch
-            if chroma_loc != 0 or colour != 0 or opts_entry or opts_entry is None:
-                self.L.check(self.L.lib.m355_frame_export_resized_opts(self.h, f, ctypes.byref(desc), self._opts(filter, chroma_loc, opts_entry, colour)))
-            elif filter != 0 or filtered_entry:
-                self.L.check(self.L.lib.m355_frame_export_resized_filtered(self.h, f, ctypes.byref(desc), filter))
-            else:
-                self.L.check(self.L.lib.m355_frame_export_resized(self.h, f, ctypes.byref(desc)))
-        except Exception:
-            for p in bufs:
-                self.L.lib.m355_host_free(p) if host else self.device_free(p)
-            raise
-        return (f, shapes, bufs, [int(desc.pitch[k]) for k in range(len(shapes))], host)
+        return self._export_into_planes(f, self.export_shapes(f, layout, samples, (0, 0, out_size[0], out_size[1])), desc, host, pad,
+                                        lambda: self._export_entry("m355_frame_export_resized", (self.h, f, ctypes.byref(desc)), *entry))
 
     @staticmethod
     def _opts(filter, chroma_loc, opts_entry, colour=0):
@@ -595,40 +597,23 @@ class Context:
         """the integers of the R'G'B' conversion (m355_rgb_coefficients) -> dict F, y0, c0, cy, crv, cgu, cgv, cbu"""
         return self.L.rgb_coefficients(matrix, full_range, bit_depth_luma, bit_depth_chroma, samples)
 
+    @staticmethod
+    def _rgb_shapes(w, h, layout, samples):
+        """packed: one plane of 3 * w elements per row; planar: R, G, B"""
+        dt = np.dtype(np.uint16 if samples == RGB_U16 else np.uint8)
+        return [(h, 3 * w, dt)] if layout == RGB_PACKED else [(h, w, dt)] * 3
+
     def frame_export_rgb(self, f, layout, samples, matrix, full_range, rect=None, host=False, pad=20, chroma_loc=0, opts_entry=False, colour=0):
         """start m355_frame_export_rgb of frame f (rect = (x0, y0, width, height) in luma samples, None: the whole frame) into buffers of its own,
         made as frame_export makes them: every byte holds DEVICE_FILL beforehand, the pitch is `pad` bytes larger than the row.  Packed: one plane
-        of 3 * width elements per row; planar: R, G, B.  -> token for frame_export_finish"""
-        w, h = self._geom[f][:2]
-        if rect is not None:
-            w, h = rect[2], rect[3]
-        dt = np.dtype(np.uint16 if samples == RGB_U16 else np.uint8)
-        shapes = [(h, 3 * w, dt)] if layout == RGB_PACKED else [(h, w, dt)] * 3
+        of 3 * width elements per row; planar: R, G, B.  (The call has no _filtered form.)  -> token for frame_export_finish"""
+        w, h = self._geom[f][:2] if rect is None else rect[2:]
+        entry = (0, False, chroma_loc, opts_entry, colour)
         desc = RgbDesc(layout=layout, samples=samples, matrix=matrix, full_range=full_range)
         if rect is not None:
             desc.x0, desc.y0, desc.width, desc.height = rect
-        bufs = []
-        try:
-            for k, (rows, n, _) in enumerate(shapes):
-                pitch = n * dt.itemsize + pad
-                if host:
-                    p = self.L.lib.m355_host_alloc(rows * pitch)
-                    if not p:
-                        raise M355Error(4, self.L.error())
-                    ctypes.memset(p, DEVICE_FILL, rows * pitch)
-                else:
-                    p = self.device_alloc(rows * pitch)
-                bufs.append(p)
-                desc.dst[k] = p; desc.pitch[k] = pitch
-            if chroma_loc != 0 or colour != 0 or opts_entry or opts_entry is None:
-                self.L.check(self.L.lib.m355_frame_export_rgb_opts(self.h, f, ctypes.byref(desc), self._opts(0, chroma_loc, opts_entry, colour)))
-            else:
-                self.L.check(self.L.lib.m355_frame_export_rgb(self.h, f, ctypes.byref(desc)))
-        except Exception:
-            for p in bufs:
-                self.L.lib.m355_host_free(p) if host else self.device_free(p)
-            raise
-        return (f, shapes, bufs, [int(desc.pitch[k]) for k in range(len(shapes))], host)
+        return self._export_into_planes(f, self._rgb_shapes(w, h, layout, samples), desc, host, pad,
+                                        lambda: self._export_entry("m355_frame_export_rgb", (self.h, f, ctypes.byref(desc)), *entry))
 
     def frame_export_resized_rgb(self, f, layout, samples, matrix, full_range, out_size, rect=None, host=False, pad=20, filter=0, filtered_entry=False,
                                  chroma_loc=0, opts_entry=False, colour=0):
@@ -638,35 +623,12 @@ class Context:
         colour: 0, or the handle of a colour transform (colour_create), which goes through the _opts entry point like a chroma_loc other than 0 —
         so it does in the two tensor calls below.  -> token for frame_export_finish"""
         w, h = out_size
-        dt = np.dtype(np.uint16 if samples == RGB_U16 else np.uint8)
-        shapes = [(h, 3 * w, dt)] if layout == RGB_PACKED else [(h, w, dt)] * 3
+        entry = (filter, filtered_entry, chroma_loc, opts_entry, colour)
         desc = ResizeRgbDesc(layout=layout, samples=samples, matrix=matrix, full_range=full_range, out_width=w, out_height=h)
         if rect is not None:
             desc.x0, desc.y0, desc.width, desc.height = rect
-        bufs = []
-        try:
-            for k, (rows, n, _) in enumerate(shapes):
-                pitch = n * dt.itemsize + pad
-                if host:
-                    p = self.L.lib.m355_host_alloc(rows * pitch)
-                    if not p:
-                        raise M355Error(4, self.L.error())
-                    ctypes.memset(p, DEVICE_FILL, rows * pitch)
-                else:
-                    p = self.device_alloc(rows * pitch)
-                bufs.append(p)
-                desc.dst[k] = p; desc.pitch[k] = pitch
-            if chroma_loc != 0 or colour != 0 or opts_entry or opts_entry is None:
-                self.L.check(self.L.lib.m355_frame_export_resized_rgb_opts(self.h, f, ctypes.byref(desc), self._opts(filter, chroma_loc, opts_entry, colour)))
-            elif filter != 0 or filtered_entry:
-                self.L.check(self.L.lib.m355_frame_export_resized_rgb_filtered(self.h, f, ctypes.byref(desc), filter))
-            else:
-                self.L.check(self.L.lib.m355_frame_export_resized_rgb(self.h, f, ctypes.byref(desc)))
-        except Exception:
-            for p in bufs:
-                self.L.lib.m355_host_free(p) if host else self.device_free(p)
-            raise
-        return (f, shapes, bufs, [int(desc.pitch[k]) for k in range(len(shapes))], host)
+        return self._export_into_planes(f, self._rgb_shapes(w, h, layout, samples), desc, host, pad,
+                                        lambda: self._export_entry("m355_frame_export_resized_rgb", (self.h, f, ctypes.byref(desc)), *entry))
 
     def tensor_element(self, v, scale, bias, dtype):
         """the float stage of m355_frames_export_tensor for one integer (m355_tensor_element) -> the element's bit pattern"""
@@ -680,8 +642,7 @@ class Context:
         of the element size) above the smallest one the call accepts — stride_h above the row, stride_c above a plane, stride_n above a slice.
         scale, bias: three floats each (R, G, B).  -> token for tensor_export_finish"""
         return self._frames_export_tensor(frames, None, layout, dtype, samples, matrix, full_range, out_size, scale, bias, rect, host, pad,
-                                          filter if filter != 0 or filtered_entry else None,
-                                          (filter, chroma_loc, opts_entry, colour) if chroma_loc != 0 or colour != 0 or opts_entry or opts_entry is None else None)
+                                          (filter, filtered_entry, chroma_loc, opts_entry, colour))
 
     def frames_export_tensor_rois(self, frames, rois, layout, dtype, samples, matrix, full_range, out_size, scale, bias, host=False, pad=20, filter=0,
                                   filtered_entry=False, chroma_loc=0, opts_entry=False, colour=0):
@@ -689,10 +650,9 @@ class Context:
         whole of that frame; flags: 0 or ROI_MIRROR), resized to out_size.  The buffer is made as frames_export_tensor makes it: DEVICE_FILL in every
         byte, every stride `pad` bytes above the smallest one the call accepts.  -> token for tensor_export_finish"""
         return self._frames_export_tensor(frames, [r if r is not None else (0, 0, 0, 0, 0) for r in rois], layout, dtype, samples, matrix, full_range,
-                                          out_size, scale, bias, None, host, pad, filter if filter != 0 or filtered_entry else None,
-                                          (filter, chroma_loc, opts_entry, colour) if chroma_loc != 0 or colour != 0 or opts_entry or opts_entry is None else None)
+                                          out_size, scale, bias, None, host, pad, (filter, filtered_entry, chroma_loc, opts_entry, colour))
 
-    def _frames_export_tensor(self, frames, rois, layout, dtype, samples, matrix, full_range, out_size, scale, bias, rect, host, pad, filter=None, opts=None):
+    def _frames_export_tensor(self, frames, rois, layout, dtype, samples, matrix, full_range, out_size, scale, bias, rect, host, pad, entry):
         w, h = out_size
         n, eb = len(frames), (4 if dtype == TENSOR_F32 else 2)
         row = w * eb * (3 if layout == TENSOR_NHWC else 1)
@@ -707,33 +667,16 @@ class Context:
         desc.bias = (ctypes.c_float * 3)(*bias)
         if rect is not None:
             desc.x0, desc.y0, desc.width, desc.height = rect
-        if host:
-            p = self.L.lib.m355_host_alloc(nbytes)
-            if not p:
-                raise M355Error(4, self.L.error())
-            ctypes.memset(p, DEVICE_FILL, nbytes)
-        else:
-            p = self.device_alloc(nbytes)
-        desc.dst = p
+        p = desc.dst = self._buffer(nbytes, host)
         try:
             if rois is None:
-                if opts is not None:
-                    self.L.check(self.L.lib.m355_frames_export_tensor_opts(self.h, (ctypes.c_int * n)(*frames), n, ctypes.byref(desc), self._opts(*opts)))
-                elif filter is not None:
-                    self.L.check(self.L.lib.m355_frames_export_tensor_filtered(self.h, (ctypes.c_int * n)(*frames), n, ctypes.byref(desc), filter))
-                else:
-                    self.L.check(self.L.lib.m355_frames_export_tensor(self.h, (ctypes.c_int * n)(*frames), n, ctypes.byref(desc)))
+                self._export_entry("m355_frames_export_tensor", (self.h, (ctypes.c_int * n)(*frames), n, ctypes.byref(desc)), *entry)
             else:
                 assert len(rois) == n
                 arr = (TensorRoi * n)(*[TensorRoi(*r) for r in rois])
-                if opts is not None:
-                    self.L.check(self.L.lib.m355_frames_export_tensor_rois_opts(self.h, (ctypes.c_int * n)(*frames), arr, n, ctypes.byref(desc), self._opts(*opts)))
-                elif filter is not None:
-                    self.L.check(self.L.lib.m355_frames_export_tensor_rois_filtered(self.h, (ctypes.c_int * n)(*frames), arr, n, ctypes.byref(desc), filter))
-                else:
-                    self.L.check(self.L.lib.m355_frames_export_tensor_rois(self.h, (ctypes.c_int * n)(*frames), arr, n, ctypes.byref(desc)))
+                self._export_entry("m355_frames_export_tensor_rois", (self.h, (ctypes.c_int * n)(*frames), arr, n, ctypes.byref(desc)), *entry)
         except Exception:
-            self.L.lib.m355_host_free(p) if host else self.device_free(p)
+            self._buffer_free(p, host)
             raise
         return (list(frames), (n, h, w), layout, eb, p, nbytes, (stride_n, stride_c, stride_h), host)
 

@@ -2,6 +2,7 @@
  * runtime_internal.h — what the parts of the host runtime share: the context and its lanes, frames, resident pictures, the event
  * ring, the layout of an uploaded picture, and the prototypes of the functions one part calls in another.
  *   runtime.hip        context / lanes / frames / hashes / arenas / submit / wait / timing (the C ABI's entry points of those)
+ *   runtime_export.hip the exports of a frame into memory of the caller (m355_frame_export* / m355_frames_export_tensor*), colour transform objects
  *   runtime_upload.hip host pool, validation, intra schedule, upload (lists -> one pinned arena -> device)
  *   runtime_decode.hip prepare, the per-picture launch sequence, decode status, m355_decode_batch
  *   runtime_shard.hip  tile sharding: phases, exchanges, the in-process group, the built-in RCCL transport
@@ -360,6 +361,7 @@ void make_layout(const m355_arena_caps& k, int nCtb, int halo_units, bool sharde
 int mark_done(m355_ctx* c, Resident& r, Frame* dstf, hipStream_t st, const DevPic* d = nullptr);
 int prepare(m355_ctx* c, Resident& r, DevPic& d_out, bool& want_sao_out, hipStream_t st);
 size_t slot_bytes(const m355_pic_params& pp, int nranks);
+int stage_reserve(m355_ctx* c, size_t bytes);   /* runtime.hip: the context's pinned staging buffer holds at least `bytes` */
 int status_of(m355_ctx* c, m355_ctx::Status& s);
 hipError_t sync_all(m355_ctx* c);
 int upload(m355_ctx* c, Resident& r, const m355_picture* pic);
