@@ -88,7 +88,8 @@ namespace {
   X(m355_host_alloc) X(m355_host_free) X(m355_frame_hash) X(m355_arena_begin) X(m355_last_serial) X(m355_decode_status) \
   X(m355_frame_download_async) X(m355_frame_download_wait) X(m355_frame_export) X(m355_frame_export_scaled) X(m355_frame_export_rgb_opts) X(m355_frame_export_resized_opts) X(m355_frame_export_resized_rgb_opts) X(m355_frames_export_tensor_opts) X(m355_frames_export_tensor_rois_opts) X(m355_frame_export_order) X(m355_colour_create) X(m355_colour_destroy) X(m355_colour_preset) \
   X(m355_group_create) X(m355_group_destroy) X(m355_group_decode) X(m355_picture_upload) X(m355_picture_replace) X(m355_shard_owner_of_tile) \
-  X(m355_picture_arena_begin) X(m355_frame_hash_async) X(m355_frame_hash_result) X(m355_frame_measure_async) X(m355_frame_measure_result)
+  X(m355_picture_arena_begin) X(m355_frame_hash_async) X(m355_frame_hash_result) X(m355_frame_measure_async) X(m355_frame_measure_result) \
+  X(m355_frame_stats_async) X(m355_frame_stats_result) X(m355_stats_quantile) X(m355_colour_linear)
 
 struct Api {
   void* handle = nullptr;
@@ -2077,6 +2078,60 @@ LIBDE265_API int m355_glue_measure_image(const struct de265_image* img, const in
   if (rc == M355_OK) rc = A->m355_frame_measure_result(g->mctx, ticket, 1, out);
   if (rc != M355_OK) g->error = A->m355_last_error();
   return rc;
+}
+/* What is IN the picture, measured on the device (m355_frame_stats_async: histograms, min, max and sums per plane, the box of the luma samples > black and,
+ * with light == 1, the histogram of max(R, G, B) of every pixel's 16-bit R'G'B').  rect = {x0, y0, width, height} in luma samples, NULL: the image's
+ * conformance window.  With light == 1, matrix, full_range and chroma_loc are resolved as m355_glue_export_image_rgb_sited resolves them (-1: what the
+ * stream signals; an unmapped matrix or a bottom-sited type is M355_ERR_INVALID); with light == 0 they are passed on as given and must be 0.  Preconditions
+ * of m355_glue_export_image.  Like m355_glue_measure_image the call enqueues the request behind the picture's decode and collects it with block = 1: it waits
+ * for THIS request only, and nothing is downloaded.  -> M355_OK with *out filled, or an M355_ERR_* code. */
+LIBDE265_API int m355_glue_stats_image(const struct de265_image* img, const int rect[4], int black, int light, int matrix, int full_range, int chroma_loc,
+                                       m355_stats* out)
+{
+  ExportCall x;
+  const int given_loc = chroma_loc;
+  int rc = x.begin(&img, 1, out != nullptr, light ? &matrix : nullptr, light ? &full_range : nullptr, 0, light ? chroma_loc : 0);
+  if (rc != M355_OK) return rc;
+  int r[4];
+  const int frame = frame_and_rect(x.g, img, rect, r);
+  if (frame < 0) return M355_ERR_INVALID;
+  m355_stats_desc d;
+  memset(&d, 0, sizeof(d));
+  d.x0 = r[0]; d.y0 = r[1]; d.width = r[2]; d.height = r[3];
+  d.black = black; d.light = light; d.matrix = matrix; d.full_range = full_range; d.chroma_loc = light ? x.o.chroma_loc : given_loc;
+  unsigned long long ticket = 0;
+  rc = x.A->m355_frame_stats_async(x.g->mctx, frame, &d, &ticket);
+  if (rc == M355_OK) rc = x.A->m355_frame_stats_result(x.g->mctx, ticket, 1, out);
+  if (rc != M355_OK) x.g->error = x.A->m355_last_error();
+  return rc;
+}
+/* The picture's CONTENT PEAK in nits from statistics taken with light == 1 — what m355_glue_colour_preset_for_image takes as peak_nits where the stream
+ * carries no light-level metadata (libde265 parses none):
+ *   b = m355_stats_quantile(stats->light_hist, num, den)          e.g. 999 / 1000: the level 99.9 % of the pixels stay at or below
+ *   v = min(65535, (b << 8) | 255)                                the upper edge of bin b
+ *   L = m355_colour_linear(tables, v), tables = the input side of the preset for the image's signalled transfer
+ *   S = 10000 for transfer 16 (PQ), 1000 for 18 (HLG), else white;  white = white_nits, or 203 for 0
+ *   *peak_nits = max(white, (L * S + M355_COLOUR_ONE - 1) >> 24)   rounded up, never below white: valid as peak_nits of the preset
+ * M355_ERR_INVALID: null pointers, statistics taken with light == 0 (an empty light histogram), num / den outside m355_stats_quantile's bounds, a
+ * negative white_nits, a transfer the presets do not know. */
+LIBDE265_API int m355_glue_image_content_peak(const struct de265_image* img, const m355_stats* stats, uint32_t num, uint32_t den, int white_nits, int* peak_nits)
+{
+  Api* A = api();
+  if (!A) return M355_ERR_NO_DEVICE;
+  if (!img || !stats || !peak_nits || white_nits < 0) return M355_ERR_INVALID;
+  int b = 0;
+  if (A->m355_stats_quantile(stats->light_hist, num, den, &b) != M355_OK) return M355_ERR_INVALID;
+  m355_colour_tables tables;
+  const int rc = m355_glue_colour_preset_for_image(img, 1, 1, M355_TONE_CLIP, white_nits, 0, &tables);
+  if (rc != M355_OK) return rc;
+  int primaries = 2, transfer = 2;
+  m355_glue_image_colour(img, &primaries, &transfer);
+  const uint32_t v = std::min<uint32_t>(65535u, ((uint32_t)b << 8) | 255u);
+  uint32_t L = 0;
+  if (A->m355_colour_linear(&tables, v, &L) != M355_OK) return M355_ERR_INVALID;
+  const int64_t white = white_nits ? white_nits : 203, S = transfer == 16 ? 10000 : (transfer == 18 ? 1000 : white);
+  *peak_nits = (int)std::max<int64_t>(white, ((int64_t)L * S + M355_COLOUR_ONE - 1) >> 24);
+  return M355_OK;
 }
 /* the backend context behind a decoder, for the m355_device_* calls that go with the export (device memory without a second HIP runtime) */
 LIBDE265_API void* m355_glue_backend_context(de265_decoder_context* c) { Glue* g = glue_of((decoder_context*)c); return g ? (void*)g->mctx : nullptr; }

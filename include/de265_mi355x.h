@@ -899,6 +899,67 @@ typedef struct m355_measure {
 M355_API int m355_frame_measure_async(m355_ctx* ctx, int frame, const m355_measure_desc* desc, unsigned long long* ticket);
 M355_API int m355_frame_measure_result(m355_ctx* ctx, unsigned long long ticket, int block, m355_measure* out);
 
+/* What is IN a frame, measured where it lies: histograms, the active area, the light level — what a tone mapper without metadata (a high percentile
+ * of max(R, G, B)), a crop detector (the box of the content in letterboxed material) and a scene-cut / fade / black-frame detector (luma histograms and
+ * means) need of every picture, in one pass over the planes and without a download.  A request queued behind the frame's decode, like
+ * m355_frame_measure_async.  EVERYTHING IS AN INTEGER AND EXACT.
+ * PLANES.  For each plane the frame has, over the samples s of the rectangle on THAT PLANE'S OWN GRID (no siting is known or needed):
+ *   hist[p][b] = #{s : (s >> (bd - 8)) == b}, bd the PLANE's bit depth      min[p], max[p]      sum[p] = sum s      sum_sq[p] = sum s * s
+ * A plane a monochrome frame does not have reads 0 in all of its fields.
+ * ACTIVE AREA.  box = {x0, y0, x1, y1}, inclusive, in luma coordinates OF THE FRAME, around the luma samples of the rectangle that are > black;
+ * n_active = how many there are; none: box = {-1, -1, -1, -1}, n_active = 0.
+ * LIGHT (light == 1).  For every luma position of the rectangle, (R, G, B) is BY DEFINITION what m355_frame_export_rgb_opts delivers for that pixel
+ * with samples = M355_RGB_U16, this matrix and full_range, and opts.chroma_loc = chroma_loc: the integers of m355_rgb_coefficients(..., M355_RGB_U16,
+ * ...), the bilinear chroma reconstruction with indices clamped to the FRAME — a rectangle's values are those of the same rectangle of a whole-frame
+ * request: its rim reads chroma outside the rectangle.  m = max(R, G, B); a monochrome frame gives m = R.
+ *   light_hist[b] = #{pixels : (m >> 8) == b}      light_min, light_max = min m, max m      light_sum = sum m
+ * No R'G'B' sample passes through memory.  With light == 0 these fields read 0.  Linear light is the host's: m355_stats_quantile on light_hist,
+ * then m355_colour_linear on the bin's upper edge (below).
+ * COUNT RANGE.  Counts are 32-bit: the largest frame, 16384 x 16384, has 2^28 samples per plane.
+ * ORDERING AND VERDICTS are those of m355_frame_measure_async.  The request is a READER of the frame (a kind of its own): it runs on the stream of the
+ * frame's last writer, and a later decode into the frame waits for it in front of its first write; the host waits for nothing at enqueue.  *ticket
+ * counts 1, 2, ... per context (a count of its own); at most M355_STATS_REQUESTS requests may be outstanding: one more returns M355_ERR_BUSY and
+ * enqueues nothing.  The slots are separate from the comparison and hash slots.
+ * M355_ERR_INVALID, nothing enqueued: what m355_frame_measure_async rejects for the frame and the rectangle (bad handle; a rectangle that leaves the
+ * frame or is off the chroma grid); a tile-sharded context; black outside 0 .. 2^bdl - 1; light not 0 or 1; with light == 1 an unknown matrix or
+ * range, chroma_loc outside 0..3 or non-zero for a frame that is not 4:2:0; with light == 0 a non-zero matrix, full_range or chroma_loc; a non-zero
+ * `reserved`; null pointers.
+ * m355_frame_stats_result collects a request and frees its slot: block = 0 -> M355_ERR_BUSY while it runs (the request stays), block = 1 -> the
+ * host waits for THAT request only.  M355_ERR_INVALID: an unknown or collected ticket; or — the request is collected all the same — a request
+ * queued behind a decode whose lists were rejected: it has read nothing.  m355_wait completes every request and collects none; a frame may be
+ * destroyed with requests pending.
+ * HOST-ONLY HELPERS (exact, no context; csrc/stats_quantile.h and csrc/colour_transform.h are the one definition of each).
+ *   m355_stats_quantile: the smallest bin b with den * (hist[0] + ... + hist[b]) >= num * total, total = the sum of all bins, in 64-bit arithmetic;
+ *     0 < num <= den <= 1 << 20.  M355_ERR_INVALID: total == 0, num or den outside that, null pointers.
+ *   m355_colour_linear: step 1 of m355_colour_pixel for one value — k = v16 >> 6, f = v16 & 63, *L = (lut_in[k] (64 - f) + lut_in[k + 1] f + 32) >> 6,
+ *     the code m355_colour_pixel runs.  M355_ERR_INVALID: v16 > 65535, null pointers, tables outside their bounds.
+ * Not offered: statistics in linear light on the device, per-channel R, G, B histograms, more than 256 bins, row and column profiles, a batch of
+ * frames or several rectangles in one launch, sharded contexts. */
+#define M355_STATS_REQUESTS 16
+#define M355_STATS_BINS     256
+typedef struct m355_stats_desc {
+  int32_t x0, y0, width, height;   /* luma rectangle, rules of m355_measure_desc (width == 0: whole frame; on the chroma grid) */
+  int32_t black;                   /* active area: luma samples > black count as content (sample units of the luma bit depth; 0 .. 2^bdl - 1) */
+  int32_t light;                   /* 0: planes only; 1: also the R'G'B' light level */
+  int32_t matrix, full_range;      /* light == 1: as in m355_rgb_desc; light == 0: must be 0 */
+  int32_t chroma_loc;              /* light == 1: as in m355_export_opts (0..3, non-zero for 4:2:0 only); light == 0: must be 0 */
+  int32_t reserved[7];             /* 0 */
+} m355_stats_desc;
+typedef struct m355_stats {
+  uint32_t hist[3][M355_STATS_BINS];   /* per plane: samples with (s >> (bd - 8)) == bin, bd the PLANE's bit depth */
+  uint32_t min[3], max[3];             /* sample values; a plane that does not exist: all of its fields 0 */
+  uint64_t sum[3], sum_sq[3];          /* sum of s, sum of s * s */
+  int32_t  box[4];                     /* x0, y0, x1, y1 (inclusive, luma coordinates IN THE FRAME) around the rectangle's luma samples > black; -1 x 4: none */
+  uint64_t n_active;                   /* how many such samples */
+  uint32_t light_hist[M355_STATS_BINS];/* light == 1: pixels with (m >> 8) == bin, m = max(R, G, B) of the pixel's 16-bit R'G'B'; else 0 */
+  uint32_t light_min, light_max;       /* of m */
+  uint64_t light_sum;                  /* sum of m */
+} m355_stats;
+M355_API int m355_frame_stats_async(m355_ctx* ctx, int frame, const m355_stats_desc* desc, unsigned long long* ticket);
+M355_API int m355_frame_stats_result(m355_ctx* ctx, unsigned long long ticket, int block, m355_stats* out);
+M355_API int m355_stats_quantile(const uint32_t hist[M355_STATS_BINS], uint32_t num, uint32_t den, int* bin);   /* host only */
+M355_API int m355_colour_linear(const m355_colour_tables* tables, uint32_t v16, uint32_t* L);                    /* host only */
+
 /* Replaces (deferred): decode_TU (slice.cc:3460), decode_prediction_unit (motion.cc:2190) and
  * run_postprocessing_filters_sequential/_parallel (decctx.cc:1783/1811) for one picture. Asynchronous:
  * returns after the work is enqueued on the context's stream. */

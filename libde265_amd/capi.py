@@ -154,11 +154,35 @@ class Measure(ctypes.Structure):
                 ("first_x", ctypes.c_int32 * 3), ("first_y", ctypes.c_int32 * 3), ("mse", ctypes.c_double * 3)]
 
 
+STATS_REQUESTS, STATS_BINS = 16, 256        # M355_STATS_*
+
+
+class StatsDesc(ctypes.Structure):
+    """m355_stats_desc (include/de265_mi355x.h)"""
+    _fields_ = [(n, ctypes.c_int32) for n in ("x0", "y0", "width", "height", "black", "light", "matrix", "full_range", "chroma_loc")] + \
+               [("reserved", ctypes.c_int32 * 7)]
+
+
+class Stats(ctypes.Structure):
+    """m355_stats (include/de265_mi355x.h)"""
+    _fields_ = [("hist", (ctypes.c_uint32 * STATS_BINS) * 3), ("min", ctypes.c_uint32 * 3), ("max", ctypes.c_uint32 * 3), ("sum", ctypes.c_uint64 * 3),
+                ("sum_sq", ctypes.c_uint64 * 3), ("box", ctypes.c_int32 * 4), ("n_active", ctypes.c_uint64), ("light_hist", ctypes.c_uint32 * STATS_BINS),
+                ("light_min", ctypes.c_uint32), ("light_max", ctypes.c_uint32), ("light_sum", ctypes.c_uint64)]
+
+
 class ArenaCaps(ctypes.Structure):
     """m355_arena_caps (include/de265_mi355x.h)"""
     _fields_ = [(n, ctypes.c_int32) for n in ("n_slices", "n_ctbs", "n_cus", "n_tus", "n_pbs", "n_wts", "n_ibs")] + \
                [("n_rbs", ctypes.c_int32 * 4), ("n_coeffs", ctypes.c_uint32), ("n_pcm", ctypes.c_uint32), ("scaling", ctypes.c_int32),
                 ("rb_bin", ctypes.c_void_p * 4)]
+
+
+def stats_dict(out, n_planes, light):
+    """a Stats structure as plain Python values (Context.frame_stats_result)"""
+    planes = [dict(hist=[int(v) for v in out.hist[c]], min=int(out.min[c]), max=int(out.max[c]), sum=int(out.sum[c]), sum_sq=int(out.sum_sq[c]))
+              for c in range(n_planes)]
+    return dict(planes=planes, box=None if out.box[0] < 0 else tuple(int(v) for v in out.box), n_active=int(out.n_active),
+                light=dict(hist=[int(v) for v in out.light_hist], min=int(out.light_min), max=int(out.light_max), sum=int(out.light_sum)) if light else None)
 
 
 class Library:
@@ -245,6 +269,11 @@ class Library:
         if hasattr(L, "m355_frame_measure_async"):      # (absent from older builds loaded through M355_LIB for an A/B)
             L.m355_frame_measure_async.argtypes = [vp, i, ctypes.POINTER(MeasureDesc), ctypes.POINTER(ctypes.c_ulonglong)]
             L.m355_frame_measure_result.argtypes = [vp, ctypes.c_ulonglong, i, ctypes.POINTER(Measure)]
+        if hasattr(L, "m355_frame_stats_async"):        # (absent from older builds loaded through M355_LIB for an A/B)
+            L.m355_frame_stats_async.argtypes = [vp, i, ctypes.POINTER(StatsDesc), ctypes.POINTER(ctypes.c_ulonglong)]
+            L.m355_frame_stats_result.argtypes = [vp, ctypes.c_ulonglong, i, ctypes.POINTER(Stats)]
+            L.m355_stats_quantile.argtypes = [ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(i)]
+            L.m355_colour_linear.argtypes = [ctypes.POINTER(ColourTables), ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]
         L.m355_submit_picture.argtypes = [vp, vp]
         L.m355_wait.argtypes = [vp]
         L.m355_last_serial.argtypes = [vp]
@@ -333,6 +362,19 @@ class Library:
         self.check(self.lib.m355_colour_pixel(ctypes.byref(tables), (ctypes.c_uint32 * 3)(*[int(v) for v in rgb16]), samples, out))
         return tuple(int(v) for v in out)
 
+    def stats_quantile(self, hist, num, den):
+        """the smallest bin b of a 256-bin histogram with den * (hist[0] + ... + hist[b]) >= num * total (m355_stats_quantile; host only)"""
+        b = ctypes.c_int(-1)
+        h = None if hist is None else (ctypes.c_uint32 * STATS_BINS)(*[int(v) for v in hist])
+        self.check(self.lib.m355_stats_quantile(h, num, den, ctypes.byref(b)))
+        return int(b.value)
+
+    def colour_linear(self, tables, v16):
+        """step 1 of the colour transform stage for one 16-bit value (m355_colour_linear; host only) -> linear light, 0 .. COLOUR_ONE"""
+        out = ctypes.c_uint32(0)
+        self.check(self.lib.m355_colour_linear(ctypes.byref(tables), int(v16), ctypes.byref(out)))
+        return int(out.value)
+
     def pack_narrow(self, pic):
         """m355_pack_narrow on a picture's residual records and coefficient list (host only; worklist.pack_narrow is the numpy
         statement of the same): a copy with every block that fits in the 16-bit entry form (worklist.RBF_NARROW)"""
@@ -356,6 +398,7 @@ class Context:
         self._geom = {}
         self._hash_reqs = {}            # ticket -> (hash type, planes) of the requests not collected yet
         self._measure_reqs = {}         # ticket -> (planes, reference buffers to free, host?) of the comparison requests not collected yet
+        self._stats_reqs = {}           # ticket -> (planes, light?) of the statistics requests not collected yet
 
     def close(self):
         if self.h:
@@ -839,6 +882,35 @@ class Context:
         self._measure_free(bufs, host)                          # (collected: nothing reads the buffers any more)
         return [dict(ssd=int(out.ssd[c]), sad=int(out.sad[c]), n_diff=int(out.n_diff[c]), max_abs=int(out.max_abs[c]),
                      first=None if out.first_x[c] < 0 else (int(out.first_x[c]), int(out.first_y[c])), mse=float(out.mse[c])) for c in range(n)]
+
+    # ---- what is in the frame (m355_frame_stats_async) ----
+    def frame_stats_async(self, f, rect=None, black=0, light=False, matrix=0, full_range=0, chroma_loc=0):
+        """enqueue the statistics of frame f (rect = (x0, y0, width, height) in luma samples, None: the whole frame): histograms, min, max and sums
+        per plane, the box of the luma samples > black and, with light, the same for max(R, G, B) of every pixel's 16-bit R'G'B' under matrix /
+        full_range / chroma_loc.  Nothing is waited for -> ticket for frame_stats_result"""
+        desc = StatsDesc(black=black, light=1 if light else 0, matrix=matrix, full_range=full_range, chroma_loc=chroma_loc)
+        if rect is not None:
+            desc.x0, desc.y0, desc.width, desc.height = rect
+        t = ctypes.c_ulonglong(0)
+        self.L.check(self.L.lib.m355_frame_stats_async(self.h, f, ctypes.byref(desc), ctypes.byref(t)))
+        self._stats_reqs[t.value] = (3 if self._geom[f][2] else 1, bool(light))
+        return int(t.value)
+
+    def frame_stats_result(self, ticket, block=True):
+        """collect a request (m355_frame_stats_result) -> dict: planes = one dict per plane of the frame (hist: 256 ints, min, max, sum, sum_sq), box =
+        (x0, y0, x1, y1) or None, n_active, light = None or a dict (hist, min, max, sum); None while it has not finished (block=False); raises M355Error
+        for an unknown / collected ticket and behind a rejected decode"""
+        out = Stats()
+        rc = self.L.lib.m355_frame_stats_result(self.h, ticket, 1 if block else 0, ctypes.byref(out))
+        if rc == 6 and not block:                               # M355_ERR_BUSY
+            return None
+        if rc:
+            text = self.L.error()
+            if rc == 3:                                         # M355_ERR_INVALID: collected without a value, or no such request
+                self._stats_reqs.pop(ticket, None)
+            raise M355Error(rc, text)
+        n, light = self._stats_reqs.pop(ticket)
+        return stats_dict(out, n, light)
 
     # ---- pictures ----
     def submit(self, pic):

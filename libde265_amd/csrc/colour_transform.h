@@ -64,14 +64,18 @@ M355_CT_FN uint32_t m355_ct_encode(uint32_t lo, uint32_t hi, uint32_t fr) { retu
 /* step 4 */
 M355_CT_FN uint32_t m355_ct_deliver(uint32_t o, bool u8) { return u8 ? (2u * o + 257u) / 514u : o; }
 
+/* step 1 for one channel from tables in addressable memory, v = 0 .. 65535: what m355_colour_linear is */
+M355_CT_FN uint32_t m355_ct_linear_of(const m355_colour_tables* t, uint32_t v)
+{
+  const uint32_t k = v >> 6;
+  return m355_ct_linear(t->lut_in[k], t->lut_in[k + 1], v & 63u);
+}
+
 /* the whole stage for one pixel from tables in addressable memory: what m355_colour_pixel is */
 M355_CT_FN void m355_ct_pixel(const m355_colour_tables* t, const uint32_t rgb16[3], int samples, uint32_t out[3])
 {
   uint32_t l[3];
-  for (int c = 0; c < 3; c++) {
-    const uint32_t v = rgb16[c] > 65535u ? 65535u : rgb16[c], k = v >> 6;
-    l[c] = m355_ct_linear(t->lut_in[k], t->lut_in[k + 1], v & 63u);
-  }
+  for (int c = 0; c < 3; c++) l[c] = m355_ct_linear_of(t, rgb16[c] > 65535u ? 65535u : rgb16[c]);
   for (int c = 0; c < 3; c++) {
     const uint32_t p = m355_ct_matrix_row(t->matrix[3 * c], t->matrix[3 * c + 1], t->matrix[3 * c + 2], l[0], l[1], l[2]);
     uint32_t idx, fr;

@@ -35,79 +35,7 @@
  */
 #include "k_common.h"
 
-#ifdef SIMT_EMU
-static inline int d_mad24(int a, int b, int c) { return (int)((unsigned)a * (unsigned)b + (unsigned)c); }
-#else
-/* v_mad_i32_i24: a, b within 24 signed bits */
-__device__ __forceinline__ int d_mad24(int a, int b, int c) { return (int)((unsigned)__mul24(a, b) + (unsigned)c); }
-#endif
-
-/* sample k of a 16-byte vector */
-template <int SB> __device__ __forceinline__ int d_rgb_sample(const unsigned* w, int k)
-{
-  return SB == 1 ? (int)((w[k >> 2] >> (8 * (k & 3))) & 0xFFu) : (int)((w[k >> 1] >> (16 * (k & 1))) & 0xFFFFu);
-}
-
-/* the NP chroma samples of one plane at the lane's luma positions, minus c0.  r0 / r1: the vectors of chroma rows j / jn (4:2:0; else r0 only),
-   last = CW - 1 - i0 >= 0: the index inside the vector of the plane's last column */
-template <int SB, int CF, int LOC>
-__device__ __forceinline__ void d_rgb_chroma(const unsigned* r0, const unsigned* r1, int last, int c0, int* out, bool yodd, bool lead)
-{
-  constexpr int NP = 16 / SB, NC = NP / 2;
-  if (CF == 3) {
-#pragma unroll
-    for (int k = 0; k < NP; k++) out[k] = d_rgb_sample<SB>(r0, k) - c0;
-    return;
-  }
-  if constexpr (LOC != 0) {
-    /* chroma sample location types 1..3 (4:2:0 only): the vertical sums T in quarters — MID 3 C[j] + C[jn], TOP 4 C[j] on an even luma row (yodd,
-       wave-uniform: a wave is one row) and 2 C[j] + 2 C[j + 1] on an odd one —, then LEFT as type 0, or CENTRE {i: 3, i -+ 1: 1} with one
-       rounding, (sum + 8) >> 4, c0 folded into the constant.  CENTRE: the vectors start at column i0 - 1 (lead) or, for the lane at column 0, at
-       i0 = 0, where the clamp makes sample 0 its own left neighbour: s[m] is column max(i0 - 1 + m, 0), m = 0 .. NC + 1 <= NP - 1 */
-    constexpr bool CENTRE = (LOC & 1) != 0, TOP = (LOC >> 1) != 0;
-    constexpr int NT = NC + 1 + (CENTRE ? 1 : 0);
-    int t[NT];
-    if (TOP && !yodd) {
-#pragma unroll
-      for (int k = 0; k < NT; k++) t[k] = 4 * d_rgb_sample<SB>(r0, k);
-    } else {
-#pragma unroll
-      for (int k = 0; k < NT; k++) t[k] = TOP ? 2 * (d_rgb_sample<SB>(r0, k) + d_rgb_sample<SB>(r1, k)) : 3 * d_rgb_sample<SB>(r0, k) + d_rgb_sample<SB>(r1, k);
-    }
-    if (!CENTRE) {
-#pragma unroll
-      for (int k = 0; k < NC; k++) {
-        const int tn = k < last ? t[k + 1] : t[k];
-        out[2 * k] = (t[k] + 2 - 4 * c0) >> 2;
-        out[2 * k + 1] = (t[k] + tn + 4 - 8 * c0) >> 3;
-      }
-    } else {
-      int s[NT];
-#pragma unroll
-      for (int m = 0; m < NT; m++) s[m] = lead ? t[m] : t[m ? m - 1 : 0];
-#pragma unroll
-      for (int k = 0; k < NC; k++) {
-        const int tr = k < last ? s[k + 2] : s[k + 1];            /* column min(i + 1, CW - 1) */
-        out[2 * k] = (3 * s[k + 1] + s[k] + 8 - 16 * c0) >> 4;
-        out[2 * k + 1] = (3 * s[k + 1] + tr + 8 - 16 * c0) >> 4;
-      }
-    }
-    return;
-  }
-  int t[NC + 1];
-#pragma unroll
-  for (int k = 0; k <= NC; k++) {
-    const int s = d_rgb_sample<SB>(r0, k);
-    t[k] = CF == 1 ? 3 * s + d_rgb_sample<SB>(r1, k) : s;
-  }
-  const int ke = CF == 1 ? 2 - 4 * c0 : -c0, ko = CF == 1 ? 4 - 8 * c0 : 1 - 2 * c0;
-#pragma unroll
-  for (int k = 0; k < NC; k++) {
-    const int tn = k < last ? t[k + 1] : t[k];                /* column min(i + 1, CW - 1) */
-    out[2 * k] = CF == 1 ? (t[k] + ke) >> 2 : t[k] + ke;
-    out[2 * k + 1] = (t[k] + tn + ko) >> (CF == 1 ? 3 : 1);
-  }
-}
+#include "k_rgb_dev.h"   /* d_mad24, d_rgb_sample, d_rgb_chroma, d_rgb_load, d_rgb_pixel: shared with k_stats.hip */
 
 /* N values of one byte / one 16-bit half each -> N * DB / 4 dwords */
 template <int DB, int N> __device__ __forceinline__ void d_rgb_pack(const unsigned* e, unsigned* o)
@@ -150,53 +78,17 @@ __global__ void __launch_bounds__(256) k_export_rgb(ExportRgbArgs a)
   if (p0 >= a.width) return;
   const uint32_t n = a.width - p0 < (uint32_t)NP ? a.width - p0 : (uint32_t)NP;
   const uint32_t X0 = a.x0 + p0, Y = a.y0 + row;
-  unsigned ry[4], rc[2][2][4];
-  d_ldg16((const M355_GLOBAL uint8_t*)a.src[0] + (size_t)Y * a.src_pitch[0] + (size_t)X0 * SB, ry);
-  int last = 0;
-  bool lead = false;                                            /* CENTRE: the chroma vectors start one column before i0 */
-  bool yodd = false;                                            /* TOP: an odd luma row (wave-uniform: a wave is one row) */
-  if constexpr ((LOC >> 1) != 0) yodd = (Y & 1u) != 0;
-  if (CF != 0) {
-    const uint32_t i0 = CF == 3 ? X0 : X0 >> 1;
-    uint32_t j = Y, jn = Y;
-    if (CF == 1) {
-      j = Y >> 1;
-      if constexpr ((LOC >> 1) != 0) jn = j + 1 < a.ch ? j + 1 : a.ch - 1;   /* TOP: row j + 1, read on odd rows only */
-      else jn = (Y & 1u) ? (j + 1 < a.ch ? j + 1 : a.ch - 1) : (j ? j - 1 : 0u);
-    }
-    last = (int)(a.cw - 1u - i0);
-    uint32_t is = i0;
-    if constexpr ((LOC & 1) != 0) { lead = i0 != 0u; is = lead ? i0 - 1u : 0u; }
-#pragma unroll
-    for (int c = 0; c < 2; c++) {
-      const M355_GLOBAL uint8_t* s = (const M355_GLOBAL uint8_t*)a.src[1 + c] + (size_t)is * SB;
-      d_ldg16(s + (size_t)j * a.src_pitch[1], rc[c][0]);
-      if constexpr ((LOC >> 1) != 0) { if (yodd) d_ldg16(s + (size_t)jn * a.src_pitch[1], rc[c][1]); }
-      else if (CF == 1) d_ldg16(s + (size_t)jn * a.src_pitch[1], rc[c][1]);
-    }
-  }
-  /* the constants of the launch (scalar): the rounding term and the luma offset in one */
-  const int F = a.k.F, ky = (int)((1u << (F - 1)) - (unsigned)a.k.cy * (unsigned)a.k.y0);
-  const int cy = a.k.cy, crv = a.k.crv, ncgu = -a.k.cgu, ncgv = -a.k.cgv, cbu = a.k.cbu;
+  RgbLane<SB, CF, LOC> l;
+  d_rgb_load<SB, CF, LOC>(a, X0, Y, l);
+  const RgbMatrix m = d_rgb_matrix_of(a.k);
   int u[NP], v[NP];
   if (CF != 0) {
-    d_rgb_chroma<SB, CF, LOC>(rc[0][0], rc[0][1], last, a.k.c0, u, yodd, lead);
-    d_rgb_chroma<SB, CF, LOC>(rc[1][0], rc[1][1], last, a.k.c0, v, yodd, lead);
+    d_rgb_chroma<SB, CF, LOC>(l.rc[0][0], l.rc[0][1], l.last, m.c0, u, l.yodd, l.lead);
+    d_rgb_chroma<SB, CF, LOC>(l.rc[1][0], l.rc[1][1], l.last, m.c0, v, l.yodd, l.lead);
   }
   unsigned e[3][NP];
 #pragma unroll
-  for (int k = 0; k < NP; k++) {
-    const int base = d_mad24(cy, d_rgb_sample<SB>(ry, k), ky);
-    int r = base, g = base, b = base;
-    if (CF != 0) {
-      r = d_mad24(crv, v[k], base);
-      g = d_mad24(ncgv, v[k], d_mad24(ncgu, u[k], base));
-      b = d_mad24(cbu, u[k], base);
-    }
-    e[0][k] = (unsigned)d_clip3(0, M, r >> F);
-    e[1][k] = (unsigned)d_clip3(0, M, g >> F);
-    e[2][k] = (unsigned)d_clip3(0, M, b >> F);
-  }
+  for (int k = 0; k < NP; k++) d_rgb_pixel<CF>(m, d_rgb_sample<SB>(l.ry, k), CF != 0 ? u[k] : 0, CF != 0 ? v[k] : 0, M, e[0][k], e[1][k], e[2][k]);
   if (PLANAR) {
     constexpr int ND = NP * DB / 4;
 #pragma unroll

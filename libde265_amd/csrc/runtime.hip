@@ -260,7 +260,8 @@ int m355_create(int device, m355_ctx** out)
   int rc = lane_create(c, c->lanes[0], 0);
   if (rc == M355_OK) rc = hash_requests_create(c);
   if (rc == M355_OK) rc = measure_requests_create(c);
-  if (rc) { measure_requests_destroy(c); hash_requests_destroy(c); lane_destroy(c->lanes[0]); delete c; return rc; }
+  if (rc == M355_OK) rc = stats_requests_create(c);
+  if (rc) { stats_requests_destroy(c); measure_requests_destroy(c); hash_requests_destroy(c); lane_destroy(c->lanes[0]); delete c; return rc; }
   *out = c;
   return M355_OK;
 }
@@ -301,6 +302,7 @@ void m355_destroy(m355_ctx* c)
   if (c->hash_acc) hipFree(c->hash_acc);
   hash_requests_destroy(c);
   measure_requests_destroy(c);
+  stats_requests_destroy(c);
   for (auto& e : c->inter_tabs) hipFree(e.second);
   for (auto& b : c->batch) { if (b.host) hipHostFree(b.host); if (b.dev) hipFree(b.dev); if (b.ev) hipEventDestroy(b.ev); }
   for (hipEvent_t e : c->batch_ev_pre) if (e) hipEventDestroy(e);

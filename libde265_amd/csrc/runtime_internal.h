@@ -31,6 +31,7 @@
 #include "k_common.h"
 #include "k_hash.h"
 #include "k_measure.h"
+#include "k_stats.h"
 
 
 extern thread_local std::string g_err;
@@ -84,7 +85,7 @@ constexpr bool intra_light_32x32 = false;
 struct EvRef { unsigned long long ticket = 0; hipStream_t stream = nullptr; };
 #define M355_EV_RING 256
 
-enum ReaderKind { RD_DOWNLOAD, RD_EXPORT, RD_HASH, RD_MEASURE, RD_KINDS };
+enum ReaderKind { RD_DOWNLOAD, RD_EXPORT, RD_HASH, RD_MEASURE, RD_STATS, RD_KINDS };
 struct Frame {
   bool used = false;
   int w = 0, h = 0, cf = 0, bdl = 0, bdc = 0;
@@ -97,10 +98,10 @@ struct Frame {
      rejected does nothing, like that decode's own kernels (M355_GATE) */
   const uint32_t* wr_gate = nullptr; uint32_t wr_epoch = 0;
   /* READERS queued behind the decode that wrote the frame — a download (m355_frame_download_async), an export (m355_frame_export), a hash request
-     (m355_frame_hash_async), a comparison (m355_frame_measure_async, which reads two frames and marks both): per kind the mark behind the LAST one.  reader_begin picks the stream (the writer's, so stream order stands for the wait for the
+     (m355_frame_hash_async), a comparison (m355_frame_measure_async, which reads two frames and marks both), a statistics request (m355_frame_stats_async): per kind the mark behind the LAST one.  reader_begin picks the stream (the writer's, so stream order stands for the wait for the
      picture) and lets it continue behind the kind's earlier mark, so that the one mark kept stands for both; reader_end marks; the next decode into the frame
      waits for every kind in front of its first write (readers_wait, from dst_hazards).  The kinds are separate because the HOST waits per kind
-     (m355_frame_download_wait, m355_frame_export_wait, m355_frame_hash_result, m355_frame_measure_result), and a finished wait clears its mark: readers of different kinds need no order. */
+     (m355_frame_download_wait, m355_frame_export_wait, m355_frame_hash_result, m355_frame_measure_result, m355_frame_stats_result), and a finished wait clears its mark: readers of different kinds need no order. */
   EvRef reader[RD_KINDS];
 };
 
@@ -276,6 +277,16 @@ struct m355_ctx {
   unsigned long long meas_ticket = 0;
   unsigned long long *meas_rec = nullptr, *meas_res = nullptr;   /* MEAS_REC_WORDS (device) / MEAS_RES_WORDS (pinned) per slot */
   std::vector<std::pair<unsigned long long*, size_t>> meas_pool; /* idle pinned row arrays (entries) */
+  /* m355_frame_stats_async (runtime_stats.hip): M355_STATS_REQUESTS slots of their own like the comparison slots — a device record the kernel leaves zero and a
+     pinned result record of STATS_REC_WORDS 32-bit words each (k_stats.h), the request's mark and the frame it reads */
+  struct StatsSlot {
+    unsigned long long ticket = 0;
+    int np = 0, light = 0;
+    EvRef mark; int frame = -1;
+  };
+  StatsSlot stats_slot[M355_STATS_REQUESTS];
+  unsigned long long stats_ticket = 0;
+  uint32_t *stats_rec = nullptr, *stats_res = nullptr;
   /* pinned staging buffer of the blocking frame transfers (m355_frame_upload / _download / _fill, MD5 of m355_frame_hash): the copy itself is queued on the
      stream that last wrote the frame, between pinned memory and the frame (frame_stage_* in runtime.hip) */
   void* stage = nullptr; size_t stage_bytes = 0;
@@ -353,6 +364,8 @@ Frame* get_frame(m355_ctx* c, int h);
 hipStream_t reader_begin(m355_ctx* c, Frame* f, int kind, const uint32_t** gate = nullptr, uint32_t* epoch = nullptr);
 int reader_end(m355_ctx* c, Frame* f, int kind, hipStream_t st);
 void readers_wait(m355_ctx* c, hipStream_t st, const Frame* f);
+int stats_requests_create(m355_ctx* c);            /* runtime_stats.hip: the slots of m355_frame_stats_async, made and dropped with the context */
+void stats_requests_destroy(m355_ctx* c);
 void halo_layout(const m355_pic_params& pp, HaloLayout& h);
 int lane_class_priority(int index);
 int lane_priorities_mode();
