@@ -89,7 +89,8 @@ namespace {
   X(m355_frame_download_async) X(m355_frame_download_wait) X(m355_frame_export) X(m355_frame_export_scaled) X(m355_frame_export_rgb_opts) X(m355_frame_export_resized_opts) X(m355_frame_export_resized_rgb_opts) X(m355_frames_export_tensor_opts) X(m355_frames_export_tensor_rois_opts) X(m355_frame_export_order) X(m355_colour_create) X(m355_colour_destroy) X(m355_colour_preset) \
   X(m355_group_create) X(m355_group_destroy) X(m355_group_decode) X(m355_picture_upload) X(m355_picture_replace) X(m355_shard_owner_of_tile) \
   X(m355_picture_arena_begin) X(m355_frame_hash_async) X(m355_frame_hash_result) X(m355_frame_measure_async) X(m355_frame_measure_result) \
-  X(m355_frame_stats_async) X(m355_frame_stats_result) X(m355_stats_quantile) X(m355_colour_linear)
+  X(m355_frame_stats_async) X(m355_frame_stats_result) X(m355_stats_quantile) X(m355_colour_linear) \
+  X(m355_colour_create_tone) X(m355_colour_preset_tone)
 
 struct Api {
   void* handle = nullptr;
@@ -1863,6 +1864,32 @@ LIBDE265_API int m355_glue_colour_preset_for_image(const struct de265_image* img
   if (m355_glue_image_colour(img, &d.in_primaries, &d.in_transfer) != M355_OK) return M355_ERR_INVALID;
   d.out_transfer = out_transfer; d.out_primaries = out_primaries; d.tone = tone; d.white_nits = white_nits; d.peak_nits = peak_nits;
   return A->m355_colour_preset(&d, tables);
+}
+/* Tone objects (m355_colour_create_tone: the tables and one gain per pixel, looked up at its maxRGB or luminance): the handle goes wherever
+ * m355_glue_colour_create's does — the _colour forms of the composed exports take it as it is — and m355_glue_colour_destroy destroys it. */
+LIBDE265_API int m355_glue_colour_create_tone(de265_decoder_context* ctx, const m355_colour_tables* tables, const m355_colour_tone* tone, int* handle)
+{
+  Api* A = api();
+  if (!A) return M355_ERR_NO_DEVICE;
+  Glue* g = ctx ? glue_of((const decoder_context*)ctx) : nullptr;
+  if (!g || g->n_ranks > 1) return M355_ERR_INVALID;
+  std::lock_guard<std::mutex> api_lock(g->api_mu);
+  const int rc = A->m355_colour_create_tone(g->mctx, tables, tone, handle);
+  if (rc != M355_OK) g->error = A->m355_last_error();
+  return rc;
+}
+/* m355_colour_preset_tone from what the picture's stream signals (m355_glue_image_colour) to out_transfer / out_primaries; tone = M355_TONE_*
+ * (M355_TONE_BT2390 included), norm = M355_NORM_* */
+LIBDE265_API int m355_glue_colour_preset_tone_for_image(const struct de265_image* img, int out_transfer, int out_primaries, int tone, int norm, int white_nits,
+                                                        int peak_nits, m355_colour_tables* tables, m355_colour_tone* tone_out)
+{
+  Api* A = api();
+  if (!A) return M355_ERR_NO_DEVICE;
+  m355_colour_preset_desc d;
+  memset(&d, 0, sizeof(d));
+  if (m355_glue_image_colour(img, &d.in_primaries, &d.in_transfer) != M355_OK) return M355_ERR_INVALID;
+  d.out_transfer = out_transfer; d.out_primaries = out_primaries; d.tone = tone; d.white_nits = white_nits; d.peak_nits = peak_nits;
+  return A->m355_colour_preset_tone(&d, norm, tables, tone_out);
 }
 /* The picture as R'G'B' (m355_frame_export_rgb: layout / samples = M355_RGB_*, one chroma reconstruction filter, integer-exact), with the waiting
  * behaviour of m355_glue_export_image: the only wait is for the worker to have enqueued the picture.  matrix = M355_MATRIX_*, or -1: what the stream

@@ -778,7 +778,29 @@ M355_API int   m355_frames_export_tensor_rois_opts(m355_ctx* ctx, const int* fra
  *     M355_TONE_CLIP y = min(1, x);  M355_TONE_REINHARD y = min(1, x (1 + x / w^2) / (1 + x));
  *     the inverse of out_transfer: 1 / 6 / 14 / 15 y^(1 / 2.4), 13 sRGB, 8 y; the entry is floor(y' * 65535 + 0.5).
  *   M355_ERR_INVALID: any other code point; out_transfer 16 or 18; a non-zero `reserved`; negative nits; peak < white when given; null pointers.
- * Not offered: HDR outputs (PQ / HLG out, linear above SDR white); luminance- or maxRGB-based tone mapping; the luminance-dependent HLG OOTF; 3-D
+ * TONE OBJECTS (m355_colour_create_tone): tables plus a m355_colour_tone.  The tone curve of a plain object is baked into lut_out and so acts per
+ * channel, which changes R : G : B above SDR white: saturated highlights shift in hue and desaturate.  A tone object looks ONE gain per pixel up, at
+ * the pixel's maxRGB or luminance, and multiplies it into the three linear channels (BT.2390's advice).  Per pixel (m355_colour_pixel_tone; host only)
+ * steps 1 and 2 run unchanged and give P_r, P_g, P_b in 0..ONE; then
+ *   2b. n = max(P_r, P_g, P_b) for M355_NORM_MAXRGB; for M355_NORM_LUMA n = clip(0, ONE, (w[0] P_r + w[1] P_g + w[2] P_b + (1 << 13)) >> 14), the
+ *       arithmetic of step 2 with `weights` as the row.  (idx, fr) from n as in step 3;
+ *       g = (gain[idx] (256 - fr) + gain[min(idx + 1, 1216)] fr + 128) >> 8  (Q24, <= M355_TONE_GAIN_ONE);
+ *       P'_c = (P_c g + (1 << 23)) >> 24 in exact integers (49 bits), so P'_c <= ONE, and P'_a P_b and P'_b P_a differ by at most (P_a + P_b) / 2:
+ *       the ratios are kept to the one rounding.
+ *   Steps 3 and 4 run unchanged on P'.  With every gain = M355_TONE_GAIN_ONE a tone object delivers what the plain object of the same tables does.
+ * m355_colour_create_tone shares the handle space, the limit of M355_COLOUR_OBJECTS and m355_colour_destroy with m355_colour_create; its handle goes
+ * wherever `colour` does.  M355_ERR_INVALID, nothing allocated: whatever m355_colour_create rejects; a null tone; an unknown norm; a gain above
+ * M355_TONE_GAIN_ONE; a weight outside -65535..65535; a non-zero weight with M355_NORM_MAXRGB; a non-zero `reserved`.
+ * m355_colour_preset_tone (host only, doubles) takes the descriptor of m355_colour_preset and a norm: lut_in and matrix are those of m355_colour_preset
+ *   byte for byte; lut_out is that of M355_TONE_CLIP (the inverse of out_transfer on min(1, x)); weights = the Y row of RGB -> XYZ of out_primaries,
+ *   Q14 rounded, the largest entry adjusted so that the row sums to 1 << 14 (all 0 for M355_NORM_MAXRGB); gain[0] = M355_TONE_GAIN_ONE and
+ *   gain[i] = floor(min(1, y(x) / x) 2^24 + 0.5) at x = knot(i) / ONE * S / white, with y the curve of `tone`: M355_TONE_CLIP y = min(1, x), a
+ *   hue-preserving clip; M355_TONE_REINHARD as above; M355_TONE_BT2390 the EETF of BT.2390 in the PQ domain with black 0: L_w = peak (or S),
+ *   maxLum = PQ^-1(white) / PQ^-1(L_w), KS = 1.5 maxLum - 0.5, E1 = PQ^-1(x white) / PQ^-1(L_w), E2 = E1 below KS and the Hermite spline
+ *   (2 t^3 - 3 t^2 + 1) KS + (t^3 - 2 t^2 + t) (1 - KS) + (-2 t^3 + 3 t^2) maxLum with t = (E1 - KS) / (1 - KS) above, clamped to 0..1,
+ *   y = PQ(E2 PQ^-1(L_w)) / white.  maxLum >= 1 is the identity; KS < 0 (a peak too far above white for the spline) is M355_ERR_INVALID, like
+ *   everything m355_colour_preset rejects and an unknown norm.  M355_TONE_BT2390 is the new call's alone: m355_colour_preset rejects it.
+ * Not offered: HDR outputs (PQ / HLG out, linear above SDR white); a gain above 1; the luminance-dependent HLG OOTF; 3-D
  * LUTs; dynamic metadata; colour in m355_frame_export_rgb_opts; a transform per slice. */
 #define M355_COLOUR_ONE        (1 << 24)     /* linear light, full scale */
 #define M355_COLOUR_IN_KNOTS   1025
@@ -786,6 +808,10 @@ M355_API int   m355_frames_export_tensor_rois_opts(m355_ctx* ctx, const int* fra
 #define M355_COLOUR_OBJECTS    16
 #define M355_TONE_CLIP         0
 #define M355_TONE_REINHARD     1
+#define M355_TONE_BT2390       2             /* m355_colour_preset_tone only */
+#define M355_TONE_GAIN_ONE     (1 << 24)     /* a gain of 1, Q24 */
+#define M355_NORM_MAXRGB       0
+#define M355_NORM_LUMA         1
 typedef struct m355_colour_tables {
   uint32_t lut_in[M355_COLOUR_IN_KNOTS];     /* every entry <= M355_COLOUR_ONE */
   int32_t  matrix[9];                        /* row-major, Q14, every |entry| <= 65535 */
@@ -795,6 +821,15 @@ typedef struct m355_colour_tables {
 typedef struct m355_colour_preset_desc {
   int32_t in_transfer, in_primaries, out_transfer, out_primaries, tone, white_nits, peak_nits, reserved;
 } m355_colour_preset_desc;
+typedef struct m355_colour_tone {
+  int32_t  norm;                             /* M355_NORM_* */
+  int32_t  weights[3];                       /* M355_NORM_LUMA: Q14 row, every |entry| <= 65535; M355_NORM_MAXRGB: 0 */
+  uint32_t gain[M355_COLOUR_OUT_KNOTS];      /* Q24, every entry <= M355_TONE_GAIN_ONE; indexed like lut_out */
+  uint32_t reserved[3];                      /* 0 */
+} m355_colour_tone;                          /* (4896 bytes) */
+M355_API int   m355_colour_create_tone(m355_ctx* ctx, const m355_colour_tables* tables, const m355_colour_tone* tone, int* handle);
+M355_API int   m355_colour_preset_tone(const m355_colour_preset_desc* desc, int norm, m355_colour_tables* tables_out, m355_colour_tone* tone_out);
+M355_API int   m355_colour_pixel_tone(const m355_colour_tables* tables, const m355_colour_tone* tone, const uint32_t rgb16[3], int samples, uint32_t out[3]);
 M355_API int   m355_colour_create(m355_ctx* ctx, const m355_colour_tables* tables, int* handle);
 M355_API int   m355_colour_destroy(m355_ctx* ctx, int handle);
 M355_API int   m355_colour_preset(const m355_colour_preset_desc* desc, m355_colour_tables* out);

@@ -114,6 +114,9 @@ class ExportOpts(ctypes.Structure):
 
 COLOUR_ONE, COLOUR_IN_KNOTS, COLOUR_OUT_KNOTS, COLOUR_OBJECTS = 1 << 24, 1025, 1217, 16   # M355_COLOUR_*
 TONE_CLIP, TONE_REINHARD = 0, 1               # M355_TONE_*
+TONE_BT2390 = 2                               # (colour_preset_tone only)
+TONE_GAIN_ONE = 1 << 24                       # M355_TONE_GAIN_ONE
+NORM_MAXRGB, NORM_LUMA = 0, 1                 # M355_NORM_*
 
 
 class ColourTables(ctypes.Structure):
@@ -126,6 +129,20 @@ class ColourPresetDesc(ctypes.Structure):
     """m355_colour_preset_desc (include/de265_mi355x.h)"""
     _fields_ = [(n, ctypes.c_int32) for n in ("in_transfer", "in_primaries", "out_transfer", "out_primaries", "tone", "white_nits", "peak_nits",
                                               "reserved")]
+
+
+class ColourTone(ctypes.Structure):
+    """m355_colour_tone (include/de265_mi355x.h)"""
+    _fields_ = [("norm", ctypes.c_int32), ("weights", ctypes.c_int32 * 3), ("gain", ctypes.c_uint32 * COLOUR_OUT_KNOTS), ("reserved", ctypes.c_uint32 * 3)]
+
+
+def colour_tone(norm, weights, gain, reserved=(0, 0, 0)):
+    """a ColourTone from its norm and three sequences (3, 1217 and 3 entries)"""
+    q = ColourTone(norm=norm)
+    q.weights[:] = [int(v) for v in weights]
+    q.gain[:] = [int(v) for v in gain]
+    q.reserved[:] = [int(v) for v in reserved]
+    return q
 
 
 def colour_tables(lut_in, matrix, lut_out, pad=0):
@@ -259,6 +276,11 @@ class Library:
             L.m355_colour_destroy.argtypes = [vp, i]
             L.m355_colour_preset.argtypes = [ctypes.POINTER(ColourPresetDesc), ctypes.POINTER(ColourTables)]
             L.m355_colour_pixel.argtypes = [ctypes.POINTER(ColourTables), ctypes.POINTER(ctypes.c_uint32), i, ctypes.POINTER(ctypes.c_uint32)]
+        if hasattr(L, "m355_colour_create_tone"):
+            L.m355_colour_create_tone.argtypes = [vp, ctypes.POINTER(ColourTables), ctypes.POINTER(ColourTone), ctypes.POINTER(i)]
+            L.m355_colour_preset_tone.argtypes = [ctypes.POINTER(ColourPresetDesc), i, ctypes.POINTER(ColourTables), ctypes.POINTER(ColourTone)]
+            L.m355_colour_pixel_tone.argtypes = [ctypes.POINTER(ColourTables), ctypes.POINTER(ColourTone), ctypes.POINTER(ctypes.c_uint32), i,
+                                                 ctypes.POINTER(ctypes.c_uint32)]
         L.m355_host_alloc.argtypes = [ctypes.c_size_t]
         L.m355_host_alloc.restype = vp
         L.m355_host_free.argtypes = [vp]
@@ -360,6 +382,20 @@ class Library:
         """the colour transform stage for one pixel (m355_colour_pixel; host only) -> (R, G, B)"""
         out = (ctypes.c_uint32 * 3)()
         self.check(self.lib.m355_colour_pixel(ctypes.byref(tables), (ctypes.c_uint32 * 3)(*[int(v) for v in rgb16]), samples, out))
+        return tuple(int(v) for v in out)
+
+    def colour_preset_tone(self, in_transfer, in_primaries, out_transfer, out_primaries, tone=TONE_BT2390, norm=NORM_MAXRGB, white_nits=0, peak_nits=0,
+                           reserved=0):
+        """the tables and the gain of a tone preset (m355_colour_preset_tone; host only) -> (ColourTables, ColourTone)"""
+        d = ColourPresetDesc(in_transfer, in_primaries, out_transfer, out_primaries, tone, white_nits, peak_nits, reserved)
+        t, q = ColourTables(), ColourTone()
+        self.check(self.lib.m355_colour_preset_tone(ctypes.byref(d), norm, ctypes.byref(t), ctypes.byref(q)))
+        return t, q
+
+    def colour_pixel_tone(self, tables, tone, rgb16, samples):
+        """the colour transform stage of a tone object for one pixel (m355_colour_pixel_tone; host only) -> (R, G, B)"""
+        out = (ctypes.c_uint32 * 3)()
+        self.check(self.lib.m355_colour_pixel_tone(ctypes.byref(tables), ctypes.byref(tone), (ctypes.c_uint32 * 3)(*[int(v) for v in rgb16]), samples, out))
         return tuple(int(v) for v in out)
 
     def stats_quantile(self, hist, num, den):
@@ -631,6 +667,14 @@ class Context:
         the `colour` keyword of the composed exports takes"""
         h = ctypes.c_int(0)
         self.L.check(self.L.lib.m355_colour_create(self.h, None if tables is None else ctypes.byref(tables), ctypes.byref(h)))
+        return int(h.value)
+
+    def colour_create_tone(self, tables, tone):
+        """m355_colour_create_tone: the tables and the tone (ColourTables, ColourTone; None for a NULL pointer) as a tone object of this context ->
+        its handle, which goes wherever colour_create's does; colour_destroy destroys it"""
+        h = ctypes.c_int(0)
+        self.L.check(self.L.lib.m355_colour_create_tone(self.h, None if tables is None else ctypes.byref(tables), None if tone is None else ctypes.byref(tone),
+                                                        ctypes.byref(h)))
         return int(h.value)
 
     def colour_destroy(self, handle):

@@ -6,6 +6,7 @@
  *               row lacks to 1 << 14; equal primaries: the identity
  *   lut_out[i]  nits = knot(i) / ONE * S, x = nits / white, the tone curve, the inverse of out_transfer, times 65535, rounded
  * Returns 0, or 1 for a descriptor outside the contract.
+ * m355_cp_build_tone, behind m355_colour_preset_tone, builds a tone object's tables and gain from the same descriptor (stated at the function).
  */
 #ifndef M355_COLOUR_PRESET_H
 #define M355_COLOUR_PRESET_H
@@ -108,6 +109,66 @@ static inline int m355_cp_build(const m355_colour_preset_desc* d, m355_colour_ta
     if (y > 1.0) y = 1.0;
     const double v = floor(m355_cp_oetf(ot, y) * 65535.0 + 0.5);
     out->lut_out[i] = (uint16_t)(v >= 65535.0 ? 65535.0 : (v <= 0.0 ? 0.0 : v));
+  }
+  return 0;
+}
+
+/* the inverse of the ST 2084 EOTF: nits -> the non-linear value */
+static inline double m355_cp_pq_inverse(double nits)
+{
+  const double m1 = 2610.0 / 16384.0, m2 = 2523.0 / 4096.0 * 128.0, c1 = 3424.0 / 4096.0, c2 = 2413.0 / 4096.0 * 32.0, c3 = 2392.0 / 4096.0 * 32.0;
+  const double p = pow((nits > 0.0 ? nits : 0.0) / 10000.0, m1);
+  return pow((c1 + c2 * p) / (1.0 + c3 * p), m2);
+}
+/* The preset of a TONE OBJECT behind m355_colour_preset_tone: lut_in and matrix of m355_cp_build, lut_out that of M355_TONE_CLIP, and the curve y(x) of
+ * d->tone as the gain min(1, y / x) at the knots of lut_out:
+ *   gain[i]     x = knot(i) / ONE * S / white; M355_TONE_CLIP y = min(1, x); M355_TONE_REINHARD as in m355_cp_build; M355_TONE_BT2390 the EETF of BT.2390
+ *               in the PQ domain, black 0: E1 = PQ^-1(x white) / PQ^-1(L_w) (at most 1), maxLum = PQ^-1(white) / PQ^-1(L_w), KS = 1.5 maxLum - 0.5,
+ *               the Hermite spline above KS, E2 in 0 .. 1, y = PQ(E2 PQ^-1(L_w)) / white; maxLum >= 1: y = x.  floor(min(1, y / x) 2^24 + 0.5); gain[0] = 2^24
+ *   weights     M355_NORM_LUMA: the Y row of RGB -> XYZ of out_primaries, Q14 rounded, the largest entry takes what the row lacks to 1 << 14
+ * Returns 0, or 1 for what m355_cp_build rejects, an unknown tone or norm, or KS < 0. */
+static inline int m355_cp_build_tone(const m355_colour_preset_desc* d, int norm, m355_colour_tables* out, m355_colour_tone* tone)
+{
+  if (!d || !out || !tone || (norm != M355_NORM_MAXRGB && norm != M355_NORM_LUMA)) return 1;
+  if (d->tone != M355_TONE_CLIP && d->tone != M355_TONE_REINHARD && d->tone != M355_TONE_BT2390) return 1;
+  m355_colour_preset_desc clip = *d;
+  clip.tone = M355_TONE_CLIP;
+  if (m355_cp_build(&clip, out)) return 1;
+  const double white = d->white_nits ? (double)d->white_nits : 203.0, one = (double)M355_COLOUR_ONE;
+  const double S = m355_cp_eotf(m355_cp_transfer(d->in_transfer), 1.0, white), peak = d->peak_nits ? (double)d->peak_nits : S;
+  const double w = peak / white > 1.0 ? peak / white : 1.0;
+  const double lw = m355_cp_pq_inverse(peak), max_lum = m355_cp_pq_inverse(white) / lw, ks = 1.5 * max_lum - 0.5;
+  if (d->tone == M355_TONE_BT2390 && max_lum < 1.0 && ks < 0.0) return 1;
+  memset(tone, 0, sizeof(*tone));
+  tone->norm = norm;
+  if (norm == M355_NORM_LUMA) {
+    double m[9];
+    int32_t sum = 0, big = 0;
+    m355_cp_rgb_to_xyz(d->out_primaries == 2 ? 1 : d->out_primaries, m);
+    for (int c = 0; c < 3; c++) {
+      tone->weights[c] = (int32_t)floor(m[3 + c] * 16384.0 + 0.5); sum += tone->weights[c];
+      if (tone->weights[c] > tone->weights[big]) big = c;
+    }
+    tone->weights[big] += (1 << 14) - sum;
+  }
+  tone->gain[0] = (uint32_t)M355_TONE_GAIN_ONE;
+  for (int i = 1; i < M355_COLOUR_OUT_KNOTS; i++) {
+    const double x = (double)m355_ct_out_knot((uint32_t)i) / one * S / white;
+    double y = x;
+    if (d->tone == M355_TONE_REINHARD) y = x * (1.0 + x / (w * w)) / (1.0 + x);
+    else if (d->tone == M355_TONE_BT2390 && max_lum < 1.0) {
+      double e1 = m355_cp_pq_inverse(x * white) / lw;
+      if (e1 > 1.0) e1 = 1.0;
+      if (e1 > ks) {
+        const double t = (e1 - ks) / (1.0 - ks), t2 = t * t, t3 = t2 * t;
+        double e2 = (2.0 * t3 - 3.0 * t2 + 1.0) * ks + (t3 - 2.0 * t2 + t) * (1.0 - ks) + (-2.0 * t3 + 3.0 * t2) * max_lum;
+        e2 = e2 < 0.0 ? 0.0 : (e2 > 1.0 ? 1.0 : e2);
+        y = m355_cp_eotf(16, e2 * lw, white) / white;
+      }
+    }
+    if (y > 1.0) y = 1.0;
+    const double g = y / x < 1.0 ? y / x : 1.0;
+    tone->gain[i] = (uint32_t)floor(g * (double)M355_TONE_GAIN_ONE + 0.5);
   }
   return 0;
 }

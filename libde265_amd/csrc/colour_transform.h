@@ -10,6 +10,15 @@
  *   3. encode      P < 64: idx = P, fr = 0; else e = floor(log2 P), n = P << (24 - e), idx = 64 (e - 5) + ((n >> 18) & 63), fr = (n >> 10) & 255
  *                  o = (lut_out[idx] (256 - fr) + lut_out[min(idx + 1, 1216)] fr + 128) >> 8
  *   4. deliver     M355_RGB_U16: o; M355_RGB_U8: (2 o + 257) / 514 = o / 257 rounded
+ * A TONE OBJECT (m355_colour_tone beside the tables; m355_colour_pixel_tone) puts step 2b between 2 and 3: ONE gain for the pixel's three channels
+ *   2b. gain       n = max(P_r, P_g, P_b) (M355_NORM_MAXRGB) or the matrix row of step 2 with `weights` over P (M355_NORM_LUMA: its clip keeps n in
+ *                  0 .. ONE); (idx, fr) of step 3 from n; g = (gain[idx] (256 - fr) + gain[min(idx + 1, 1216)] fr + 128) >> 8;
+ *                  P'_c = (P_c g + (1 << 23)) >> 24, and steps 3 and 4 run on P'
+ *                  computed as 32 x 32 -> 64-bit multiply-adds (the kernel: v_mad_u64_u32, or v_mul_lo_u32 / v_mul_hi_u32 and an add with carry): gain
+ *                  entries are at most 2^24 and the two weights sum to 256, so the interpolation's sum is at most 2^32 + 128 — one bit more than 32, which
+ *                  is why it is not taken in 32 bits as step 3's is — and g <= 2^24 again; P_c <= 2^24, so P_c g + 2^23 <= 2^48 + 2^23 < 2^64 and
+ *                  P'_c <= (2^48 + 2^23) >> 24 = 2^24 = ONE.  Nothing is truncated before the one shift of each line, so both are the statements above
+ *                  bit for bit.
  * M355_CT_MAD24(a, b, c) = a * b + c for operands that fit 24 bits signed, and M355_CT_FLOG2(x) = floor(log2 x) for x > 0, may be defined by the
  * including file (the kernel: v_mad_i32_i24 and v_ffbh_u32, k_resize_dev.h); the functions are static, so that a file with its own pair and one without
  * link into one library.
@@ -61,6 +70,18 @@ M355_CT_FN uint32_t m355_ct_out_knot(uint32_t idx) { return idx < 64u ? idx : (6
 /* step 3, the interpolation: lo = lut_out[idx], hi = lut_out[min(idx + 1, 1216)] */
 M355_CT_FN uint32_t m355_ct_encode(uint32_t lo, uint32_t hi, uint32_t fr) { return (lo * (256u - fr) + hi * fr + 128u) >> 8; }
 
+/* step 2b of a tone object, the interpolation: lo = gain[idx], hi = gain[min(idx + 1, 1216)], both <= GAIN_ONE: 33 bits before the shift */
+M355_CT_FN uint32_t m355_ct_gain(uint32_t lo, uint32_t hi, uint32_t fr) { return (uint32_t)(((uint64_t)lo * (256u - fr) + (uint64_t)hi * fr + 128u) >> 8); }
+/* step 2b, the gain on one channel: p <= ONE, g <= GAIN_ONE: 49 bits before the shift, at most ONE behind it */
+M355_CT_FN uint32_t m355_ct_apply(uint32_t p, uint32_t g) { return (uint32_t)(((uint64_t)p * g + (1u << 23)) >> 24); }
+/* step 2b, what the gain is looked up at */
+M355_CT_FN uint32_t m355_ct_norm(int32_t norm, int32_t w0, int32_t w1, int32_t w2, uint32_t pr, uint32_t pg, uint32_t pb)
+{
+  if (norm == M355_NORM_LUMA) return m355_ct_matrix_row(w0, w1, w2, pr, pg, pb);
+  const uint32_t a = pr > pg ? pr : pg;
+  return a > pb ? a : pb;
+}
+
 /* step 4 */
 M355_CT_FN uint32_t m355_ct_deliver(uint32_t o, bool u8) { return u8 ? (2u * o + 257u) / 514u : o; }
 
@@ -85,12 +106,35 @@ M355_CT_FN void m355_ct_pixel(const m355_colour_tables* t, const uint32_t rgb16[
   }
 }
 
+/* the whole stage of a tone object for one pixel: what m355_colour_pixel_tone is */
+M355_CT_FN void m355_ct_pixel_tone(const m355_colour_tables* t, const m355_colour_tone* q, const uint32_t rgb16[3], int samples, uint32_t out[3])
+{
+  uint32_t l[3], p[3], idx, fr;
+  for (int c = 0; c < 3; c++) l[c] = m355_ct_linear_of(t, rgb16[c] > 65535u ? 65535u : rgb16[c]);
+  for (int c = 0; c < 3; c++) p[c] = m355_ct_matrix_row(t->matrix[3 * c], t->matrix[3 * c + 1], t->matrix[3 * c + 2], l[0], l[1], l[2]);
+  m355_ct_out_index(m355_ct_norm(q->norm, q->weights[0], q->weights[1], q->weights[2], p[0], p[1], p[2]), &idx, &fr);
+  const uint32_t g = m355_ct_gain(q->gain[idx], q->gain[idx < M355_COLOUR_OUT_LAST ? idx + 1 : M355_COLOUR_OUT_LAST], fr);
+  for (int c = 0; c < 3; c++) {
+    m355_ct_out_index(m355_ct_apply(p[c], g), &idx, &fr);
+    const uint32_t o = m355_ct_encode(t->lut_out[idx], t->lut_out[idx < M355_COLOUR_OUT_LAST ? idx + 1 : M355_COLOUR_OUT_LAST], fr);
+    out[c] = m355_ct_deliver(o, samples == M355_RGB_U8);
+  }
+}
+
 /* the bounds m355_colour_create checks: 0 = within them */
 M355_CT_FN int m355_ct_tables_check(const m355_colour_tables* t)
 {
   for (int k = 0; k < M355_COLOUR_IN_KNOTS; k++) if (t->lut_in[k] > (uint32_t)M355_COLOUR_ONE) return 1;
   for (int k = 0; k < 9; k++) if (t->matrix[k] > 65535 || t->matrix[k] < -65535) return 2;
   return t->pad ? 3 : 0;
+}
+/* the bounds m355_colour_create_tone checks beyond those: 0 = within them */
+M355_CT_FN int m355_ct_tone_check(const m355_colour_tone* q)
+{
+  if (q->norm != M355_NORM_MAXRGB && q->norm != M355_NORM_LUMA) return 1;
+  for (int k = 0; k < 3; k++) if (q->weights[k] > 65535 || q->weights[k] < -65535 || (q->norm == M355_NORM_MAXRGB && q->weights[k])) return 2;
+  for (int k = 0; k < M355_COLOUR_OUT_KNOTS; k++) if (q->gain[k] > (uint32_t)M355_TONE_GAIN_ONE) return 3;
+  return q->reserved[0] || q->reserved[1] || q->reserved[2] ? 4 : 0;
 }
 
 #endif

@@ -8,6 +8,14 @@
  * 24-bit multiplies, three v_ffbh_u32, six 16-bit LDS reads.
  * Reads: lut_in[k], lut_in[k + 1] with k = v >> 6 <= 1023 for v <= 65535 (the caller's clip); LDS entries idx, idx + 1 with idx <= 1216 (P <= ONE by
  * the clip of m355_ct_matrix_row), of the 1218 the fill wrote.
+ * A tone object's gain table (1217 x 32 bits, and the last entry once more: 1218 dwords behind the tables in the object's allocation) stays in GLOBAL
+ * memory like lut_in: in LDS it is 4 880 bytes more, 55 344 B for the F32 instantiations, which is two workgroups per CU instead of three
+ * (3 x 55 344 = 166 032 > 163 840), and was built and measured no faster (profiles/export_tone_bench.txt): one gather of two neighbouring dwords per
+ * pixel beside the three of lut_in is cheap.  LDS is what it is for a
+ * plain object: 44 320 B, F32 50 464 B.  Reads: gain[idx], gain[idx + 1] with idx <= 1216 — n is a maximum of three values the clip of
+ * m355_ct_matrix_row holds in 0 .. ONE, or such a clipped row itself — of the 1218 m355_colour_create_tone wrote; the LDS entries as above, since
+ * P' <= ONE (m355_ct_apply with g <= GAIN_ONE, which m355_ct_gain keeps for entries <= GAIN_ONE, checked at creation).  Per pixel beyond the plain
+ * stage: that gather, five 32 x 32 -> 64-bit multiply-adds, one more v_ffbh_u32, and for M355_NORM_LUMA six 24-bit multiplies.
  */
 #pragma once
 #include <stddef.h>
@@ -42,6 +50,28 @@ __device__ __forceinline__ void d_colour_pixel(const uint8_t* tables, const unsi
   for (int c = 0; c < 3; c++) {
     uint32_t idx, fr;
     m355_ct_out_index(m355_ct_matrix_row(m[3 * c], m[3 * c + 1], m[3 * c + 2], l[0], l[1], l[2]), &idx, &fr);
+    e[c] = m355_ct_encode(lo[idx], lo[idx + 1], fr);
+  }
+}
+/* the same for a tone object: step 2b between the matrix and the output table — gain = the object's gain table (global memory, two neighbouring
+   dwords in one gather per pixel), norm and w = its norm and weights (scalars) */
+__device__ __forceinline__ void d_colour_pixel_tone(const uint8_t* tables, const unsigned short* lo, const int32_t* m, const uint32_t* gain, int32_t norm, const int32_t* w,
+                                                    unsigned (&e)[3])
+{
+  const M355_GLOBAL uint32_t* lin = (const M355_GLOBAL uint32_t*)tables;
+  const M355_GLOBAL uint32_t* gt = (const M355_GLOBAL uint32_t*)gain;
+  uint32_t ta[3], tb[3], l[3], p[3], idx, fr;
+#pragma unroll
+  for (int c = 0; c < 3; c++) { const uint32_t k = e[c] >> 6; ta[c] = lin[k]; tb[c] = lin[k + 1]; }
+#pragma unroll
+  for (int c = 0; c < 3; c++) l[c] = m355_ct_linear(ta[c], tb[c], e[c] & 63u);
+#pragma unroll
+  for (int c = 0; c < 3; c++) p[c] = m355_ct_matrix_row(m[3 * c], m[3 * c + 1], m[3 * c + 2], l[0], l[1], l[2]);
+  m355_ct_out_index(m355_ct_norm(norm, w[0], w[1], w[2], p[0], p[1], p[2]), &idx, &fr);
+  const uint32_t g = m355_ct_gain(gt[idx], gt[idx + 1], fr);
+#pragma unroll
+  for (int c = 0; c < 3; c++) {
+    m355_ct_out_index(m355_ct_apply(p[c], g), &idx, &fr);
     e[c] = m355_ct_encode(lo[idx], lo[idx + 1], fr);
   }
 }

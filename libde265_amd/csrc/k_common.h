@@ -345,10 +345,14 @@ void m355_launch_export_resized(const ExportResizedArgs& a, int src_bytes, int d
 
 /* the colour transform stage of a launch of k_export_resized_rgb.hip (m355_export_opts.colour; colour_transform.h): t = the object's tables in device
    memory (m355_colour_tables; null: no stage, and the instantiations without it run), m = its matrix, wave-uniform like t.  With a stage, k are the
-   coefficients of M355_RGB_U16 whatever the descriptor's samples, which pick the delivery (RR_FRAME: the element bytes; tensors: u16). */
+   coefficients of M355_RGB_U16 whatever the descriptor's samples, which pick the delivery (RR_FRAME: the element bytes; tensors: u16).
+   A tone object (m355_colour_create_tone) adds g = its gain table in device memory (1218 dwords, the last entry repeated; null: a plain object, and the
+   instantiations without the gain run), norm and the weights w of M355_NORM_LUMA, wave-uniform too. */
 struct ColourArgs {
   const uint8_t* t;
-  int32_t m[9], pad;
+  int32_t m[9], norm;
+  const uint32_t* g;
+  int32_t w[3], pad;
 };
 /* one m355_frame_export_resized_rgb (k_export_resized_rgb.hip, RR_FRAME).  src[] = the rectangle's first sample of Y, Cb, Cr (the resize clamps to the rectangle),
    pitches in BYTES (src_pitch[0] luma, [1] both chroma planes); dst[0] alone for the packed layout, else R, G, B.  Index 0 of sn / dn is the luma

@@ -50,13 +50,15 @@
  *   staged row (the channels of an NHWC pixel keep their order), and the tile's first destination column is out_width - c0 - ncols.
  * Layout, chroma format, F16 against BF16 and U8 against U16 of the tensors' integer stage are wave-uniform run-time switches (kernel arguments in
  * scalar registers): source sample bytes, element bytes, the mode, the filter, SITED and COLOUR are the template parameters, twelve instantiations per filter and
- * value of SITED and of COLOUR.
+ * value of SITED and of COLOUR (off, tables, tables + tone: 144 in all).
  * COLOUR (m355_export_opts.colour; colour_transform.h, k_colour_dev.h) puts the colour transform stage between the clip and the staging: the launch's
  *   coefficients are then those of M355_RGB_U16 and the clip is to 65 535 whatever the samples; the pixel's three 16-bit values go through the input
  *   table (global memory, two neighbouring knots per channel in one load), the 3 x 3 matrix (wave-uniform kernel arguments, 24-bit multiplies) and the
  *   output table (LDS: 2 436 bytes more, filled behind the gate and ahead of the prologue's barrier), and the delivery the samples ask for (U8: one
- *   rounding division) hands the integer to the pack or to tensor_element.h as before.  COLOUR = false compiles none of it: those instantiations are
- *   what they were.
+ *   rounding division) hands the integer to the pack or to tensor_element.h as before.  COLOUR = off compiles none of it: those instantiations are
+ *   what they were.  COLOUR = tone (an object of m355_colour_create_tone) puts step 2b between the matrix and the output table: one gain per pixel, looked
+ *   up at the pixel's maxRGB or luminance (norm and the weights: wave-uniform kernel arguments) in the object's gain table (global memory, one gather of two
+ *   neighbouring dwords: k_colour_dev.h bounds it) and multiplied into the three linear values in 64 bits.  COLOUR = tables is what COLOUR = true was.
  *
  * Reads stay inside the planes' allocations, by the argument of k_export_resized.hip for every plane of every slice: the host admits a frame only
  * if it contains the slice's rectangle (export_plan per frame), whose size is the source size the slice's rows are derived from.  A filter row's
@@ -183,6 +185,7 @@ __device__ __forceinline__ int d_rr_row(int64_t sn, int64_t dn, int cosited, int
 /* The modes and their kernel arguments.  RR_SRC(i) / RR_PITCH(i): plane i's first sample and pitch class i of the frame or of the slice's record;
    RR_GEOM(field): a field of the source's geometry, the slice's in RR_ROIS, else the launch's — each read at the place of its use. */
 enum { RR_FRAME = 0, RR_BATCH = 1, RR_ROIS = 2 };
+enum { RR_COLOUR_OFF = 0, RR_COLOUR_TABLES = 1, RR_COLOUR_TONE = 2 };   /* COLOUR: no stage, a plain object, a tone object */
 template <int MODE> struct RrArgs { typedef ExportResizedRgbArgs T; };
 template <> struct RrArgs<RR_BATCH> { typedef ExportTensorArgs T; };
 template <> struct RrArgs<RR_ROIS> { typedef ExportTensorRoisArgs T; };
@@ -190,7 +193,7 @@ template <> struct RrArgs<RR_ROIS> { typedef ExportTensorRoisArgs T; };
 #define RR_PITCH(i) ({ uint32_t g_; if constexpr (MODE == RR_FRAME) g_ = (uint32_t)a.src_pitch[i]; else g_ = (uint32_t)a.fr[slice].src_pitch[i]; g_; })
 #define RR_GEOM(field) ({ uint32_t g_; if constexpr (MODE == RR_ROIS) g_ = a.fr[slice].field; else g_ = a.field; g_; })
 
-template <int SB, int EB, int MODE, int FILTER, bool SITED, bool COLOUR>
+template <int SB, int EB, int MODE, int FILTER, bool SITED, int COLOUR>
 __global__ void __launch_bounds__(256) k_export_resized_rgb(typename RrArgs<MODE>::T a)
 {
   constexpr bool CUBIC = FILTER == M355_FILTER_CUBIC;
@@ -215,7 +218,7 @@ __global__ void __launch_bounds__(256) k_export_resized_rgb(typename RrArgs<MODE
   const uint32_t tid = threadIdx.x;
   /* the colour transform stage (m355_export_opts.colour): its output table goes to LDS here, behind the gate and ahead of the prologue's barrier */
   const unsigned short* s_lo = nullptr;
-  if constexpr (COLOUR) {
+  if constexpr (COLOUR != RR_COLOUR_OFF) {
     __shared__ unsigned s_lut[M355_COLOUR_LDS_DWORDS];
     d_colour_fill(a.colour.t, s_lut, tid);
     s_lo = (const unsigned short*)s_lut;
@@ -349,7 +352,7 @@ __global__ void __launch_bounds__(256) k_export_resized_rgb(typename RrArgs<MODE
   const bool odd = swl && (X & 1u);
   /* the epilogue of the launch (scalar): the clip of the integer stage; tensors: the element format, scale and bias per channel (RR_TE: 0 for a frame) */
 #define RR_TE(T, expr) ({ T g_ = 0; if constexpr (MODE != RR_FRAME) g_ = (expr); g_; })
-  const int M = COLOUR ? 65535 : (MODE == RR_FRAME ? (EB == 1 ? 255 : 65535) : (RR_TE(int, a.u16) ? 65535 : 255));   /* (COLOUR: k is the U16 set) */
+  const int M = COLOUR != RR_COLOUR_OFF ? 65535 : (MODE == RR_FRAME ? (EB == 1 ? 255 : 65535) : (RR_TE(int, a.u16) ? 65535 : 255));   /* (COLOUR: k is the U16 set) */
   const bool deliver_u8 = MODE == RR_FRAME ? EB == 1 : !RR_TE(int, a.u16);   /* COLOUR: step 4 of colour_transform.h */
   const uint32_t bf16_mask = RR_TE(int, a.bf16) ? 0xFFFFFFFFu : 0u;
   const float sc[3] = {RR_TE(float, a.scale[0]), RR_TE(float, a.scale[1]), RR_TE(float, a.scale[2])};
@@ -448,8 +451,9 @@ __global__ void __launch_bounds__(256) k_export_resized_rgb(typename RrArgs<MODE
           b = d_mad24(cbu, uv[0], base);
         }
         unsigned e[3] = {(unsigned)d_clip3(0, M, r >> F), (unsigned)d_clip3(0, M, g >> F), (unsigned)d_clip3(0, M, b >> F)};
-        if constexpr (COLOUR) {                                /* table, matrix, table on the 16-bit R'G'B', then the delivery the samples ask for */
-          d_colour_pixel(a.colour.t, s_lo, a.colour.m, e);
+        if constexpr (COLOUR != RR_COLOUR_OFF) {               /* table, matrix, (tone: the gain,) table on the 16-bit R'G'B', then the delivery the samples ask for */
+          if constexpr (COLOUR == RR_COLOUR_TONE) d_colour_pixel_tone(a.colour.t, s_lo, a.colour.m, a.colour.g, a.colour.norm, a.colour.w, e);
+          else d_colour_pixel(a.colour.t, s_lo, a.colour.m, e);
 #pragma unroll
           for (int c = 0; c < 3; c++) e[c] = m355_ct_deliver(e[c], deliver_u8);
         }
@@ -487,8 +491,9 @@ __global__ void __launch_bounds__(256) k_export_resized_rgb(typename RrArgs<MODE
   if (src_bytes == 2 && elem_bytes == B0) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_export_resized_rgb<2, B0, MODE, F, S, C>), g_, block, 0, st, a); \
   if (src_bytes == 2 && elem_bytes == B1) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_export_resized_rgb<2, B1, MODE, F, S, C>), g_, block, 0, st, a);
 #define RR_LAUNCH_S(MODE, B0, B1, F, S) \
-  if (a.colour.t) { RR_LAUNCH_C(MODE, B0, B1, F, S, true) } \
-  else { RR_LAUNCH_C(MODE, B0, B1, F, S, false) }
+  if (a.colour.t && a.colour.g) { RR_LAUNCH_C(MODE, B0, B1, F, S, RR_COLOUR_TONE) } \
+  else if (a.colour.t) { RR_LAUNCH_C(MODE, B0, B1, F, S, RR_COLOUR_TABLES) } \
+  else { RR_LAUNCH_C(MODE, B0, B1, F, S, RR_COLOUR_OFF) }
 #define RR_LAUNCH_F(MODE, B0, B1, F) \
   if (a.chroma_loc != 0) { RR_LAUNCH_S(MODE, B0, B1, F, true) } \
   else { RR_LAUNCH_S(MODE, B0, B1, F, false) }

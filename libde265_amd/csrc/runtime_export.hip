@@ -143,6 +143,8 @@ int opts_check(const char* who, m355_ctx* c, const m355_export_opts* o, const Fr
     if (!obj) return fail(M355_ERR_INVALID, "%s: colour %d (reserved[0]) is no live colour transform of this context", who, o->colour);
     colour->t = obj->dev;
     for (int k = 0; k < 9; k++) colour->m[k] = obj->matrix[k];
+    colour->g = obj->gain; colour->norm = obj->norm;
+    for (int k = 0; k < 3; k++) colour->w[k] = obj->weights[k];
   }
   if (!resizes && o->filter != M355_FILTER_TRIANGLE) return fail(M355_ERR_INVALID, "%s: filter %d where nothing is resized", who, o->filter);
   if (o->chroma_loc < 0 || o->chroma_loc > 3) return fail(M355_ERR_INVALID, "%s: chroma sample location type %d is not 0..3", who, o->chroma_loc);
@@ -465,29 +467,52 @@ int m355_frame_export_resized_filtered(m355_ctx* c, int h, const m355_resize_des
 int m355_frame_export_resized(m355_ctx* c, int h, const m355_resize_desc* e) { return m355_frame_export_resized_opts(c, h, e, nullptr); }
 /* The colour transform objects (include/de265_mi355x.h, COLOUR TRANSFORM): the tables go to device memory of the context through its pinned staging
  * buffer and the active lane's stream, like m355_device_write's bytes; the exports find an object by its handle (opts_check). */
-int m355_colour_create(m355_ctx* c, const m355_colour_tables* t, int* handle)
+/* A tone object (q != null) is the same object with its gain table behind the tables in one allocation: M355_COLOUR_GAIN_DWORDS dwords at
+ * M355_COLOUR_GAIN_OFFSET, the last entry repeated so that the kernel's idx + 1 needs no clamp. */
+constexpr size_t M355_COLOUR_GAIN_OFFSET = (sizeof(m355_colour_tables) + 7) & ~(size_t)7, M355_COLOUR_GAIN_DWORDS = M355_COLOUR_OUT_KNOTS + 1;
+static int colour_create(const char* who, m355_ctx* c, const m355_colour_tables* t, const m355_colour_tone* q, bool tone, int* handle)
 {
-  if (!c || !t || !handle) return fail(M355_ERR_INVALID, "m355_colour_create: no context / tables / handle");
+  if (!c || !t || !handle || (tone && !q)) return fail(M355_ERR_INVALID, "%s: no context / tables / %shandle", who, tone ? "tone / " : "");
   const int bad = m355_ct_tables_check(t);
-  if (bad) return fail(M355_ERR_INVALID, "m355_colour_create: %s", bad == 1 ? "an entry of lut_in is above M355_COLOUR_ONE" : (bad == 2 ? "a matrix entry is outside -65535..65535" : "pad is not 0"));
+  if (bad) return fail(M355_ERR_INVALID, "%s: %s", who, bad == 1 ? "an entry of lut_in is above M355_COLOUR_ONE" : (bad == 2 ? "a matrix entry is outside -65535..65535" : "pad is not 0"));
+  const int badq = tone ? m355_ct_tone_check(q) : 0;
+  if (badq) return fail(M355_ERR_INVALID, "%s: %s", who, badq == 1 ? "unknown norm" : (badq == 2 ? "a weight is outside -65535..65535, or not 0 with M355_NORM_MAXRGB" :
+                                                          (badq == 3 ? "a gain is above M355_TONE_GAIN_ONE" : "reserved is not 0")));
   m355_ctx::ColourObj* obj = nullptr;
-  for (auto& q : c->colour) if (!q.handle && !obj) obj = &q;
-  if (!obj) return fail(M355_ERR_BUSY, "m355_colour_create: %d colour transforms live (destroy one: m355_colour_destroy)", M355_COLOUR_OBJECTS);
+  for (auto& o : c->colour) if (!o.handle && !obj) obj = &o;
+  if (!obj) return fail(M355_ERR_BUSY, "%s: %d colour transforms live (destroy one: m355_colour_destroy)", who, M355_COLOUR_OBJECTS);
   hipSetDevice(c->device);
-  int rc = stage_reserve(c, sizeof(*t));
+  const size_t bytes = tone ? M355_COLOUR_GAIN_OFFSET + 4 * M355_COLOUR_GAIN_DWORDS : sizeof(*t);
+  int rc = stage_reserve(c, bytes);
   if (rc) return rc;
   uint8_t* dev = nullptr;
-  if (hipMalloc(&dev, sizeof(*t)) != hipSuccess) return fail(M355_ERR_NOMEM, "m355_colour_create: hipMalloc(%zu) failed", sizeof(*t));
+  if (hipMalloc(&dev, bytes) != hipSuccess) return fail(M355_ERR_NOMEM, "%s: hipMalloc(%zu) failed", who, bytes);
+  memset(c->stage, 0, bytes);
   memcpy(c->stage, t, sizeof(*t));
-  const hipStream_t st = lane(c).stream;
-  if (hipMemcpyAsync(dev, c->stage, sizeof(*t), hipMemcpyHostToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-    hipFree(dev);
-    return fail(M355_ERR_HIP, "m355_colour_create: the copy of the tables failed");
+  if (tone) {
+    uint32_t* g = (uint32_t*)((uint8_t*)c->stage + M355_COLOUR_GAIN_OFFSET);
+    memcpy(g, q->gain, sizeof(q->gain));
+    g[M355_COLOUR_OUT_KNOTS] = q->gain[M355_COLOUR_OUT_KNOTS - 1];
   }
+  const hipStream_t st = lane(c).stream;
+  if (hipMemcpyAsync(dev, c->stage, bytes, hipMemcpyHostToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
+    hipFree(dev);
+    return fail(M355_ERR_HIP, "%s: the copy of the tables failed", who);
+  }
+  *obj = m355_ctx::ColourObj();
   obj->dev = dev;
   for (int k = 0; k < 9; k++) obj->matrix[k] = t->matrix[k];
+  if (tone) {
+    obj->gain = (uint32_t*)(dev + M355_COLOUR_GAIN_OFFSET); obj->norm = q->norm;
+    for (int k = 0; k < 3; k++) obj->weights[k] = q->weights[k];
+  }
   *handle = obj->handle = g_colour_handle.fetch_add(1);
   return M355_OK;
+}
+int m355_colour_create(m355_ctx* c, const m355_colour_tables* t, int* handle) { return colour_create("m355_colour_create", c, t, nullptr, false, handle); }
+int m355_colour_create_tone(m355_ctx* c, const m355_colour_tables* t, const m355_colour_tone* q, int* handle)
+{
+  return colour_create("m355_colour_create_tone", c, t, q, true, handle);
 }
 int m355_colour_destroy(m355_ctx* c, int handle)
 {
@@ -512,6 +537,19 @@ int m355_colour_pixel(const m355_colour_tables* t, const uint32_t rgb16[3], int 
   if (!t || !rgb16 || !out || (samples != M355_RGB_U8 && samples != M355_RGB_U16) || m355_ct_tables_check(t))
     return fail(M355_ERR_INVALID, "m355_colour_pixel: null pointer, unknown samples %d, or tables outside their bounds", samples);
   m355_ct_pixel(t, rgb16, samples, out);
+  return M355_OK;
+}
+int m355_colour_preset_tone(const m355_colour_preset_desc* d, int norm, m355_colour_tables* out, m355_colour_tone* tone)
+{
+  if (m355_cp_build_tone(d, norm, out, tone))
+    return fail(M355_ERR_INVALID, "m355_colour_preset_tone: what m355_colour_preset rejects, an unknown tone or norm %d, or a peak so far above white that BT.2390's KS < 0", norm);
+  return M355_OK;
+}
+int m355_colour_pixel_tone(const m355_colour_tables* t, const m355_colour_tone* q, const uint32_t rgb16[3], int samples, uint32_t out[3])
+{
+  if (!t || !q || !rgb16 || !out || (samples != M355_RGB_U8 && samples != M355_RGB_U16) || m355_ct_tables_check(t) || m355_ct_tone_check(q))
+    return fail(M355_ERR_INVALID, "m355_colour_pixel_tone: null pointer, unknown samples %d, or tables / tone outside their bounds", samples);
+  m355_ct_pixel_tone(t, q, rgb16, samples, out);
   return M355_OK;
 }
 /* The same resize with the R'G'B' conversion of the resized picture behind it, in one launch (k_export_resized_rgb.hip, RR_FRAME): the frame handle and

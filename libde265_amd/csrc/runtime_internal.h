@@ -291,8 +291,9 @@ struct m355_ctx {
      stream that last wrote the frame, between pinned memory and the frame (frame_stage_* in runtime.hip) */
   void* stage = nullptr; size_t stage_bytes = 0;
   /* m355_colour_create: the colour transform objects of the composed exports — the tables in device memory, the matrix for the kernel arguments.
-     handle == 0: the slot is free; handles count up over all contexts of the process and are never given twice */
-  struct ColourObj { int handle = 0; uint8_t* dev = nullptr; int32_t matrix[9] = {}; };
+     handle == 0: the slot is free; handles count up over all contexts of the process and are never given twice.  A tone object
+     (m355_colour_create_tone) has its gain table behind the tables in the same allocation (gain != null), and norm and weights for the arguments */
+  struct ColourObj { int handle = 0; uint8_t* dev = nullptr; int32_t matrix[9] = {}; uint32_t* gain = nullptr; int32_t norm = 0, weights[3] = {}; };
   ColourObj colour[M355_COLOUR_OBJECTS];
   /* m355_decode_batch: ring of picture-record arrays (pinned staging + device copy + the batch's ticket word); a slot's event is
      recorded behind the batch's k_intra — what the pictures' filter stages wait for, and what guards the slot's reuse */

@@ -38,6 +38,8 @@
       BT.2020 -> gamma 2.4 / BT.709, Reinhard, 203 / 1000 nits) as (Kq), (Kw), (Kz8), (Kz32), (KT32), (KQ8), (KQ32), on frames of seeded RANDOM samples — the
       stage gathers from its tables by the pixel's value, so a constant frame would show its best case —, the colour-off calls on those frames as (K0q),
       (K0z32), and the ratios in the result line; no bar is set for them
+  --tone (implies --colour) adds, beside the seven K rows, the same calls with a tone object (m355_colour_create_tone: the preset PQ / BT.2020 -> gamma
+      2.4 / BT.709, BT.2390, maxRGB, 203 / 1000 nits) as (Gq), (Gw), (Gz8), (Gz32), (GT32), (GQ8), (GQ32), and their ratios to the K rows; no bar is set
 
 and, beside them, m355_measure_copy_rate for the frame's byte count.  Every figure is the median of --iters launches; (b) is measured in
 --rounds separate rounds spread over the run, and the spread of their medians is the margin (c), (d), (g)-(j) and (m)-(p) are held against: a scaled or resized export reads exactly (b)'s source bytes and writes at most a
@@ -81,7 +83,9 @@ def main():
     ap.add_argument("--chroma-loc", type=int, choices=(1, 2, 3), action="append", default=[],
                     help="also measure this chroma sample location type's rows beside the type-0 rows (may repeat)")
     ap.add_argument("--colour", action="store_true", help="also measure the composed exports with a colour transform, on frames of random samples")
+    ap.add_argument("--tone", action="store_true", help="also measure the colour rows with a tone object (one gain per pixel: BT.2390, maxRGB); implies --colour")
     args = ap.parse_args()
+    args.colour = args.colour or args.tone
 
     lib = capi.Library()
     ctx = capi.Context(lib, 0)
@@ -348,6 +352,7 @@ def main():
             sited_of[n] = [t for t in variants if t.startswith(key)][0]
         variants.update(rows)
     colour_of, made = {}, []           # a row with a colour transform -> the colour-off row of the same call
+    tone_of = {}                       # a row with a tone object -> the row of the same call with the plain colour transform
     if args.colour:
         import numpy as np
         rng_c = np.random.default_rng(ROI_SEED)
@@ -376,6 +381,20 @@ def main():
             key = n[2 if n[1] == "0" else 1:].split("_")[0] + "_"
             colour_of[n] = [t for t in variants if t.startswith(key)][0]
         variants.update(rows)
+        if args.tone:
+            G = ctx.colour_create_tone(*lib.colour_preset_tone(16, 9, 1, 1, tone=capi.TONE_BT2390, norm=capi.NORM_MAXRGB, white_nits=203, peak_nits=1000))
+            gains = {
+                "Gq_tone_resized_rgb_u8_packed_1080p": export_resized_rgb(capi.RGB_PACKED, capi.RGB_U8, (1920, 1080), 1, colour=G, frame=cframe),
+                "Gw_tone_tensor_f16_nhwc_1080p": export_tensor([cframe], capi.TENSOR_NHWC, capi.TENSOR_F16, capi.RGB_U16, (1920, 1080), colour=G),
+                "Gz8_tone_tensor_f16_nchw_224_batch8": export_tensor(cbatch[:8], capi.TENSOR_NCHW, capi.TENSOR_F16, capi.RGB_U8, (224, 224), SQUARE, colour=G),
+                "Gz32_tone_tensor_f16_nchw_224_batch32": export_tensor(cbatch, capi.TENSOR_NCHW, capi.TENSOR_F16, capi.RGB_U8, (224, 224), SQUARE, colour=G),
+                "GT32_tone_tensor_rois_f16_nchw_224_32_regions": export_tensor_rois([cbatch[0]] * 32, rois32, capi.TENSOR_NCHW, capi.TENSOR_F16, capi.RGB_U8, (224, 224), colour=G),
+            }
+            gains.update({"GQ%d_tone_tensor_rois_f16_nchw_224_of_896_batch%d" % (n, n):
+                          export_tensor_rois(cbatch[:n], [SQUARE4 + (0,)] * n, capi.TENSOR_NCHW, capi.TENSOR_F16, capi.RGB_U8, (224, 224), colour=G) for n in (8, 32)})
+            for n in gains:
+                tone_of[n] = [t for t in rows if t.startswith("K" + n[1:].split("_")[0] + "_")][0]
+            variants.update(gains)
     scaled = [n for n in variants if n[0] in "ghijmnop"]
     ms = {n: [] for n in variants}
     for _ in range(args.rounds):
@@ -414,6 +433,8 @@ def main():
         "sited_over_type_0": {n: res[n] / res[t] for n, t in sited_of.items()},
         "colour_over_colour_off": {n: res[n] / res[t] for n, t in colour_of.items()},
         "colour_rounds_ms": {n: ms[n] for n in colour_of},
+        "tone_over_colour": {n: res[n] / res[t] for n, t in tone_of.items()},
+        "tone_rounds_ms": {n: ms[n] for n in tone_of},
         "copy_rate_GBps_same_bytes": ctx.measure_copy_rate(frame_bytes, 9),
         "bars": {"b_le_a": res["b_native_planar"] <= res["a_memcpy2d_x3"],
                  "c_le_b_plus_spread": res["c_msb16_semiplanar_crop8"] <= res["b_native_planar"] + spread,
