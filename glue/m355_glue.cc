@@ -90,7 +90,7 @@ namespace {
   X(m355_group_create) X(m355_group_destroy) X(m355_group_decode) X(m355_picture_upload) X(m355_picture_replace) X(m355_shard_owner_of_tile) \
   X(m355_picture_arena_begin) X(m355_frame_hash_async) X(m355_frame_hash_result) X(m355_frame_measure_async) X(m355_frame_measure_result) \
   X(m355_frame_stats_async) X(m355_frame_stats_result) X(m355_stats_quantile) X(m355_colour_linear) \
-  X(m355_colour_create_tone) X(m355_colour_preset_tone)
+  X(m355_colour_create_tone) X(m355_colour_preset_tone) X(m355_frame_export_pixels) X(m355_frame_export_resized_pixels)
 
 struct Api {
   void* handle = nullptr;
@@ -1988,6 +1988,29 @@ LIBDE265_API int m355_glue_export_image_resized_rgb(const struct de265_image* im
                                                     const int out_size[2], void* const dst[3], const int64_t pitch[3], void* consumer_stream)
 {
   return m355_glue_export_image_resized_rgb_filtered(img, layout, samples, matrix, full_range, rect, out_size, dst, pitch, M355_FILTER_TRIANGLE, consumer_stream);
+}
+/* The picture as PIXELS a compositor takes (m355_frame_export_pixels / m355_frame_export_resized_pixels: format = M355_PIXEL_*, alpha the constant of
+ * the format's alpha bits, one dst and one pitch in BYTES), with the waiting behaviour of m355_glue_export_image.  out_size = NULL: no resize, and filter
+ * must be M355_FILTER_TRIANGLE and colour 0, as in m355_frame_export_rgb_opts; else {out_width, out_height} with the filter and the colour / tone object of
+ * m355_glue_export_image_resized_rgb_colour (out_size equal to the rectangle: a colour transform without a resize).  The frame, the rectangle (NULL: the
+ * image's conformance window), matrix == -1, full_range == -1 and chroma_loc == -1 are resolved as that call resolves them. */
+LIBDE265_API int m355_glue_export_image_pixels(const struct de265_image* img, int format, int alpha, int matrix, int full_range, const int rect[4],
+                                               const int out_size[2], void* dst, int64_t pitch, int filter, int chroma_loc, int colour, void* consumer_stream)
+{
+  ExportCall x;
+  const int rc = x.begin(&img, 1, dst != nullptr, &matrix, &full_range, filter, chroma_loc, colour);
+  if (rc != M355_OK) return rc;
+  int r[4];
+  const int frame = frame_and_rect(x.g, img, rect, r);
+  if (frame < 0) return M355_ERR_INVALID;
+  m355_pixel_desc d;
+  memset(&d, 0, sizeof(d));
+  d.format = format; d.alpha = alpha; d.matrix = matrix; d.full_range = full_range;
+  d.x0 = r[0]; d.y0 = r[1]; d.width = r[2]; d.height = r[3];
+  d.dst = dst; d.pitch = pitch;
+  if (!out_size) return x.finish(x.A->m355_frame_export_pixels(x.g->mctx, frame, &d, &x.o), frame, consumer_stream);
+  d.out_width = out_size[0]; d.out_height = out_size[1];
+  return x.finish(x.A->m355_frame_export_resized_pixels(x.g->mctx, frame, &d, &x.o), frame, consumer_stream);
 }
 /* A BATCH of pictures of ONE decoder, each resized, converted to R'G'B', normalised and delivered as one float tensor in one launch
  * (m355_frames_export_tensor: layout / dtype = M355_TENSOR_*, samples = M355_RGB_* of the integer stage; scale / bias per channel; dst and the strides in

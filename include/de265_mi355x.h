@@ -834,6 +834,45 @@ M355_API int   m355_colour_create(m355_ctx* ctx, const m355_colour_tables* table
 M355_API int   m355_colour_destroy(m355_ctx* ctx, int handle);
 M355_API int   m355_colour_preset(const m355_colour_preset_desc* desc, m355_colour_tables* out);
 M355_API int   m355_colour_pixel(const m355_colour_tables* tables, const uint32_t rgb16[3], int samples, uint32_t out[3]);
+/* PIXEL FORMATS: the last stage of the export line for a compositor on the same GPU — a swap chain, a Vulkan or GL image, a DRM plane, a HIP texture —,
+ * which takes B8G8R8A8, R8G8B8A8 or a 2:10:10:10 dword and no 24-bit texel, and for consumers that want B, G, R order (k_export_rgb.hip,
+ * k_export_resized_rgb.hip RR_FRAME).  The definition is a COMPOSITION and adds one formula:
+ *   1. S(format) = M355_RGB_U8 for RGBA8, BGRA8 and BGR8, M355_RGB_U16 for the two 10-bit formats;
+ *   2. (R, G, B) of a pixel are the three values the existing call delivers with M355_RGB_PACKED, samples S(format) and the same matrix, range,
+ *      rectangle, output size and options: m355_frame_export_rgb_opts for m355_frame_export_pixels, m355_frame_export_resized_rgb_opts — with its
+ *      filter, chroma siting and colour / tone object — for m355_frame_export_resized_pixels;
+ *   3. the pixel's bytes are m355_pixel_pack(format, {R, G, B}, alpha) (host only; csrc/pixel_pack.h is the one definition, compiled into the kernels
+ *      too).  8-bit formats: the values as they are, in the byte order below.  10-bit formats: each channel first becomes
+ *      c10 = (2046 c + 65535) / 131070 in unsigned 32-bit arithmetic = round(c * 1023 / 65535), the 10-bit sibling of step 4 of m355_colour_pixel,
+ *      then the dword below, stored little-endian.  With a colour object the 10-bit delivery is therefore c10 of step 3's 16-bit result.
+ * Every rule of the call underneath carries over: the whole-frame and sub-rectangle rim rules of the two calls as stated above; the colour stage exists
+ * in the resized call only (a non-zero `colour` in m355_frame_export_pixels is M355_ERR_INVALID, as in m355_frame_export_rgb_opts), and
+ * m355_frame_export_resized_pixels with the output size equal to the rectangle is the way to tone-map without resizing.
+ * M355_ERR_INVALID (nothing is enqueued, no destination byte written): whatever the call underneath rejects for the frame handle, the rectangle, the
+ * output size, the ratio, matrix, full_range and the options; an unknown format; alpha outside the format's range; a null descriptor or a null dst;
+ * a pitch below width * bytes per pixel (the resized call: out_width * bytes per pixel); for the 4-byte formats a dst or a pitch that is no multiple
+ * of 4; for m355_frame_export_pixels a non-zero out_width or out_height.  m355_pixel_pack rejects an unknown format, a channel above 255 (8-bit
+ * formats) or 65535 (10-bit formats), alpha outside the range and null pointers; *n_bytes = the bytes written to out (3 or 4).
+ * Ordering, the gate behind a rejected decode, reader marks, m355_frame_export_wait and m355_frame_export_order, and sharded contexts are exactly
+ * those of m355_frame_export_rgb, and destination bytes beyond a row are never written.
+ * Not offered: 16-bit and half-float four-channel pixels (the composed kernel's staged row has 1536 bytes for 256 columns); ARGB and ABGR byte orders;
+ * an alpha plane taken from a picture; pixel formats in the tensor exports; premultiplication. */
+#define M355_PIXEL_RGBA8        0   /* 4 bytes per pixel: R, G, B, A */
+#define M355_PIXEL_BGRA8        1   /* 4 bytes per pixel: B, G, R, A */
+#define M355_PIXEL_BGR8         2   /* 3 bytes per pixel: B, G, R */
+#define M355_PIXEL_A2B10G10R10  3   /* one little-endian dword: R | G << 10 | B << 20 | A << 30 */
+#define M355_PIXEL_A2R10G10B10  4   /* one little-endian dword: B | G << 10 | R << 20 | A << 30 */
+typedef struct m355_pixel_desc {
+  int32_t format, alpha;            /* M355_PIXEL_*; A: 0..255 (RGBA8 / BGRA8), 0..3 (2:10:10:10), 0 (BGR8) */
+  int32_t matrix, full_range;       /* as m355_rgb_desc */
+  int32_t x0, y0, width, height;    /* source luma rectangle, as m355_export_desc (width == 0: whole frame) */
+  int32_t out_width, out_height;    /* m355_frame_export_resized_pixels: luma size of the result; m355_frame_export_pixels: both 0 */
+  void*   dst;                      /* device memory or m355_host_alloc memory */
+  int64_t pitch;                    /* BYTES per destination row */
+} m355_pixel_desc;                  /* LP64: 56 bytes */
+M355_API int   m355_frame_export_pixels(m355_ctx* ctx, int frame, const m355_pixel_desc* desc, const m355_export_opts* opts);           /* asynchronous */
+M355_API int   m355_frame_export_resized_pixels(m355_ctx* ctx, int frame, const m355_pixel_desc* desc, const m355_export_opts* opts);   /* asynchronous */
+M355_API int   m355_pixel_pack(int format, const uint32_t rgb[3], uint32_t alpha, uint8_t out[4], int* n_bytes);   /* host only */
 M355_API int   m355_frame_export_wait(m355_ctx* ctx, int frame);
 M355_API int   m355_frame_export_order(m355_ctx* ctx, int frame, void* consumer_hipStream);
 /* Device memory for export destinations and blocking copies out of / into it, for applications (and the tests) that keep a second HIP

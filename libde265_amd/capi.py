@@ -80,6 +80,23 @@ class ResizeRgbDesc(ctypes.Structure):
                 ("dst", ctypes.c_void_p * 3), ("pitch", ctypes.c_int64 * 3)]
 
 
+PIXEL_RGBA8, PIXEL_BGRA8, PIXEL_BGR8, PIXEL_A2B10G10R10, PIXEL_A2R10G10B10 = 0, 1, 2, 3, 4     # M355_PIXEL_*
+PIXEL_FORMATS = (PIXEL_RGBA8, PIXEL_BGRA8, PIXEL_BGR8, PIXEL_A2B10G10R10, PIXEL_A2R10G10B10)
+
+
+def pixel_bytes(format):
+    """bytes per pixel of a PIXEL_* format"""
+    return 3 if format == PIXEL_BGR8 else 4
+
+
+class PixelDesc(ctypes.Structure):
+    """m355_pixel_desc (include/de265_mi355x.h)"""
+    _fields_ = [("format", ctypes.c_int32), ("alpha", ctypes.c_int32), ("matrix", ctypes.c_int32), ("full_range", ctypes.c_int32),
+                ("x0", ctypes.c_int32), ("y0", ctypes.c_int32), ("width", ctypes.c_int32), ("height", ctypes.c_int32),
+                ("out_width", ctypes.c_int32), ("out_height", ctypes.c_int32),
+                ("dst", ctypes.c_void_p), ("pitch", ctypes.c_int64)]
+
+
 TENSOR_MAX_FRAMES = 32
 TENSOR_NCHW, TENSOR_NHWC = 0, 1
 TENSOR_F32, TENSOR_F16, TENSOR_BF16 = 0, 1, 2
@@ -276,6 +293,10 @@ class Library:
             L.m355_colour_destroy.argtypes = [vp, i]
             L.m355_colour_preset.argtypes = [ctypes.POINTER(ColourPresetDesc), ctypes.POINTER(ColourTables)]
             L.m355_colour_pixel.argtypes = [ctypes.POINTER(ColourTables), ctypes.POINTER(ctypes.c_uint32), i, ctypes.POINTER(ctypes.c_uint32)]
+        if hasattr(L, "m355_frame_export_pixels"):      # (absent from older builds loaded through M355_LIB for an A/B)
+            L.m355_frame_export_pixels.argtypes = [vp, i, ctypes.POINTER(PixelDesc), ctypes.POINTER(ExportOpts)]
+            L.m355_frame_export_resized_pixels.argtypes = [vp, i, ctypes.POINTER(PixelDesc), ctypes.POINTER(ExportOpts)]
+            L.m355_pixel_pack.argtypes = [i, ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(i)]
         if hasattr(L, "m355_colour_create_tone"):
             L.m355_colour_create_tone.argtypes = [vp, ctypes.POINTER(ColourTables), ctypes.POINTER(ColourTone), ctypes.POINTER(i)]
             L.m355_colour_preset_tone.argtypes = [ctypes.POINTER(ColourPresetDesc), i, ctypes.POINTER(ColourTables), ctypes.POINTER(ColourTone)]
@@ -377,6 +398,12 @@ class Library:
         t = ColourTables()
         self.check(self.lib.m355_colour_preset(ctypes.byref(d), ctypes.byref(t)))
         return t
+
+    def pixel_pack(self, format, rgb, alpha):
+        """one pixel's bytes (m355_pixel_pack; host only) -> bytes of length 3 or 4"""
+        out, n = (ctypes.c_uint8 * 4)(), ctypes.c_int(0)
+        self.check(self.lib.m355_pixel_pack(format, (ctypes.c_uint32 * 3)(*[int(v) for v in rgb]), alpha, out, ctypes.byref(n)))
+        return bytes(out[:n.value])
 
     def colour_pixel(self, tables, rgb16, samples):
         """the colour transform stage for one pixel (m355_colour_pixel; host only) -> (R, G, B)"""
@@ -716,6 +743,44 @@ class Context:
             desc.x0, desc.y0, desc.width, desc.height = rect
         return self._export_into_planes(f, self._rgb_shapes(w, h, layout, samples), desc, host, pad,
                                         lambda: self._export_entry("m355_frame_export_resized_rgb", (self.h, f, ctypes.byref(desc)), *entry))
+
+    def _frame_export_pixels(self, name, f, format, alpha, matrix, full_range, w, h, out_size, rect, host, pad, opts):
+        """what the two pixel exports share: ONE buffer of h rows of w * pixel_bytes(format) bytes, made as frame_export_rgb makes its buffers — every
+        byte holds DEVICE_FILL beforehand (the guard bytes), the pitch is `pad` bytes (a multiple of 4) larger than the row —, the descriptor, the call;
+        the buffer is freed again if the call raises.  -> token for frame_export_finish, whose one plane is (h, w * pixel_bytes) uint8"""
+        shapes = [(h, w * pixel_bytes(format), np.dtype(np.uint8))]
+        desc = PixelDesc(format=format, alpha=alpha, matrix=matrix, full_range=full_range, out_width=out_size[0], out_height=out_size[1])
+        if rect is not None:
+            desc.x0, desc.y0, desc.width, desc.height = rect
+        pitch = shapes[0][1] + pad
+        buf = self._buffer(h * pitch, host)
+        desc.dst, desc.pitch = buf, pitch
+        try:
+            self.L.check(getattr(self.L.lib, name)(self.h, f, ctypes.byref(desc), opts))
+        except Exception:
+            self._buffer_free(buf, host)
+            raise
+        return (f, shapes, [buf], [pitch], host)
+
+    def frame_export_pixels(self, f, format, alpha, matrix, full_range, rect=None, host=False, pad=20, chroma_loc=0, opts_entry=False, colour=0):
+        """start m355_frame_export_pixels of frame f (PIXEL_* format; rect = (x0, y0, width, height) in luma samples, None: the whole frame) into a
+        buffer of its own with guard bytes, as frame_export_rgb does.  A NULL options pointer unless chroma_loc, colour or opts_entry ask for one.
+        -> token for frame_export_finish"""
+        w, h = self._geom[f][:2] if rect is None else rect[2:]
+        opts = self._opts(0, chroma_loc, opts_entry, colour) if (chroma_loc or colour or opts_entry) else None
+        return self._frame_export_pixels("m355_frame_export_pixels", f, format, alpha, matrix, full_range, w, h, (0, 0), rect, host, pad, opts)
+
+    def frame_export_resized_pixels(self, f, format, alpha, matrix, full_range, out_size, rect=None, host=False, pad=20, filter=0, chroma_loc=0,
+                                    opts_entry=False, colour=0):
+        """start m355_frame_export_resized_pixels of frame f to out_size = (out_width, out_height) luma samples, with the filter, the chroma siting and
+        the colour / tone object of frame_export_resized_rgb; the buffer as in frame_export_pixels.  -> token for frame_export_finish"""
+        opts = self._opts(filter, chroma_loc, opts_entry, colour) if (filter or chroma_loc or colour or opts_entry) else None
+        return self._frame_export_pixels("m355_frame_export_resized_pixels", f, format, alpha, matrix, full_range, out_size[0], out_size[1], out_size,
+                                         rect, host, pad, opts)
+
+    def pixel_pack(self, format, rgb, alpha):
+        """one pixel's bytes (m355_pixel_pack)"""
+        return self.L.pixel_pack(format, rgb, alpha)
 
     def tensor_element(self, v, scale, bias, dtype):
         """the float stage of m355_frames_export_tensor for one integer (m355_tensor_element) -> the element's bit pattern"""

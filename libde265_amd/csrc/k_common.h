@@ -316,10 +316,14 @@ struct ExportRgbArgs {
   m355_rgb_coeffs k;
   const uint32_t* timeout;
   uint32_t epoch;
+  uint32_t alpha_bits;                    /* k_export_pixels: the alpha in its place in the pixel's dword (pixel_pack.h); in what was padding: no offset moves */
 };
 /* src_bytes / dst_bytes: 1 or 2 per sample / channel; chroma_format: 0..3; chroma_loc: the chroma sample location type 0..3 of a 4:2:0 frame
    (m355_export_opts), 0 for every other chroma format — a template parameter of the kernel */
 void m355_launch_export_rgb(const ExportRgbArgs& a, int src_bytes, int dst_bytes, bool planar, int chroma_format, int chroma_loc, hipStream_t st);
+/* one m355_frame_export_pixels of a 4-byte format (k_export_rgb.hip, k_export_pixels): dst[0] takes a dword per pixel; ten: a 2:10:10:10 format (k = the
+   coefficients of M355_RGB_U16), else 8 bits per channel (those of M355_RGB_U8).  B-first formats: the host exchanges src[1] / src[2] and their coefficients */
+void m355_launch_export_pixels(const ExportRgbArgs& a, int src_bytes, bool ten, int chroma_format, int chroma_loc, hipStream_t st);
 
 /* one m355_frame_export_resized (k_export_resized.hip), planes as in ExportArgs (semi-planar: plane 1 = Cb and Cr, read from src[1] and src[2] and
    stored interleaved).  Plane k maps the rectangle's sn_x[k] x sn_y[k] source samples to dn_x[k] x dn_y[k] output samples; cosited[k]: the
@@ -373,9 +377,13 @@ struct ExportResizedRgbArgs {
   uint32_t epoch;
   int32_t chroma_loc;
   ColourArgs colour;                      /* behind everything that was here: no offset moves */
+  uint32_t px_bytes, px_swapped, px_alpha_bits, px_pad;   /* m355_frame_export_resized_pixels (pixel_pack.h): bytes per pixel (3 / 4), B goes lowest, the alpha in its place; behind the rest again */
 };
 /* src_bytes / dst_bytes: 1 or 2 per sample / channel */
 void m355_launch_export_resized_rgb(const ExportResizedRgbArgs& a, int src_bytes, int dst_bytes, int filter, hipStream_t st);
+/* one m355_frame_export_resized_pixels: the same launch with PX = 8-bit (ten = false: k of M355_RGB_U8 unless a colour stage runs) or 2:10:10:10 pixels
+   (k of M355_RGB_U16); dst[0] takes a.px_bytes bytes per pixel, planar = 0 */
+void m355_launch_export_resized_pixels(const ExportResizedRgbArgs& a, int src_bytes, bool ten, int filter, hipStream_t st);
 
 /* one m355_frames_export_tensor (k_export_resized_rgb.hip, RR_BATCH): the tile procedure over n frames in one grid, unit = slice * units + the
    tile inside the slice (units tiles per slice).  Per slice: src[] = the rectangle's first sample of Y, Cb, Cr in that frame, its two pitches (BYTES)

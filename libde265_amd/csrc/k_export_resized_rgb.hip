@@ -59,6 +59,13 @@
  *   what they were.  COLOUR = tone (an object of m355_colour_create_tone) puts step 2b between the matrix and the output table: one gain per pixel, looked
  *   up at the pixel's maxRGB or luminance (norm and the weights: wave-uniform kernel arguments) in the object's gain table (global memory, one gather of two
  *   neighbouring dwords: k_colour_dev.h bounds it) and multiplied into the three linear values in 64 bits.  COLOUR = tables is what COLOUR = true was.
+ * PX (m355_frame_export_resized_pixels; pixel_pack.h; RR_FRAME only) replaces the staging of three elements by ONE pixel of bpp = 3 or 4 bytes at
+ *   pos * bpp of the staged row — PX = 8-bit pixels: the three clipped (or delivered) bytes in the format's order and, bpp = 4, the alpha; PX = 10-bit
+ *   pixels: the integer stage of EB = 2 (the coefficients of M355_RGB_U16, clip to 65 535; COLOUR: step 3's 16-bit result, not m355_ct_deliver's),
+ *   then c10 per channel and the dword —, and RR_STORE_ROW's seg_bytes = ncols * bpp.  bpp, the channel order and the alpha in its place are
+ *   wave-uniform kernel arguments, so the five formats are two values of PX; a staged row holds at most 256 * 4 = 1024 of its 1536 bytes, LDS and the
+ *   two staging sets are what they were, and a 4-byte pixel row ends in whole dwords (BGR8: the byte tail of the 3-byte packed row).  PX = off
+ *   compiles none of it: those 144 instantiations are what they were; 48 more (2 sample bytes x 2 PX x 2 filters x SITED x 3 COLOUR) make 192.
  *
  * Reads stay inside the planes' allocations, by the argument of k_export_resized.hip for every plane of every slice: the host admits a frame only
  * if it contains the slice's rectangle (export_plan per frame), whose size is the source size the slice's rows are derived from.  A filter row's
@@ -81,6 +88,7 @@
 #include "tensor_element.h"
 #include "k_resize_dev.h"
 #include "k_colour_dev.h"
+#include "pixel_pack.h"
 
 #define RR_TW M355_RESIZE_TILE_W
 #define RR_TH M355_RESIZE_TILE_H
@@ -186,6 +194,7 @@ __device__ __forceinline__ int d_rr_row(int64_t sn, int64_t dn, int cosited, int
    RR_GEOM(field): a field of the source's geometry, the slice's in RR_ROIS, else the launch's — each read at the place of its use. */
 enum { RR_FRAME = 0, RR_BATCH = 1, RR_ROIS = 2 };
 enum { RR_COLOUR_OFF = 0, RR_COLOUR_TABLES = 1, RR_COLOUR_TONE = 2 };   /* COLOUR: no stage, a plain object, a tone object */
+enum { RR_PX_OFF = 0, RR_PX_8 = 1, RR_PX_10 = 2 };                      /* PX: R'G'B' elements, 8-bit pixels (3 or 4 bytes), 2:10:10:10 pixels */
 template <int MODE> struct RrArgs { typedef ExportResizedRgbArgs T; };
 template <> struct RrArgs<RR_BATCH> { typedef ExportTensorArgs T; };
 template <> struct RrArgs<RR_ROIS> { typedef ExportTensorRoisArgs T; };
@@ -193,9 +202,10 @@ template <> struct RrArgs<RR_ROIS> { typedef ExportTensorRoisArgs T; };
 #define RR_PITCH(i) ({ uint32_t g_; if constexpr (MODE == RR_FRAME) g_ = (uint32_t)a.src_pitch[i]; else g_ = (uint32_t)a.fr[slice].src_pitch[i]; g_; })
 #define RR_GEOM(field) ({ uint32_t g_; if constexpr (MODE == RR_ROIS) g_ = a.fr[slice].field; else g_ = a.field; g_; })
 
-template <int SB, int EB, int MODE, int FILTER, bool SITED, int COLOUR>
+template <int SB, int EB, int MODE, int FILTER, bool SITED, int COLOUR, int PX>
 __global__ void __launch_bounds__(256) k_export_resized_rgb(typename RrArgs<MODE>::T a)
 {
+  static_assert(PX == RR_PX_OFF || (MODE == RR_FRAME && EB == (PX == RR_PX_10 ? 2 : 1)), "pixel formats: RR_FRAME, with the integer stage of their channel bits");
   constexpr bool CUBIC = FILTER == M355_FILTER_CUBIC;
   constexpr int S = 16 / SB;
   constexpr uint32_t OB = RR_TW * 3 * (MODE == RR_FRAME ? 2 : EB);   /* bytes of a staged output row: 256 pixels x 3 channels x 2 (tensors: EB) bytes */
@@ -229,7 +239,8 @@ __global__ void __launch_bounds__(256) k_export_resized_rgb(typename RrArgs<MODE
   const uint32_t ncols = dnx - c0 < tw ? dnx - c0 : tw, nrows = dny - j0 < (uint32_t)RR_TH ? dny - j0 : (uint32_t)RR_TH;
   const int cf = a.cf;
   bool planar;                                                  /* planar R'G'B' / NCHW: three staged segments */
-  if constexpr (MODE == RR_FRAME) planar = a.planar != 0; else planar = a.nhwc == 0;
+  if constexpr (PX != RR_PX_OFF) planar = false;              /* (a pixel is one element of the packed row) */
+  else if constexpr (MODE == RR_FRAME) planar = a.planar != 0; else planar = a.nhwc == 0;
   const uint32_t swl = (cf == 1 || cf == 2) ? 1u : 0u, shl = cf == 1 ? 1u : 0u;
   /* the siting of 4:2:0 chroma (m355_export_opts; the host passes 0 for every other format): horizontally CENTRE, vertically TOP.  SITED = false is
      type 0, whose statements stand as they were in the other branch of each `if constexpr`: those instantiations are what they were before */
@@ -359,7 +370,12 @@ __global__ void __launch_bounds__(256) k_export_resized_rgb(typename RrArgs<MODE
   const float bi[3] = {RR_TE(float, a.bias[0]), RR_TE(float, a.bias[1]), RR_TE(float, a.bias[2])};
   /* where the staged row's bytes go: packed / NHWC one segment of up to OB / 4 dwords, planar / NCHW three of up to SEGW (512 or 1024 bytes apart) */
   constexpr uint32_t SEGW = OB / 12u, SEGSH = SEGW == 256u ? 8 : 7;
-  const uint32_t seg_bytes = ncols * (uint32_t)EB * (planar ? 1u : 3u);
+  /* PX: bytes per pixel (3: BGR8, else 4), the channel order and the alpha in its place — wave-uniform kernel arguments (pixel_pack.h) */
+  uint32_t px_bytes = 0, px_alpha = 0;
+  bool px_swapped = false;
+  if constexpr (PX != RR_PX_OFF) { px_bytes = a.px_bytes; px_alpha = a.px_alpha_bits; px_swapped = a.px_swapped != 0; }
+  uint32_t seg_bytes = ncols * (uint32_t)EB * (planar ? 1u : 3u);
+  if constexpr (PX != RR_PX_OFF) seg_bytes = ncols * px_bytes;
   /* a mirrored slice: the lane of tile column t stages its pixel at position ncols - 1 - t, and the tile's first destination column is
      out_width - c0 - ncols; the stores themselves do not change */
   bool mirror = false;
@@ -368,7 +384,8 @@ __global__ void __launch_bounds__(256) k_export_resized_rgb(typename RrArgs<MODE
   /* the first byte of the tile's row of segment seg (RR_DST): in the frame's planes, or in the slice's place in the tensor */
   size_t col_bytes = 0, stride_c = 0, stride_h = 0;
   M355_GLOBAL uint8_t* dst0 = nullptr;
-  if constexpr (MODE == RR_FRAME) col_bytes = (size_t)col0 * (size_t)EB * (planar ? 1u : 3u);
+  if constexpr (PX != RR_PX_OFF) col_bytes = (size_t)col0 * px_bytes;
+  else if constexpr (MODE == RR_FRAME) col_bytes = (size_t)col0 * (size_t)EB * (planar ? 1u : 3u);
   else {
     dst0 = (M355_GLOBAL uint8_t*)a.dst + (size_t)slice * (size_t)a.stride_n + (size_t)col0 * (size_t)EB * (planar ? 1u : 3u);
     stride_c = (size_t)a.stride_c; stride_h = (size_t)a.stride_h;
@@ -458,17 +475,23 @@ __global__ void __launch_bounds__(256) k_export_resized_rgb(typename RrArgs<MODE
           for (int c = 0; c < 3; c++) e[c] = m355_ct_deliver(e[c], deliver_u8);
         }
         uint8_t* o = s_o[par][ri];
+        if constexpr (PX != RR_PX_OFF) {                       /* the pixel's dword (10-bit: c10 of each 16-bit value), bpp bytes at pos * bpp */
+          const uint32_t dw = m355_pp_pixel(PX == RR_PX_10, px_swapped, e, px_alpha);
+          if (px_bytes == 4u) __builtin_memcpy(o + 4u * pos, &dw, 4);
+          else { o[3u * pos] = (uint8_t)dw; o[3u * pos + 1u] = (uint8_t)(dw >> 8); o[3u * pos + 2u] = (uint8_t)(dw >> 16); }
+        } else {
 #pragma unroll
-        for (int c = 0; c < 3; c++) {
-          uint32_t bits = e[c];                                /* a frame: the clipped integer; a tensor: through the float stage */
-          if constexpr (MODE != RR_FRAME) {
-            const float f = m355_te_affine(e[c], sc[c], bi[c]);
-            bits = EB == 4 ? m355_te_bits(f) : m355_te_half(f, bf16_mask);
+          for (int c = 0; c < 3; c++) {
+            uint32_t bits = e[c];                              /* a frame: the clipped integer; a tensor: through the float stage */
+            if constexpr (MODE != RR_FRAME) {
+              const float f = m355_te_affine(e[c], sc[c], bi[c]);
+              bits = EB == 4 ? m355_te_bits(f) : m355_te_half(f, bf16_mask);
+            }
+            const uint32_t at = planar ? (uint32_t)c * (SEGW * 4u) + pos * (uint32_t)EB : (3u * pos + (uint32_t)c) * (uint32_t)EB;
+            if (EB == 4) __builtin_memcpy(o + at, &bits, 4);
+            else if (EB == 1) o[at] = (uint8_t)bits;
+            else { const unsigned short h = (unsigned short)bits; __builtin_memcpy(o + at, &h, 2); }
           }
-          const uint32_t at = planar ? (uint32_t)c * (SEGW * 4u) + pos * (uint32_t)EB : (3u * pos + (uint32_t)c) * (uint32_t)EB;
-          if (EB == 4) __builtin_memcpy(o + at, &bits, 4);
-          else if (EB == 1) o[at] = (uint8_t)bits;
-          else { const unsigned short h = (unsigned short)bits; __builtin_memcpy(o + at, &h, 2); }
         }
       }
     }
@@ -486,25 +509,39 @@ __global__ void __launch_bounds__(256) k_export_resized_rgb(typename RrArgs<MODE
 
 /* src_bytes: 1 or 2 per sample; elem_bytes: 1 or 2 per channel of a frame, 2 or 4 per element of a tensor */
 #define RR_LAUNCH_C(MODE, B0, B1, F, S, C) \
-  if (src_bytes == 1 && elem_bytes == B0) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_export_resized_rgb<1, B0, MODE, F, S, C>), g_, block, 0, st, a); \
-  if (src_bytes == 1 && elem_bytes == B1) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_export_resized_rgb<1, B1, MODE, F, S, C>), g_, block, 0, st, a); \
-  if (src_bytes == 2 && elem_bytes == B0) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_export_resized_rgb<2, B0, MODE, F, S, C>), g_, block, 0, st, a); \
-  if (src_bytes == 2 && elem_bytes == B1) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_export_resized_rgb<2, B1, MODE, F, S, C>), g_, block, 0, st, a);
-#define RR_LAUNCH_S(MODE, B0, B1, F, S) \
-  if (a.colour.t && a.colour.g) { RR_LAUNCH_C(MODE, B0, B1, F, S, RR_COLOUR_TONE) } \
-  else if (a.colour.t) { RR_LAUNCH_C(MODE, B0, B1, F, S, RR_COLOUR_TABLES) } \
-  else { RR_LAUNCH_C(MODE, B0, B1, F, S, RR_COLOUR_OFF) }
-#define RR_LAUNCH_F(MODE, B0, B1, F) \
-  if (a.chroma_loc != 0) { RR_LAUNCH_S(MODE, B0, B1, F, true) } \
-  else { RR_LAUNCH_S(MODE, B0, B1, F, false) }
-#define RR_LAUNCH(MODE, B0, B1, grid) \
+  if (src_bytes == 1 && elem_bytes == B0) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_export_resized_rgb<1, B0, MODE, F, S, C, RR_PX_OFF>), g_, block, 0, st, a); \
+  if (src_bytes == 1 && elem_bytes == B1) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_export_resized_rgb<1, B1, MODE, F, S, C, RR_PX_OFF>), g_, block, 0, st, a); \
+  if (src_bytes == 2 && elem_bytes == B0) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_export_resized_rgb<2, B0, MODE, F, S, C, RR_PX_OFF>), g_, block, 0, st, a); \
+  if (src_bytes == 2 && elem_bytes == B1) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_export_resized_rgb<2, B1, MODE, F, S, C, RR_PX_OFF>), g_, block, 0, st, a);
+/* the pixel formats (RR_FRAME only): element bytes 1 / 2 stand for PX = 8-bit / 10-bit pixels, whose integer stage has those element bytes */
+#define RR_LAUNCH_PX(MODE, B0, B1, F, S, C) \
+  if (src_bytes == 1 && elem_bytes == 1) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_export_resized_rgb<1, 1, RR_FRAME, F, S, C, RR_PX_8>), g_, block, 0, st, a); \
+  if (src_bytes == 1 && elem_bytes == 2) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_export_resized_rgb<1, 2, RR_FRAME, F, S, C, RR_PX_10>), g_, block, 0, st, a); \
+  if (src_bytes == 2 && elem_bytes == 1) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_export_resized_rgb<2, 1, RR_FRAME, F, S, C, RR_PX_8>), g_, block, 0, st, a); \
+  if (src_bytes == 2 && elem_bytes == 2) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_export_resized_rgb<2, 2, RR_FRAME, F, S, C, RR_PX_10>), g_, block, 0, st, a);
+#define RR_LAUNCH_S(L, MODE, B0, B1, F, S) \
+  if (a.colour.t && a.colour.g) { L(MODE, B0, B1, F, S, RR_COLOUR_TONE) } \
+  else if (a.colour.t) { L(MODE, B0, B1, F, S, RR_COLOUR_TABLES) } \
+  else { L(MODE, B0, B1, F, S, RR_COLOUR_OFF) }
+#define RR_LAUNCH_F(L, MODE, B0, B1, F) \
+  if (a.chroma_loc != 0) { RR_LAUNCH_S(L, MODE, B0, B1, F, true) } \
+  else { RR_LAUNCH_S(L, MODE, B0, B1, F, false) }
+#define RR_LAUNCH_WITH(L, MODE, B0, B1, grid) \
   const dim3 g_ grid, block(256); \
-  if (filter == M355_FILTER_CUBIC) { RR_LAUNCH_F(MODE, B0, B1, M355_FILTER_CUBIC) } \
-  else { RR_LAUNCH_F(MODE, B0, B1, M355_FILTER_TRIANGLE) }
+  if (filter == M355_FILTER_CUBIC) { RR_LAUNCH_F(L, MODE, B0, B1, M355_FILTER_CUBIC) } \
+  else { RR_LAUNCH_F(L, MODE, B0, B1, M355_FILTER_TRIANGLE) }
+#define RR_LAUNCH(MODE, B0, B1, grid) RR_LAUNCH_WITH(RR_LAUNCH_C, MODE, B0, B1, grid)
 void m355_launch_export_resized_rgb(const ExportResizedRgbArgs& a, int src_bytes, int elem_bytes, int filter, hipStream_t st)
 {
   if (!a.units) return;
   RR_LAUNCH(RR_FRAME, 1, 2, (a.units))
+}
+/* the same frame as pixels of a.px_bytes bytes (m355_frame_export_resized_pixels): ten = a 2:10:10:10 format */
+void m355_launch_export_resized_pixels(const ExportResizedRgbArgs& a, int src_bytes, bool ten, int filter, hipStream_t st)
+{
+  if (!a.units) return;
+  const int elem_bytes = ten ? 2 : 1;
+  RR_LAUNCH_WITH(RR_LAUNCH_PX, RR_FRAME, 1, 2, (a.units))
 }
 void m355_launch_export_tensor(const ExportTensorArgs& a, int src_bytes, int elem_bytes, int filter, hipStream_t st)
 {
@@ -518,6 +555,8 @@ void m355_launch_export_tensor_rois(const ExportTensorRoisArgs& a, int src_bytes
   RR_LAUNCH(RR_ROIS, 2, 4, (a.max_units, a.n))
 }
 #undef RR_LAUNCH
+#undef RR_LAUNCH_WITH
+#undef RR_LAUNCH_PX
 #undef RR_LAUNCH_F
 #undef RR_LAUNCH_S
 #undef RR_LAUNCH_C

@@ -36,6 +36,7 @@
 #include "k_common.h"
 
 #include "k_rgb_dev.h"   /* d_mad24, d_rgb_sample, d_rgb_chroma, d_rgb_load, d_rgb_pixel: shared with k_stats.hip */
+#include "pixel_pack.h"  /* m355_pp_dword: the pixel formats of k_export_pixels below */
 
 /* N values of one byte / one 16-bit half each -> N * DB / 4 dwords */
 template <int DB, int N> __device__ __forceinline__ void d_rgb_pack(const unsigned* e, unsigned* o)
@@ -126,4 +127,60 @@ void m355_launch_export_rgb(const ExportRgbArgs& a, int src_bytes, int dst_bytes
 #undef M355_EXPORT_RGB_CASE
 #undef M355_EXPORT_RGB_PL
 #undef M355_EXPORT_RGB_CF
+}
+
+/* The pixel-format store path (m355_frame_export_pixels; pixel_pack.h): the same units, loads, chroma reconstruction and matrix — k_rgb_dev.h as it
+   is —, then a DWORD per pixel: the three channels (TEN: matrix with the coefficients of M355_RGB_U16, clip to 65535, then c10 per channel) and the
+   alpha, which arrives in its place (a.alpha_bits, wave-uniform), joined by shift-or / v_perm_b32.  A lane's NP dwords (64 or 32 bytes) leave as 16-byte
+   stores; a pixel is a dword, so the row's last lane stores whole dwords only (d_rgb_store with a multiple of 4: its byte tail is never reached).
+   The channel order is not the kernel's business: B, G, R is R, G, B of the frame with Cb and Cr and their coefficients exchanged (R = cy y + crv v,
+   B = cy y + cbu u, G is symmetric in the two), which the host does (runtime_export.hip) — the sums are the same integers modulo 2^32, so BGRA8,
+   A2R10G10B10 and BGR8 (the packed path above, unchanged) cost no instruction and no instantiation.  Reads and bounds: as argued in the header
+   comment; writes: dwords p0 .. p0 + n - 1 of row `row`, p0 + n <= width. */
+template <int SB, bool TEN, int CF, int LOC>
+__global__ void __launch_bounds__(256) k_export_pixels(ExportRgbArgs a)
+{
+  M355_GATE(a);
+  constexpr int NP = 16 / SB, M = TEN ? 65535 : 255;
+  const uint32_t unit = __builtin_amdgcn_readfirstlane((uint32_t)(blockIdx.x * 4u + (threadIdx.x >> 6)));
+  if (unit >= a.units) return;
+  const uint32_t row = unit / a.chunks, chunk = unit - row * a.chunks;
+  const uint32_t p0 = (chunk * 64u + (threadIdx.x & 63u)) * NP;
+  if (p0 >= a.width) return;
+  const uint32_t n = a.width - p0 < (uint32_t)NP ? a.width - p0 : (uint32_t)NP;
+  const uint32_t X0 = a.x0 + p0, Y = a.y0 + row;
+  RgbLane<SB, CF, LOC> l;
+  d_rgb_load<SB, CF, LOC>(a, X0, Y, l);
+  const RgbMatrix m = d_rgb_matrix_of(a.k);
+  int u[NP], v[NP];
+  if (CF != 0) {
+    d_rgb_chroma<SB, CF, LOC>(l.rc[0][0], l.rc[0][1], l.last, m.c0, u, l.yodd, l.lead);
+    d_rgb_chroma<SB, CF, LOC>(l.rc[1][0], l.rc[1][1], l.last, m.c0, v, l.yodd, l.lead);
+  }
+  const uint32_t alpha_bits = a.alpha_bits;
+  unsigned o[NP];
+#pragma unroll
+  for (int k = 0; k < NP; k++) {
+    unsigned R, G, B;
+    d_rgb_pixel<CF>(m, d_rgb_sample<SB>(l.ry, k), CF != 0 ? u[k] : 0, CF != 0 ? v[k] : 0, M, R, G, B);
+    o[k] = m355_pp_dword(TEN, R, G, B, alpha_bits);
+  }
+  d_rgb_store<NP>((M355_GLOBAL uint8_t*)a.dst[0] + (size_t)row * a.dst_pitch[0] + (size_t)p0 * 4u, o, n * 4u);
+}
+
+void m355_launch_export_pixels(const ExportRgbArgs& a, int src_bytes, bool ten, int chroma_format, int chroma_loc, hipStream_t st)
+{
+  if (!a.units) return;
+  const dim3 grid((a.units + 3) / 4), block(256);
+  const int loc = chroma_format == 1 ? chroma_loc : 0;          /* (the siting is 4:2:0's alone) */
+#define M355_EXPORT_PX_CF(SB, TEN, CF, LOC) \
+  if (chroma_format == CF && loc == LOC) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_export_pixels<SB, TEN, CF, LOC>), grid, block, 0, st, a);
+#define M355_EXPORT_PX_CASE(SB, TEN) \
+  if (src_bytes == SB && ten == TEN) { \
+    M355_EXPORT_PX_CF(SB, TEN, 0, 0) M355_EXPORT_PX_CF(SB, TEN, 1, 0) M355_EXPORT_PX_CF(SB, TEN, 2, 0) M355_EXPORT_PX_CF(SB, TEN, 3, 0) \
+    M355_EXPORT_PX_CF(SB, TEN, 1, 1) M355_EXPORT_PX_CF(SB, TEN, 1, 2) M355_EXPORT_PX_CF(SB, TEN, 1, 3) \
+  }
+  M355_EXPORT_PX_CASE(1, false) M355_EXPORT_PX_CASE(1, true) M355_EXPORT_PX_CASE(2, false) M355_EXPORT_PX_CASE(2, true)
+#undef M355_EXPORT_PX_CASE
+#undef M355_EXPORT_PX_CF
 }

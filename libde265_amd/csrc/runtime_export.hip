@@ -14,6 +14,8 @@
 #include "tensor_element.h"
 #include "colour_transform.h"
 #include "colour_preset.h"
+#include "pixel_pack.h"
+#include <utility>
 
 namespace {
 /* What the exports share per plane of the launch (semi-planar: plane 1 = Cb and Cr interleaved): where the rectangle starts in the frame, its size and
@@ -586,6 +588,97 @@ int m355_frame_export_resized_rgb_filtered(m355_ctx* c, int h, const m355_resize
   return m355_frame_export_resized_rgb_opts(c, h, e, &o);
 }
 int m355_frame_export_resized_rgb(m355_ctx* c, int h, const m355_resize_rgb_desc* e) { return m355_frame_export_resized_rgb_opts(c, h, e, nullptr); }
+/* The pixel formats (pixel_pack.h): the two R'G'B' exports above with a pixel of 3 or 4 bytes in place of three elements.  The descriptor check behind
+ * the plan, the options and (resized) the resize check: the format and its alpha, the conversion of the format's channel bits (into k), the destination
+ * of rows of `width` pixels, whole dwords for the 4-byte formats. */
+static int pixel_desc_check(const char* who, const m355_pixel_desc* e, const Frame* f, int64_t width, m355_rgb_coeffs* k)
+{
+  if (!m355_pp_known(e->format)) return fail(M355_ERR_INVALID, "%s: unknown pixel format %d", who, e->format);
+  if (e->alpha < 0 || (uint32_t)e->alpha > m355_pp_alpha_max(e->format)) return fail(M355_ERR_INVALID, "%s: alpha %d is not 0..%u (format %d)", who, e->alpha, m355_pp_alpha_max(e->format), e->format);
+  int rc = m355_rgb_coefficients(e->matrix, e->full_range, f->bdl, f->bdc, m355_pp_ten(e->format) ? M355_RGB_U16 : M355_RGB_U8, k);
+  if (rc) return rc;
+  const int bpp = m355_pp_bytes(e->format);
+  if ((rc = dst_check(who, 0, e->dst, e->pitch, width * bpp, 1)) != 0) return rc;
+  if (bpp == 4 && (((uintptr_t)e->dst | (uint64_t)e->pitch) & 3)) return fail(M355_ERR_INVALID, "%s: 4-byte pixels at an address or a pitch that is no multiple of 4", who);
+  return M355_OK;
+}
+/* (k_export_rgb.hip: k_export_pixels for the 4-byte formats, the packed U8 path of k_export_rgb for BGR8.)  B, G, R order is R, G, B of the frame with
+ * Cb and Cr and their coefficients exchanged — R = cy y + crv v and B = cy y + cbu u change places, G's sum keeps its terms —, so the kernels have
+ * one channel order. */
+int m355_frame_export_pixels(m355_ctx* c, int h, const m355_pixel_desc* e, const m355_export_opts* opts)
+{
+  const char* who = "m355_frame_export_pixels";
+  ExportPlan P;
+  int rc = export_plan_rect(c, h, e, e ? e->dst : nullptr, who, P);
+  if (rc) return rc;
+  Frame* f = P.f;
+  m355_export_opts o;
+  rc = opts_check(who, c, opts, f, false, o);
+  if (rc) return rc;
+  if (e->out_width || e->out_height) return fail(M355_ERR_INVALID, "%s: output size %dx%d in a call that resizes nothing", who, e->out_width, e->out_height);
+  ExportRgbArgs a = {};
+  const int sb = f->bpp[0];
+  const int64_t w = P.p[0].pw;
+  rc = pixel_desc_check(who, e, f, w, &a.k);
+  if (rc) return rc;
+  a.dst[0] = (uint8_t*)e->dst; a.dst_pitch[0] = e->pitch;
+  for (int p = 0; p < 3; p++) a.src[p] = (const uint8_t*)f->plane[p];
+  if (m355_pp_swapped(e->format)) { std::swap(a.src[1], a.src[2]); std::swap(a.k.crv, a.k.cbu); std::swap(a.k.cgu, a.k.cgv); }
+  a.src_pitch[0] = (long long)f->stride[0] * sb; a.src_pitch[1] = (long long)f->stride[1] * sb;
+  a.x0 = e->width ? (uint32_t)e->x0 : 0u; a.y0 = e->width ? (uint32_t)e->y0 : 0u;
+  a.width = (uint32_t)w; a.height = (uint32_t)P.p[0].ph;
+  a.cw = (uint32_t)f->pw[1]; a.ch = (uint32_t)f->ph[1];
+  const uint32_t per_chunk = 64u * 16u / (uint32_t)sb;
+  a.chunks = (a.width + per_chunk - 1) / per_chunk;
+  a.units = a.chunks * a.height;
+  a.alpha_bits = m355_pp_alpha_bits(e->format, (uint32_t)e->alpha);
+  const int format = e->format;
+  return export_launch(c, f, a, [&](hipStream_t cs) {
+    if (m355_pp_bytes(format) == 3) m355_launch_export_rgb(a, sb, 1, false, f->cf, o.chroma_loc, cs);
+    else m355_launch_export_pixels(a, sb, m355_pp_ten(format), f->cf, o.chroma_loc, cs);
+  });
+}
+/* (k_export_resized_rgb.hip, RR_FRAME with PX: the colour stage sits between the matrix and the pack, so the channel order is the kernel's here.) */
+int m355_frame_export_resized_pixels(m355_ctx* c, int h, const m355_pixel_desc* e, const m355_export_opts* opts)
+{
+  const char* who = "m355_frame_export_resized_pixels";
+  ExportPlan P;
+  int rc = export_plan_rect(c, h, e, e ? e->dst : nullptr, who, P);
+  if (rc) return rc;
+  Frame* f = P.f;
+  m355_export_opts o;
+  ColourArgs colour = {};
+  rc = opts_check(who, c, opts, f, true, o, &colour);
+  if (rc) return rc;
+  const int filter = o.filter;
+  rc = resize_check(who, &P, 0, e->out_width, e->out_height, filter);
+  if (rc) return rc;
+  ExportResizedRgbArgs a = {};
+  rc = pixel_desc_check(who, e, f, e->out_width, &a.k);
+  if (rc) return rc;
+  a.dst[0] = (uint8_t*)e->dst; a.dst_pitch[0] = e->pitch;
+  if ((rc = colour_apply(colour, e, f, a)) != 0) return rc;
+  plan_sources(P, a);
+  plan_geometry(P, e->out_width, e->out_height, filter, o.chroma_loc, a, a);
+  a.cf = f->cf; a.planar = 0; a.bdl = f->bdl; a.bdc = f->bdc; a.chroma_loc = o.chroma_loc;
+  a.px_bytes = (uint32_t)m355_pp_bytes(e->format); a.px_swapped = m355_pp_swapped(e->format) ? 1u : 0u;
+  a.px_alpha_bits = m355_pp_alpha_bits(e->format, (uint32_t)e->alpha);
+  const bool ten = m355_pp_ten(e->format);
+  return export_launch(c, f, a, [&](hipStream_t cs) { m355_launch_export_resized_pixels(a, f->bpp[0], ten, filter, cs); });
+}
+/* one pixel's bytes (pixel_pack.h: the function the kernels call) */
+int m355_pixel_pack(int format, const uint32_t rgb[3], uint32_t alpha, uint8_t out[4], int* n_bytes)
+{
+  if (!rgb || !out || !n_bytes || !m355_pp_known(format)) return fail(M355_ERR_INVALID, "m355_pixel_pack: null pointer / unknown format %d", format);
+  const uint32_t top = m355_pp_channel_max(format);
+  if (rgb[0] > top || rgb[1] > top || rgb[2] > top || alpha > m355_pp_alpha_max(format))
+    return fail(M355_ERR_INVALID, "m355_pixel_pack: a channel above %u or alpha %u above %u (format %d)", top, alpha, m355_pp_alpha_max(format), format);
+  const uint32_t dw = m355_pp_pixel(m355_pp_ten(format), m355_pp_swapped(format), rgb, m355_pp_alpha_bits(format, alpha));
+  const int n = m355_pp_bytes(format);
+  for (int i = 0; i < n; i++) out[i] = (uint8_t)(dw >> (8 * i));
+  *n_bytes = n;
+  return M355_OK;
+}
 /* the float stage of m355_frames_export_tensor for one value (tensor_element.h: the function the kernel calls) */
 int m355_tensor_element(uint32_t v, float scale, float bias, int dtype, uint32_t* bits)
 {

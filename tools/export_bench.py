@@ -40,6 +40,12 @@
       (K0z32), and the ratios in the result line; no bar is set for them
   --tone (implies --colour) adds, beside the seven K rows, the same calls with a tone object (m355_colour_create_tone: the preset PQ / BT.2020 -> gamma
       2.4 / BT.709, BT.2390, maxRGB, 203 / 1000 nits) as (Gq), (Gw), (Gz8), (Gz32), (GT32), (GQ8), (GQ32), and their ratios to the K rows; no bar is set
+  --pixels adds the pixel formats (m355_frame_export_pixels, m355_frame_export_resized_pixels) and, beside them, the packed R'G'B' rows of the same frame
+      and size they are held against — a pixel is 4 bytes, between the 3 of U8 packed and the 6 of U16 packed, and the destination is the larger side of
+      the traffic: (Pk16) m355_frame_export_rgb U16 packed of the whole frame, beside (k); (Xk8), (Xk10) BGRA8 and A2R10G10B10 of the whole frame;
+      (Pq8), (Pq16) m355_frame_export_resized_rgb U8 / U16 packed to 3840x2160 of a frame of seeded RANDOM samples, (Xq8), (Xq10) the two pixel formats of
+      the same call, and (PG8), (PG16), (XG8), (XG10) the four with the tone object of --tone.  A library without the pixel entry points (a parent build
+      loaded through M355_LIB) runs the P rows only.  No bar is set; the result line says whether each X row lies between its two P rows
 
 and, beside them, m355_measure_copy_rate for the frame's byte count.  Every figure is the median of --iters launches; (b) is measured in
 --rounds separate rounds spread over the run, and the spread of their medians is the margin (c), (d), (g)-(j) and (m)-(p) are held against: a scaled or resized export reads exactly (b)'s source bytes and writes at most a
@@ -84,6 +90,7 @@ def main():
                     help="also measure this chroma sample location type's rows beside the type-0 rows (may repeat)")
     ap.add_argument("--colour", action="store_true", help="also measure the composed exports with a colour transform, on frames of random samples")
     ap.add_argument("--tone", action="store_true", help="also measure the colour rows with a tone object (one gain per pixel: BT.2390, maxRGB); implies --colour")
+    ap.add_argument("--pixels", action="store_true", help="also measure the pixel-format exports beside the packed R'G'B' rows of the same frame and size")
     args = ap.parse_args()
     args.colour = args.colour or args.tone
 
@@ -395,6 +402,60 @@ def main():
             for n in gains:
                 tone_of[n] = [t for t in rows if t.startswith("K" + n[1:].split("_")[0] + "_")][0]
             variants.update(gains)
+    pixel_of = {}                      # a pixel-format row -> (the U8 packed row, the U16 packed row) of the same frame and size
+    if args.pixels:
+        import numpy as np
+        rng_p = np.random.default_rng(ROI_SEED + 1)
+        pframe = ctx.frame_create(W, H, 1, BD, BD)
+        ctx.frame_upload(pframe, [rng_p.integers(0, 1 << BD, (ph, pw)).astype(np.uint16) for pw, ph in planes])
+        made.append(pframe)
+        px_dst = ctx.device_alloc(W * 6 * H, fill=None)
+        PG = ctx.colour_create_tone(*lib.colour_preset_tone(16, 9, 1, 1, tone=capi.TONE_BT2390, norm=capi.NORM_MAXRGB, white_nits=203, peak_nits=1000))
+        UHD = (3840, 2160)
+
+        def packed(samples, elem, out_size=None, colour=0):
+            """the packed R'G'B' row: m355_frame_export_rgb of the whole frame, or m355_frame_export_resized_rgb_opts of the random frame to out_size"""
+            if out_size is None:
+                d = capi.RgbDesc(layout=capi.RGB_PACKED, samples=samples, matrix=capi.MATRIX_BT709, full_range=0)
+                d.dst[0] = px_dst; d.pitch[0] = W * elem * 3
+                return lambda: lib.check(lib.lib.m355_frame_export_rgb(ctx.h, frame, ctypes.byref(d)))
+            d = capi.ResizeRgbDesc(layout=capi.RGB_PACKED, samples=samples, matrix=capi.MATRIX_BT709, full_range=0, out_width=out_size[0], out_height=out_size[1])
+            d.dst[0] = px_dst; d.pitch[0] = out_size[0] * elem * 3
+            o = opts_of(0, 0, colour)
+            return lambda: lib.check(lib.lib.m355_frame_export_resized_rgb_opts(ctx.h, pframe, ctypes.byref(d), ctypes.byref(o)))
+
+        def pixels(format, out_size=None, colour=0):
+            d = capi.PixelDesc(format=format, alpha=3, matrix=capi.MATRIX_BT709, full_range=0)
+            d.dst = px_dst
+            if out_size is None:
+                d.pitch = W * 4
+                return lambda: lib.check(lib.lib.m355_frame_export_pixels(ctx.h, frame, ctypes.byref(d), None))
+            d.out_width, d.out_height = out_size
+            d.pitch = out_size[0] * 4
+            o = opts_of(0, 0, colour)
+            return lambda: lib.check(lib.lib.m355_frame_export_resized_pixels(ctx.h, pframe, ctypes.byref(d), ctypes.byref(o)))
+
+        variants.update({
+            "Pk16_rgb_u16_packed": packed(capi.RGB_U16, 2),
+            "Pq8_random_resized_rgb_u8_packed_2160p": packed(capi.RGB_U8, 1, UHD),
+            "Pq16_random_resized_rgb_u16_packed_2160p": packed(capi.RGB_U16, 2, UHD),
+            "PG8_tone_resized_rgb_u8_packed_2160p": packed(capi.RGB_U8, 1, UHD, PG),
+            "PG16_tone_resized_rgb_u16_packed_2160p": packed(capi.RGB_U16, 2, UHD, PG),
+        })
+        if hasattr(lib.lib, "m355_frame_export_pixels"):
+            rows = {
+                "Xk8_pixels_bgra8": (pixels(capi.PIXEL_BGRA8), "k_rgb_u8_packed", "Pk16_rgb_u16_packed"),
+                "Xk10_pixels_a2r10g10b10": (pixels(capi.PIXEL_A2R10G10B10), "k_rgb_u8_packed", "Pk16_rgb_u16_packed"),
+                "Xq8_random_resized_pixels_bgra8_2160p": (pixels(capi.PIXEL_BGRA8, UHD), "Pq8_random_resized_rgb_u8_packed_2160p", "Pq16_random_resized_rgb_u16_packed_2160p"),
+                "Xq10_random_resized_pixels_a2r10g10b10_2160p": (pixels(capi.PIXEL_A2R10G10B10, UHD), "Pq8_random_resized_rgb_u8_packed_2160p",
+                                                                 "Pq16_random_resized_rgb_u16_packed_2160p"),
+                "XG8_tone_resized_pixels_bgra8_2160p": (pixels(capi.PIXEL_BGRA8, UHD, PG), "PG8_tone_resized_rgb_u8_packed_2160p", "PG16_tone_resized_rgb_u16_packed_2160p"),
+                "XG10_tone_resized_pixels_a2r10g10b10_2160p": (pixels(capi.PIXEL_A2R10G10B10, UHD, PG), "PG8_tone_resized_rgb_u8_packed_2160p",
+                                                               "PG16_tone_resized_rgb_u16_packed_2160p"),
+            }
+            for n, (fn, u8, u16) in rows.items():
+                variants[n] = fn
+                pixel_of[n] = (u8, u16)
     scaled = [n for n in variants if n[0] in "ghijmnop"]
     ms = {n: [] for n in variants}
     for _ in range(args.rounds):
@@ -435,6 +496,8 @@ def main():
         "colour_rounds_ms": {n: ms[n] for n in colour_of},
         "tone_over_colour": {n: res[n] / res[t] for n, t in tone_of.items()},
         "tone_rounds_ms": {n: ms[n] for n in tone_of},
+        "pixels": {n: {"ms": res[n], "u8_packed_ms": res[a], "u16_packed_ms": res[b_], "at_most_u16_packed": res[n] <= res[b_]} for n, (a, b_) in pixel_of.items()},
+        "pixels_rounds_ms": {n: ms[n] for n in variants if n[0] in "PX"},
         "copy_rate_GBps_same_bytes": ctx.measure_copy_rate(frame_bytes, 9),
         "bars": {"b_le_a": res["b_native_planar"] <= res["a_memcpy2d_x3"],
                  "c_le_b_plus_spread": res["c_msb16_semiplanar_crop8"] <= res["b_native_planar"] + spread,
@@ -457,7 +520,7 @@ def main():
     if args.out:
         with open(args.out, "a") as f:
             f.write(line + "\n")
-    for p in src + dst + rgb_dst:
+    for p in src + dst + rgb_dst + ([px_dst] if args.pixels else []):
         ctx.device_free(p)
     for f in list(small.values()) + batch + made:
         ctx.frame_destroy(f)
