@@ -89,7 +89,7 @@ namespace {
   X(m355_frame_download_async) X(m355_frame_download_wait) X(m355_frame_export) X(m355_frame_export_scaled) X(m355_frame_export_rgb_opts) X(m355_frame_export_resized_opts) X(m355_frame_export_resized_rgb_opts) X(m355_frames_export_tensor_opts) X(m355_frames_export_tensor_rois_opts) X(m355_frame_export_order) X(m355_colour_create) X(m355_colour_destroy) X(m355_colour_preset) \
   X(m355_group_create) X(m355_group_destroy) X(m355_group_decode) X(m355_picture_upload) X(m355_picture_replace) X(m355_shard_owner_of_tile) \
   X(m355_picture_arena_begin) X(m355_frame_hash_async) X(m355_frame_hash_result) X(m355_frame_measure_async) X(m355_frame_measure_result) \
-  X(m355_frame_stats_async) X(m355_frame_stats_result) X(m355_stats_quantile) X(m355_colour_linear) \
+  X(m355_frame_stats_async) X(m355_frame_stats_result) X(m355_stats_quantile) X(m355_colour_linear) X(m355_frame_ssim_async) X(m355_frame_ssim_result) \
   X(m355_colour_create_tone) X(m355_colour_preset_tone) X(m355_frame_export_pixels) X(m355_frame_export_resized_pixels)
 
 struct Api {
@@ -2126,6 +2126,39 @@ LIBDE265_API int m355_glue_measure_image(const struct de265_image* img, const in
   unsigned long long ticket = 0;
   int rc = A->m355_frame_measure_async(g->mctx, frame, &d, &ticket);
   if (rc == M355_OK) rc = A->m355_frame_measure_result(g->mctx, ticket, 1, out);
+  if (rc != M355_OK) g->error = A->m355_last_error();
+  return rc;
+}
+/* The SSIM of the picture against another one, on the device — the second number dec265 -m prints per picture (dec265.cc:423-504), as m355_frame_ssim_async
+ * defines it (integer weights, exact sums, q in Q30 per window; per plane the sum, the count, the worst window and ssim).  rect, ref and pitch as in
+ * m355_glue_measure_image; planes: bit p = measure plane p, 0 = every plane; map / map_pitch: NULL, or per plane NULL / device memory for q of every window
+ * (m355_ssim_desc).  Enqueued behind the picture's decode and collected with block = 1: the call waits for THIS request only, and nothing is downloaded.
+ * -> M355_OK with *out filled (and the maps complete), or an M355_ERR_* code. */
+LIBDE265_API int m355_glue_ssim_image(const struct de265_image* img, const int rect[4], const void* const ref[3], const int64_t pitch[3], int planes,
+                                      void* const map[3], const int64_t map_pitch[3], m355_ssim* out)
+{
+  Api* A = api();
+  if (!A) return M355_ERR_NO_DEVICE;
+  if (!img || !img->decctx || !ref || !pitch || !out || (map && !map_pitch)) return M355_ERR_INVALID;
+  Glue* g = glue_of(img->decctx);
+  if (!g || g->n_ranks > 1) return M355_ERR_INVALID;
+  wait_submitted(g, img->get_ID());
+  std::lock_guard<std::mutex> api_lock(g->api_mu);
+  int r[4];
+  const int frame = frame_and_rect(g, img, rect, r);
+  if (frame < 0) return M355_ERR_INVALID;
+  m355_ssim_desc d;
+  memset(&d, 0, sizeof(d));
+  d.ref_frame = -1;
+  d.x0 = r[0]; d.y0 = r[1]; d.width = r[2]; d.height = r[3];
+  d.planes = planes;
+  for (int c = 0; c < 3; c++) {
+    d.ref[c] = ref[c]; d.pitch[c] = pitch[c];
+    if (map) { d.map[c] = map[c]; d.map_pitch[c] = map_pitch[c]; }
+  }
+  unsigned long long ticket = 0;
+  int rc = A->m355_frame_ssim_async(g->mctx, frame, &d, &ticket);
+  if (rc == M355_OK) rc = A->m355_frame_ssim_result(g->mctx, ticket, 1, out);
   if (rc != M355_OK) g->error = A->m355_last_error();
   return rc;
 }

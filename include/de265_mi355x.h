@@ -973,6 +973,64 @@ typedef struct m355_measure {
 M355_API int m355_frame_measure_async(m355_ctx* ctx, int frame, const m355_measure_desc* desc, unsigned long long* ticket);
 M355_API int m355_frame_measure_result(m355_ctx* ctx, unsigned long long ticket, int block, m355_measure* out);
 
+/* The SSIM of a frame against another picture where both lie — the second number `dec265 -m` prints per picture (dec265.cc:423-504, there behind
+ * libvideogfx's float Gaussian) — per plane, as a request queued behind the frame's decode like m355_frame_measure_async.  No float code is the
+ * reference here: THE DEFINITION IS INTEGER-EXACT and this library's own (csrc/ssim_window.h is the one statement of it; the kernel and the host
+ * helpers below run that code).
+ * WEIGHTS.  The 11-tap Gaussian with sigma = 1.5 in 14 bits, w = {17, 124, 590, 1792, 3490, 4358, 3490, 1792, 590, 124, 17}: exp(-(i - 5)^2 / 4.5)
+ * normalised, times 16384, rounded half up; they sum to exactly 16384 (m355_ssim_weights).
+ * WINDOWS.  Each measured plane on its own grid, valid windows only: a plane of the rectangle with pw x ph samples has (pw - 10) x (ph - 10) windows,
+ * window (i, j) covers the samples [i, i + 10] x [j, j + 10] with weights w[dx] w[dy] (total 2^28).  With a = the frame's sample values as stored and
+ * b = the reference's, five unsigned 64-bit sums, exact:
+ *   MA = sum w a    MB = sum w b    SAA = sum w a^2    SBB = sum w b^2    SAB = sum w a b
+ * POINT.  In IEEE double, each operation rounded by itself in exactly this order (no fused multiply-add), peak = 2^bd - 1 with bd the PLANE's bit depth:
+ *   c1 = (double)(peak peak) 2^56 / 10000.0        c2 = (double)(9 peak peak) 2^56 / 10000.0                    (K1 = 0.01, K2 = 0.03)
+ *   fa = (double)MA, fb = (double)MB;  ab = fa fb, aa = fa fa, bb = fb fb
+ *   cov = 2^28 (double)SAB - ab,  va = 2^28 (double)SAA - aa,  vb = 2^28 (double)SBB - bb
+ *   s = ((2.0 ab + c1) (2.0 cov + c2)) / (((aa + bb) + c1) ((va + vb) + c2))
+ *   q = clamp((int64)floor(s 2^30 + 0.5), -2^30, 2^30)                                                          (Q30; m355_ssim_window)
+ * RESULT per measured plane: sum_q = the sum of q over the plane's windows (exact, independent of order; it can be negative), n = the number of
+ * windows, min_q = the worst window, ssim = (double)sum_q / ((double)n 2^30), computed by the host at collection.  Planes that are not selected or
+ * that the frame does not have read 0 in every field.  Identical planes give q = 2^30 in every window and ssim = 1.0 exactly.
+ * MAP (optional, per measured plane): q of every window as int32 in device memory, (pw - 10) elements per row, (ph - 10) rows map_pitch bytes apart;
+ * bytes of a row beyond its elements are not written.  The map is complete when the request has been collected, or behind m355_wait.
+ * ORDERING AND VERDICTS are those of m355_frame_measure_async: a READER of the frame and of ref_frame (a kind of its own), queued on the stream of the
+ * frame's last writer behind ref_frame's last writer; a later decode into either frame waits for it; the host waits for nothing at enqueue.  *ticket
+ * counts 1, 2, ... per context (a count of its own); at most M355_SSIM_REQUESTS requests may be outstanding: one more returns M355_ERR_BUSY and
+ * enqueues nothing.  The slots are separate from the comparison, statistics and hash slots.
+ * M355_ERR_INVALID, nothing enqueued: everything m355_frame_measure_async rejects (handles, null pointers, the rectangle, ref_frame, ref[] and pitch[]
+ * of every plane the frame has, a tile-sharded context); a selected plane of the rectangle narrower or lower than 11 samples; a `planes` bit for a
+ * plane the frame does not have, or bits above 2; a non-zero `reserved`; a map pointer or pitch that is no multiple of 4, or a pitch below
+ * 4 (pw - 10); a map for a plane that is not selected.
+ * m355_frame_ssim_result collects a request and frees its slot: block = 0 -> M355_ERR_BUSY while it runs (the request stays), block = 1 -> the host
+ * waits for THAT request only.  M355_ERR_INVALID: an unknown or collected ticket; or — the request is collected all the same — a request queued
+ * behind a decode whose lists were rejected, for either frame (the limit of the per-lane gate stated at m355_frame_measure_async holds): it has read
+ * nothing and written no map element.  m355_wait completes every request and collects none; a frame may be destroyed with requests pending.
+ * HOST-ONLY HELPERS (exact, no context): m355_ssim_weights fills w[11]; m355_ssim_window computes q from sums = {MA, MB, SAA, SBB, SAB} for a bit
+ * depth 1..16 (the point above).  M355_ERR_INVALID: null pointers, a bit depth outside 1..16.
+ * Not offered: other window sizes or K1 / K2, border padding, automatic downscaling, MS-SSIM, a batch of frames in one launch, sharded contexts. */
+#define M355_SSIM_REQUESTS 16
+typedef struct m355_ssim_desc {
+  int32_t     ref_frame;              /* as m355_measure_desc */
+  int32_t     x0, y0, width, height;  /* as m355_measure_desc */
+  const void* ref[3];                 /* as m355_measure_desc */
+  int64_t     pitch[3];               /* as m355_measure_desc */
+  int32_t     planes;                 /* bit p = measure plane p; 0 = every plane the frame has */
+  int32_t     reserved[7];            /* 0 */
+  void*       map[3];                 /* optional, device memory: int32 q per window, (pw - 10) per row, (ph - 10) rows; null = none */
+  int64_t     map_pitch[3];           /* BYTES per row of map[]; a multiple of 4, >= 4 (pw - 10) */
+} m355_ssim_desc;
+typedef struct m355_ssim {
+  int64_t  sum_q[3];
+  uint64_t n[3];
+  int32_t  min_q[3];
+  double   ssim[3];
+} m355_ssim;
+M355_API int m355_frame_ssim_async(m355_ctx* ctx, int frame, const m355_ssim_desc* desc, unsigned long long* ticket);
+M355_API int m355_frame_ssim_result(m355_ctx* ctx, unsigned long long ticket, int block, m355_ssim* out);
+M355_API int m355_ssim_window(const uint64_t sums[5], int bit_depth, int32_t* q);   /* host only */
+M355_API int m355_ssim_weights(int32_t w[11]);                                      /* host only */
+
 /* What is IN a frame, measured where it lies: histograms, the active area, the light level — what a tone mapper without metadata (a high percentile
  * of max(R, G, B)), a crop detector (the box of the content in letterboxed material) and a scene-cut / fade / black-frame detector (luma histograms and
  * means) need of every picture, in one pass over the planes and without a download.  A request queued behind the frame's decode, like

@@ -188,6 +188,21 @@ class Measure(ctypes.Structure):
                 ("first_x", ctypes.c_int32 * 3), ("first_y", ctypes.c_int32 * 3), ("mse", ctypes.c_double * 3)]
 
 
+SSIM_REQUESTS, SSIM_TAPS, SSIM_ONE = 16, 11, 1 << 30     # M355_SSIM_REQUESTS; the window's taps; q of two identical windows
+
+
+class SsimDesc(ctypes.Structure):
+    """m355_ssim_desc (include/de265_mi355x.h)"""
+    _fields_ = [("ref_frame", ctypes.c_int32), ("x0", ctypes.c_int32), ("y0", ctypes.c_int32), ("width", ctypes.c_int32), ("height", ctypes.c_int32),
+                ("ref", ctypes.c_void_p * 3), ("pitch", ctypes.c_int64 * 3), ("planes", ctypes.c_int32), ("reserved", ctypes.c_int32 * 7),
+                ("map", ctypes.c_void_p * 3), ("map_pitch", ctypes.c_int64 * 3)]
+
+
+class Ssim(ctypes.Structure):
+    """m355_ssim (include/de265_mi355x.h)"""
+    _fields_ = [("sum_q", ctypes.c_int64 * 3), ("n", ctypes.c_uint64 * 3), ("min_q", ctypes.c_int32 * 3), ("ssim", ctypes.c_double * 3)]
+
+
 STATS_REQUESTS, STATS_BINS = 16, 256        # M355_STATS_*
 
 
@@ -316,6 +331,11 @@ class Library:
             L.m355_frame_stats_async.argtypes = [vp, i, ctypes.POINTER(StatsDesc), ctypes.POINTER(ctypes.c_ulonglong)]
             L.m355_frame_stats_result.argtypes = [vp, ctypes.c_ulonglong, i, ctypes.POINTER(Stats)]
             L.m355_stats_quantile.argtypes = [ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(i)]
+        if hasattr(L, "m355_frame_ssim_async"):         # (absent from older builds loaded through M355_LIB for an A/B)
+            L.m355_frame_ssim_async.argtypes = [vp, i, ctypes.POINTER(SsimDesc), ctypes.POINTER(ctypes.c_ulonglong)]
+            L.m355_frame_ssim_result.argtypes = [vp, ctypes.c_ulonglong, i, ctypes.POINTER(Ssim)]
+            L.m355_ssim_window.argtypes = [ctypes.POINTER(ctypes.c_uint64), i, ctypes.POINTER(ctypes.c_int32)]
+            L.m355_ssim_weights.argtypes = [ctypes.POINTER(ctypes.c_int32)]
             L.m355_colour_linear.argtypes = [ctypes.POINTER(ColourTables), ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]
         L.m355_submit_picture.argtypes = [vp, vp]
         L.m355_wait.argtypes = [vp]
@@ -432,6 +452,19 @@ class Library:
         self.check(self.lib.m355_stats_quantile(h, num, den, ctypes.byref(b)))
         return int(b.value)
 
+    def ssim_window(self, sums, bit_depth):
+        """q (Q30) of one window from its five sums (MA, MB, SAA, SBB, SAB) at a plane's bit depth (m355_ssim_window; host only)"""
+        q = ctypes.c_int32(0)
+        v = None if sums is None else (ctypes.c_uint64 * 5)(*[int(x) for x in sums])
+        self.check(self.lib.m355_ssim_window(v, bit_depth, ctypes.byref(q)))
+        return int(q.value)
+
+    def ssim_weights(self):
+        """the window's eleven integer weights (m355_ssim_weights; host only)"""
+        w = (ctypes.c_int32 * SSIM_TAPS)()
+        self.check(self.lib.m355_ssim_weights(w))
+        return [int(x) for x in w]
+
     def colour_linear(self, tables, v16):
         """step 1 of the colour transform stage for one 16-bit value (m355_colour_linear; host only) -> linear light, 0 .. COLOUR_ONE"""
         out = ctypes.c_uint32(0)
@@ -462,6 +495,7 @@ class Context:
         self._hash_reqs = {}            # ticket -> (hash type, planes) of the requests not collected yet
         self._measure_reqs = {}         # ticket -> (planes, reference buffers to free, host?) of the comparison requests not collected yet
         self._stats_reqs = {}           # ticket -> (planes, light?) of the statistics requests not collected yet
+        self._ssim_reqs = {}            # ticket -> (reference buffers to free, host?) of the SSIM requests not collected yet
 
     def close(self):
         if self.h:
@@ -1020,6 +1054,46 @@ class Context:
             raise M355Error(rc, text)
         n, light = self._stats_reqs.pop(ticket)
         return stats_dict(out, n, light)
+
+    # ---- SSIM against another picture on the device (m355_frame_ssim_async) ----
+    def frame_ssim_async(self, f, ref_frame=None, ref_planes=None, rect=None, planes=0, maps=None, host=False, pad=None):
+        """enqueue the SSIM of frame f (rect = (x0, y0, width, height) in luma samples, None: the whole frame; planes: bit p = measure plane p, 0: all)
+        against frame `ref_frame` or `ref_planes` (as frame_measure_async).  maps: None, or per plane None / (device pointer, pitch in bytes) for the
+        map of q.  Nothing is waited for behind the enqueue -> ticket for frame_ssim_result, which frees the reference's buffers"""
+        desc = SsimDesc(ref_frame=-1 if ref_frame is None else ref_frame, planes=planes)
+        if rect is not None:
+            desc.x0, desc.y0, desc.width, desc.height = rect
+        if ref_planes is not None and not (isinstance(ref_planes, tuple) and ref_planes[:1] == ("measure_reference",)):
+            ref_planes = self.measure_reference(ref_planes, host, pad)
+        _, bufs, pitches, host = ref_planes or (None, [], [], False)
+        for k, (p, pitch) in enumerate(zip(bufs, pitches)):
+            desc.ref[k] = p; desc.pitch[k] = pitch
+        for k, m in enumerate(maps or []):
+            if m is not None:
+                desc.map[k] = m[0]; desc.map_pitch[k] = m[1]
+        t = ctypes.c_ulonglong(0)
+        rc = self.L.lib.m355_frame_ssim_async(self.h, f, ctypes.byref(desc), ctypes.byref(t))
+        if rc:
+            text = self.L.error()
+            self._measure_free(bufs, host)
+            raise M355Error(rc, text)
+        self._ssim_reqs[t.value] = (bufs, host)
+        return int(t.value)
+
+    def frame_ssim_result(self, ticket, block=True):
+        """collect a request (m355_frame_ssim_result) -> one dict per plane (always three): sum_q, n, min_q, ssim — all 0 for a plane that was not
+        measured; None while it has not finished (block=False); raises M355Error for an unknown / collected ticket and behind a rejected decode"""
+        out = Ssim()
+        rc = self.L.lib.m355_frame_ssim_result(self.h, ticket, 1 if block else 0, ctypes.byref(out))
+        if rc == 6 and not block:                               # M355_ERR_BUSY
+            return None
+        if rc:
+            text = self.L.error()
+            if rc == 3:                                         # M355_ERR_INVALID: collected without a value (behind a rejected decode), or no such request
+                self._measure_free(*self._ssim_reqs.pop(ticket, ([], False)))
+            raise M355Error(rc, text)
+        self._measure_free(*self._ssim_reqs.pop(ticket))        # (collected: nothing reads the buffers any more)
+        return [dict(sum_q=int(out.sum_q[c]), n=int(out.n[c]), min_q=int(out.min_q[c]), ssim=float(out.ssim[c])) for c in range(3)]
 
     # ---- pictures ----
     def submit(self, pic):

@@ -261,7 +261,8 @@ int m355_create(int device, m355_ctx** out)
   if (rc == M355_OK) rc = hash_requests_create(c);
   if (rc == M355_OK) rc = measure_requests_create(c);
   if (rc == M355_OK) rc = stats_requests_create(c);
-  if (rc) { stats_requests_destroy(c); measure_requests_destroy(c); hash_requests_destroy(c); lane_destroy(c->lanes[0]); delete c; return rc; }
+  if (rc == M355_OK) rc = ssim_requests_create(c);
+  if (rc) { ssim_requests_destroy(c); stats_requests_destroy(c); measure_requests_destroy(c); hash_requests_destroy(c); lane_destroy(c->lanes[0]); delete c; return rc; }
   *out = c;
   return M355_OK;
 }
@@ -303,6 +304,7 @@ void m355_destroy(m355_ctx* c)
   hash_requests_destroy(c);
   measure_requests_destroy(c);
   stats_requests_destroy(c);
+  ssim_requests_destroy(c);
   for (auto& e : c->inter_tabs) hipFree(e.second);
   for (auto& b : c->batch) { if (b.host) hipHostFree(b.host); if (b.dev) hipFree(b.dev); if (b.ev) hipEventDestroy(b.ev); }
   for (hipEvent_t e : c->batch_ev_pre) if (e) hipEventDestroy(e);
@@ -813,51 +815,27 @@ static void meas_slot_free(m355_ctx* c, m355_ctx::MeasSlot& s)
    earlier comparison mark; ONE mark behind the launch is kept by both frames and by the slot. */
 int m355_frame_measure_async(m355_ctx* c, int h, const m355_measure_desc* e, unsigned long long* ticket)
 {
-  Frame* f = c ? get_frame(c, h) : nullptr;
-  if (!f || !e || !ticket) return fail(M355_ERR_INVALID, "m355_frame_measure_async: bad frame handle %d / null descriptor / null ticket", h);
-  if (c->shard_n > 0) return fail(M355_ERR_INVALID, "m355_frame_measure_async: not on a tile-sharded context (its frames are complete only behind the gather)");
-  const int sw = (f->cf == 1 || f->cf == 2) ? 2 : 1, sh = f->cf == 1 ? 2 : 1;
-  int x0 = 0, y0 = 0, w = f->w, hgt = f->h;
-  if (e->width != 0) {
-    x0 = e->x0; y0 = e->y0; w = e->width; hgt = e->height;
-    if (x0 < 0 || y0 < 0 || w <= 0 || hgt <= 0 || x0 > f->w - w || y0 > f->h - hgt) return fail(M355_ERR_INVALID, "m355_frame_measure_async: rectangle %d,%d %dx%d leaves the %dx%d frame", x0, y0, w, hgt, f->w, f->h);
-    if (f->cf && ((x0 | w) % sw || (y0 | hgt) % sh)) return fail(M355_ERR_INVALID, "m355_frame_measure_async: rectangle %d,%d %dx%d is not aligned to the chroma grid (%dx%d luma samples)", x0, y0, w, hgt, sw, sh);
-  }
-  Frame* r = nullptr;
-  if (e->ref_frame != -1) {
-    r = get_frame(c, e->ref_frame);
-    if (!r) return fail(M355_ERR_INVALID, "m355_frame_measure_async: bad reference frame handle %d", e->ref_frame);
-    if (r->cf != f->cf || r->bdl != f->bdl || r->bdc != f->bdc || r->bpp[0] != f->bpp[0]) return fail(M355_ERR_INVALID, "m355_frame_measure_async: the reference frame's chroma format / bit depths differ from the frame's");
-    if (x0 > r->w - w || y0 > r->h - hgt) return fail(M355_ERR_INVALID, "m355_frame_measure_async: the %dx%d reference frame does not contain the rectangle %d,%d %dx%d", r->w, r->h, x0, y0, w, hgt);
-  }
-  const int np = f->cf == 0 ? 1 : 3;
+  PairGeom g = {};
+  const int grc = pair_geometry(c, "m355_frame_measure_async", h, e && ticket, e ? e->ref_frame : -1, e ? e->x0 : 0, e ? e->y0 : 0, e ? e->width : 0, e ? e->height : 0,
+                                e ? e->ref : nullptr, e ? e->pitch : nullptr, &g);
+  if (grc) return grc;
+  Frame *f = g.f, *r = g.r;
+  const int np = g.np;
   MeasArgs a = {};
   int rows = 0, nw = 0;
-  for (int p = 0; p < np; p++) rows += p ? hgt / sh : hgt;
+  for (int p = 0; p < np; p++) rows += g.pl[p].ph;
   a.rows_per_wave = std::max(1, rows / 4096);                                   /* (hash_args_fill: enough waves to fill 1024 SIMDs a few times over) */
   m355_ctx::MeasSlot geom;
   for (int p = 0, row0 = 0; p < 3; p++) {
     a.first[p] = nw;
     if (p >= np) continue;
-    const int sb = f->bpp[p];
-    const int pw = p ? w / sw : w, ph = p ? hgt / sh : hgt, px = p ? x0 / sw : x0, py = p ? y0 / sh : y0;
+    const PairPlane& gp = g.pl[p];
     MeasPlane& m = a.pl[p];
-    m.pitch_a = (long long)f->stride[p] * sb;
-    m.a = (const uint8_t*)f->plane[p] + (size_t)py * m.pitch_a + (size_t)px * sb;
-    if (r) {
-      m.pitch_b = (long long)r->stride[p] * sb;
-      m.b = (const uint8_t*)r->plane[p] + (size_t)py * m.pitch_b + (size_t)px * sb;
-    } else {
-      if (!e->ref[p]) return fail(M355_ERR_INVALID, "m355_frame_measure_async: no reference for plane %d", p);
-      if (e->pitch[p] < (int64_t)pw * sb) return fail(M355_ERR_INVALID, "m355_frame_measure_async: pitch %lld of plane %d is below its row of %lld bytes", (long long)e->pitch[p], p, (long long)pw * sb);
-      if (((uintptr_t)e->ref[p] | (uintptr_t)e->pitch[p]) & (uintptr_t)(sb - 1)) return fail(M355_ERR_INVALID, "m355_frame_measure_async: pointer / pitch of plane %d is no multiple of the %d-byte element", p, sb);
-      m.pitch_b = e->pitch[p];
-      m.b = (const uint8_t*)e->ref[p];
-    }
-    m.row_bytes = pw * sb; m.h = ph; m.px = px; m.py = py; m.row0 = row0;
-    geom.pw[p] = pw; geom.ph[p] = ph; geom.row0[p] = row0;
-    row0 += ph;
-    nw += (ph + a.rows_per_wave - 1) / a.rows_per_wave;
+    m.a = gp.a; m.b = gp.b; m.pitch_a = gp.pitch_a; m.pitch_b = gp.pitch_b;
+    m.row_bytes = gp.pw * f->bpp[p]; m.h = gp.ph; m.px = gp.px; m.py = gp.py; m.row0 = row0;
+    geom.pw[p] = gp.pw; geom.ph[p] = gp.ph; geom.row0[p] = row0;
+    row0 += gp.ph;
+    nw += (gp.ph + a.rows_per_wave - 1) / a.rows_per_wave;
   }
   a.first[3] = nw;
   m355_ctx::MeasSlot* s = nullptr;

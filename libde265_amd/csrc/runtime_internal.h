@@ -5,6 +5,8 @@
  *   runtime_export.hip the exports of a frame into memory of the caller (m355_frame_export* / m355_frames_export_tensor*), colour transform objects
  *   runtime_upload.hip host pool, validation, intra schedule, upload (lists -> one pinned arena -> device)
  *   runtime_decode.hip prepare, the per-picture launch sequence, decode status, m355_decode_batch
+ *   runtime_stats.hip  statistics requests (m355_frame_stats_async)
+ *   runtime_ssim.hip   SSIM requests (m355_frame_ssim_async)
  *   runtime_shard.hip  tile sharding: phases, exchanges, the in-process group, the built-in RCCL transport
  */
 #ifndef M355_RUNTIME_INTERNAL_H
@@ -32,6 +34,7 @@
 #include "k_hash.h"
 #include "k_measure.h"
 #include "k_stats.h"
+#include "k_ssim.h"
 
 
 extern thread_local std::string g_err;
@@ -85,7 +88,7 @@ constexpr bool intra_light_32x32 = false;
 struct EvRef { unsigned long long ticket = 0; hipStream_t stream = nullptr; };
 #define M355_EV_RING 256
 
-enum ReaderKind { RD_DOWNLOAD, RD_EXPORT, RD_HASH, RD_MEASURE, RD_STATS, RD_KINDS };
+enum ReaderKind { RD_DOWNLOAD, RD_EXPORT, RD_HASH, RD_MEASURE, RD_STATS, RD_SSIM, RD_KINDS };
 struct Frame {
   bool used = false;
   int w = 0, h = 0, cf = 0, bdl = 0, bdc = 0;
@@ -98,10 +101,10 @@ struct Frame {
      rejected does nothing, like that decode's own kernels (M355_GATE) */
   const uint32_t* wr_gate = nullptr; uint32_t wr_epoch = 0;
   /* READERS queued behind the decode that wrote the frame — a download (m355_frame_download_async), an export (m355_frame_export), a hash request
-     (m355_frame_hash_async), a comparison (m355_frame_measure_async, which reads two frames and marks both), a statistics request (m355_frame_stats_async): per kind the mark behind the LAST one.  reader_begin picks the stream (the writer's, so stream order stands for the wait for the
+     (m355_frame_hash_async), a comparison (m355_frame_measure_async, which reads two frames and marks both), a statistics request (m355_frame_stats_async), an SSIM request (m355_frame_ssim_async, two frames like the comparison): per kind the mark behind the LAST one.  reader_begin picks the stream (the writer's, so stream order stands for the wait for the
      picture) and lets it continue behind the kind's earlier mark, so that the one mark kept stands for both; reader_end marks; the next decode into the frame
      waits for every kind in front of its first write (readers_wait, from dst_hazards).  The kinds are separate because the HOST waits per kind
-     (m355_frame_download_wait, m355_frame_export_wait, m355_frame_hash_result, m355_frame_measure_result, m355_frame_stats_result), and a finished wait clears its mark: readers of different kinds need no order. */
+     (m355_frame_download_wait, m355_frame_export_wait, m355_frame_hash_result, m355_frame_measure_result, m355_frame_stats_result, m355_frame_ssim_result), and a finished wait clears its mark: readers of different kinds need no order. */
   EvRef reader[RD_KINDS];
 };
 
@@ -287,6 +290,17 @@ struct m355_ctx {
   StatsSlot stats_slot[M355_STATS_REQUESTS];
   unsigned long long stats_ticket = 0;
   uint32_t *stats_rec = nullptr, *stats_res = nullptr;
+  /* m355_frame_ssim_async (runtime_ssim.hip): M355_SSIM_REQUESTS slots of their own — a device record the kernel leaves zero and a pinned result record of
+     SSIM_REC_WORDS 64-bit words each (k_ssim.h), the request's mark, the frames it reads (frame[1]: the reference frame, -1 with memory), and per plane the
+     number of windows (0: not measured) */
+  struct SsimSlot {
+    unsigned long long ticket = 0;
+    uint64_t n[3] = {0, 0, 0};
+    EvRef mark; int frame[2] = {-1, -1};
+  };
+  SsimSlot ssim_slot[M355_SSIM_REQUESTS];
+  unsigned long long ssim_ticket = 0;
+  unsigned long long *ssim_rec = nullptr, *ssim_res = nullptr;
   /* pinned staging buffer of the blocking frame transfers (m355_frame_upload / _download / _fill, MD5 of m355_frame_hash): the copy itself is queued on the
      stream that last wrote the frame, between pinned memory and the frame (frame_stage_* in runtime.hip) */
   void* stage = nullptr; size_t stage_bytes = 0;
@@ -379,6 +393,59 @@ int stage_reserve(m355_ctx* c, size_t bytes);   /* runtime.hip: the context's pi
 int status_of(m355_ctx* c, m355_ctx::Status& s);
 hipError_t sync_all(m355_ctx* c);
 int upload(m355_ctx* c, Resident& r, const m355_picture* pic);
+int ssim_requests_create(m355_ctx* c);             /* runtime_ssim.hip: the slots of m355_frame_ssim_async, made and dropped with the context */
+void ssim_requests_destroy(m355_ctx* c);
+}
+
+/* What the requests that compare a frame with another picture share (m355_frame_measure_async, m355_frame_ssim_async): the frame, the rectangle
+   (width == 0: the whole frame) and the other picture — ref_frame >= 0, or ref[] / pitch[] — checked, and per plane of the frame both sides'
+   first sample of the rectangle.  `who` opens the error texts.  -> M355_OK, or M355_ERR_INVALID with nothing touched. */
+struct PairPlane {
+  const uint8_t *a, *b;         /* the frame's / the reference's samples at the rectangle's first sample */
+  long long pitch_a, pitch_b;   /* bytes between rows */
+  int pw, ph, px, py;           /* the rectangle on this plane: size, first sample in plane coordinates of the frame */
+};
+struct PairGeom {
+  Frame *f, *r;                 /* r: the reference frame, null with ref[] */
+  int np;                       /* planes of the frame */
+  PairPlane pl[3];
+};
+static int pair_geometry(m355_ctx* c, const char* who, int h, bool have_args, int ref_frame, int x0, int y0, int w, int hgt, const void* const* ref, const int64_t* pitch, PairGeom* g)
+{
+  Frame* f = c ? get_frame(c, h) : nullptr;
+  if (!f || !have_args) return fail(M355_ERR_INVALID, "%s: bad frame handle %d / null descriptor / null ticket", who, h);
+  if (c->shard_n > 0) return fail(M355_ERR_INVALID, "%s: not on a tile-sharded context (its frames are complete only behind the gather)", who);
+  const int sw = (f->cf == 1 || f->cf == 2) ? 2 : 1, sh = f->cf == 1 ? 2 : 1;
+  if (w != 0) {
+    if (x0 < 0 || y0 < 0 || w <= 0 || hgt <= 0 || x0 > f->w - w || y0 > f->h - hgt) return fail(M355_ERR_INVALID, "%s: rectangle %d,%d %dx%d leaves the %dx%d frame", who, x0, y0, w, hgt, f->w, f->h);
+    if (f->cf && ((x0 | w) % sw || (y0 | hgt) % sh)) return fail(M355_ERR_INVALID, "%s: rectangle %d,%d %dx%d is not aligned to the chroma grid (%dx%d luma samples)", who, x0, y0, w, hgt, sw, sh);
+  } else { x0 = y0 = 0; w = f->w; hgt = f->h; }
+  Frame* r = nullptr;
+  if (ref_frame != -1) {
+    r = get_frame(c, ref_frame);
+    if (!r) return fail(M355_ERR_INVALID, "%s: bad reference frame handle %d", who, ref_frame);
+    if (r->cf != f->cf || r->bdl != f->bdl || r->bdc != f->bdc || r->bpp[0] != f->bpp[0]) return fail(M355_ERR_INVALID, "%s: the reference frame's chroma format / bit depths differ from the frame's", who);
+    if (x0 > r->w - w || y0 > r->h - hgt) return fail(M355_ERR_INVALID, "%s: the %dx%d reference frame does not contain the rectangle %d,%d %dx%d", who, r->w, r->h, x0, y0, w, hgt);
+  }
+  g->f = f; g->r = r; g->np = f->cf == 0 ? 1 : 3;
+  for (int p = 0; p < g->np; p++) {
+    const int sb = f->bpp[p];
+    PairPlane& m = g->pl[p];
+    m.pw = p ? w / sw : w; m.ph = p ? hgt / sh : hgt; m.px = p ? x0 / sw : x0; m.py = p ? y0 / sh : y0;
+    m.pitch_a = (long long)f->stride[p] * sb;
+    m.a = (const uint8_t*)f->plane[p] + (size_t)m.py * m.pitch_a + (size_t)m.px * sb;
+    if (r) {
+      m.pitch_b = (long long)r->stride[p] * sb;
+      m.b = (const uint8_t*)r->plane[p] + (size_t)m.py * m.pitch_b + (size_t)m.px * sb;
+    } else {
+      if (!ref[p]) return fail(M355_ERR_INVALID, "%s: no reference for plane %d", who, p);
+      if (pitch[p] < (int64_t)m.pw * sb) return fail(M355_ERR_INVALID, "%s: pitch %lld of plane %d is below its row of %lld bytes", who, (long long)pitch[p], p, (long long)m.pw * sb);
+      if (((uintptr_t)ref[p] | (uintptr_t)pitch[p]) & (uintptr_t)(sb - 1)) return fail(M355_ERR_INVALID, "%s: pointer / pitch of plane %d is no multiple of the %d-byte element", who, p, sb);
+      m.pitch_b = pitch[p];
+      m.b = (const uint8_t*)ref[p];
+    }
+  }
+  return M355_OK;
 }
 
 #endif
