@@ -90,7 +90,8 @@ namespace {
   X(m355_group_create) X(m355_group_destroy) X(m355_group_decode) X(m355_picture_upload) X(m355_picture_replace) X(m355_shard_owner_of_tile) \
   X(m355_picture_arena_begin) X(m355_frame_hash_async) X(m355_frame_hash_result) X(m355_frame_measure_async) X(m355_frame_measure_result) \
   X(m355_frame_stats_async) X(m355_frame_stats_result) X(m355_stats_quantile) X(m355_colour_linear) X(m355_frame_ssim_async) X(m355_frame_ssim_result) \
-  X(m355_colour_create_tone) X(m355_colour_preset_tone) X(m355_frame_export_pixels) X(m355_frame_export_resized_pixels)
+  X(m355_colour_create_tone) X(m355_colour_preset_tone) X(m355_frame_export_pixels) X(m355_frame_export_resized_pixels) \
+  X(m355_picture_maps_async) X(m355_picture_maps_result) X(m355_device_alloc) X(m355_device_free)
 
 struct Api {
   void* handle = nullptr;
@@ -227,7 +228,20 @@ struct Glue {
     de265_image* img = nullptr; uint32_t id = 0; int dslot = -1;
     std::vector<ThreadRec*> recs;
     const de265_image* dpb_img[M355_MAX_REF_FRAMES]; uint32_t dpb_id[M355_MAX_REF_FRAMES];   /* the DPB as it was when the picture completed */
+    int dpb_poc[M355_MAX_REF_FRAMES]; uint32_t dpb_ref;   /* ... each slot's POC, and bit s: slot s held a picture marked as a reference (side maps) */
   };
+  /* m355_glue_set_side_maps: from the next picture on, the submit step enqueues a side-map request (m355_picture_maps_async on M355_PICTURE_LAST)
+     right behind a picture's m355_submit_picture, into device buffers kept PER DPB SLOT (reallocated only when the unit grid or the set of maps
+     changes), and remembers the ticket, the image and the slot -> POC table of the job's DPB snapshot.  Under api_mu. */
+  unsigned maps_mask = 0; int maps_log2 = 2;
+  struct SlotMaps {
+    void* dst[M355_N_MAPS] = {}; int64_t pitch[M355_N_MAPS] = {};
+    int units_w = 0, units_h = 0, log2_unit = 0; unsigned mask = 0;
+    unsigned long long ticket = 0; bool pending = false, have = false;   /* a request not collected yet / `info` is the picture's */
+    uint32_t img_id = 0xFFFFFFFFu;
+    m355_maps_info info;
+    int32_t ref_poc[M355_MAX_REF_FRAMES]; uint32_t ref_valid = 0;
+  } smaps[M355_MAX_REF_FRAMES];
   std::mutex job_mu, api_mu;
   std::condition_variable job_cv, idle_cv;
   std::deque<Job> jobs;
@@ -535,6 +549,59 @@ void hash_verdicts(Glue* g, uint32_t id, bool decoder_thread)
 }
 
 /* ------------------------------------------------------------------ picture submission ----------- */
+
+/* side maps of the picture just submitted (api_mu held): its slot's buffers, a request on M355_PICTURE_LAST, the ticket and the DPB table kept with the slot.
+   A failure leaves the slot without maps (m355_glue_image_side_maps reports it); the picture itself is not affected. */
+void side_maps_collect(Glue* g, Glue::SlotMaps& m)
+{
+  if (!m.pending) return;
+  m.have = api()->m355_picture_maps_result(g->mctx, m.ticket, 1, &m.info) == M355_OK;
+  m.pending = false;
+}
+void side_maps_free(Glue* g, Glue::SlotMaps& m)
+{
+  side_maps_collect(g, m);
+  for (int k = 0; k < M355_N_MAPS; k++) { if (m.dst[k]) api()->m355_device_free(g->mctx, m.dst[k]); m.dst[k] = nullptr; m.pitch[k] = 0; }
+  m.mask = 0; m.have = false; m.img_id = 0xFFFFFFFFu;
+}
+void enqueue_side_maps(Glue* g, const Glue::Job& job, const de265_image* img)
+{
+  static const int es[M355_N_MAPS] = {4, 1, 1, 1, 8, 4, 2};
+  Api* A = api();
+  Glue::SlotMaps& m = g->smaps[job.dslot];
+  side_maps_collect(g, m);                                   /* (the slot's earlier picture: nobody asked for its maps) */
+  m.have = false; m.img_id = 0xFFFFFFFFu;
+  const seq_parameter_set& sps = img->get_sps();
+  const int lu = g->maps_log2, U = 1 << lu;
+  const int uw = (sps.pic_width_in_luma_samples + U - 1) >> lu, uh = (sps.pic_height_in_luma_samples + U - 1) >> lu;
+  if (m.units_w != uw || m.units_h != uh || m.log2_unit != lu || m.mask != g->maps_mask) {
+    side_maps_free(g, m);
+    m.units_w = uw; m.units_h = uh; m.log2_unit = lu;
+    for (int k = 0; k < M355_N_MAPS; k++) {
+      if (!((g->maps_mask >> k) & 1u)) continue;
+      m.pitch[k] = (int64_t)uw * es[k];
+      m.dst[k] = A->m355_device_alloc(g->mctx, (size_t)m.pitch[k] * uh);
+      if (!m.dst[k]) { side_maps_free(g, m); return; }
+    }
+    m.mask = g->maps_mask;
+  }
+  m355_maps_desc d;
+  memset(&d, 0, sizeof(d));
+  d.log2_unit = lu;
+  for (int k = 0; k < M355_N_MAPS; k++) { d.dst[k] = m.dst[k]; d.pitch[k] = m.pitch[k]; }
+  int rc = A->m355_picture_maps_async(g->mctx, M355_PICTURE_LAST, &d, &m.ticket);
+  while (rc == M355_ERR_BUSY) {                              /* every request slot is taken by pictures nobody has asked about: collect the oldest */
+    Glue::SlotMaps* oldest = nullptr;
+    for (Glue::SlotMaps& o : g->smaps) if (o.pending && (!oldest || o.ticket < oldest->ticket)) oldest = &o;
+    if (!oldest) break;
+    side_maps_collect(g, *oldest);
+    rc = A->m355_picture_maps_async(g->mctx, M355_PICTURE_LAST, &d, &m.ticket);
+  }
+  if (rc != M355_OK) return;
+  m.pending = true; m.img_id = img->get_ID();
+  for (int s = 0; s < M355_MAX_REF_FRAMES; s++) m.ref_poc[s] = job.dpb_poc[s];
+  m.ref_valid = job.dpb_ref;
+}
 
 void walk_tu(const de265_image* img, int x0, int y0, int log2, int depth, std::vector<m355_tu>& out)
 {
@@ -1183,6 +1250,7 @@ bool submit_picture(Glue* g, Glue::Job& job)
   if (from_damaged && img->integrity == INTEGRITY_CORRECT) img->integrity = INTEGRITY_DERIVED_FROM_FAULTY_REFERENCE;
   g->n_pictures++;
   g->dl_id[dslot] = 0xFFFFFFFFu;
+  if (g->maps_mask && g->n_ranks == 1) enqueue_side_maps(g, job, img);
   if (g->app_reads.load() && img->PicOutputFlag && !getenv("M355_GLUE_NO_PREFETCH")) {
     void* dst[3] = {nullptr, nullptr, nullptr};
     ptrdiff_t str[3] = {0, 0, 0};
@@ -1264,6 +1332,11 @@ void picture_complete(decoder_context* d, de265_image* img)
   for (int s = 0; s < M355_MAX_REF_FRAMES; s++) {
     job.dpb_img[s] = d->has_image(s) ? d->get_image(s) : nullptr;
     job.dpb_id[s] = job.dpb_img[s] ? job.dpb_img[s]->get_ID() : 0xFFFFFFFFu;
+  }
+  job.dpb_ref = 0;
+  for (int s = 0; s < M355_MAX_REF_FRAMES; s++) {
+    job.dpb_poc[s] = job.dpb_img[s] ? job.dpb_img[s]->PicOrderCntVal : 0;
+    if (job.dpb_img[s] && job.dpb_img[s]->PicState != UnusedForReference) job.dpb_ref |= 1u << s;
   }
   {
     std::lock_guard<std::mutex> lk(g->mu);
@@ -1627,6 +1700,7 @@ LIBDE265_API de265_error de265_free_decoder(de265_decoder_context* c)
       fprintf(stderr, "libde265 (MI355X glue): at shutdown: %s\n", api()->m355_last_error());
       if (++g->n_rejected > 1000) break;
     }
+    for (Glue::SlotMaps& m : g->smaps) side_maps_free(g, m);
   }
   if (g && getenv("M355_GLUE_STATS"))
     fprintf(stderr, "m355 glue: %lld pictures submitted, %lld uploaded, %lld downloaded; host ms per picture: on the decoder's thread %.3f, on the worker: lists %.3f, submit %.3f; download %.3f ms each; cpu pixel calls %lld\n",
@@ -2187,6 +2261,153 @@ LIBDE265_API int m355_glue_stats_image(const struct de265_image* img, const int 
   if (rc == M355_OK) rc = x.A->m355_frame_stats_result(x.g->mctx, ticket, 1, out);
   if (rc != M355_OK) x.g->error = x.A->m355_last_error();
   return rc;
+}
+/* HOW the pictures were coded, as dense per-unit maps in device memory (m355_picture_maps_async, include/de265_mi355x.h): maps_mask bit m = map m
+ * (M355_MAP_CU .. M355_MAP_SLICE), units of 1 << log2_unit samples (2..6); mask 0 turns it off.  From the next picture on, the submit step enqueues
+ * the request right behind the picture's m355_submit_picture, into buffers the glue keeps per DPB slot; nothing is downloaded and no decode waits.
+ * M355_ERR_INVALID: no decoder of this glue, M355_GLUE_RANKS > 1 (a rank's lists hold its tiles only), a mask with bits beyond the seven maps, a
+ * log2_unit outside 2..6. */
+LIBDE265_API int m355_glue_set_side_maps(de265_decoder_context* c, unsigned maps_mask, int log2_unit)
+{
+  if (!api()) return M355_ERR_NO_DEVICE;
+  Glue* g = glue_of((decoder_context*)c);
+  if (!g || g->n_ranks > 1 || (maps_mask >> M355_N_MAPS) || (maps_mask && (log2_unit < 2 || log2_unit > 6))) return M355_ERR_INVALID;
+  wait_submitted(g, 0xFFFFFFFFu);
+  std::lock_guard<std::mutex> api_lock(g->api_mu);
+  g->maps_mask = maps_mask;
+  if (maps_mask) g->maps_log2 = log2_unit;
+  return M355_OK;
+}
+/* The maps of one picture: the device pointers and pitches (dst[m] NULL: map m was not asked for), the unit grid, the request's summary and the table
+ * that turns MAP_REF's slots into pictures — ref_poc[s] = the POC of the picture DPB slot s held when this picture was decoded, bit s of ref_valid =
+ * that picture was marked as a reference.  block = 0: M355_ERR_BUSY while the request runs.  The memory is the glue's; it holds this picture's maps
+ * until the image's DPB slot is decoded into again.  M355_ERR_INVALID: maps were off when the picture was submitted, or the image's slot holds another
+ * picture by now.  Nothing is downloaded. */
+typedef struct m355_glue_side_maps {
+  void*    dst[M355_N_MAPS];
+  int64_t  pitch[M355_N_MAPS];
+  int32_t  log2_unit, units_w, units_h;
+  uint32_t ref_valid;
+  int32_t  ref_poc[M355_MAX_REF_FRAMES];
+  m355_maps_info info;
+} m355_glue_side_maps;
+LIBDE265_API int m355_glue_image_side_maps(const struct de265_image* img, int block, m355_glue_side_maps* out)
+{
+  Api* A = api();
+  if (!A) return M355_ERR_NO_DEVICE;
+  if (!img || !img->decctx || !out) return M355_ERR_INVALID;
+  Glue* g = glue_of(img->decctx);
+  if (!g || g->n_ranks > 1) return M355_ERR_INVALID;
+  wait_submitted(g, img->get_ID());
+  std::lock_guard<std::mutex> api_lock(g->api_mu);
+  const int slot = slot_of(g->dctx, img);
+  if (slot < 0) return M355_ERR_INVALID;
+  Glue::SlotMaps& m = g->smaps[slot];
+  if (m.img_id != img->get_ID() || !(m.pending || m.have)) return M355_ERR_INVALID;
+  if (m.pending) {
+    const int rc = A->m355_picture_maps_result(g->mctx, m.ticket, block ? 1 : 0, &m.info);
+    if (rc == M355_ERR_BUSY) return rc;
+    m.pending = false; m.have = rc == M355_OK;
+    if (rc != M355_OK) { g->error = A->m355_last_error(); return rc; }
+  }
+  memset(out, 0, sizeof(*out));
+  for (int k = 0; k < M355_N_MAPS; k++) { out->dst[k] = m.dst[k]; out->pitch[k] = m.pitch[k]; }
+  out->log2_unit = m.log2_unit; out->units_w = m.units_w; out->units_h = m.units_h;
+  out->ref_valid = m.ref_valid;
+  for (int s = 0; s < M355_MAX_REF_FRAMES; s++) out->ref_poc[s] = m.ref_poc[s];
+  out->info = m.info;
+  return M355_OK;
+}
+/* THE INDEPENDENT STATEMENT of the same maps, in host memory, from the reference's own per-picture arrays alone (image.h: get_pred_mode, get_PartMode,
+ * get_log2CbSize, get_QPY, get_pcm_flag, get_cu_transquant_bypass, get_IntraPredMode, get_split_transform_flag / get_nonzero_coefficient, get_mv_info, the CTBs'
+ * slice header index) — never the recorder's lists or the submit step's walk.  Per unit, at its top-left luma position P:
+ *   the coding block: the largest size n = CTB .. min CB whose aligned origin holds log2CbSize == log2(n) (the arrays keep size and PartMode at the origin only)
+ *   the transform block: from that origin, depth 0, into the quadrant that holds P while split_transform_flag says so
+ *   MAP_INTRA: pred_mode MODE_INTRA and no pcm_flag -> IntraPredMode at P, else 255
+ *   MAP_MV / MAP_REF: pred_mode not MODE_INTRA -> the PBMotion at P; a list's slot = the valid slot of ref_poc[] whose POC is the slice header's
+ *   RefPicList_POC[l][refIdx] (0xFF: none).  Byte 2, the prediction block's flags: PRED_Lx as stored; MC_Lx after the demotion of motion.cc:348-357
+ *   (equal vectors and equal POCs, no weighted_pred_flag) and WEIGHTED from the PPS' flag for the slice type; the FILL bits, which say that a reference
+ *   picture was missing WHEN the block was predicted, are in no array: they read 0 here.
+ * ref_poc / ref_valid are those m355_glue_image_side_maps returns for the image (no table: every slot reads 0xFF).  Rows of units_w elements, pitch[m] bytes apart; dst[m] NULL or a bit
+ * not in maps_mask: not written.  M355_ERR_INVALID: null pointers, log2_unit outside 2..6, an image without parameter sets. */
+LIBDE265_API int m355_glue_image_side_maps_host(const struct de265_image* img, unsigned maps_mask, int log2_unit, void* const dst[M355_N_MAPS],
+                                                const int64_t pitch[M355_N_MAPS])
+{
+  if (!img || !img->decctx || !dst || !pitch || log2_unit < 2 || log2_unit > 6 || !img->has_sps() || !img->has_pps()) return M355_ERR_INVALID;
+  int32_t ref_poc[M355_MAX_REF_FRAMES] = {};
+  uint32_t ref_valid = 0;
+  if (Glue* g = glue_of(img->decctx)) {                          /* the slot -> POC table kept with the picture: the one m355_glue_image_side_maps returns */
+    wait_submitted(g, img->get_ID());
+    std::lock_guard<std::mutex> api_lock(g->api_mu);
+    const int slot = slot_of(g->dctx, img);
+    if (slot >= 0 && g->smaps[slot].img_id == img->get_ID()) { memcpy(ref_poc, g->smaps[slot].ref_poc, sizeof(ref_poc)); ref_valid = g->smaps[slot].ref_valid; }
+  }
+  de265_image* im = const_cast<de265_image*>(img);               /* (get_SliceHeader is not const) */
+  const seq_parameter_set& sps = img->get_sps();
+  const int W = sps.pic_width_in_luma_samples, H = sps.pic_height_in_luma_samples, U = 1 << log2_unit;
+  const int uw = (W + U - 1) >> log2_unit, uh = (H + U - 1) >> log2_unit;
+  auto want = [&](int m) { return ((maps_mask >> m) & 1u) && dst[m]; };
+  auto at = [&](int m, int ux, int uy, int bytes) { return (uint8_t*)dst[m] + (int64_t)uy * pitch[m] + (int64_t)ux * bytes; };
+  for (int uy = 0; uy < uh; uy++)
+    for (int ux = 0; ux < uw; ux++) {
+      const int x = ux << log2_unit, y = uy << log2_unit;
+      int x0 = 0, y0 = 0, l2 = 0;
+      for (int s = sps.Log2CtbSizeY; s >= sps.Log2MinCbSizeY && !l2; s--) {
+        const int xa = x & ~((1 << s) - 1), ya = y & ~((1 << s) - 1);
+        if (img->get_log2CbSize(xa, ya) == s) { x0 = xa; y0 = ya; l2 = s; }
+      }
+      const int pm = l2 ? (int)img->get_pred_mode(x, y) : -1;
+      if (want(M355_MAP_CU)) {
+        uint32_t v = 0xFFFFFFFFu;
+        if (l2) v = (uint32_t)pm | (uint32_t)img->get_PartMode(x0, y0) << 8 | (uint32_t)l2 << 16 |
+                    (uint32_t)((img->get_pcm_flag(x, y) ? M355_CUF_PCM : 0) | (img->get_cu_transquant_bypass(x, y) ? M355_CUF_TRANSQUANT_BYPASS : 0)) << 24;
+        memcpy(at(M355_MAP_CU, ux, uy, 4), &v, 4);
+      }
+      if (want(M355_MAP_QP)) *(int8_t*)at(M355_MAP_QP, ux, uy, 1) = l2 ? (int8_t)img->get_QPY(x, y) : (int8_t)-128;
+      if (want(M355_MAP_TU)) {
+        uint8_t v = 0;
+        if (l2) {
+          int xb = x0, yb = y0, lt = l2, depth = 0;
+          while (lt > 2 && img->get_split_transform_flag(xb, yb, depth)) {
+            lt--; depth++;
+            if (x >= xb + (1 << lt)) xb += 1 << lt;
+            if (y >= yb + (1 << lt)) yb += 1 << lt;
+          }
+          v = (uint8_t)(lt | (img->get_nonzero_coefficient(xb, yb) ? 0x80 : 0));
+        }
+        *at(M355_MAP_TU, ux, uy, 1) = v;
+      }
+      if (want(M355_MAP_INTRA)) *at(M355_MAP_INTRA, ux, uy, 1) = (pm == MODE_INTRA && !img->get_pcm_flag(x, y)) ? (uint8_t)img->get_IntraPredMode(x, y) : (uint8_t)255;
+      if (want(M355_MAP_MV) || want(M355_MAP_REF)) {
+        int16_t mv[4] = {0, 0, 0, 0};
+        uint8_t ref[4] = {0xFF, 0xFF, 0, 0};
+        const slice_segment_header* sh = (l2 && pm != MODE_INTRA) ? im->get_SliceHeader(x, y) : nullptr;
+        if (sh) {
+          const PBMotion& mi = img->get_mv_info(x, y);
+          const pic_parameter_set& pps = img->get_pps();
+          int poc[2] = {0, 0}, mc[2] = {mi.predFlag[0] ? 1 : 0, mi.predFlag[1] ? 1 : 0};
+          for (int l = 0; l < 2; l++) {
+            if (!mi.predFlag[l]) continue;
+            mv[2 * l] = mi.mv[l].x; mv[2 * l + 1] = mi.mv[l].y;
+            ref[2] |= (uint8_t)(M355_PBF_PRED_L0 << l);
+            poc[l] = sh->RefPicList_POC[l][mi.refIdx[l]];
+            for (int s = 0; s < M355_MAX_REF_FRAMES; s++)
+              if (((ref_valid >> s) & 1u) && ref_poc[s] == poc[l]) { ref[l] = (uint8_t)s; break; }
+          }
+          if (!pps.weighted_pred_flag && mc[0] && mc[1] && mi.mv[0].x == mi.mv[1].x && mi.mv[0].y == mi.mv[1].y && poc[0] == poc[1]) mc[1] = 0;
+          if (sh->slice_type == SLICE_TYPE_P) mc[1] = 0;
+          for (int l = 0; l < 2; l++) if (mc[l]) ref[2] |= (uint8_t)(M355_PBF_MC_L0 << l);
+          if (sh->slice_type == SLICE_TYPE_P ? pps.weighted_pred_flag : pps.weighted_bipred_flag) ref[2] |= M355_PBF_WEIGHTED;
+        }
+        if (want(M355_MAP_MV)) memcpy(at(M355_MAP_MV, ux, uy, 8), mv, 8);
+        if (want(M355_MAP_REF)) memcpy(at(M355_MAP_REF, ux, uy, 4), ref, 4);
+      }
+      if (want(M355_MAP_SLICE)) {
+        const uint16_t v = img->get_SliceHeaderIndex(x, y);
+        memcpy(at(M355_MAP_SLICE, ux, uy, 2), &v, 2);
+      }
+    }
+  return M355_OK;
 }
 /* The picture's CONTENT PEAK in nits from statistics taken with light == 1 — what m355_glue_colour_preset_for_image takes as peak_nits where the stream
  * carries no light-level metadata (libde265 parses none):

@@ -1092,6 +1092,69 @@ M355_API int m355_frame_stats_result(m355_ctx* ctx, unsigned long long ticket, i
 M355_API int m355_stats_quantile(const uint32_t hist[M355_STATS_BINS], uint32_t num, uint32_t den, int* bin);   /* host only */
 M355_API int m355_colour_linear(const m355_colour_tables* tables, uint32_t v16, uint32_t* L);                    /* host only */
 
+/* HOW a picture was coded, as dense maps in the caller's device memory: where the coding units are, which are intra, inter or skipped, the QP, the
+ * transform tree, the intra modes, the motion field with its reference slots, the slices — what the reference shows through its per-picture arrays
+ * (image.h get_pred_mode / get_QPY / get_mv_info ...) and a compressed-domain model, a quality-aware filter, a transcoder or a scene-cut detector
+ * wants without a round trip over the host.  The request reads the work LISTS of one picture (cus, tus, pbs, ibs, ctbs), not a frame; no decode is
+ * needed.  csrc/map_element.h is the one statement of the definition, for the kernels and for m355_maps_unit.  EVERYTHING IS AN INTEGER AND EXACT.
+ * UNIT GRID.  U = 1 << log2_unit (2..6); units_w = ceil(pp.width / U), units_h = ceil(pp.height / U) (the coded size).  Unit (ux, uy) takes its
+ * value at the luma position P = (ux * U, uy * U), which always lies inside the picture.  "The record covering P" is the record whose luma rectangle
+ * contains P: x .. x + size for a CU, a TU and a luma intra block, x .. x + w, y .. y + h for a prediction block.  Every map is computed from its own
+ * list only.  Elements are little-endian, a row is units_w elements, rows are pitch[m] bytes apart:
+ *   M355_MAP_CU     u32     pred_mode | part_mode << 8 | log2_size << 16 | flags << 24 of the CU          no covering record: 0xFFFFFFFF
+ *   M355_MAP_QP     i8      cu.qp_y                                                                        -128
+ *   M355_MAP_TU     u8      tu.log2_size | 0x80 if M355_TUF_NONZERO_COEFF                                  0
+ *   M355_MAP_INTRA  u8      ib.mode of the luma (cidx == 0) intra block without M355_IBF_PCM               255 (inter, PCM, uncovered)
+ *   M355_MAP_MV     i16[4]  mv[0][0], mv[0][1], mv[1][0], mv[1][1]; a list's pair is 0, 0 unless its M355_PBF_PRED_Lx is set     all 0
+ *   M355_MAP_REF    u8[4]   (u8)ref_slot[0] if M355_PBF_PRED_L0 else 0xFF; the same for L1; pb.flags; 0    FF FF 00 00
+ *   M355_MAP_SLICE  u16     ctbs[CTB of P].slice_idx                                                       (always defined)
+ * SKIPPED RECORDS.  The lists need not have been validated (lists recorded in place are checked on the device, by the decode).  A record that fails
+ * the geometry clause of its record check (csrc/record_checks.h) is skipped and counted in skipped[]: for a CU, a TU and an intra block (of any
+ * component) the whole `malformed` clause, for a prediction block m355_check_pb_geometry alone — reference slots do not matter here.  Positions need
+ * not be aligned: a record covers exactly the positions P its rectangle contains.  Where valid records of one list overlap, a unit gets the value of
+ * one of them, unspecified which.
+ * SUMMARY (m355_maps_info).  units_w, units_h; from MAP_CU the units by pred_mode — n_intra, n_inter, n_skip — and covered, their sum; from MAP_QP
+ * qp_sum, qp_min, qp_max over the covered units (none: 0, 127, -128); from MAP_REF n_bipred, the units whose prediction block has both PRED flags;
+ * skipped[4], the cu, tu, pb and ib records skipped, counted for the lists the request read.  A field whose map was not requested reads as its empty
+ * value.
+ * THE REQUEST.  `handle` is a resident picture (m355_picture_upload / _replace) or M355_PICTURE_LAST, the lists of this context's most recent
+ * m355_submit_picture.  dst[m] == NULL: map m is not wanted.  dst[m] is device memory or m355_host_alloc memory; pointer and pitch are multiples of
+ * the element size (4, 1, 1, 1, 8, 4, 2) and need no more alignment; the pitch is at least the row's bytes.  Bytes beyond a row and rows beyond
+ * units_h are never written.
+ * ORDERING.  The host waits for nothing at enqueue.  All map requests of a context run in order on one stream of their own, behind the upload of
+ * their lists; they delay no decode and none delays them (decodes only read the lists too).  m355_picture_replace, m355_picture_release, the reuse of
+ * a submit arena (three rotate) and m355_destroy wait for the requests that read the lists they overwrite.  *ticket counts 1, 2, ... per context (a
+ * count of its own); at most M355_MAPS_REQUESTS requests may be outstanding: one more returns M355_ERR_BUSY and enqueues nothing.
+ * M355_ERR_INVALID, nothing enqueued, no slot taken, no byte written: a bad handle, M355_PICTURE_LAST before any submit, a tile-sharded context;
+ * null desc or ticket, log2_unit outside 2..6, reserved != 0; all dst null, a pitch below the row, a misaligned pointer or pitch.
+ * m355_picture_maps_result collects a request and frees its slot: block = 0 -> M355_ERR_BUSY while it runs (the request stays), block = 1 -> the host
+ * waits for THAT request only; an unknown or collected ticket: M355_ERR_INVALID.  m355_picture_maps_order makes the consumer's stream wait for the
+ * request instead of the host (the request stays to be collected).  m355_wait completes every request and collects none.
+ * m355_maps_unit (host only, no context): element (ux, uy) of map `map` from HOST lists by a linear search — the same definition through the same
+ * header; `element` receives the element's bytes (4, 1, 1, 1, 8, 4, 2).  M355_ERR_INVALID: null pointers, map or log2_unit out of range, a unit
+ * outside the grid. */
+#define M355_N_MAPS        7
+#define M355_MAPS_REQUESTS 16
+#define M355_PICTURE_LAST  (-1)   /* the lists of this context's most recent m355_submit_picture */
+enum { M355_MAP_CU = 0, M355_MAP_QP = 1, M355_MAP_TU = 2, M355_MAP_INTRA = 3, M355_MAP_MV = 4, M355_MAP_REF = 5, M355_MAP_SLICE = 6 };
+typedef struct m355_maps_desc {
+  int32_t log2_unit, reserved;     /* 2..6; 0 */
+  void*   dst[M355_N_MAPS];        /* device memory, or m355_host_alloc memory; NULL: not wanted */
+  int64_t pitch[M355_N_MAPS];      /* bytes between rows */
+} m355_maps_desc;                  /* (LP64: 120 bytes) */
+typedef struct m355_maps_info {
+  int32_t  units_w, units_h;
+  uint32_t covered, n_intra, n_inter, n_skip;   /* MAP_CU: units by pred_mode, and their sum */
+  int64_t  qp_sum;                              /* MAP_QP, over covered units */
+  int32_t  qp_min, qp_max;                      /* none covered: 127, -128 */
+  uint32_t n_bipred;                            /* MAP_REF: units whose prediction block has both PRED flags */
+  uint32_t skipped[4];                          /* cu, tu, pb, ib records skipped (of the lists the request read) */
+} m355_maps_info;                              /* (64 bytes) */
+M355_API int m355_picture_maps_async(m355_ctx* ctx, int handle, const m355_maps_desc* desc, unsigned long long* ticket);
+M355_API int m355_picture_maps_result(m355_ctx* ctx, unsigned long long ticket, int block, m355_maps_info* out);
+M355_API int m355_picture_maps_order(m355_ctx* ctx, unsigned long long ticket, void* consumer_hipStream);
+M355_API int m355_maps_unit(const m355_picture* pic, int map, int log2_unit, int ux, int uy, void* element);   /* host only */
+
 /* Replaces (deferred): decode_TU (slice.cc:3460), decode_prediction_unit (motion.cc:2190) and
  * run_postprocessing_filters_sequential/_parallel (decctx.cc:1783/1811) for one picture. Asynchronous:
  * returns after the work is enqueued on the context's stream. */

@@ -219,6 +219,34 @@ class Stats(ctypes.Structure):
                 ("light_min", ctypes.c_uint32), ("light_max", ctypes.c_uint32), ("light_sum", ctypes.c_uint64)]
 
 
+N_MAPS, MAPS_REQUESTS, PICTURE_LAST = 7, 16, -1     # M355_N_MAPS, M355_MAPS_REQUESTS, M355_PICTURE_LAST
+MAP_CU, MAP_QP, MAP_TU, MAP_INTRA, MAP_MV, MAP_REF, MAP_SLICE = range(7)
+MAP_NAMES = ("cu", "qp", "tu", "intra", "mv", "ref", "slice")
+# per map: the element as numpy sees it, and how many of them make one unit (MV: four int16, REF: four bytes)
+MAP_DTYPES = (np.dtype("<u4"), np.dtype("i1"), np.dtype("u1"), np.dtype("u1"), np.dtype("<i2"), np.dtype("u1"), np.dtype("<u2"))
+MAP_PER_UNIT = (1, 1, 1, 1, 4, 4, 1)
+MAP_ELEM_BYTES = (4, 1, 1, 1, 8, 4, 2)
+
+
+class MapsDesc(ctypes.Structure):
+    """m355_maps_desc (include/de265_mi355x.h)"""
+    _fields_ = [("log2_unit", ctypes.c_int32), ("reserved", ctypes.c_int32), ("dst", ctypes.c_void_p * N_MAPS), ("pitch", ctypes.c_int64 * N_MAPS)]
+
+
+class MapsInfo(ctypes.Structure):
+    """m355_maps_info (include/de265_mi355x.h)"""
+    _fields_ = [("units_w", ctypes.c_int32), ("units_h", ctypes.c_int32), ("covered", ctypes.c_uint32), ("n_intra", ctypes.c_uint32),
+                ("n_inter", ctypes.c_uint32), ("n_skip", ctypes.c_uint32), ("qp_sum", ctypes.c_int64), ("qp_min", ctypes.c_int32),
+                ("qp_max", ctypes.c_int32), ("n_bipred", ctypes.c_uint32), ("skipped", ctypes.c_uint32 * 4)]
+
+
+def maps_info_dict(out):
+    """a MapsInfo structure as plain Python values (Context.picture_maps_result)"""
+    d = {n: int(getattr(out, n)) for n in ("units_w", "units_h", "covered", "n_intra", "n_inter", "n_skip", "qp_sum", "qp_min", "qp_max", "n_bipred")}
+    d["skipped"] = [int(v) for v in out.skipped]
+    return d
+
+
 class ArenaCaps(ctypes.Structure):
     """m355_arena_caps (include/de265_mi355x.h)"""
     _fields_ = [(n, ctypes.c_int32) for n in ("n_slices", "n_ctbs", "n_cus", "n_tus", "n_pbs", "n_wts", "n_ibs")] + \
@@ -337,6 +365,11 @@ class Library:
             L.m355_ssim_window.argtypes = [ctypes.POINTER(ctypes.c_uint64), i, ctypes.POINTER(ctypes.c_int32)]
             L.m355_ssim_weights.argtypes = [ctypes.POINTER(ctypes.c_int32)]
             L.m355_colour_linear.argtypes = [ctypes.POINTER(ColourTables), ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]
+        if hasattr(L, "m355_picture_maps_async"):
+            L.m355_picture_maps_async.argtypes = [vp, i, ctypes.POINTER(MapsDesc), ctypes.POINTER(ctypes.c_ulonglong)]
+            L.m355_picture_maps_result.argtypes = [vp, ctypes.c_ulonglong, i, ctypes.POINTER(MapsInfo)]
+            L.m355_picture_maps_order.argtypes = [vp, ctypes.c_ulonglong, vp]
+            L.m355_maps_unit.argtypes = [vp, i, i, i, i, vp]
         L.m355_submit_picture.argtypes = [vp, vp]
         L.m355_wait.argtypes = [vp]
         L.m355_last_serial.argtypes = [vp]
@@ -471,6 +504,16 @@ class Library:
         self.check(self.lib.m355_colour_linear(ctypes.byref(tables), int(v16), ctypes.byref(out)))
         return int(out.value)
 
+    def maps_unit(self, pic, map, log2_unit, ux, uy, c_pic=None):
+        """element (ux, uy) of one side map from HOST lists (m355_maps_unit, host only) -> u32 / i8 / u8 / u8 / four int16 / four u8 / u16 as Python
+        ints; c_pic: the (CPicture, keepalive) of pic.to_c(), for callers that ask for many units of one picture"""
+        c, keep = c_pic if c_pic is not None else pic.to_c()
+        buf = (ctypes.c_uint8 * 8)()
+        self.check(self.lib.m355_maps_unit(ctypes.addressof(c), map, log2_unit, ux, uy, buf))
+        v = np.frombuffer(bytes(buf)[:MAP_ELEM_BYTES[map]], MAP_DTYPES[map])
+        del keep
+        return int(v[0]) if MAP_PER_UNIT[map] == 1 else [int(x) for x in v]
+
     def pack_narrow(self, pic):
         """m355_pack_narrow on a picture's residual records and coefficient list (host only; worklist.pack_narrow is the numpy
         statement of the same): a copy with every block that fits in the 16-bit entry form (worklist.RBF_NARROW)"""
@@ -496,6 +539,8 @@ class Context:
         self._measure_reqs = {}         # ticket -> (planes, reference buffers to free, host?) of the comparison requests not collected yet
         self._stats_reqs = {}           # ticket -> (planes, light?) of the statistics requests not collected yet
         self._ssim_reqs = {}            # ticket -> (reference buffers to free, host?) of the SSIM requests not collected yet
+        self._maps_reqs = {}            # ticket -> (per map None or (buffer, offset, pitch, rows, row bytes), units, host?) of the side-map requests not collected yet
+        self._pic_size = {}             # picture handle (PICTURE_LAST: the most recent submit) -> (width, height), for the side maps' unit grid
 
     def close(self):
         if self.h:
@@ -1095,10 +1140,78 @@ class Context:
         self._measure_free(*self._ssim_reqs.pop(ticket))        # (collected: nothing reads the buffers any more)
         return [dict(sum_q=int(out.sum_q[c]), n=int(out.n[c]), min_q=int(out.min_q[c]), ssim=float(out.ssim[c])) for c in range(3)]
 
+    # ---- how the picture was coded (m355_picture_maps_async) ----
+    def picture_maps_async(self, handle, log2_unit, maps=tuple(range(N_MAPS)), host=False, pad=20, misalign=0):
+        """enqueue the side maps `maps` (MAP_* indices) of the lists of picture `handle` (a resident picture, or PICTURE_LAST) at units of
+        1 << log2_unit samples.  Every destination is a buffer of its own holding DEVICE_FILL, its pitch `pad` bytes (rounded up to whole elements) larger than the row, with one
+        guard row in front and one behind, and starts `misalign` ELEMENTS behind the buffer's (256-byte aligned) start.  Nothing is waited for ->
+        ticket for picture_maps_result, which frees the buffers"""
+        w, h = self._pic_size[handle]
+        uw, uh = (w + (1 << log2_unit) - 1) >> log2_unit, (h + (1 << log2_unit) - 1) >> log2_unit
+        desc = MapsDesc(log2_unit=log2_unit)
+        bufs = [None] * N_MAPS
+        try:
+            for m in maps:
+                es = MAP_ELEM_BYTES[m]
+                row = uw * es
+                pitch = row + -(-pad // es) * es                 # (a pitch is a multiple of the element: 20 bytes become 24 for MAP_MV)
+                ofs = pitch + misalign * es                      # one guard row, then the misalignment
+                nbytes = ofs + (uh + 1) * pitch
+                p = self._buffer(nbytes, host)
+                bufs[m] = (p, ofs, pitch, uh, row, nbytes)
+                desc.dst[m] = p + ofs; desc.pitch[m] = pitch
+            t = ctypes.c_ulonglong(0)
+            self.L.check(self.L.lib.m355_picture_maps_async(self.h, handle, ctypes.byref(desc), ctypes.byref(t)))
+        except Exception:
+            for b in bufs:
+                if b is not None:
+                    self._buffer_free(b[0], host)
+            raise
+        self._maps_reqs[t.value] = (bufs, (uw, uh), host)
+        return int(t.value)
+
+    def picture_maps_result(self, ticket, block=True):
+        """collect a request (m355_picture_maps_result) -> (maps, info, guards_intact): maps = {map index: numpy array (units_h, units_w), MV and
+        REF (units_h, units_w, 4)}, info = the m355_maps_info as a dict, guards_intact = every byte of the buffers outside the rows still holds
+        DEVICE_FILL; None while it has not finished (block=False); raises M355Error for an unknown / collected ticket"""
+        out = MapsInfo()
+        rc = self.L.lib.m355_picture_maps_result(self.h, ticket, 1 if block else 0, ctypes.byref(out))
+        if rc == 6 and not block:                               # M355_ERR_BUSY
+            return None
+        bufs, (uw, uh), host = self._maps_reqs.pop(ticket, ([], (0, 0), False))
+        if rc:
+            text = self.L.error()
+            for b in bufs:
+                if b is not None:
+                    self._buffer_free(b[0], host)
+            raise M355Error(rc, text)
+        maps, intact = {}, True
+        for m, b in enumerate(bufs):
+            if b is None:
+                continue
+            p, ofs, pitch, rows, row, nbytes = b
+            if host:
+                raw = np.ctypeslib.as_array(ctypes.cast(p, ctypes.POINTER(ctypes.c_uint8)), (nbytes,)).copy()
+            else:
+                raw = self.device_read(p, nbytes)
+            self._buffer_free(p, host)
+            body = raw[ofs:ofs + rows * pitch].reshape(rows, pitch)
+            a = np.ascontiguousarray(body[:, :row]).view(MAP_DTYPES[m])
+            maps[m] = a.reshape(uh, uw, 4) if MAP_PER_UNIT[m] == 4 else a.reshape(uh, uw)
+            inside = np.zeros(nbytes, bool)
+            inside[ofs:ofs + rows * pitch].reshape(rows, pitch)[:, :row] = True
+            intact = intact and bool((raw[~inside] == DEVICE_FILL).all())
+        return maps, maps_info_dict(out), intact
+
+    def picture_maps_order(self, ticket, stream):
+        """the consumer's stream (a hipStream_t as an integer) waits for the request (m355_picture_maps_order)"""
+        self.L.check(self.L.lib.m355_picture_maps_order(self.h, ticket, stream))
+
     # ---- pictures ----
     def submit(self, pic):
         c, keep = pic.to_c()
         self.L.check(self.L.lib.m355_submit_picture(self.h, ctypes.addressof(c)))
+        self._pic_size[PICTURE_LAST] = (int(pic.pp["width"][0]), int(pic.pp["height"][0]))
         del keep
 
     def submit_in_place(self, src_pic, slack=1.0, fill_threads=16, refill=True, state=None):
@@ -1136,6 +1249,7 @@ class Context:
         rc = self.L.lib.m355_submit_picture(self.h, state["a_dst"])
         if rc:
             self.L.check(rc)
+        self._pic_size[PICTURE_LAST] = (int(src_pic.pp["width"][0]), int(src_pic.pp["height"][0]))
         return state
 
     def wait(self):
@@ -1183,7 +1297,15 @@ class Context:
         del keep
         if r < 0:
             raise M355Error(-r, self.L.error())
+        self._pic_size[r] = (int(pic.pp["width"][0]), int(pic.pp["height"][0]))
         return r
+
+    def replace(self, handle, pic):
+        """other lists into the arenas of an uploaded picture (m355_picture_replace)"""
+        c, keep = pic.to_c()
+        self.L.check(self.L.lib.m355_picture_replace(self.h, handle, ctypes.addressof(c)))
+        self._pic_size[handle] = (int(pic.pp["width"][0]), int(pic.pp["height"][0]))
+        del keep
 
     def upload_in_place(self, src_pic, handle=-1, slack=1.0, fill_threads=4):
         """The in-place path of a RESIDENT picture (m355_picture_arena_begin -> the lists are written into the handle's pinned arena
@@ -1207,6 +1329,7 @@ class Context:
         dst.dst_frame = src.dst_frame
         ctypes.memmove(dst.ref_frames, src.ref_frames, 4 * worklist.MAX_REF_FRAMES)
         self.L.check(self.L.lib.m355_picture_replace(self.h, h, ctypes.addressof(dst)))
+        self._pic_size[h] = (int(src_pic.pp["width"][0]), int(src_pic.pp["height"][0]))
         del keep
         return h
 

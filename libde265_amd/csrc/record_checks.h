@@ -33,9 +33,14 @@ M355_RC_FN int m355_check_cu(const m355_cu& cu, const M355RecLimits& L)
   return (cu.log2_size < L.log2_min_cb_size || cu.log2_size > L.log2_ctb_size || cu.x >= L.width || cu.y >= L.height || cu.pred_mode > 2 || cu.part_mode > 7) ? M355_RC_MALFORMED : 0;
 }
 M355_RC_FN int m355_check_tu(const m355_tu& tu, const M355RecLimits& L) { return (tu.log2_size < 2 || tu.log2_size > 6 || tu.x >= L.width || tu.y >= L.height) ? M355_RC_MALFORMED : 0; }
+/* the geometry clause of a prediction block alone: all that a reader of the motion field needs (map_element.h), whatever the reference slots hold */
+M355_RC_FN int m355_check_pb_geometry(const m355_pb& pb, const M355RecLimits& L)
+{
+  return (pb.w < 4 || pb.h < 4 || pb.w > 64 || pb.h > 64 || (pb.w & 3) || (pb.h & 3) || pb.x + pb.w > L.width || pb.y + pb.h > L.height) ? M355_RC_GEOMETRY : 0;
+}
 M355_RC_FN int m355_check_pb(const m355_pb& pb, const M355RecLimits& L)
 {
-  if (pb.w < 4 || pb.h < 4 || pb.w > 64 || pb.h > 64 || (pb.w & 3) || (pb.h & 3) || pb.x + pb.w > L.width || pb.y + pb.h > L.height) return M355_RC_GEOMETRY;
+  if (m355_check_pb_geometry(pb, L)) return M355_RC_GEOMETRY;
   if (!(pb.flags & (M355_PBF_MC_L0 | M355_PBF_MC_L1))) return M355_RC_NO_LIST;
   for (int l = 0; l < 2; l++) {
     if (!(pb.flags & (M355_PBF_MC_L0 << l))) continue;

@@ -129,6 +129,7 @@ hipError_t sync_all(m355_ctx* c) {
   auto sync = [&](hipStream_t s) { if (s) { hipError_t e2 = hipStreamSynchronize(s); if (e == hipSuccess) e = e2; } };
   for (const Lane& l : c->lanes) { sync(l.stream); sync(l.stream_hi); }
   for (hipStream_t bs : c->batch_stream) sync(bs);
+  sync(c->maps_stream);                                     /* the side-map requests (runtime_maps.hip) */
   return e;
 }
 
@@ -262,7 +263,8 @@ int m355_create(int device, m355_ctx** out)
   if (rc == M355_OK) rc = measure_requests_create(c);
   if (rc == M355_OK) rc = stats_requests_create(c);
   if (rc == M355_OK) rc = ssim_requests_create(c);
-  if (rc) { ssim_requests_destroy(c); stats_requests_destroy(c); measure_requests_destroy(c); hash_requests_destroy(c); lane_destroy(c->lanes[0]); delete c; return rc; }
+  if (rc == M355_OK) rc = maps_requests_create(c);
+  if (rc) { maps_requests_destroy(c); ssim_requests_destroy(c); stats_requests_destroy(c); measure_requests_destroy(c); hash_requests_destroy(c); lane_destroy(c->lanes[0]); delete c; return rc; }
   *out = c;
   return M355_OK;
 }
@@ -305,6 +307,7 @@ void m355_destroy(m355_ctx* c)
   measure_requests_destroy(c);
   stats_requests_destroy(c);
   ssim_requests_destroy(c);
+  maps_requests_destroy(c);
   for (auto& e : c->inter_tabs) hipFree(e.second);
   for (auto& b : c->batch) { if (b.host) hipHostFree(b.host); if (b.dev) hipFree(b.dev); if (b.ev) hipEventDestroy(b.ev); }
   for (hipEvent_t e : c->batch_ev_pre) if (e) hipEventDestroy(e);
@@ -920,9 +923,10 @@ static int arena_into(m355_ctx* c, Resident& r, m355_arena_caps* k, int halo_uni
     r.cap = L.total + L.total / 4;
     HIPCHK(hipMalloc(&r.dev, r.cap));
     HIPCHK(hipHostMalloc(&r.host, r.cap, hipHostMallocDefault));
-  } else if (r.done.ticket) {
-    HIPCHK(ev_sync(c, r.done));                            /* the last decode of the lists that lived here */
-    r.done = EvRef();
+  } else {
+    if (r.done.ticket) { HIPCHK(ev_sync(c, r.done)); r.done = EvRef(); }   /* the last decode of the lists that lived here */
+    const int rcm = maps_lists_idle(c, r);                 /* ... and the side-map requests that read them */
+    if (rcm) return rcm;
   }
   memset(pic, 0, sizeof(*pic));
   pic->slices = (const m355_slice*)(r.host + L.seg[L.i_sl].ofs);
@@ -1030,6 +1034,7 @@ int m355_submit_picture(m355_ctx* c, const m355_picture* pic)
   const auto t0 = std::chrono::steady_clock::now();
   int rc = upload(c, t, pic);
   t.arena = false;                                          /* pointers handed out by m355_arena_begin are spent */
+  c->last_transient = rc ? -1 : (int)(&t - c->transient);   /* M355_PICTURE_LAST (runtime_maps.hip) */
   if (rc) return rc;
   const auto t1 = std::chrono::steady_clock::now();
   rc = decode(c, t, false);
@@ -1084,6 +1089,7 @@ int m355_picture_replace(m355_ctx* c, int h, const m355_picture* pic)
   Resident& r = c->resident[h];
   hipSetDevice(c->device);
   if (r.done.ticket) { HIPCHK(ev_sync(c, r.done)); r.done = EvRef(); }
+  { const int rcm = maps_lists_idle(c, r); if (rcm) return rcm; }   /* side-map requests read the old lists on a stream of their own */
   if (r.xb[0] && (memcmp(&r.hdr.pp, &pic->pp, sizeof(pic->pp)) != 0 || r.shard_n != c->shard_n || r.shard_rank != c->shard_rank)) {
     /* the exchange buffers of a sharded picture are sized by its geometry and tile structure */
     if (c->ipc) ipc_before_free(c, h);

@@ -7,6 +7,7 @@
  *   runtime_decode.hip prepare, the per-picture launch sequence, decode status, m355_decode_batch
  *   runtime_stats.hip  statistics requests (m355_frame_stats_async)
  *   runtime_ssim.hip   SSIM requests (m355_frame_ssim_async)
+ *   runtime_maps.hip   side maps of a picture's lists (m355_picture_maps_async)
  *   runtime_shard.hip  tile sharding: phases, exchanges, the in-process group, the built-in RCCL transport
  */
 #ifndef M355_RUNTIME_INTERNAL_H
@@ -35,6 +36,7 @@
 #include "k_measure.h"
 #include "k_stats.h"
 #include "k_ssim.h"
+#include "k_maps.h"
 
 
 extern thread_local std::string g_err;
@@ -178,7 +180,8 @@ struct Resident {
   unsigned long long xb_epoch = 0;   /* which allocation xb[] is (counted per process: the interprocess transport exports a new one again) */
   std::vector<int> peers;      /* ranks this rank exchanges halos with */
   EvRef up;                    /* lists copied to the device (decodes on another lane continue behind it) */
-  EvRef done;                  /* last decode of these lists: behind it the arenas may be overwritten */
+  EvRef done;                  /* last decode of these lists: behind it the arenas may be overwritten ... */
+  EvRef maps;                  /* ... and behind the last side-map request that reads them (m355_picture_maps_async, on a stream of its own): maps_lists_idle */
   bool fresh = false;          /* uploaded and not decoded since: nothing in flight reads its reference table */
   bool arena = false;          /* m355_arena_begin handed out list pointers into `host`: the next upload of lists that sit there copies nothing */
   m355_arena_caps caps;        /* ... with room for this many entries */
@@ -233,6 +236,7 @@ struct m355_ctx {
      profiles/r04_ai_submit_ring.txt). */
   Resident transient[M355_TRANSIENT_MAX];
   int next_transient = 0;
+  int last_transient = -1;     /* the arena that holds the lists of the most recent m355_submit_picture (M355_PICTURE_LAST); -1: none, or that submit's upload failed */
   int transient_ring() const { return 3; }
   uint32_t epoch = 0;
   /* per-decode status (m355_decode_status): the last M355_STATUS_RING decodes; a device-validated decode copies its lane's gate
@@ -301,6 +305,18 @@ struct m355_ctx {
   SsimSlot ssim_slot[M355_SSIM_REQUESTS];
   unsigned long long ssim_ticket = 0;
   unsigned long long *ssim_rec = nullptr, *ssim_res = nullptr;
+  /* m355_picture_maps_async (runtime_maps.hip): M355_MAPS_REQUESTS slots of their own — a device record the kernels leave zero and a pinned result record of
+     MAPS_REC_WORDS 32-bit words each (k_maps.h), the request's mark, the unit grid and the maps it wrote (bit m: map m).  The requests run in order on
+     maps_stream (made with the first request) and share maps_scratch, the planes on the picture's 4x4 grid, grown on demand. */
+  struct MapsSlot {
+    unsigned long long ticket = 0;
+    EvRef mark; int units_w = 0, units_h = 0; uint32_t want = 0;
+  };
+  MapsSlot maps_slot[M355_MAPS_REQUESTS];
+  unsigned long long maps_ticket = 0;
+  uint32_t *maps_rec = nullptr, *maps_res = nullptr;
+  hipStream_t maps_stream = nullptr;
+  uint8_t* maps_scratch = nullptr; size_t maps_scratch_cap = 0;
   /* pinned staging buffer of the blocking frame transfers (m355_frame_upload / _download / _fill, MD5 of m355_frame_hash): the copy itself is queued on the
      stream that last wrote the frame, between pinned memory and the frame (frame_stage_* in runtime.hip) */
   void* stage = nullptr; size_t stage_bytes = 0;
@@ -395,6 +411,9 @@ hipError_t sync_all(m355_ctx* c);
 int upload(m355_ctx* c, Resident& r, const m355_picture* pic);
 int ssim_requests_create(m355_ctx* c);             /* runtime_ssim.hip: the slots of m355_frame_ssim_async, made and dropped with the context */
 void ssim_requests_destroy(m355_ctx* c);
+int maps_requests_create(m355_ctx* c);             /* runtime_maps.hip: the slots of m355_picture_maps_async, made and dropped with the context */
+void maps_requests_destroy(m355_ctx* c);
+int maps_lists_idle(m355_ctx* c, Resident& r);     /* the host waits for the side-map requests that read the lists of `r` (Resident::maps) */
 }
 
 /* What the requests that compare a frame with another picture share (m355_frame_measure_async, m355_frame_ssim_async): the frame, the rectangle

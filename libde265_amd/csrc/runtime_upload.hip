@@ -750,10 +750,11 @@ int upload(m355_ctx* c, Resident& r, const m355_picture* pic) {
     r.cap = total + total / 4;
     HIPCHK(hipMalloc(&r.dev, r.cap));
     HIPCHK(hipHostMalloc(&r.host, r.cap, hipHostMallocDefault));
-  } else if (r.done.ticket) {
-    /* the arenas may still be in use by the last decode of these lists */
-    HIPCHK(ev_sync(c, r.done));
-    r.done = EvRef();
+  } else {
+    /* the arenas may still be in use by the last decode of these lists, or by a side-map request that reads them (runtime_maps.hip) */
+    if (r.done.ticket) { HIPCHK(ev_sync(c, r.done)); r.done = EvRef(); }
+    const int rcm = maps_lists_idle(c, r);
+    if (rcm) return rcm;
   }
   const auto t_wait = now();
   for (int i = 0; i < ns; i++)
