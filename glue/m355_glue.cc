@@ -91,7 +91,7 @@ namespace {
   X(m355_picture_arena_begin) X(m355_frame_hash_async) X(m355_frame_hash_result) X(m355_frame_measure_async) X(m355_frame_measure_result) \
   X(m355_frame_stats_async) X(m355_frame_stats_result) X(m355_stats_quantile) X(m355_colour_linear) X(m355_frame_ssim_async) X(m355_frame_ssim_result) \
   X(m355_colour_create_tone) X(m355_colour_preset_tone) X(m355_frame_export_pixels) X(m355_frame_export_resized_pixels) \
-  X(m355_picture_maps_async) X(m355_picture_maps_result) X(m355_device_alloc) X(m355_device_free)
+  X(m355_picture_maps_async) X(m355_picture_maps_result) X(m355_device_alloc) X(m355_device_free) X(m355_frame_msssim_async) X(m355_frame_msssim_result)
 
 struct Api {
   void* handle = nullptr;
@@ -2233,6 +2233,36 @@ LIBDE265_API int m355_glue_ssim_image(const struct de265_image* img, const int r
   unsigned long long ticket = 0;
   int rc = A->m355_frame_ssim_async(g->mctx, frame, &d, &ticket);
   if (rc == M355_OK) rc = A->m355_frame_ssim_result(g->mctx, ticket, 1, out);
+  if (rc != M355_OK) g->error = A->m355_last_error();
+  return rc;
+}
+/* The multi-scale SSIM of the picture against another one, on the device, as m355_frame_msssim_async defines it: per plane and level the sums of q and of
+ * the contrast-structure term and the number of windows, and with levels == 5 msssim by Wang's weights.  rect, ref, pitch and planes as in
+ * m355_glue_ssim_image; levels: 1..5, and every selected plane of the rectangle must keep 11 x 11 samples on the last level.  Enqueued behind the picture's
+ * decode and collected with block = 1: the call waits for THIS request only, and nothing is downloaded.  -> M355_OK with *out filled, or an M355_ERR_* code. */
+LIBDE265_API int m355_glue_msssim_image(const struct de265_image* img, const int rect[4], const void* const ref[3], const int64_t pitch[3], int planes,
+                                        int levels, m355_msssim* out)
+{
+  Api* A = api();
+  if (!A) return M355_ERR_NO_DEVICE;
+  if (!img || !img->decctx || !ref || !pitch || !out) return M355_ERR_INVALID;
+  Glue* g = glue_of(img->decctx);
+  if (!g || g->n_ranks > 1) return M355_ERR_INVALID;
+  wait_submitted(g, img->get_ID());
+  std::lock_guard<std::mutex> api_lock(g->api_mu);
+  int r[4];
+  const int frame = frame_and_rect(g, img, rect, r);
+  if (frame < 0) return M355_ERR_INVALID;
+  m355_msssim_desc d;
+  memset(&d, 0, sizeof(d));
+  d.ref_frame = -1;
+  d.x0 = r[0]; d.y0 = r[1]; d.width = r[2]; d.height = r[3];
+  d.planes = planes;
+  d.levels = levels;
+  for (int c = 0; c < 3; c++) { d.ref[c] = ref[c]; d.pitch[c] = pitch[c]; }
+  unsigned long long ticket = 0;
+  int rc = A->m355_frame_msssim_async(g->mctx, frame, &d, &ticket);
+  if (rc == M355_OK) rc = A->m355_frame_msssim_result(g->mctx, ticket, 1, out);
   if (rc != M355_OK) g->error = A->m355_last_error();
   return rc;
 }

@@ -1008,7 +1008,8 @@ M355_API int m355_frame_measure_result(m355_ctx* ctx, unsigned long long ticket,
  * nothing and written no map element.  m355_wait completes every request and collects none; a frame may be destroyed with requests pending.
  * HOST-ONLY HELPERS (exact, no context): m355_ssim_weights fills w[11]; m355_ssim_window computes q from sums = {MA, MB, SAA, SBB, SAB} for a bit
  * depth 1..16 (the point above).  M355_ERR_INVALID: null pointers, a bit depth outside 1..16.
- * Not offered: other window sizes or K1 / K2, border padding, automatic downscaling, MS-SSIM, a batch of frames in one launch, sharded contexts. */
+ * Not offered: other window sizes or K1 / K2, border padding, a batch of frames in one launch, sharded contexts.  (Downscaled levels and their
+ * combination: m355_frame_msssim_async below.) */
 #define M355_SSIM_REQUESTS 16
 typedef struct m355_ssim_desc {
   int32_t     ref_frame;              /* as m355_measure_desc */
@@ -1030,6 +1031,65 @@ M355_API int m355_frame_ssim_async(m355_ctx* ctx, int frame, const m355_ssim_des
 M355_API int m355_frame_ssim_result(m355_ctx* ctx, unsigned long long ticket, int block, m355_ssim* out);
 M355_API int m355_ssim_window(const uint64_t sums[5], int bit_depth, int32_t* q);   /* host only */
 M355_API int m355_ssim_weights(int32_t w[11]);                                      /* host only */
+
+/* MULTI-SCALE SSIM (Wang, Simoncelli, Bovik 2003) of a frame against another picture where both lie, per plane, on up to five levels, as a request
+ * queued behind the frame's decode like m355_frame_ssim_async.  The definition is integer-exact and this library's own; it is stated here once.
+ * PLANES, RECTANGLE, REFERENCE, a AND b are exactly those of m355_frame_ssim_async: each measured plane on its own grid, with the plane's own bit depth.
+ * LEVELS.  levels = L, 1 .. M355_MSSSIM_LEVELS.  Level j (j = 0 .. L - 1) of a plane of the rectangle with pw x ph samples has (pw >> j) x (ph >> j)
+ * samples.  Level 0 is the plane itself.  For j >= 1, with f = 1 << j and S(x, y) the sum of the f x f block of ORIGINAL samples whose first sample is
+ * (f x, f y) relative to the rectangle's first sample:  a_j(x, y) = (S + f f / 2) >> 2j  — one rounding from the exact sum, the NATIVE formula of
+ * m355_frame_export_scaled continued to j = 4, NOT a rounding of the level above.  Samples of the rectangle beyond f (pw >> j) columns or f (ph >> j)
+ * rows do not take part in level j.  The same for b.  A level is a picture of the plane's bit depth.
+ * PER LEVEL.  Valid windows only, ((pw >> j) - 10) x ((ph >> j) - 10) of them; weights and the five exact sums as at m355_frame_ssim_async; two points
+ * per window from the same sums and the same intermediates, every double operation rounded by itself in the written order (no fused multiply-add):
+ *   q   as at m355_frame_ssim_async (m355_ssim_window)
+ *   cs = (2.0 cov + c2) / ((va + vb) + c2),   qc = clamp((int64)floor(cs 2^30 + 0.5), -2^30, 2^30)              (Q30; m355_ssim_window_cs)
+ * RESULT per measured plane p and level j: sum_q[p][j], sum_cs[p][j] (exact, independent of order; either can be negative) and n[p][j], the number of
+ * windows.  Levels >= L, planes that are not selected and planes the frame does not have read 0 in every field.
+ * THE NUMBER is the host's, at collection, in IEEE double:  m_j = (double)sum_cs[p][j] / ((double)n[p][j] 2^30) for j < L - 1,
+ * m_{L-1} = (double)sum_q[p][L-1] / ((double)n[p][L-1] 2^30);  m355_msssim_combine(m, L, weight, &out) multiplies, in level order from 1.0,
+ * pow(max(m_j, 0.0), weight[j]).  weight == NULL stands for Wang's {0.0448, 0.2856, 0.3001, 0.2363, 0.1333} and is accepted for L == 5 only; they sum to
+ * 1.0001 and are used as published.  msssim[p] is that value for L == 5 and 0.0 for fewer levels, which the caller combines with weights of their own.
+ * Identical planes give exactly 1.0; a level whose mean is negative gives exactly 0.0.  The integers are the contract: msssim goes through the C library's
+ * pow and may differ from another C library's by a few units in the last place.
+ * ORDERING, VERDICTS AND COLLECTION are those of m355_frame_ssim_async: a READER of the frame and of ref_frame (a kind of its own), queued on the stream of
+ * the frame's last writer behind ref_frame's last writer; a later decode into either frame waits for it; the host waits for nothing at enqueue, with the
+ * one exception under SCRATCH.  *ticket counts 1, 2, ... per context (a count of its own); at most M355_MSSSIM_REQUESTS requests may be outstanding: one
+ * more returns M355_ERR_BUSY and enqueues nothing.  m355_frame_msssim_result collects a request and frees its slot: block = 0 -> M355_ERR_BUSY while it
+ * runs (the request stays), block = 1 -> the host waits for THAT request only.  M355_ERR_INVALID: an unknown or collected ticket; or — the request is
+ * collected all the same — a request queued behind a decode whose lists were rejected, for either frame: it has read nothing.  m355_wait completes every
+ * request and collects none; a frame may be destroyed with requests pending.
+ * M355_ERR_INVALID, nothing enqueued: everything m355_frame_ssim_async rejects for handles, pointers, the rectangle, ref_frame, ref[] / pitch[], planes,
+ * reserved and a tile-sharded context; levels outside 1 .. 5; a selected plane with (pw >> (levels - 1)) < 11 or (ph >> (levels - 1)) < 11.
+ * SCRATCH.  The levels 1 .. L - 1 of both sides pass through device memory of the request's slot, in the frame's element type: a third of the pair's
+ * bytes at most (66 MB for an 8K 10-bit 4:2:0 pair).  A slot's scratch is allocated when a request needs more than the slot holds, and kept: it grows
+ * only and is freed with the context.  Such a request pays an allocation at enqueue, and where it replaces a smaller one, a free, which waits for the
+ * device's queued work.  No sample of any level is produced or touched by the host; the originals are read from memory once per request.
+ * HOST-ONLY HELPERS (exact, no context): m355_ssim_window_cs computes qc from sums = {MA, MB, SAA, SBB, SAB} for a bit depth 1..16;
+ * m355_msssim_combine as above, from mean[0 .. levels - 1].  M355_ERR_INVALID: null pointers, a bit depth outside 1..16, levels outside 1..5, weight ==
+ * NULL with levels != 5, a mean that is NaN, a weight that is negative or not finite.
+ * Not offered: maps per level, other weights inside the call, more than five levels, border padding, a batch of frames, sharded contexts. */
+#define M355_MSSSIM_REQUESTS 4
+#define M355_MSSSIM_LEVELS   5
+typedef struct m355_msssim_desc {
+  int32_t     ref_frame;              /* as m355_ssim_desc */
+  int32_t     x0, y0, width, height;  /* as m355_ssim_desc */
+  const void* ref[3];                 /* as m355_ssim_desc */
+  int64_t     pitch[3];               /* as m355_ssim_desc */
+  int32_t     planes;                 /* as m355_ssim_desc */
+  int32_t     levels;                 /* 1..5 */
+  int32_t     reserved[6];            /* 0 */
+} m355_msssim_desc;
+typedef struct m355_msssim {
+  int64_t  sum_q[3][M355_MSSSIM_LEVELS];
+  int64_t  sum_cs[3][M355_MSSSIM_LEVELS];
+  uint64_t n[3][M355_MSSSIM_LEVELS];
+  double   msssim[3];
+} m355_msssim;
+M355_API int m355_frame_msssim_async(m355_ctx* ctx, int frame, const m355_msssim_desc* desc, unsigned long long* ticket);
+M355_API int m355_frame_msssim_result(m355_ctx* ctx, unsigned long long ticket, int block, m355_msssim* out);
+M355_API int m355_ssim_window_cs(const uint64_t sums[5], int bit_depth, int32_t* qc);                     /* host only */
+M355_API int m355_msssim_combine(const double mean[5], int levels, const double* weight, double* out);   /* host only */
 
 /* What is IN a frame, measured where it lies: histograms, the active area, the light level — what a tone mapper without metadata (a high percentile
  * of max(R, G, B)), a crop detector (the box of the content in letterboxed material) and a scene-cut / fade / black-frame detector (luma histograms and

@@ -203,6 +203,27 @@ class Ssim(ctypes.Structure):
     _fields_ = [("sum_q", ctypes.c_int64 * 3), ("n", ctypes.c_uint64 * 3), ("min_q", ctypes.c_int32 * 3), ("ssim", ctypes.c_double * 3)]
 
 
+MSSSIM_REQUESTS, MSSSIM_LEVELS = 4, 5       # M355_MSSSIM_*
+MSSSIM_WEIGHTS = [0.0448, 0.2856, 0.3001, 0.2363, 0.1333]   # Wang, Simoncelli, Bovik 2003: what m355_msssim_combine takes for weight == NULL
+
+
+class MsssimDesc(ctypes.Structure):
+    """m355_msssim_desc (include/de265_mi355x.h)"""
+    _fields_ = [("ref_frame", ctypes.c_int32), ("x0", ctypes.c_int32), ("y0", ctypes.c_int32), ("width", ctypes.c_int32), ("height", ctypes.c_int32),
+                ("ref", ctypes.c_void_p * 3), ("pitch", ctypes.c_int64 * 3), ("planes", ctypes.c_int32), ("levels", ctypes.c_int32), ("reserved", ctypes.c_int32 * 6)]
+
+
+class Msssim(ctypes.Structure):
+    """m355_msssim (include/de265_mi355x.h)"""
+    _fields_ = [("sum_q", ctypes.c_int64 * MSSSIM_LEVELS * 3), ("sum_cs", ctypes.c_int64 * MSSSIM_LEVELS * 3), ("n", ctypes.c_uint64 * MSSSIM_LEVELS * 3),
+                ("msssim", ctypes.c_double * 3)]
+
+
+def msssim_list(out):
+    """m355_msssim -> one dict per plane (always three): sum_q, sum_cs, n as lists over the five levels, msssim"""
+    return [dict(sum_q=[int(v) for v in out.sum_q[c]], sum_cs=[int(v) for v in out.sum_cs[c]], n=[int(v) for v in out.n[c]], msssim=float(out.msssim[c])) for c in range(3)]
+
+
 STATS_REQUESTS, STATS_BINS = 16, 256        # M355_STATS_*
 
 
@@ -364,6 +385,11 @@ class Library:
             L.m355_frame_ssim_result.argtypes = [vp, ctypes.c_ulonglong, i, ctypes.POINTER(Ssim)]
             L.m355_ssim_window.argtypes = [ctypes.POINTER(ctypes.c_uint64), i, ctypes.POINTER(ctypes.c_int32)]
             L.m355_ssim_weights.argtypes = [ctypes.POINTER(ctypes.c_int32)]
+        if hasattr(L, "m355_frame_msssim_async"):       # (absent from older builds loaded through M355_LIB for an A/B)
+            L.m355_frame_msssim_async.argtypes = [vp, i, ctypes.POINTER(MsssimDesc), ctypes.POINTER(ctypes.c_ulonglong)]
+            L.m355_frame_msssim_result.argtypes = [vp, ctypes.c_ulonglong, i, ctypes.POINTER(Msssim)]
+            L.m355_ssim_window_cs.argtypes = [ctypes.POINTER(ctypes.c_uint64), i, ctypes.POINTER(ctypes.c_int32)]
+            L.m355_msssim_combine.argtypes = [ctypes.POINTER(ctypes.c_double), i, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]
             L.m355_colour_linear.argtypes = [ctypes.POINTER(ColourTables), ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]
         if hasattr(L, "m355_picture_maps_async"):
             L.m355_picture_maps_async.argtypes = [vp, i, ctypes.POINTER(MapsDesc), ctypes.POINTER(ctypes.c_ulonglong)]
@@ -498,6 +524,21 @@ class Library:
         self.check(self.lib.m355_ssim_weights(w))
         return [int(x) for x in w]
 
+    def ssim_window_cs(self, sums, bit_depth):
+        """qc (Q30), the contrast-structure term of one window, from its five sums at a plane's bit depth (m355_ssim_window_cs; host only)"""
+        q = ctypes.c_int32(0)
+        v = None if sums is None else (ctypes.c_uint64 * 5)(*[int(x) for x in sums])
+        self.check(self.lib.m355_ssim_window_cs(v, bit_depth, ctypes.byref(q)))
+        return int(q.value)
+
+    def msssim_combine(self, means, weights=None):
+        """the product over the levels of max(mean, 0) ** weight, in level order (m355_msssim_combine; host only); weights None: Wang's five"""
+        m = (ctypes.c_double * MSSSIM_LEVELS)(*[float(x) for x in means])
+        w = None if weights is None else (ctypes.c_double * MSSSIM_LEVELS)(*[float(x) for x in weights])
+        out = ctypes.c_double(0.0)
+        self.check(self.lib.m355_msssim_combine(m, len(means), w, ctypes.byref(out)))
+        return float(out.value)
+
     def colour_linear(self, tables, v16):
         """step 1 of the colour transform stage for one 16-bit value (m355_colour_linear; host only) -> linear light, 0 .. COLOUR_ONE"""
         out = ctypes.c_uint32(0)
@@ -539,6 +580,7 @@ class Context:
         self._measure_reqs = {}         # ticket -> (planes, reference buffers to free, host?) of the comparison requests not collected yet
         self._stats_reqs = {}           # ticket -> (planes, light?) of the statistics requests not collected yet
         self._ssim_reqs = {}            # ticket -> (reference buffers to free, host?) of the SSIM requests not collected yet
+        self._msssim_reqs = {}          # ticket -> (reference buffers to free, host?) of the MS-SSIM requests not collected yet
         self._maps_reqs = {}            # ticket -> (per map None or (buffer, offset, pitch, rows, row bytes), units, host?) of the side-map requests not collected yet
         self._pic_size = {}             # picture handle (PICTURE_LAST: the most recent submit) -> (width, height), for the side maps' unit grid
 
@@ -1206,6 +1248,43 @@ class Context:
     def picture_maps_order(self, ticket, stream):
         """the consumer's stream (a hipStream_t as an integer) waits for the request (m355_picture_maps_order)"""
         self.L.check(self.L.lib.m355_picture_maps_order(self.h, ticket, stream))
+
+    # ---- MS-SSIM against another picture on the device (m355_frame_msssim_async) ----
+    def frame_msssim_async(self, f, ref_frame=None, ref_planes=None, rect=None, planes=0, levels=MSSSIM_LEVELS, host=False, pad=None):
+        """enqueue the multi-scale SSIM of frame f on `levels` levels (rect, planes, ref_frame / ref_planes, host, pad as frame_ssim_async).  Nothing is
+        waited for behind the enqueue -> ticket for frame_msssim_result, which frees the reference's buffers"""
+        desc = MsssimDesc(ref_frame=-1 if ref_frame is None else ref_frame, planes=planes, levels=levels)
+        if rect is not None:
+            desc.x0, desc.y0, desc.width, desc.height = rect
+        if ref_planes is not None and not (isinstance(ref_planes, tuple) and ref_planes[:1] == ("measure_reference",)):
+            ref_planes = self.measure_reference(ref_planes, host, pad)
+        _, bufs, pitches, host = ref_planes or (None, [], [], False)
+        for k, (p, pitch) in enumerate(zip(bufs, pitches)):
+            desc.ref[k] = p; desc.pitch[k] = pitch
+        t = ctypes.c_ulonglong(0)
+        rc = self.L.lib.m355_frame_msssim_async(self.h, f, ctypes.byref(desc), ctypes.byref(t))
+        if rc:
+            text = self.L.error()
+            self._measure_free(bufs, host)
+            raise M355Error(rc, text)
+        self._msssim_reqs[t.value] = (bufs, host)
+        return int(t.value)
+
+    def frame_msssim_result(self, ticket, block=True):
+        """collect a request (m355_frame_msssim_result) -> one dict per plane (always three): sum_q, sum_cs and n as lists over the five levels (0 at the
+        levels that were not asked for and for a plane that was not measured) and msssim; None while it has not finished (block=False); raises
+        M355Error for an unknown / collected ticket and behind a rejected decode"""
+        out = Msssim()
+        rc = self.L.lib.m355_frame_msssim_result(self.h, ticket, 1 if block else 0, ctypes.byref(out))
+        if rc == 6 and not block:                               # M355_ERR_BUSY
+            return None
+        if rc:
+            text = self.L.error()
+            if rc == 3:                                         # M355_ERR_INVALID: collected without a value (behind a rejected decode), or no such request
+                self._measure_free(*self._msssim_reqs.pop(ticket, ([], False)))
+            raise M355Error(rc, text)
+        self._measure_free(*self._msssim_reqs.pop(ticket))      # (collected: nothing reads the buffers any more)
+        return msssim_list(out)
 
     # ---- pictures ----
     def submit(self, pic):

@@ -264,7 +264,8 @@ int m355_create(int device, m355_ctx** out)
   if (rc == M355_OK) rc = stats_requests_create(c);
   if (rc == M355_OK) rc = ssim_requests_create(c);
   if (rc == M355_OK) rc = maps_requests_create(c);
-  if (rc) { maps_requests_destroy(c); ssim_requests_destroy(c); stats_requests_destroy(c); measure_requests_destroy(c); hash_requests_destroy(c); lane_destroy(c->lanes[0]); delete c; return rc; }
+  if (rc == M355_OK) rc = msssim_requests_create(c);
+  if (rc) { msssim_requests_destroy(c); maps_requests_destroy(c); ssim_requests_destroy(c); stats_requests_destroy(c); measure_requests_destroy(c); hash_requests_destroy(c); lane_destroy(c->lanes[0]); delete c; return rc; }
   *out = c;
   return M355_OK;
 }
@@ -308,6 +309,7 @@ void m355_destroy(m355_ctx* c)
   stats_requests_destroy(c);
   ssim_requests_destroy(c);
   maps_requests_destroy(c);
+  msssim_requests_destroy(c);
   for (auto& e : c->inter_tabs) hipFree(e.second);
   for (auto& b : c->batch) { if (b.host) hipHostFree(b.host); if (b.dev) hipFree(b.dev); if (b.ev) hipEventDestroy(b.ev); }
   for (hipEvent_t e : c->batch_ev_pre) if (e) hipEventDestroy(e);

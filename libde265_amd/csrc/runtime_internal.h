@@ -7,6 +7,7 @@
  *   runtime_decode.hip prepare, the per-picture launch sequence, decode status, m355_decode_batch
  *   runtime_stats.hip  statistics requests (m355_frame_stats_async)
  *   runtime_ssim.hip   SSIM requests (m355_frame_ssim_async)
+ *   runtime_msssim.hip MS-SSIM requests (m355_frame_msssim_async)
  *   runtime_maps.hip   side maps of a picture's lists (m355_picture_maps_async)
  *   runtime_shard.hip  tile sharding: phases, exchanges, the in-process group, the built-in RCCL transport
  */
@@ -36,6 +37,7 @@
 #include "k_measure.h"
 #include "k_stats.h"
 #include "k_ssim.h"
+#include "k_msssim.h"
 #include "k_maps.h"
 
 
@@ -90,7 +92,7 @@ constexpr bool intra_light_32x32 = false;
 struct EvRef { unsigned long long ticket = 0; hipStream_t stream = nullptr; };
 #define M355_EV_RING 256
 
-enum ReaderKind { RD_DOWNLOAD, RD_EXPORT, RD_HASH, RD_MEASURE, RD_STATS, RD_SSIM, RD_KINDS };
+enum ReaderKind { RD_DOWNLOAD, RD_EXPORT, RD_HASH, RD_MEASURE, RD_STATS, RD_SSIM, RD_MSSSIM, RD_KINDS };
 struct Frame {
   bool used = false;
   int w = 0, h = 0, cf = 0, bdl = 0, bdc = 0;
@@ -103,10 +105,10 @@ struct Frame {
      rejected does nothing, like that decode's own kernels (M355_GATE) */
   const uint32_t* wr_gate = nullptr; uint32_t wr_epoch = 0;
   /* READERS queued behind the decode that wrote the frame — a download (m355_frame_download_async), an export (m355_frame_export), a hash request
-     (m355_frame_hash_async), a comparison (m355_frame_measure_async, which reads two frames and marks both), a statistics request (m355_frame_stats_async), an SSIM request (m355_frame_ssim_async, two frames like the comparison): per kind the mark behind the LAST one.  reader_begin picks the stream (the writer's, so stream order stands for the wait for the
+     (m355_frame_hash_async), a comparison (m355_frame_measure_async, which reads two frames and marks both), a statistics request (m355_frame_stats_async), an SSIM request (m355_frame_ssim_async, two frames like the comparison), an MS-SSIM request (m355_frame_msssim_async, likewise): per kind the mark behind the LAST one.  reader_begin picks the stream (the writer's, so stream order stands for the wait for the
      picture) and lets it continue behind the kind's earlier mark, so that the one mark kept stands for both; reader_end marks; the next decode into the frame
      waits for every kind in front of its first write (readers_wait, from dst_hazards).  The kinds are separate because the HOST waits per kind
-     (m355_frame_download_wait, m355_frame_export_wait, m355_frame_hash_result, m355_frame_measure_result, m355_frame_stats_result, m355_frame_ssim_result), and a finished wait clears its mark: readers of different kinds need no order. */
+     (m355_frame_download_wait, m355_frame_export_wait, m355_frame_hash_result, m355_frame_measure_result, m355_frame_stats_result, m355_frame_ssim_result, m355_frame_msssim_result), and a finished wait clears its mark: readers of different kinds need no order. */
   EvRef reader[RD_KINDS];
 };
 
@@ -305,6 +307,20 @@ struct m355_ctx {
   SsimSlot ssim_slot[M355_SSIM_REQUESTS];
   unsigned long long ssim_ticket = 0;
   unsigned long long *ssim_rec = nullptr, *ssim_res = nullptr;
+  /* m355_frame_msssim_async (runtime_msssim.hip): M355_MSSSIM_REQUESTS slots of their own, as the SSIM slots — records of MSSSIM_REC_WORDS 64-bit words
+     (k_msssim.h), the mark, the frames, the level count and per plane and level the number of windows (0: not measured) — and per slot the SCRATCH that
+     holds levels 1 .. L - 1 of both sides between the request's two launches: allocated when a request needs more than the slot has, kept, freed with the context */
+  struct MsssimSlot {
+    unsigned long long ticket = 0;
+    uint64_t n[3][M355_MSSSIM_LEVELS] = {};
+    int levels = 0;
+    EvRef mark; int frame[2] = {-1, -1};
+  };
+  MsssimSlot msssim_slot[M355_MSSSIM_REQUESTS];
+  uint8_t* msssim_scratch[M355_MSSSIM_REQUESTS] = {};
+  size_t msssim_scratch_cap[M355_MSSSIM_REQUESTS] = {};
+  unsigned long long msssim_ticket = 0;
+  unsigned long long *msssim_rec = nullptr, *msssim_res = nullptr;
   /* m355_picture_maps_async (runtime_maps.hip): M355_MAPS_REQUESTS slots of their own — a device record the kernels leave zero and a pinned result record of
      MAPS_REC_WORDS 32-bit words each (k_maps.h), the request's mark, the unit grid and the maps it wrote (bit m: map m).  The requests run in order on
      maps_stream (made with the first request) and share maps_scratch, the planes on the picture's 4x4 grid, grown on demand. */
@@ -411,12 +427,14 @@ hipError_t sync_all(m355_ctx* c);
 int upload(m355_ctx* c, Resident& r, const m355_picture* pic);
 int ssim_requests_create(m355_ctx* c);             /* runtime_ssim.hip: the slots of m355_frame_ssim_async, made and dropped with the context */
 void ssim_requests_destroy(m355_ctx* c);
+int msssim_requests_create(m355_ctx* c);           /* runtime_msssim.hip: the slots of m355_frame_msssim_async and their scratch, made and dropped with the context */
+void msssim_requests_destroy(m355_ctx* c);
 int maps_requests_create(m355_ctx* c);             /* runtime_maps.hip: the slots of m355_picture_maps_async, made and dropped with the context */
 void maps_requests_destroy(m355_ctx* c);
 int maps_lists_idle(m355_ctx* c, Resident& r);     /* the host waits for the side-map requests that read the lists of `r` (Resident::maps) */
 }
 
-/* What the requests that compare a frame with another picture share (m355_frame_measure_async, m355_frame_ssim_async): the frame, the rectangle
+/* What the requests that compare a frame with another picture share (m355_frame_measure_async, m355_frame_ssim_async, m355_frame_msssim_async): the frame, the rectangle
    (width == 0: the whole frame) and the other picture — ref_frame >= 0, or ref[] / pitch[] — checked, and per plane of the frame both sides'
    first sample of the rectangle.  `who` opens the error texts.  -> M355_OK, or M355_ERR_INVALID with nothing touched. */
 struct PairPlane {

@@ -8,6 +8,8 @@
  * SUMS.  Over the window's samples a (the frame) and b (the reference), unsigned 64-bit and exact:
  *   MA = sum w a    MB = sum w b    SAA = sum w a^2    SBB = sum w b^2    SAB = sum w a b        (SAA <= 2^28 * 65535^2 < 2^60)
  * POINT.  In IEEE double, every operation rounded by itself in exactly the order written in m355_ssim_point.
+ * m355_ssim_point_cs is the contrast-structure factor of the same point alone, for the levels of m355_frame_msssim_async (k_msssim.hip,
+ * runtime_msssim.hip: m355_ssim_window_cs).
  *
  * CONTRACTION IS OFF: a fused multiply-add rounds once where this definition rounds twice.  The pragma below switches it off for the rest of
  * every translation unit that includes this header under clang (hipcc: host and device side); the SIMT-interpreter build (g++, which does not
@@ -56,6 +58,22 @@ M355_SSIM_HD int32_t m355_ssim_point(uint64_t MA, uint64_t MB, uint64_t SAA, uin
   double r = floor(s * 1073741824.0 + 0.5);
   if (r < -1073741824.0) r = -1073741824.0;
   if (r > 1073741824.0) r = 1073741824.0;
+  return (int32_t)(int64_t)r;
+}
+
+/* the five sums of one window -> qc = the window's contrast-structure term in Q30, -2^30 .. 2^30: the second factor of s above, from the same
+   intermediates by the same expressions (m355_frame_msssim_async: every level of MS-SSIM but the last takes this term alone) */
+M355_SSIM_HD int32_t m355_ssim_point_cs(uint64_t MA, uint64_t MB, uint64_t SAA, uint64_t SBB, uint64_t SAB, double c1, double c2)
+{
+  const double k28 = 268435456.0;
+  const double fa = (double)MA, fb = (double)MB;
+  const double ab = fa * fb, aa = fa * fa, bb = fb * fb;
+  const double cov = k28 * (double)SAB - ab, va = k28 * (double)SAA - aa, vb = k28 * (double)SBB - bb;
+  const double cs = (2.0 * cov + c2) / ((va + vb) + c2);
+  double r = floor(cs * 1073741824.0 + 0.5);
+  if (r < -1073741824.0) r = -1073741824.0;
+  if (r > 1073741824.0) r = 1073741824.0;
+  (void)c1;
   return (int32_t)(int64_t)r;
 }
 
