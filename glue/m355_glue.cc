@@ -91,6 +91,7 @@ namespace {
   X(m355_picture_arena_begin) X(m355_frame_hash_async) X(m355_frame_hash_result) X(m355_frame_measure_async) X(m355_frame_measure_result) \
   X(m355_frame_stats_async) X(m355_frame_stats_result) X(m355_stats_quantile) X(m355_colour_linear) X(m355_frame_ssim_async) X(m355_frame_ssim_result) \
   X(m355_colour_create_tone) X(m355_colour_preset_tone) X(m355_frame_export_pixels) X(m355_frame_export_resized_pixels) \
+  X(m355_frame_export_oriented) X(m355_frame_export_pixels_oriented) \
   X(m355_picture_maps_async) X(m355_picture_maps_result) X(m355_device_alloc) X(m355_device_free) X(m355_frame_msssim_async) X(m355_frame_msssim_result)
 
 struct Api {
@@ -2085,6 +2086,42 @@ LIBDE265_API int m355_glue_export_image_pixels(const struct de265_image* img, in
   if (!out_size) return x.finish(x.A->m355_frame_export_pixels(x.g->mctx, frame, &d, &x.o), frame, consumer_stream);
   d.out_width = out_size[0]; d.out_height = out_size[1];
   return x.finish(x.A->m355_frame_export_resized_pixels(x.g->mctx, frame, &d, &x.o), frame, consumer_stream);
+}
+/* m355_glue_export_image and m355_glue_export_image_pixels (without a resize) with the picture turned in the same launch (m355_frame_export_oriented /
+ * m355_frame_export_pixels_oriented: orientation = M355_ORIENT_*, 0..7; with M355_ORIENT_TRANSPOSE the destination rows are the rectangle's columns).  The
+ * orientation is the CALLER's — from the container's rotation, a HEIF irot / imir or an EXIF tag, through m355_orientation_from_exif and
+ * m355_orientation_compose —: the decoder underneath names the display orientation SEI (payload 47) and does not parse it, so no image carries one.  A NULL
+ * rectangle is the conformance window; everything else, the waiting included, is as in the two calls. */
+LIBDE265_API int m355_glue_export_image_oriented(const struct de265_image* img, int layout, int samples, const int rect[4], int orientation, void* const dst[3],
+                                                 const int64_t pitch[3], void* consumer_stream)
+{
+  ExportCall x;
+  const int rc = x.begin(&img, 1, dst && pitch);
+  if (rc != M355_OK) return rc;
+  int r[4];
+  const int frame = frame_and_rect(x.g, img, rect, r);
+  if (frame < 0) return M355_ERR_INVALID;
+  m355_export_desc d;
+  memset(&d, 0, sizeof(d));
+  d.layout = layout; d.samples = samples;
+  rect_and_planes(d, r, dst, pitch);
+  return x.finish(x.A->m355_frame_export_oriented(x.g->mctx, frame, &d, orientation), frame, consumer_stream);
+}
+LIBDE265_API int m355_glue_export_image_pixels_oriented(const struct de265_image* img, int format, int alpha, int matrix, int full_range, const int rect[4],
+                                                        int orientation, void* dst, int64_t pitch, int chroma_loc, void* consumer_stream)
+{
+  ExportCall x;
+  const int rc = x.begin(&img, 1, dst != nullptr, &matrix, &full_range, M355_FILTER_TRIANGLE, chroma_loc, 0);
+  if (rc != M355_OK) return rc;
+  int r[4];
+  const int frame = frame_and_rect(x.g, img, rect, r);
+  if (frame < 0) return M355_ERR_INVALID;
+  m355_pixel_desc d;
+  memset(&d, 0, sizeof(d));
+  d.format = format; d.alpha = alpha; d.matrix = matrix; d.full_range = full_range;
+  d.x0 = r[0]; d.y0 = r[1]; d.width = r[2]; d.height = r[3];
+  d.dst = dst; d.pitch = pitch;
+  return x.finish(x.A->m355_frame_export_pixels_oriented(x.g->mctx, frame, &d, &x.o, orientation), frame, consumer_stream);
 }
 /* A BATCH of pictures of ONE decoder, each resized, converted to R'G'B', normalised and delivered as one float tensor in one launch
  * (m355_frames_export_tensor: layout / dtype = M355_TENSOR_*, samples = M355_RGB_* of the integer stage; scale / bias per channel; dst and the strides in

@@ -873,6 +873,50 @@ typedef struct m355_pixel_desc {
 M355_API int   m355_frame_export_pixels(m355_ctx* ctx, int frame, const m355_pixel_desc* desc, const m355_export_opts* opts);           /* asynchronous */
 M355_API int   m355_frame_export_resized_pixels(m355_ctx* ctx, int frame, const m355_pixel_desc* desc, const m355_export_opts* opts);   /* asynchronous */
 M355_API int   m355_pixel_pack(int format, const uint32_t rgb[3], uint32_t alpha, uint8_t out[4], int* n_bytes);   /* host only */
+/* ORIENTATION — m355_frame_export and m355_frame_export_pixels with the picture turned in the same launch: a phone's portrait video (landscape samples
+ * plus a 90 degree flag in the container), the irot / imir of a HEIF still, HEVC's display orientation SEI.  The source is read once and the
+ * destination written once (k_export_oriented.hip); csrc/orientation.h is the one definition, compiled into the kernels too.
+ * An orientation o is 0..7, three bits: TRANSPOSE is applied FIRST, then FLIP, then MIRROR.  A source rectangle S of w columns and h rows of ELEMENTS
+ * becomes D of W' x H' = h x w with TRANSPOSE, else w x h, and for every (X, Y)
+ *   u = MIRROR ? W' - 1 - X : X      v = FLIP ? H' - 1 - Y : Y      D[Y][X] = TRANSPOSE ? S[u][v] : S[v][u]        (S[row][column])
+ * — numpy: T = S.T if o & 4 else S; T = T[::-1] if o & 2 else T; T = T[:, ::-1] if o & 1 else T.  0 identity, 1 mirror, 2 flip, 3 rotation by 180
+ * degrees, 4 transpose, 5 rotation by 90 degrees clockwise (np.rot90(S, -1)), 6 by 90 degrees anticlockwise (np.rot90(S, 1)), 7 anti-transpose.
+ *   m355_orientation_compose    *out = the one orientation equal to `first` and then `then` (an irot followed by an imir, a container matrix on top of
+ *                               an SEI); M355_ERR_INVALID for a value outside 0..7 or a null result
+ *   m355_orientation_from_exif  *out = the orientation that brings a picture stored with EXIF / TIFF Orientation 1..8 upright: 1 -> 0, 2 -> 1, 3 -> 3,
+ *                               4 -> 2, 5 -> 4, 6 -> 5, 7 -> 7, 8 -> 6; anything else is M355_ERR_INVALID
+ * m355_frame_export_oriented is m355_frame_export with every plane of the rectangle oriented ON ITS OWN GRID.  desc keeps its meaning: the layout, the
+ * samples with the formulas above, the crop, the caller's pitches.  An element is one converted sample; for the interleaved chroma plane of the
+ * semi-planar layout it is the (Cb, Cr) pair, which moves as a unit.  With TRANSPOSE plane p of pw x ph elements becomes ph x pw, and its pitch is
+ * checked against the ORIENTED row's bytes; bytes beyond an oriented row are never written.  Orientation 0 IS m355_frame_export: the call dispatches
+ * to it.  Like m355_frame_export this call moves samples and knows no siting: the chroma samples keep their values, so what a 4:2:0 siting becomes is
+ * the consumer's to note.  An axis with chroma MIDWAY between two luma samples (horizontally types 1, 3, 5; vertically
+ * types 0, 1) stays midway when it is reversed.  Reversing an axis on which chroma is CO-SITED with the even luma samples puts it on the ODD ones:
+ * vertically that exchanges the top-sited types 2, 3 with the bottom-sited 4, 5; horizontally (types 0, 2, 4 under MIRROR) it LEAVES the types 0..5,
+ * none of which has chroma on odd luma columns.  TRANSPOSE exchanges the two axes' sitings (type 0 becomes 3, 3 becomes 0, 1 and 2 stay; 4 and 5 leave
+ * the types).  A consumer that needs R'G'B' takes m355_frame_export_pixels_oriented, which reconstructs chroma BEFORE the picture is turned.
+ * M355_ERR_INVALID (nothing is enqueued, no destination byte written): whatever m355_frame_export rejects; an orientation outside 0..7; TRANSPOSE on a
+ * 4:2:2 frame (the result would be 4:4:0, which no layout here describes).
+ * m355_frame_export_pixels_oriented is a COMPOSITION: the pixels m355_frame_export_pixels delivers for the same arguments, permuted as whole pixels by
+ * the definition above — chroma reconstruction, chroma_loc and the matrix happen in the SOURCE's orientation.  The four-byte formats RGBA8, BGRA8 and
+ * both 2:10:10:10; with TRANSPOSE the pitch is checked against height * 4.  Orientation 0 dispatches to m355_frame_export_pixels.  M355_ERR_INVALID:
+ * whatever that call rejects, an orientation outside 0..7, M355_PIXEL_BGR8 with an orientation other than 0.
+ * Ordering, the gate behind a rejected decode, reader marks, m355_frame_export_wait and m355_frame_export_order, and sharded contexts are exactly those
+ * of m355_frame_export.
+ * Not offered: orientation in the resized, colour / tone and tensor exports (the composed kernel of k_export_resized_rgb.hip, which stores rows as it
+ * filters them); M355_PIXEL_BGR8 (a three-byte element in the transposing tile, whose elements are 1, 2 or 4 bytes); planar R'G'B'
+ * (m355_frame_export_rgb); arbitrary angles (a resampling, not a permutation). */
+#define M355_ORIENT_MIRROR        1   /* columns reversed */
+#define M355_ORIENT_FLIP          2   /* rows reversed */
+#define M355_ORIENT_TRANSPOSE     4   /* rows and columns exchanged (applied FIRST) */
+#define M355_ORIENT_ROTATE_0      0
+#define M355_ORIENT_ROTATE_180    3   /* MIRROR | FLIP */
+#define M355_ORIENT_ROTATE_90_CW  5   /* TRANSPOSE | MIRROR */
+#define M355_ORIENT_ROTATE_90_CCW 6   /* TRANSPOSE | FLIP */
+M355_API int   m355_orientation_compose(int first, int then, int* out);                /* host only */
+M355_API int   m355_orientation_from_exif(int exif_1_to_8, int* out);                  /* host only */
+M355_API int   m355_frame_export_oriented(m355_ctx* ctx, int frame, const m355_export_desc* desc, int orientation);   /* asynchronous */
+M355_API int   m355_frame_export_pixels_oriented(m355_ctx* ctx, int frame, const m355_pixel_desc* desc, const m355_export_opts* opts, int orientation);   /* asynchronous */
 M355_API int   m355_frame_export_wait(m355_ctx* ctx, int frame);
 M355_API int   m355_frame_export_order(m355_ctx* ctx, int frame, void* consumer_hipStream);
 /* Device memory for export destinations and blocking copies out of / into it, for applications (and the tests) that keep a second HIP

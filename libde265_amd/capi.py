@@ -89,6 +89,12 @@ def pixel_bytes(format):
     return 3 if format == PIXEL_BGR8 else 4
 
 
+# M355_ORIENT_*: three bits (TRANSPOSE first, then FLIP, then MIRROR) and the four rotations
+ORIENT_MIRROR, ORIENT_FLIP, ORIENT_TRANSPOSE = 1, 2, 4
+ORIENT_ROTATE_0, ORIENT_ROTATE_180, ORIENT_ROTATE_90_CW, ORIENT_ROTATE_90_CCW = 0, 3, 5, 6
+ORIENTATIONS = tuple(range(8))
+
+
 class PixelDesc(ctypes.Structure):
     """m355_pixel_desc (include/de265_mi355x.h)"""
     _fields_ = [("format", ctypes.c_int32), ("alpha", ctypes.c_int32), ("matrix", ctypes.c_int32), ("full_range", ctypes.c_int32),
@@ -361,6 +367,11 @@ class Library:
             L.m355_frame_export_pixels.argtypes = [vp, i, ctypes.POINTER(PixelDesc), ctypes.POINTER(ExportOpts)]
             L.m355_frame_export_resized_pixels.argtypes = [vp, i, ctypes.POINTER(PixelDesc), ctypes.POINTER(ExportOpts)]
             L.m355_pixel_pack.argtypes = [i, ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(i)]
+        if hasattr(L, "m355_frame_export_oriented"):    # (absent from older builds loaded through M355_LIB for an A/B)
+            L.m355_frame_export_oriented.argtypes = [vp, i, ctypes.POINTER(ExportDesc), i]
+            L.m355_frame_export_pixels_oriented.argtypes = [vp, i, ctypes.POINTER(PixelDesc), ctypes.POINTER(ExportOpts), i]
+            L.m355_orientation_compose.argtypes = [i, i, ctypes.POINTER(i)]
+            L.m355_orientation_from_exif.argtypes = [i, ctypes.POINTER(i)]
         if hasattr(L, "m355_colour_create_tone"):
             L.m355_colour_create_tone.argtypes = [vp, ctypes.POINTER(ColourTables), ctypes.POINTER(ColourTone), ctypes.POINTER(i)]
             L.m355_colour_preset_tone.argtypes = [ctypes.POINTER(ColourPresetDesc), i, ctypes.POINTER(ColourTables), ctypes.POINTER(ColourTone)]
@@ -483,6 +494,18 @@ class Library:
         out, n = (ctypes.c_uint8 * 4)(), ctypes.c_int(0)
         self.check(self.lib.m355_pixel_pack(format, (ctypes.c_uint32 * 3)(*[int(v) for v in rgb]), alpha, out, ctypes.byref(n)))
         return bytes(out[:n.value])
+
+    def orientation_compose(self, first, then):
+        """the one orientation equal to `first` and then `then` (m355_orientation_compose; host only)"""
+        out = ctypes.c_int(-1)
+        self.check(self.lib.m355_orientation_compose(first, then, ctypes.byref(out)))
+        return out.value
+
+    def orientation_from_exif(self, exif):
+        """the orientation that brings a picture stored with EXIF Orientation 1..8 upright (m355_orientation_from_exif; host only)"""
+        out = ctypes.c_int(-1)
+        self.check(self.lib.m355_orientation_from_exif(exif, ctypes.byref(out)))
+        return out.value
 
     def colour_pixel(self, tables, rgb16, samples):
         """the colour transform stage for one pixel (m355_colour_pixel; host only) -> (R, G, B)"""
@@ -784,6 +807,29 @@ class Context:
                 self.L.check(self.L.lib.m355_frame_export(self.h, f, ctypes.byref(desc)))
         return self._export_into_planes(f, self.export_shapes(f, layout, samples, rect, log2_scale), desc, host, pad, call)
 
+    def frame_export_oriented(self, f, layout, samples, orientation, rect=None, host=False, pad=20):
+        """start m355_frame_export_oriented of frame f: frame_export's buffers with the shapes of the ORIENTED planes (TRANSPOSE: rows and elements per
+        row exchanged; an interleaved plane keeps its pairs).  -> token for frame_export_finish"""
+        desc = ExportDesc(layout=layout, samples=samples)
+        if rect is not None:
+            desc.x0, desc.y0, desc.width, desc.height = rect
+        shapes = self.export_shapes(f, layout, samples, rect)
+        if orientation & ORIENT_TRANSPOSE:
+            semi = [layout == EXPORT_SEMIPLANAR and k == 1 for k in range(len(shapes))]
+            shapes = [(n // 2, rows * 2, dt) if s else (n, rows, dt) for (rows, n, dt), s in zip(shapes, semi)]
+        return self._export_into_planes(f, shapes, desc, host, pad,
+                                        lambda: self.L.check(self.L.lib.m355_frame_export_oriented(self.h, f, ctypes.byref(desc), orientation)))
+
+    def frame_export_pixels_oriented(self, f, format, alpha, matrix, full_range, orientation, rect=None, host=False, pad=20, chroma_loc=0):
+        """start m355_frame_export_pixels_oriented of frame f: frame_export_pixels' buffer with the shape of the ORIENTED picture.
+        -> token for frame_export_finish"""
+        w, h = self._geom[f][:2] if rect is None else rect[2:]
+        if orientation & ORIENT_TRANSPOSE:
+            w, h = h, w
+        opts = self._opts(0, chroma_loc, False) if chroma_loc else None
+        return self._frame_export_pixels("m355_frame_export_pixels_oriented", f, format, alpha, matrix, full_range, w, h, (0, 0), rect, host, pad, opts,
+                                         (orientation,))
+
     def resize_taps(self, src_n, dst_n, cosited, i, filter=0, filtered_entry=False):
         """row i of one axis of the resize filter (m355_resize_taps) -> (first source index, [coefficients]), or None for arguments it rejects"""
         return self.L.resize_taps(src_n, dst_n, cosited, i, filter, filtered_entry)
@@ -865,7 +911,7 @@ class Context:
         return self._export_into_planes(f, self._rgb_shapes(w, h, layout, samples), desc, host, pad,
                                         lambda: self._export_entry("m355_frame_export_resized_rgb", (self.h, f, ctypes.byref(desc)), *entry))
 
-    def _frame_export_pixels(self, name, f, format, alpha, matrix, full_range, w, h, out_size, rect, host, pad, opts):
+    def _frame_export_pixels(self, name, f, format, alpha, matrix, full_range, w, h, out_size, rect, host, pad, opts, more=()):
         """what the two pixel exports share: ONE buffer of h rows of w * pixel_bytes(format) bytes, made as frame_export_rgb makes its buffers — every
         byte holds DEVICE_FILL beforehand (the guard bytes), the pitch is `pad` bytes (a multiple of 4) larger than the row —, the descriptor, the call;
         the buffer is freed again if the call raises.  -> token for frame_export_finish, whose one plane is (h, w * pixel_bytes) uint8"""
@@ -877,7 +923,7 @@ class Context:
         buf = self._buffer(h * pitch, host)
         desc.dst, desc.pitch = buf, pitch
         try:
-            self.L.check(getattr(self.L.lib, name)(self.h, f, ctypes.byref(desc), opts))
+            self.L.check(getattr(self.L.lib, name)(self.h, f, ctypes.byref(desc), opts, *more))
         except Exception:
             self._buffer_free(buf, host)
             raise

@@ -325,6 +325,31 @@ void m355_launch_export_rgb(const ExportRgbArgs& a, int src_bytes, int dst_bytes
    coefficients of M355_RGB_U16), else 8 bits per channel (those of M355_RGB_U8).  B-first formats: the host exchanges src[1] / src[2] and their coefficients */
 void m355_launch_export_pixels(const ExportRgbArgs& a, int src_bytes, bool ten, int chroma_format, int chroma_loc, hipStream_t st);
 
+/* one m355_frame_export_oriented (k_export_oriented.hip), planes as in ExportArgs.  An ELEMENT is one converted sample, or the (Cb, Cr) pair of an
+   interleaved row; pw[k] x ph[k]: the SOURCE rectangle on plane k in elements.  mirror / flip / transpose: the orientation's bits (orientation.h), 0 or 1.
+   Without transpose a wavefront takes one 64-lane chunk (1024 destination bytes) of one row, as in k_export: per_row[k] = chunks per row; with it a
+   workgroup takes one tile of M355_ORIENT_TILE x M355_ORIENT_TILE elements: per_row[k] = tiles per row of tiles of the SOURCE.  unit_end[k] = the
+   chunks / tiles of planes 0..k.  shift[k] as in ExportArgs.  timeout / epoch: the gate (M355_GATE). */
+#define M355_ORIENT_TILE 64
+struct ExportOrientedArgs {
+  const uint8_t* src[3];
+  uint8_t* dst[3];
+  long long src_pitch[3], dst_pitch[3];
+  uint32_t pw[3], ph[3], per_row[3], unit_end[3];
+  int32_t shift[3];
+  uint32_t mirror, flip, transpose;
+  const uint32_t* timeout;
+  uint32_t epoch;
+};
+void m355_launch_export_oriented(const ExportOrientedArgs& a, int src_bytes, int dst_bytes, bool semiplanar, hipStream_t st);
+/* one m355_frame_export_pixels_oriented (k_export_oriented.hip): r = what k_export_pixels takes (r.chunks, r.units: without transpose its chunks and
+   units; with it the tiles per row of tiles of the source rectangle and the tiles), and the orientation's bits */
+struct ExportPixelsOrientedArgs {
+  ExportRgbArgs r;
+  uint32_t mirror, flip, transpose;
+};
+void m355_launch_export_pixels_oriented(const ExportPixelsOrientedArgs& a, int src_bytes, bool ten, int chroma_format, int chroma_loc, hipStream_t st);
+
 /* one m355_frame_export_resized (k_export_resized.hip), planes as in ExportArgs (semi-planar: plane 1 = Cb and Cr, read from src[1] and src[2] and
    stored interleaved).  Plane k maps the rectangle's sn_x[k] x sn_y[k] source samples to dn_x[k] x dn_y[k] output samples; cosited[k]: the
    horizontal axis is co-sited (4:2:0 / 4:2:2 chroma unless the siting is CENTRE), cosited_y[k]: the vertical axis is (4:2:0 chroma sited TOP:

@@ -35,8 +35,7 @@
  */
 #include "k_common.h"
 
-#include "k_rgb_dev.h"   /* d_mad24, d_rgb_sample, d_rgb_chroma, d_rgb_load, d_rgb_pixel: shared with k_stats.hip */
-#include "pixel_pack.h"  /* m355_pp_dword: the pixel formats of k_export_pixels below */
+#include "k_rgb_dev.h"   /* d_mad24, d_rgb_sample, d_rgb_chroma, d_rgb_load, d_rgb_pixel: shared with k_stats.hip; d_rgb_pixels_lane: with k_export_oriented.hip */
 
 /* N values of one byte / one 16-bit half each -> N * DB / 4 dwords */
 template <int DB, int N> __device__ __forceinline__ void d_rgb_pack(const unsigned* e, unsigned* o)
@@ -141,7 +140,7 @@ template <int SB, bool TEN, int CF, int LOC>
 __global__ void __launch_bounds__(256) k_export_pixels(ExportRgbArgs a)
 {
   M355_GATE(a);
-  constexpr int NP = 16 / SB, M = TEN ? 65535 : 255;
+  constexpr int NP = 16 / SB;
   const uint32_t unit = __builtin_amdgcn_readfirstlane((uint32_t)(blockIdx.x * 4u + (threadIdx.x >> 6)));
   if (unit >= a.units) return;
   const uint32_t row = unit / a.chunks, chunk = unit - row * a.chunks;
@@ -149,22 +148,8 @@ __global__ void __launch_bounds__(256) k_export_pixels(ExportRgbArgs a)
   if (p0 >= a.width) return;
   const uint32_t n = a.width - p0 < (uint32_t)NP ? a.width - p0 : (uint32_t)NP;
   const uint32_t X0 = a.x0 + p0, Y = a.y0 + row;
-  RgbLane<SB, CF, LOC> l;
-  d_rgb_load<SB, CF, LOC>(a, X0, Y, l);
-  const RgbMatrix m = d_rgb_matrix_of(a.k);
-  int u[NP], v[NP];
-  if (CF != 0) {
-    d_rgb_chroma<SB, CF, LOC>(l.rc[0][0], l.rc[0][1], l.last, m.c0, u, l.yodd, l.lead);
-    d_rgb_chroma<SB, CF, LOC>(l.rc[1][0], l.rc[1][1], l.last, m.c0, v, l.yodd, l.lead);
-  }
-  const uint32_t alpha_bits = a.alpha_bits;
   unsigned o[NP];
-#pragma unroll
-  for (int k = 0; k < NP; k++) {
-    unsigned R, G, B;
-    d_rgb_pixel<CF>(m, d_rgb_sample<SB>(l.ry, k), CF != 0 ? u[k] : 0, CF != 0 ? v[k] : 0, M, R, G, B);
-    o[k] = m355_pp_dword(TEN, R, G, B, alpha_bits);
-  }
+  d_rgb_pixels_lane<SB, TEN, CF, LOC>(a, X0, Y, o);
   d_rgb_store<NP>((M355_GLOBAL uint8_t*)a.dst[0] + (size_t)row * a.dst_pitch[0] + (size_t)p0 * 4u, o, n * 4u);
 }
 

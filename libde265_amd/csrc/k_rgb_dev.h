@@ -7,6 +7,7 @@
  */
 #pragma once
 #include "k_common.h"
+#include "pixel_pack.h"   /* m355_pp_dword: d_rgb_pixels_lane */
 
 #ifdef SIMT_EMU
 static inline int d_mad24(int a, int b, int c) { return (int)((unsigned)a * (unsigned)b + (unsigned)c); }
@@ -142,4 +143,28 @@ __device__ __forceinline__ void d_rgb_pixel(const RgbMatrix& m, int y, int u, in
   R = (unsigned)d_clip3(0, M, r >> m.F);
   G = (unsigned)d_clip3(0, M, g >> m.F);
   B = (unsigned)d_clip3(0, M, b >> m.F);
+}
+
+/* The NP = 16 / SB pixels from luma column X0 (even where chroma is subsampled) of luma row Y as the dwords of a 4-byte pixel format (pixel_pack.h; TEN: a
+   2:10:10:10 format, the matrix with the coefficients of M355_RGB_U16; a.alpha_bits: the alpha in its place): the lane's work in k_export_pixels and in the
+   oriented pixel export (k_export_oriented.hip), which differ in where the dwords go. */
+template <int SB, bool TEN, int CF, int LOC, class A>
+__device__ __forceinline__ void d_rgb_pixels_lane(const A& a, uint32_t X0, uint32_t Y, unsigned* o)
+{
+  constexpr int NP = 16 / SB, M = TEN ? 65535 : 255;
+  RgbLane<SB, CF, LOC> l;
+  d_rgb_load<SB, CF, LOC>(a, X0, Y, l);
+  const RgbMatrix m = d_rgb_matrix_of(a.k);
+  int u[NP], v[NP];
+  if (CF != 0) {
+    d_rgb_chroma<SB, CF, LOC>(l.rc[0][0], l.rc[0][1], l.last, m.c0, u, l.yodd, l.lead);
+    d_rgb_chroma<SB, CF, LOC>(l.rc[1][0], l.rc[1][1], l.last, m.c0, v, l.yodd, l.lead);
+  }
+  const uint32_t alpha_bits = a.alpha_bits;
+#pragma unroll
+  for (int k = 0; k < NP; k++) {
+    unsigned R, G, B;
+    d_rgb_pixel<CF>(m, d_rgb_sample<SB>(l.ry, k), CF != 0 ? u[k] : 0, CF != 0 ? v[k] : 0, M, R, G, B);
+    o[k] = m355_pp_dword(TEN, R, G, B, alpha_bits);
+  }
 }

@@ -15,6 +15,7 @@
 #include "colour_transform.h"
 #include "colour_preset.h"
 #include "pixel_pack.h"
+#include "orientation.h"
 #include <utility>
 
 namespace {
@@ -42,9 +43,10 @@ int dst_check(const char* who, int p, const void* dst, int64_t pitch, int64_t ro
   if (eb == 2 && (((uintptr_t)dst | (uint64_t)pitch) & 1)) return fail(M355_ERR_INVALID, "%s: 16-bit plane %d at an odd address or pitch", who, p);
   return M355_OK;
 }
-/* The plan of m355_frame_export and m355_frame_export_scaled: the argument checks and the planes.  log2_scale = k: the rectangle must divide into blocks
- * of 1 << k samples on every plane's grid, and row_bytes / the pitch check are those of the SCALED row. */
-int export_plan(m355_ctx* c, int h, const m355_export_desc* e, int k, const char* who, ExportPlan& P)
+/* The plan of m355_frame_export, m355_frame_export_scaled and m355_frame_export_oriented: the argument checks and the planes.  log2_scale = k: the
+ * rectangle must divide into blocks of 1 << k samples on every plane's grid, and row_bytes / the pitch check are those of the SCALED row; transposed:
+ * those of a row of the plane's ph elements. */
+int export_plan(m355_ctx* c, int h, const m355_export_desc* e, int k, const char* who, ExportPlan& P, bool transposed = false)
 {
   Frame* f = get_frame(c, h);
   if (!f || !e) return fail(M355_ERR_INVALID, "bad frame handle %d / null descriptor", h);
@@ -68,7 +70,7 @@ int export_plan(m355_ctx* c, int h, const m355_export_desc* e, int k, const char
     q.db = e->samples == M355_EXPORT_NATIVE ? q.sb : (e->samples == M355_EXPORT_MSB16 ? 2 : 1);
     q.pw = p ? w / sw : w; q.ph = p ? hgt / sh : hgt;
     const int px = p ? x0 / sw : x0, py = p ? y0 / sh : y0;
-    q.row_bytes = (int64_t)(q.pw >> k) * q.db * (P.semi && p ? 2 : 1);
+    q.row_bytes = (int64_t)((transposed ? q.ph : q.pw) >> k) * q.db * (P.semi && p ? 2 : 1);
     const int rc = dst_check(who, p, e->dst[p], e->pitch[p], q.row_bytes, 1);
     if (rc) return rc;
     q.dst = (uint8_t*)e->dst[p]; q.dst_pitch = e->pitch[p];
@@ -334,6 +336,52 @@ int m355_frame_export(m355_ctx* c, int h, const m355_export_desc* e)
     a.unit_end[p] = units;
   }
   return export_launch(c, P.f, a, [&](hipStream_t cs) { m355_launch_export(a, P.f->bpp[0], P.p[0].db, P.semi, cs); });
+}
+/* The same with every plane of the rectangle oriented on its own grid (k_export_oriented.hip; orientation.h): the plan of m355_frame_export, its pitches
+ * checked against the oriented rows.  Orientation 0 is m355_frame_export itself. */
+int m355_frame_export_oriented(m355_ctx* c, int h, const m355_export_desc* e, int orientation)
+{
+  const char* who = "m355_frame_export_oriented";
+  if (!m355_or_known(orientation)) return fail(M355_ERR_INVALID, "%s: orientation %d is not 0..7", who, orientation);
+  if (orientation == 0) return m355_frame_export(c, h, e);
+  const bool tr = m355_or_transpose(orientation);
+  const Frame* g = get_frame(c, h);
+  if (g && tr && g->cf == 2) return fail(M355_ERR_INVALID, "%s: a transposed 4:2:2 frame would be 4:4:0, which no layout describes", who);
+  ExportPlan P;
+  int rc = export_plan(c, h, e, 0, who, P, tr);
+  if (rc) return rc;
+  ExportOrientedArgs a = {};
+  uint32_t units = 0;
+  for (int p = 0; p < 3; p++) {
+    if (p < P.np) {
+      const ExportPlane& q = P.p[p];
+      plane_fill(P, p, q.dst, q.dst_pitch, a);
+      a.pw[p] = (uint32_t)q.pw; a.ph[p] = (uint32_t)q.ph;
+      a.shift[p] = e->samples == M355_EXPORT_MSB16 ? 16 - q.bd : (e->samples == M355_EXPORT_U8 ? q.bd - 8 : 0);
+      if (tr) {
+        a.per_row[p] = (uint32_t)((q.pw + M355_ORIENT_TILE - 1) / M355_ORIENT_TILE);
+        units += a.per_row[p] * (uint32_t)((q.ph + M355_ORIENT_TILE - 1) / M355_ORIENT_TILE);
+      } else {
+        a.per_row[p] = (uint32_t)((q.row_bytes + 1023) / 1024);
+        units += a.per_row[p] * (uint32_t)q.ph;
+      }
+    }
+    a.unit_end[p] = units;
+  }
+  a.mirror = m355_or_mirror(orientation); a.flip = m355_or_flip(orientation); a.transpose = tr;
+  return export_launch(c, P.f, a, [&](hipStream_t cs) { m355_launch_export_oriented(a, P.f->bpp[0], P.p[0].db, P.semi, cs); });
+}
+int m355_orientation_compose(int first, int then, int* out)
+{
+  if (!out || !m355_or_known(first) || !m355_or_known(then)) return fail(M355_ERR_INVALID, "m355_orientation_compose: null result, or %d / %d is not 0..7", first, then);
+  *out = m355_or_compose(first, then);
+  return M355_OK;
+}
+int m355_orientation_from_exif(int exif, int* out)
+{
+  if (!out || m355_or_from_exif(exif) < 0) return fail(M355_ERR_INVALID, "m355_orientation_from_exif: null result, or %d is not 1..8", exif);
+  *out = m355_or_from_exif(exif);
+  return M355_OK;
 }
 /* The same, downscaled by 1 << log2_scale in both directions (k_export_scaled.hip): a reader of the same kind, so that m355_frame_export_wait and
  * m355_frame_export_order cover it and the next decode into the frame waits for it. */
@@ -605,21 +653,19 @@ static int pixel_desc_check(const char* who, const m355_pixel_desc* e, const Fra
 /* (k_export_rgb.hip: k_export_pixels for the 4-byte formats, the packed U8 path of k_export_rgb for BGR8.)  B, G, R order is R, G, B of the frame with
  * Cb and Cr and their coefficients exchanged — R = cy y + crv v and B = cy y + cbu u change places, G's sum keeps its terms —, so the kernels have
  * one channel order. */
-int m355_frame_export_pixels(m355_ctx* c, int h, const m355_pixel_desc* e, const m355_export_opts* opts)
+static int pixels_plan(const char* who, m355_ctx* c, int h, const m355_pixel_desc* e, const m355_export_opts* opts, bool transposed, Frame** fo, ExportRgbArgs& a,
+                       m355_export_opts& o)
 {
-  const char* who = "m355_frame_export_pixels";
   ExportPlan P;
   int rc = export_plan_rect(c, h, e, e ? e->dst : nullptr, who, P);
   if (rc) return rc;
   Frame* f = P.f;
-  m355_export_opts o;
   rc = opts_check(who, c, opts, f, false, o);
   if (rc) return rc;
   if (e->out_width || e->out_height) return fail(M355_ERR_INVALID, "%s: output size %dx%d in a call that resizes nothing", who, e->out_width, e->out_height);
-  ExportRgbArgs a = {};
   const int sb = f->bpp[0];
   const int64_t w = P.p[0].pw;
-  rc = pixel_desc_check(who, e, f, w, &a.k);
+  rc = pixel_desc_check(who, e, f, transposed ? P.p[0].ph : w, &a.k);
   if (rc) return rc;
   a.dst[0] = (uint8_t*)e->dst; a.dst_pitch[0] = e->pitch;
   for (int p = 0; p < 3; p++) a.src[p] = (const uint8_t*)f->plane[p];
@@ -632,11 +678,43 @@ int m355_frame_export_pixels(m355_ctx* c, int h, const m355_pixel_desc* e, const
   a.chunks = (a.width + per_chunk - 1) / per_chunk;
   a.units = a.chunks * a.height;
   a.alpha_bits = m355_pp_alpha_bits(e->format, (uint32_t)e->alpha);
-  const int format = e->format;
+  *fo = f;
+  return M355_OK;
+}
+int m355_frame_export_pixels(m355_ctx* c, int h, const m355_pixel_desc* e, const m355_export_opts* opts)
+{
+  Frame* f = nullptr;
+  ExportRgbArgs a = {};
+  m355_export_opts o;
+  int rc = pixels_plan("m355_frame_export_pixels", c, h, e, opts, false, &f, a, o);
+  if (rc) return rc;
+  const int format = e->format, sb = f->bpp[0];
   return export_launch(c, f, a, [&](hipStream_t cs) {
     if (m355_pp_bytes(format) == 3) m355_launch_export_rgb(a, sb, 1, false, f->cf, o.chroma_loc, cs);
     else m355_launch_export_pixels(a, sb, m355_pp_ten(format), f->cf, o.chroma_loc, cs);
   });
+}
+/* The pixels of m355_frame_export_pixels permuted as whole pixels (k_export_oriented.hip): that call's plan — with TRANSPOSE the pitch checked against
+ * height * 4 — and, with TRANSPOSE, tiles of the rectangle in place of its chunks.  Orientation 0 is m355_frame_export_pixels itself. */
+int m355_frame_export_pixels_oriented(m355_ctx* c, int h, const m355_pixel_desc* e, const m355_export_opts* opts, int orientation)
+{
+  const char* who = "m355_frame_export_pixels_oriented";
+  if (!m355_or_known(orientation)) return fail(M355_ERR_INVALID, "%s: orientation %d is not 0..7", who, orientation);
+  if (orientation == 0) return m355_frame_export_pixels(c, h, e, opts);
+  if (e && e->format == M355_PIXEL_BGR8) return fail(M355_ERR_INVALID, "%s: M355_PIXEL_BGR8 with an orientation (a 3-byte element)", who);
+  Frame* f = nullptr;
+  ExportPixelsOrientedArgs a = {};
+  m355_export_opts o;
+  const bool tr = m355_or_transpose(orientation);
+  int rc = pixels_plan(who, c, h, e, opts, tr, &f, a.r, o);
+  if (rc) return rc;
+  if (tr) {
+    a.r.chunks = (a.r.width + M355_ORIENT_TILE - 1) / M355_ORIENT_TILE;
+    a.r.units = a.r.chunks * ((a.r.height + M355_ORIENT_TILE - 1) / M355_ORIENT_TILE);
+  }
+  a.mirror = m355_or_mirror(orientation); a.flip = m355_or_flip(orientation); a.transpose = tr;
+  const bool ten = m355_pp_ten(e->format);
+  return export_launch(c, f, a.r, [&](hipStream_t cs) { m355_launch_export_pixels_oriented(a, f->bpp[0], ten, f->cf, o.chroma_loc, cs); });
 }
 /* (k_export_resized_rgb.hip, RR_FRAME with PX: the colour stage sits between the matrix and the pack, so the channel order is the kernel's here.) */
 int m355_frame_export_resized_pixels(m355_ctx* c, int h, const m355_pixel_desc* e, const m355_export_opts* opts)
