@@ -7,7 +7,8 @@ from ctypes import c_ssize_t
 
 import numpy as np
 
-from test_oracle_vs_ref import coeff_scenarios
+from test_oracle_vs_ref import WP_SIZES, coeff_scenarios, inrange_intermediates
+from wpred_content import FUNCTION_DIM, corner_sets, inrange_sets
 from util import XorShift32, pixel_dtype, ptr, ptr_at
 
 
@@ -44,6 +45,25 @@ def check_weighted(tab, oracle, quick):
             getattr(tab, "put_weighted_bipred" + sfx)(ptr(a), ds, ptr(s1), ptr(s2), ss, w, h, wt1, o1, wt2, o2, log2WD, *extra)
             oracle.o_put_weighted_bipred(ptr(b), c_ssize_t(ds), pb, ptr(s1), ptr(s2), c_ssize_t(ss), w, h, wt1, o1, wt2, o2, log2WD, bd)
             assert np.array_equal(a, b), ("bipred", bd, w, h)
+        # weights whose results stay in range (tests/wpred_content.py), on the intermediates of in-range samples: every denominator with three
+        # sets, the ends of the legal ranges at denominators 5..7 on dimmed content (quick: two denominators, one set each)
+        ss, hmax = 64, 16
+        base = rng.array((ss + 5) * hmax, 0, (1 << bd) - 1, pd)
+        runs = [(inrange_intermediates(rng, bd, ss, hmax), d, st) for d in ((1, 6) if quick else range(8)) for st in inrange_sets(rng, bd, d)[:1 if quick else 3]]
+        if not quick:
+            dimmed = inrange_intermediates(rng, bd, ss, hmax, FUNCTION_DIM)
+            runs += [(dimmed, d, st) for d in (5, 6, 7) for st in corner_sets(bd, d)]
+        for turn, (sources, d, (w1, o1, w2, o2)) in enumerate(runs):
+            (w, h), (s1, s2) = WP_SIZES[turn % len(WP_SIZES)], sources[sorted(sources)[turn % len(sources)]]
+            ds, log2WD = w + 5, d + shift1
+            a = base[:ds * h].copy(); b = a.copy()
+            getattr(tab, "put_weighted_pred" + sfx)(ptr(a), ds, ptr(s1), ss, w, h, w1, o1, log2WD, *extra)
+            oracle.o_put_weighted_pred(ptr(b), c_ssize_t(ds), pb, ptr(s1), c_ssize_t(ss), w, h, w1, o1, log2WD, bd)
+            assert np.array_equal(a, b), ("weighted, in range", bd, w, h, d, w1, o1)
+            a = base[:ds * h].copy(); b = a.copy()
+            getattr(tab, "put_weighted_bipred" + sfx)(ptr(a), ds, ptr(s1), ptr(s2), ss, w, h, w1, o1, w2, o2, log2WD, *extra)
+            oracle.o_put_weighted_bipred(ptr(b), c_ssize_t(ds), pb, ptr(s1), ptr(s2), c_ssize_t(ss), w, h, w1, o1, w2, o2, log2WD, bd)
+            assert np.array_equal(a, b), ("bipred, in range", bd, w, h, d, w1, o1, w2, o2)
 
 
 def check_qpel(tab, oracle, quick):

@@ -226,6 +226,78 @@ def test_weighted_prediction(oracle, ref, bd):
             assert np.array_equal(a, b)
 
 
+def inrange_intermediates(rng, bd, ss, h, dim=0):
+    """int16 intermediates of IN-RANGE samples (>> dim): {name: (s1, s2)} — full-pel (the sample scaled to 14 bits, sample << (14 - bd);
+    above 14 bits sample >> (bd - 14), what the reference's copy path stores) and filtered (any value of [0, 2^14)), the second array
+    correlated with the first (another sample of the same content, +-256 of 2^14) and independent of it"""
+    n = ss * h
+    smp = rng.array(n, 0, (1 << bd) - 1, np.int32) >> dim
+    smp2 = rng.array(n, 0, (1 << bd) - 1, np.int32) >> dim
+    full, full2 = ((a << (14 - bd)) if bd <= 14 else (a >> (bd - 14)) for a in (smp, smp2))
+    filt = rng.array(n, 0, (1 << 14) - 1, np.int32) >> dim
+    near = np.clip(filt + rng.array(n, -256, 256, np.int32), 0, (1 << 14) - 1)
+    return {"fullpel_independent": (full.astype(np.int16), full2.astype(np.int16)),
+            "filtered_correlated": (filt.astype(np.int16), near.astype(np.int16)),
+            "filtered_independent": (filt.astype(np.int16), (rng.array(n, 0, (1 << 14) - 1, np.int32) >> dim).astype(np.int16))}
+
+
+WP_SIZES = [(8, 4), (16, 12), (6, 8), (4, 16), (64, 16), (2, 2)]
+
+
+@pytest.mark.parametrize("bd", BIT_DEPTHS)
+def test_weighted_prediction_inrange(oracle, ref, bd):
+    """test_weighted_prediction draws w = 2^denom + U[-128, 127] on intermediates that span all of int16: most outputs are 0 or maxv.  Here the
+    weights are those of tests/wpred_content.py (in range at every denominator 0..7; the ends of the legal ranges at 5..7 on dimmed content)
+    on the intermediates of in-range samples, and the in-range family must leave >= 60 % of its outputs unclipped per function and denominator"""
+    from wpred_content import FUNCTION_DIM, corner_sets, inrange_sets
+    rng = XorShift32(0x3E167ED0 + 0x100 + bd)
+    pd, pb = pixel_dtype(bd), (1 if bd <= 8 else 2)
+    ss, hmax, maxv = 64, 16, (1 << bd) - 1
+    simds = (0, 1) if bd == 8 else (0,)                # the table with the reference's SSE functions: at 8 bits
+    base = rng.array((ss + 5) * hmax, 0, maxv, pd)            # the largest destination: rows of w + 5 samples
+    assert all(w <= ss and h <= hmax for (w, h) in WP_SIZES)
+    families = [("inrange", inrange_intermediates(rng, bd, ss, hmax), lambda d: inrange_sets(rng, bd, d), range(8)),
+                ("corner", inrange_intermediates(rng, bd, ss, hmax, FUNCTION_DIM), lambda d: corner_sets(bd, d), range(5, 8))]
+    turn = 0
+    for family, sources, sets, denoms in families:
+        for denom in denoms:
+            log2WD = denom + max(2, 14 - bd)
+            inside = {"uni": [0, 0], "bi": [0, 0]}
+            for (w1, o1, w2, o2) in sets(denom):
+                for name, (s1, s2) in sorted(sources.items()):
+                    w, h = WP_SIZES[turn % len(WP_SIZES)]
+                    turn += 1
+                    ds = w + 5
+                    b = base[:ds * h].copy()
+                    oracle.o_put_weighted_pred(ptr(b), c_ssize_t(ds), pb, ptr(s1), c_ssize_t(ss), w, h, w1, o1, log2WD, bd)
+                    for simd in simds:
+                        a = base[:ds * h].copy()
+                        ref.ref_put_weighted_pred(simd, ptr(a), c_ssize_t(ds), pb, ptr(s1), c_ssize_t(ss), w, h, w1, o1, log2WD, bd)
+                        assert np.array_equal(a, b), (family, "weighted", simd, denom, name, w1, o1)
+                    blk = b.reshape(h, ds)[:, :w]
+                    inside["uni"][0] += int(((blk > 0) & (blk < maxv)).sum()); inside["uni"][1] += blk.size
+                    b = base[:ds * h].copy()
+                    oracle.o_put_weighted_bipred(ptr(b), c_ssize_t(ds), pb, ptr(s1), ptr(s2), c_ssize_t(ss), w, h, w1, o1, w2, o2, log2WD, bd)
+                    for simd in simds:
+                        a = base[:ds * h].copy()
+                        ref.ref_put_weighted_bipred(simd, ptr(a), c_ssize_t(ds), pb, ptr(s1), ptr(s2), c_ssize_t(ss), w, h, w1, o1, w2, o2, log2WD, bd)
+                        assert np.array_equal(a, b), (family, "bipred", simd, denom, name, w1, o1, w2, o2)
+                    blk = b.reshape(h, ds)[:, :w]
+                    inside["bi"][0] += int(((blk > 0) & (blk < maxv)).sum()); inside["bi"][1] += blk.size
+                    if bd == 8:
+                        # (the two unweighted forms on the same intermediates: those are the ones the reference has SSE functions for)
+                        for fn, ofn, extra in (("ref_put_unweighted_pred", "o_put_unweighted_pred", (ptr(s1),)),
+                                               ("ref_put_weighted_pred_avg", "o_put_weighted_pred_avg", (ptr(s1), ptr(s2)))):
+                            for simd in (0, 1):
+                                a, b = base[:ds * h].copy(), base[:ds * h].copy()
+                                getattr(ref, fn)(simd, ptr(a), c_ssize_t(ds), pb, *extra, c_ssize_t(ss), w, h, bd)
+                                getattr(oracle, ofn)(ptr(b), c_ssize_t(ds), pb, *extra, c_ssize_t(ss), w, h, bd)
+                                assert np.array_equal(a, b), (family, fn, simd, name)
+            if family == "inrange":
+                for form, (n_in, n_all) in inside.items():
+                    assert n_in * 100 >= 60 * n_all, "%s, %d bits, denominator %d: %d of %d outputs unclipped" % (form, bd, denom, n_in, n_all)
+
+
 @pytest.mark.parametrize("bd", [8, 10, 12])
 def test_intra_predictors(oracle, ref, bd):
     """test-intrapred.cc:163-178: all 35 modes x nT x cIdx x disableBoundaryFilter."""
